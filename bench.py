@@ -19,13 +19,16 @@ blob (commit / proof) or, for batch verification, the all-gathers of
 kateth_amd/dist.py (32-B transcript roots + first-error records, 192 B of
 partial sums).
 
-Prints ONE JSON line on rank 0 (contract in the task description) carrying
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run
+sets up, warms up, times --steps steps and prints `value` and `ms_per_step`;
+`--dump-outputs DIR` also writes what the last timed step computed as .npy
+files.  `--full` adds everything else, as measured before it became an option:
 `roofline` (dominant kernel of the workload, HIP-event timed inside the library
-on the stream it runs on) and `cpu_baseline` (the C port of the reference's CPU
-algorithm, oracle/cport, timed on the host cores on a bounded sample; rank 0,
-N = 1 only).  With the default workload the proof and verify workloads are also
-reported under "extra" (each with its own roofline object); they are not part
-of `value`.
+on the stream it runs on, live rocprofv3 --pmc passes), `cpu_baseline` (the C
+port of the reference's CPU algorithm, oracle/cport, timed on the host cores on
+a bounded sample; rank 0, N = 1 only), the golden-vector checks, and with the
+default workload the proof and verify workloads under "extra" (each with its
+own roofline object); none of them is part of `value`.
 """
 import argparse
 import json
@@ -52,6 +55,8 @@ METRIC = {
     "verify": "blobs/sec for verify_blob_kzg_proof_batch (n=4096 field elements per blob)",
 }
 DEFAULT_BATCH = {"commit": 4096, "proof": 4096, "verify": 65536}
+# the metric line of the default run (commit, secondary workloads on, one GPU): BASELINE.json's, which names two functions
+METRIC_DEFAULT_RUN = "blobs/sec for blob_to_kzg_commitment and verify_blob_kzg_proof_batch (n=4096)"
 DTYPE = "u32 limbs (381-bit Fp / 255-bit Fr Montgomery integer arithmetic; signed 30-bit limbs on v_mad_i64_i32 in the fixed-base MSM, 28/29-bit radix in the other hot loops)"
 
 
@@ -86,6 +91,10 @@ def parse():
                     "devices 0..N-1; when fewer GPUs are visible they share device 0 (a rehearsal of the code path, not a speed-up).  Same JSON line; roofline from member 0's kernels")
     ap.add_argument("--dry-run", action="store_true", help="print every rank's HBM plan for --workload/--batch/--gpus as one JSON line and exit non-zero if it cannot fit; touches no GPU")
     ap.add_argument("--assume-hbm-gib", type=float, default=0.0, help="--dry-run: HBM per GPU in GiB (default: 288, what an MI355X reports)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: kernel profile and clock probe in the timed region, roofline, golden-vector checks "
+                    "(--group: and the single-device comparison), secondary workloads, CPU baseline and the live PMC passes (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; at most "
+                    "64 MB in all, a fixed seeded sample of rows beyond that)")
     return ap.parse_args()
 
 
@@ -307,7 +316,7 @@ def live_pmc(args, workload, n, counters, timeout_s=200):
             d = os.path.join(tmp, counter)
             cmd = [prof, "--pmc", counter, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__), "--workload", workload,
                    "--batch", str(n), "--window-bits", str(args.window_bits), "--steps", str(PMC_CHILD_STEPS), "--warmup", str(PMC_CHILD_WARMUP), "--no-cpu-baseline",
-                   "--no-extra", "--no-live-traffic", "--blocking-setup"] + (["--default-budget"] if args.default_budget else [])
+                   "--no-extra", "--no-live-traffic", "--blocking-setup", "--full"] + (["--default-budget"] if args.default_budget else [])
             res = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=timeout_s)
             if res.returncode != 0:
                 return {"error": "rocprofv3 --pmc %s exited %d: %s" % (counter, res.returncode, (res.stderr or res.stdout)[-300:])}
@@ -548,7 +557,7 @@ class Rank:
         self.t_create = time.time() - t0
         self.stream = torch.cuda.current_stream().cuda_stream
         self.t_first_use, self.first_use_class = None, None
-        if not args.blocking_setup:  # (the PMC child passes run blocking: no stray launch among the counted dispatches)
+        if not args.blocking_setup and args.full:  # (the PMC child passes run blocking: no stray launch among the counted dispatches)
             first_blob = self.make_blobs(1, 0)
             out1, st1 = self.commit(first_blob, 1)
             torch.cuda.synchronize()
@@ -606,9 +615,15 @@ class Rank:
         if self.args.backend == "nccl":
             self.dist.all_gather_into_tensor(gathered, d_local)  # RCCL over xGMI: 48 B per blob
         else:  # gloo rehearsal path: stage through the host
-            host = [self.torch.empty(d_local.numel(), dtype=self.torch.uint8) for _ in range(self.world)]
+            host = [self.torch.empty(d_local.numel(), dtype=d_local.dtype) for _ in range(self.world)]
             self.dist.all_gather(host, d_local.cpu())
             gathered.copy_(self.torch.cat(host))
+
+    def gather_all(self, d_local):
+        """every rank's `d_local`, in rank order (a collective: every rank calls it)"""
+        out = self.torch.empty(self.world * d_local.numel(), dtype=d_local.dtype, device=self.dev)
+        self.gather48(d_local, out)
+        return out
 
     def fence(self):
         if self.use_dist:
@@ -616,14 +631,17 @@ class Rank:
         self.torch.cuda.synchronize()
 
     # -- the timed region -----------------------------------------------------------------------------------------
-    def _run(self, fn, reps):
-        """`reps` calls of fn between two fences: (seconds, profile)"""
-        self.setup.profile_begin()
+    def _run(self, fn, reps, profile=True):
+        """`reps` calls of fn between two fences: (seconds, profile; None without `profile`)"""
+        if profile:
+            self.setup.profile_begin()
         t0 = time.perf_counter()
         for _ in range(reps):
             fn()
         self.fence()
         elapsed = time.perf_counter() - t0
+        if not profile:
+            return elapsed, None
         prof = self.setup.profile_end()
         prof["calls"] = reps
         return elapsed, prof
@@ -654,7 +672,9 @@ class Rank:
             self.fence()
             last = time.perf_counter() - t0
         self.fence()
-        if not self.use_dist and a.warmup:  # (single process only: a repeated timed loop on one rank would break the ranks' barriers)
+        if not a.full:  # a plain run times exactly --steps calls: no kernel events, no probe waves (they feed the roofline)
+            elapsed, prof = self._run(step, a.steps, profile=False)
+        elif not self.use_dist and a.warmup:  # (single process only: a repeated timed loop on one rank would break the ranks' barriers)
             elapsed, prof = self._run_with_clock_probe(step, a.steps, last)
         else:
             elapsed, prof = self._run(step, a.steps)
@@ -683,6 +703,28 @@ def check_golden(out48, n, first_index, what):
         b = rec["index"] - first_index
         if 0 <= b < n and what in rec:
             assert out48[48 * b:48 * b + 48].hex() == rec[what], "GPU %s != oracle golden vector (blob %d)" % (what, rec["index"])
+
+
+DUMP_LIMIT_BYTES = 60 * 10**6  # below 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: array whose first axis is the item} -> out_dir/<name>.npy in float32 (bytes and status codes are
+    exact in it).  Above DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its items, a sample fixed by SEED and its
+    length, and the kept item indices go to out_dir/<name>_sample_index.npy."""
+    import numpy as np
+
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES / (total + 8 * sum(a.shape[0] for a in arrays.values()))  # each kept item: its float32 row + a float64 index
+        for k, a in list(arrays.items()):
+            idx = np.sort(np.random.default_rng(SEED).choice(a.shape[0], size=int(a.shape[0] * frac), replace=False))
+            arrays[k] = a[idx]
+            np.save(os.path.join(out_dir, k + "_sample_index.npy"), idx.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def verify_cpu_baseline(R, d_blobs, d_com, d_prf, n):
@@ -886,17 +928,26 @@ def run_rank(args, rank, local_rank, world):
         for _, _, o, stt in lanes:
             assert int(stt.abs().sum()) == 0, "synthetic blobs must all be valid"
             assert torch.equal(o, lanes[0][2]), "calls in flight side by side must not change a byte"
-        d_out.copy_(lanes[0][2])
-        d_status.copy_(lanes[0][3])
+        _, _, o, stt = lanes[(tick[0] - 1) % flight]  # the lane of the last step
+        d_out.copy_(o)
+        d_status.copy_(stt)
     assert int(d_status.abs().sum()) == 0, "synthetic blobs must all be valid"
     if wl == "verify":
         assert all(v is True for v in verdicts), "verify_blob_kzg_proof_batch rejected the engine's own proofs"
+    if args.dump_outputs and wl != "verify":  # every rank's status codes beside the gathered results (every rank takes part)
+        status_all = R.gather_all(d_status) if R.use_dist else d_status
+    if args.dump_outputs and rank == 0:  # what a caller of the timed call receives from its last step
+        if wl == "verify":
+            dump_outputs(args.dump_outputs, {"verdict": [float(verdicts[-1])]})
+        else:
+            res = (gathered if R.use_dist else d_out).cpu().numpy().reshape(-1, 48)
+            dump_outputs(args.dump_outputs, {"commitments" if wl == "commit" else "proofs": res, "status": status_all.cpu().numpy()})
 
     # ---- correctness spot check of the timed output against the oracle golden vectors
-    gpu_out = d_out.cpu().numpy().tobytes() if rank == 0 else b""
-    if rank == 0 and wl != "verify":
+    gpu_out = d_out.cpu().numpy().tobytes() if rank == 0 and args.full else b""
+    if args.full and rank == 0 and wl != "verify":
         check_golden(gpu_out, n, first, "commitment" if wl == "commit" else "proof")
-    if R.use_dist and wl != "verify":  # rank-ordered gather = global blob order
+    if args.full and R.use_dist and wl != "verify":  # rank-ordered gather = global blob order
         assert bytes(gathered[rank * n * 48:(rank + 1) * n * 48].cpu().numpy().tobytes()) == d_out.cpu().numpy().tobytes()
 
     result = {
@@ -932,7 +983,7 @@ def run_rank(args, rank, local_rank, world):
             "hbm_plan_gib": {k: round(v / GIB, 2) for k, v in R.plan.items() if k in ("table", "blobs", "workspace", "resident_total", "peak_total", "hbm_total")},
         },
     }
-    if wl == "proof" and flight == 1 and not R.use_dist and not args.no_extra:  # (the PMC child passes run --no-extra: only the counted calls)
+    if args.full and wl == "proof" and flight == 1 and not R.use_dist and not args.no_extra:  # (the PMC child passes run --no-extra: only the counted calls)
         # beside the per-call figure (`value`): the amortised rate of a caller that keeps three calls in flight on three streams
         lanes3 = R.lanes(3, n)
         tick3 = [0]
@@ -950,7 +1001,7 @@ def run_rank(args, rank, local_rank, world):
         result["ms_per_step_three_calls_in_flight"] = 1e3 * dt3
         del lanes3
     if rank == 0:
-        roof = roofline_object(wl, n, prof, setup.window_bits, call_ms=1e3 * elapsed / args.steps)
+        roof = roofline_object(wl, n, prof, setup.window_bits, call_ms=1e3 * elapsed / args.steps) if args.full else None
         if wl in ("commit", "proof") and roof and prof["msm_launches"]:
             roof["kernel"] = setup.msm_kernel_name
             # measured integer-ALU ceiling: dependent Fp Montgomery multiplies with the multiply of the MSM kernel
@@ -967,14 +1018,17 @@ def run_rank(args, rank, local_rank, world):
             roof["valu_fp_mul_per_s"] = prof["adds_per_blob"] * 9.04 * blobs_per_launch / (msm_ms * 1e-3)
             roof["valu_fp_mul_peak_per_s"] = peak
             roof["valu_frac"] = roof["valu_fp_mul_per_s"] / peak
-        result["roofline"] = roof
-        if wl == "commit" and not args.no_extra and world == 1:
+        if args.full:
+            result["roofline"] = roof
+        elif wl == "commit" and not args.no_extra and world == 1:  # the same run without --full: the same metric line, `value` unchanged
+            result["metric"] = METRIC_DEFAULT_RUN
+        if args.full and wl == "commit" and not args.no_extra and world == 1:
             try:
                 result["extra"] = extra_workloads(R, d_blobs, d_out, n)
                 # BASELINE.json's metric names TWO functions: the second one at top level too, with its own roofline fraction
                 v, p = result["extra"]["verify_blob_kzg_proof_batch"], result["extra"]["compute_blob_kzg_proof"]
                 # BASELINE.json's metric string names both functions; `value` is the first (blob_to_kzg_commitment), `values` carries both
-                result["metric"] = "blobs/sec for blob_to_kzg_commitment and verify_blob_kzg_proof_batch (n=4096)"
+                result["metric"] = METRIC_DEFAULT_RUN
                 result["values"] = {"blob_to_kzg_commitment": result["value"], "verify_blob_kzg_proof_batch": v["blobs_per_s"], "compute_blob_kzg_proof": p["blobs_per_s"],
                                     "blob_to_kzg_commitment_two_calls_in_flight": result["extra"].get("blob_to_kzg_commitment_two_calls_in_flight", {}).get("blobs_per_s"),
                                     "compute_blob_kzg_proof_three_calls_in_flight": p.get("blobs_per_s_three_calls_in_flight"),
@@ -988,7 +1042,7 @@ def run_rank(args, rank, local_rank, world):
                      "ms_per_step_three_calls_in_flight": p.get("ms_per_batch_three_calls_in_flight")}]
             except Exception as err:  # secondary numbers never hide the headline
                 result["extra"] = {"error": repr(err)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 if wl == "verify":
                     result["cpu_baseline"] = verify_cpu_baseline(R, d_blobs, d_com, d_prf, n)
@@ -1127,16 +1181,24 @@ def run_group(args):
     for _ in range(args.warmup):
         step()
     sync_all()
-    members[0].profile_begin()
+    if args.full:  # kernel events for the roofline
+        members[0].profile_begin()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     sync_all()
     elapsed = time.perf_counter() - t0
-    prof = members[0].profile_end()
-    prof["calls"] = args.steps
+    if args.full:
+        prof = members[0].profile_end()
+        prof["calls"] = args.steps
     assert all(int(t.abs().sum()) == 0 for t in stat) and all(v is True for v in verdicts)
-    if wl != "verify":  # member 0's share holds the golden blobs
+    if args.dump_outputs:  # the members' shares in member order, from the last step
+        if wl == "verify":
+            dump_outputs(args.dump_outputs, {"verdict": [float(verdicts[-1])]})
+        else:
+            dump_outputs(args.dump_outputs, {"commitments" if wl == "commit" else "proofs": torch.cat([t.cpu() for t in out]).numpy().reshape(-1, 48),
+                                             "status": torch.cat([t.cpu() for t in stat]).numpy()})
+    if args.full and wl != "verify":  # member 0's share holds the golden blobs
         check_golden(out[0].cpu().numpy().tobytes(), n, 0, "commitment" if wl == "commit" else "proof")
         # and the last member's share against the single-device call of the same member
         ref = torch.zeros_like(out[-1])
@@ -1148,7 +1210,7 @@ def run_group(args):
                 members[-1].compute_blob_proof_batch_dev(blobs[-1].data_ptr(), com[-1].data_ptr(), n, ref.data_ptr(), st2.data_ptr(), raw_streams[-1])
         sync_all()
         assert torch.equal(ref, out[-1]), "group call != single-device call on the last member's share"
-    roof = roofline_object(wl, n, prof, members[0].window_bits, call_ms=1e3 * elapsed / args.steps)
+    roof = roofline_object(wl, n, prof, members[0].window_bits, call_ms=1e3 * elapsed / args.steps) if args.full else None
     if roof is not None:
         roof["scope"] = "member 0's kernels (one of %d members); achieved = algorithmic bytes of ONE member's share / its kernel time" % S
         roof = ordered_roofline(roof)
@@ -1162,10 +1224,11 @@ def run_group(args):
                    "table_gib_per_member": members[0].table_bytes / 2**30, "plane_groups": members[0].plane_groups, "setup_s": t_setup,
                    "parallelism": "blob-sharded x%d inside one process behind the C ABI: no collective; verify: the members' 32-B roots seed one challenge, 192-B partial sums, "
                                   "one pairing" % S},
-        "roofline": roof,
         "cpu_baseline": None,
         "note": "cpu_baseline and the live PMC passes belong to the default single-GPU run (python bench.py); this mode measures the group path",
     }
+    if args.full:
+        result["roofline"] = roof
     print(json.dumps(result), flush=True)
     setup.close()
 

@@ -1451,7 +1451,7 @@ def test_bench_rank_launcher_two_real_engine_ranks_on_one_card(workload):
 
     logdir = tempfile.mkdtemp(prefix="bench_ranks_")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", workload, "--batch", "96", "--window-bits", "8",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--rank-logs", logdir]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra", "--rank-logs", logdir]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
@@ -1485,7 +1485,7 @@ def test_bench_rccl_calls_with_a_one_rank_group(workload):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dist-single", "--backend", "nccl", "--workload", workload, "--batch", "256",
-           "--window-bits", "8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--no-live-traffic"]
+           "--window-bits", "8", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra", "--no-live-traffic"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
@@ -1511,6 +1511,42 @@ def test_bench_launcher_single_rank_matches_the_direct_run():
         assert rec["n_gpus"] == 1 and rec["config"]["blobs_per_gpu"] == 1024
         vals[name] = rec["value"]
     assert abs(vals["spawn"] / vals["direct"] - 1.0) < 0.10, vals
+
+
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    """a plain `bench.py` run (no --full) prints the headline fields without the --full figures and runs exactly --warmup +
+    --steps commitment calls: counted as dispatches of the fixed-base MSM kernel (one per call at 96 blobs) in a rocprofv3
+    kernel trace of the run; --dump-outputs writes the last step's commitments and status codes, the golden blobs' among them"""
+    import csv
+    import glob
+    import re
+    import shutil
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+    dump, trace = tmp_path / "dump", tmp_path / "trace"
+    warmup, steps = 2, 5
+    cmd = [prof, "--kernel-trace", "--output-format", "csv", "-d", str(trace), "--", sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+           "--batch", "96", "--window-bits", "8", "--blocking-setup", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(dump)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    rec = json.loads([ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")][-1])
+    assert rec["steps"] == steps and rec["warmup"] == warmup and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["unit"] == "blobs/s"
+    assert not {"roofline", "cpu_baseline", "extra"} & set(rec)
+    names = [row["Kernel_Name"] for f in glob.glob(str(trace / "**" / "*kernel_trace.csv"), recursive=True) for row in csv.DictReader(open(f))]
+    msm = [k for k in names if re.search(r"\bk_msm_comb30\b", k)]
+    assert len(msm) == warmup + steps, (len(msm), len(names))
+    assert sorted(os.listdir(dump)) == ["commitments.npy", "status.npy"]
+    com, status = np.load(dump / "commitments.npy"), np.load(dump / "status.npy")
+    assert com.dtype == np.float32 and com.shape == (96, 48) and status.shape == (96,) and not status.any()
+    golden = json.load(open(os.path.join(root, "tests", "golden", "kzg_vectors.json")))
+    for b in golden["blobs"]:
+        assert bytes(com[b["index"]].astype(np.uint8)).hex() == b["commitment"]
 
 
 def test_latency_comb_of_the_class_22_table(engine, torch_cuda, monkeypatch):

@@ -6,9 +6,9 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/cohash
 mkdir -p $OUT
 for rep in 1 2; do
-  python3 $R/bench.py --workload verify --steps 5 --warmup 2 --no-cpu-baseline --no-live-traffic > $OUT/default_$rep.json 2>> $OUT/err.log || exit 1
+  python3 $R/bench.py --full --workload verify --steps 5 --warmup 2 --no-cpu-baseline --no-live-traffic > $OUT/default_$rep.json 2>> $OUT/err.log || exit 1
   for s in 20 18 22; do
-    KATETH_AMD_VERIFY_COHASH=$s python3 $R/bench.py --workload verify --steps 5 --warmup 2 --no-cpu-baseline --no-live-traffic > $OUT/cohash${s}_$rep.json 2>> $OUT/err.log || exit 1
+    KATETH_AMD_VERIFY_COHASH=$s python3 $R/bench.py --full --workload verify --steps 5 --warmup 2 --no-cpu-baseline --no-live-traffic > $OUT/cohash${s}_$rep.json 2>> $OUT/err.log || exit 1
   done
 done
 # (the parity test ran with the knob set at the experiment commit)

@@ -16,7 +16,7 @@ run() {  # name, rocprof args..., -- bench args
   echo "[profile] $name" >&2
   rocprofv3 "$@" > $OUT/$name.log 2>&1 || { tail -5 $OUT/$name.log; exit 1; }
 }
-B="--no-cpu-baseline --no-live-traffic --blocking-setup"
+B="--no-cpu-baseline --no-live-traffic --blocking-setup --full"
 if [ -z "$PMC_ONLY" ]; then
 run trace_default --kernel-trace --stats --output-format csv -d $OUT/trace_default -- python3 $R/bench.py --steps 10 --warmup 2 $B
 run trace_commit --kernel-trace --stats --output-format csv -d $OUT/trace_commit -- python3 $R/bench.py --steps 10 --warmup 2 --no-extra $B

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r05
 mkdir -p $O
 cd $R
-B="--no-extra --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic --blocking-setup"
+B="--no-extra --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic --blocking-setup --full"
 : > $O/fairsweep.txt
 for rep in 1 2; do
 for F in 20 17 18 19 21 22 23; do

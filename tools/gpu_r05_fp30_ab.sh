@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r05
 mkdir -p $O
 cd $R
-B="--no-extra --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic --blocking-setup"
+B="--no-extra --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic --blocking-setup --full"
 for rep in 1 2; do
   python bench.py $B > $O/ab_commit_fp30_$rep.json 2>> $O/ab.err
   KATETH_AMD_LIB=$R/tools/exp/ab/libkateth_amd_fp28.so python bench.py $B > $O/ab_commit_fp28_$rep.json 2>> $O/ab.err

@@ -9,10 +9,10 @@ cd $R
 timeout -k 10 400 python -m pytest tests/test_gpu_parity.py tests/test_gpu_round4.py tests/test_gpu_round5.py -x -q -m gpu -k "variable_base or verify or group_dev or workspace" > $O/glv_tests.log 2>&1
 echo "pytest rc=$?" >> $O/glv_tests.log
 tail -3 $O/glv_tests.log
-B="--workload verify --steps 20 --warmup 4 --no-cpu-baseline --no-live-traffic --window-bits 16"
+B="--workload verify --steps 20 --warmup 4 --no-cpu-baseline --no-live-traffic --window-bits 16 --full"
 for rep in 1 2; do
   python bench.py $B > $O/glv_on_$rep.json 2>> $O/glv.err
   KATETH_AMD_VAR_GLV=0 python bench.py $B > $O/glv_off_$rep.json 2>> $O/glv.err
 done
-python bench.py --workload proof --steps 10 --warmup 3 --no-cpu-baseline --no-live-traffic > $O/proof_after_slot_fix.json 2>> $O/glv.err
+python bench.py --full --workload proof --steps 10 --warmup 3 --no-cpu-baseline --no-live-traffic > $O/proof_after_slot_fix.json 2>> $O/glv.err
 echo glv done

@@ -8,8 +8,8 @@ O=$R/gpurun_out/r05
 mkdir -p $O
 cd $R
 for rep in 1 2; do
-  python bench.py --workload verify --steps 20 --warmup 4 --no-cpu-baseline --no-live-traffic --window-bits 16 > $O/host_tail_verify_mulx_$rep.json 2>> $O/host_tail.err
-  KATETH_AMD_HOST_FP=portable python bench.py --workload verify --steps 20 --warmup 4 --no-cpu-baseline --no-live-traffic --window-bits 16 > $O/host_tail_verify_portable_$rep.json 2>> $O/host_tail.err
+  python bench.py --full --workload verify --steps 20 --warmup 4 --no-cpu-baseline --no-live-traffic --window-bits 16 > $O/host_tail_verify_mulx_$rep.json 2>> $O/host_tail.err
+  KATETH_AMD_HOST_FP=portable python bench.py --full --workload verify --steps 20 --warmup 4 --no-cpu-baseline --no-live-traffic --window-bits 16 > $O/host_tail_verify_portable_$rep.json 2>> $O/host_tail.err
 done
 python tools/bench_criterion.py 16 --no-cpu > $O/host_tail_criterion_mulx.json 2>> $O/host_tail.err
 KATETH_AMD_HOST_FP=portable python tools/bench_criterion.py 16 --no-cpu > $O/host_tail_criterion_portable.json 2>> $O/host_tail.err

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r05
 mkdir -p $O
 cd $R
-B="--workload verify --steps 12 --warmup 3 --no-cpu-baseline --no-live-traffic --blocking-setup --no-extra"
+B="--workload verify --steps 12 --warmup 3 --no-cpu-baseline --no-live-traffic --blocking-setup --no-extra --full"
 for rep in 1 2; do
   python bench.py $B > $O/seg_verify_seg_$rep.json 2>> $O/seg.err
   KATETH_AMD_VAR_SEG=0 python bench.py $B > $O/seg_verify_perbucket_$rep.json 2>> $O/seg.err

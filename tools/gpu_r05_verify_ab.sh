@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r05
 mkdir -p $O
 cd $R
-B="--workload verify --steps 12 --warmup 3 --no-cpu-baseline --no-live-traffic --blocking-setup --no-extra"
+B="--workload verify --steps 12 --warmup 3 --no-cpu-baseline --no-live-traffic --blocking-setup --no-extra --full"
 for rep in 1 2 3; do
   python bench.py $B > $O/vab_new_$rep.json 2>> $O/vab.err
   KATETH_AMD_LIB=$R/tools/exp/ab/libkateth_amd_prev.so python bench.py $B > $O/vab_old_$rep.json 2>> $O/vab.err

@@ -10,7 +10,7 @@ first=1
 for wl in commit proof; do
   for b in 512 1024 2048 4096 8192; do
     for f in 1 2; do
-      line=$(python bench.py --workload $wl --batch $b --in-flight $f --steps 16 --warmup 4 --no-cpu-baseline --no-live-traffic --no-extra --blocking-setup 2>/dev/null | tail -1 | python -c "import sys,json; r=json.loads(sys.stdin.read()); print(json.dumps({'workload':'$wl','batch':$b,'in_flight':$f,'blobs_per_s':r['value'],'ms_per_step':r['ms_per_step']}))")
+      line=$(python bench.py --full --workload $wl --batch $b --in-flight $f --steps 16 --warmup 4 --no-cpu-baseline --no-live-traffic --no-extra --blocking-setup 2>/dev/null | tail -1 | python -c "import sys,json; r=json.loads(sys.stdin.read()); print(json.dumps({'workload':'$wl','batch':$b,'in_flight':$f,'blobs_per_s':r['value'],'ms_per_step':r['ms_per_step']}))")
       [ $first -eq 1 ] || echo "," >> $O/rate_vs_batch_in_flight.json
       first=0
       echo "$line" >> $O/rate_vs_batch_in_flight.json
