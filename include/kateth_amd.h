@@ -265,6 +265,35 @@ int32_t kzg_verify_blob_proof(const kzg_ctx* ctx, const uint8_t* blob, const uin
 int32_t kzg_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok);
 
 /*
+ * Setup::verify_proof for n (proof, commitment, z, y) tuples in one call: the reference's private Setup::verify_proof_batch
+ * (src/kzg/setup.rs:115-161) behind verify_proof's parsing (src/kzg/setup.rs:103-109), for callers that hold openings but
+ * no blobs.  Argument order as kzg_verify_proof; every array has n items, contiguous: 48 bytes per point, 32 bytes big-endian
+ * per scalar.  Device pointers (*_dev) are resident on ctx's device, z and y 16-byte aligned; the calls are synchronous like
+ * kzg_verify_blob_proof_batch_dev (they return the boolean); hip_stream = NULL is the default stream.
+ *   *ok = 1  iff  e(sum r^i proof_i, [tau]_2) == e(sum r^i (commitment_i - [y_i]G) + sum r^i z_i proof_i, G2)
+ *            (src/kzg/setup.rs:151-160), r being the ENGINE's challenge: bound to every input through the transcript tree of the
+ *            blob batch (leaf = H(commitment || z || y || proof)), powers r^0 .. r^(n-1) over GLOBAL indices -- the deviations
+ *            Q1 / Q2 from the reference that kzg_verify_blob_proof_batch documents.  Hence: true iff every tuple passes
+ *            kzg_verify_proof (up to the 2^-255 soundness error of the random combination).
+ *   n == 0   *ok = 1 (as kzg_verify_blob_proof_batch).  n == 1: exactly kzg_verify_proof's boolean and code.
+ *   rejected inputs: the positive KZG_ERR_* code of the FIRST rejected input, *ok = 0.  First = verify_proof's parse order
+ *            (proof, commitment, point, evaluation) lifted to arrays the way verify_blob_proof_batch lifts its own
+ *            (src/kzg/setup.rs:259-271): every proof before any commitment, every commitment before any z, every z before any
+ *            y; the lowest index within the first kind that has an error.  z or y >= r: KZG_ERR_FF_NOT_IN_FIELD; points:
+ *            KZG_ERR_EC_* as kzg_g1_decompress_batch reports them.  The length checks of the reference stay in the caller.
+ * On a GROUP context the host-buffer call cuts the batch into contiguous shares, one per member, like
+ * kzg_verify_blob_proof_batch; kzg_verify_proof_batch_group_dev takes member k's share resident on member k's GPU (arrays of
+ * kzg_ctx_members(ctx) entries, global order = member order, n_local[k] may be 0) like kzg_verify_blob_proof_batch_group_dev.
+ * One share is exactly the single-device call; several shares seed r with all their roots: same boolean, same code.
+ */
+int32_t kzg_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                               int32_t* ok);
+int32_t kzg_verify_proof_batch_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32, uint64_t n,
+                                   int32_t* ok, void* hip_stream);
+int32_t kzg_verify_proof_batch_group_dev(const kzg_ctx* ctx, const void* const* d_proofs48, const void* const* d_commitments48, const void* const* d_z32,
+                                         const void* const* d_y32, const uint64_t* n_local, int32_t* ok, void* const* hip_streams);
+
+/*
  * DEVICE-RESIDENT sharded calls on a GROUP context (kzg_config.devices / ndev): member k's share of the batch is resident on
  * member k's GPU -- what a node keeps when blobs arrive over the network or are produced on the devices, and the only way a
  * group verifies faster than PCIe delivers (host-buffer verification tops out near 0.37 M blobs/s per GPU, device-resident
@@ -318,6 +347,16 @@ void kzg_verify_session_destroy(kzg_verify_session* session);
  * y_i (Polynomial::evaluate, src/kzg/poly.rs:10-33) phase 1 computed for items [first, first+count), 32 B big-endian each */
 int32_t kzg_verify_session_zy(kzg_verify_session* session, uint64_t first, uint64_t count, uint8_t* out_z32, uint8_t* out_y32);
 int32_t kzg_verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint64_t world, int32_t* ok);
+/*
+ * Phase 1 of kzg_verify_proof_batch for a rank's n_local tuples (z and y from the caller instead of the hash and the
+ * evaluation): err8 = {proof_idx, proof_code, commitment_idx, commitment_code, z_idx, z_code, y_idx, y_code}, LOCAL index of
+ * the first rejected input of each kind (-1 = none), found on the device.  The session is an ordinary kzg_verify_session:
+ * kzg_verify_phase2_dev, kzg_verify_session_zy (the parsed z_i, y_i; zero for a rejected one), kzg_verify_batch_finish and
+ * kzg_verify_session_destroy work on it unchanged, and its root is the one kzg_verify_phase1_dev returns for blobs whose
+ * challenges and evaluations are these z and y.
+ */
+int32_t kzg_verify_proof_phase1_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
+                                    uint64_t n_local, uint8_t* out_root32, int32_t* err8, kzg_verify_session** session, void* hip_stream);
 
 /*
  * Synthetic-input generator used by bench.py and the parity tests

@@ -287,6 +287,12 @@ int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
                            int32_t* err6, kzg_verify_session** session);  // engine_verify.hip
 int32_t verify_batch_host_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, int32_t* ok);
 int32_t verify_proof_single(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok);
+// Setup::verify_proof_batch over host buffers (engine_verify.hip): the whole call on one device, and its phase 1 alone (err8 = {proof, commitment, z, y} x {local
+// index, code}) for a group's shares
+int32_t verify_proof_batch_host_single(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                       int32_t* ok);
+int32_t verify_proof_phase1_host(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                 uint8_t* out_root32, int32_t* err8, kzg_verify_session** session);
 int32_t g1_decompress_single(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
 int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
 // engine_multi.hip
@@ -296,6 +302,8 @@ int32_t multi_proof(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* sid
                     uint8_t* out_affine96, uint8_t* out_y32, int32_t* status);
 int32_t multi_verify_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, int32_t* ok);
 int32_t multi_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok);
+int32_t multi_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                 int32_t* ok);
 int32_t multi_g1_decompress(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
 int32_t multi_evaluate_blobs(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
 // one member's device-resident share of a group verification (kzg_verify_blob_proof_batch_group_dev): global range [first, first + count)
@@ -306,6 +314,14 @@ struct GroupDevShare {
   hipStream_t st;
 };
 int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& shares, uint64_t n_total, int32_t* ok);  // engine_verify.hip
+// the same for kzg_verify_proof_batch_group_dev
+struct GroupDevPointsShare {
+  const kzg_ctx* member;
+  const uint8_t *proofs48, *commitments48, *z32, *y32;  // resident on member->device
+  uint64_t first, count;
+  hipStream_t st;
+};
+int32_t verify_points_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevPointsShare>& shares, uint64_t n_total, int32_t* ok);  // engine_verify.hip
 int32_t stage_init(const kzg_ctx* ctx);                                             // caller holds stage_lock
 int32_t stage_reserve(const kzg_ctx* ctx, size_t arena_bytes, size_t io_bytes);   // caller holds stage_lock
 void stage_destroy(const kzg_ctx* ctx);

@@ -14,6 +14,7 @@
 
 using kzg::multi::Share;
 using kzg::multi::merged_first_error;
+using kzg::multi::merged_first_error4;
 
 namespace {
 
@@ -150,6 +151,45 @@ int32_t multi_verify_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
   return kzg_verify_batch_finish(ctx, partials.data(), W, ok);
 }
 
+// Setup::verify_proof_batch (src/kzg/setup.rs:115-161) over the members, cut like multi_verify_batch: one share is exactly the
+// single-device call; several seed the challenge with all their roots (another r, the same boolean and first-error code).
+int32_t multi_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                 int32_t* ok) {
+  *ok = 0;
+  const std::vector<Share> shares = shares_of(ctx, n);
+  const uint32_t W = (uint32_t)shares.size();
+  if (W == 1) return verify_proof_batch_host_single(member_of(ctx, shares[0].member), proofs48, commitments48, z32, y32, n, ok);
+  std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
+  std::vector<int32_t> err8(8 * (size_t)W);
+  std::vector<kzg_verify_session*> sessions(W, nullptr);
+  auto release = [&]() {
+    const ErrorSnapshot keep = error_snapshot();
+    for (kzg_verify_session* s : sessions)
+      if (s) kzg_verify_session_destroy(s);
+    error_publish(keep);
+  };
+  int32_t rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
+    const Share& sh = shares[j];
+    return verify_proof_phase1_host(member_of(ctx, sh.member), proofs48 + sh.first * 48, commitments48 + sh.first * 48, z32 + sh.first * 32, y32 + sh.first * 32,
+                                    sh.count, roots.data() + 32 * (size_t)j, err8.data() + 8 * (size_t)j, &sessions[j]);
+  });
+  if (rc) {
+    release();
+    return rc;
+  }
+  const int32_t code = merged_first_error4(shares, err8.data());
+  if (code) {
+    release();
+    return code;
+  }
+  rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
+    return kzg_verify_phase2_dev(sessions[j], roots.data(), W, shares[j].first, n, partials.data() + 192 * (size_t)j);
+  });
+  release();
+  if (rc) return rc;
+  return kzg_verify_batch_finish(ctx, partials.data(), W, ok);
+}
+
 // ---- device-resident sharded calls (include/kateth_amd.h: kzg_*_group_dev) -------------------------------------------------
 // Member k's share is resident on member k's GPU.  Commitments and proofs only ENQUEUE (like the *_dev calls), one pooled host
 // thread per member so that the members' launches go out side by side; nothing is gathered -- results stay where they were
@@ -200,6 +240,26 @@ extern "C" int32_t kzg_verify_blob_proof_batch_group_dev(const kzg_ctx* ctx, con
     total += n_local[k];
   }
   return verify_group_dev(ctx, shares, total, ok);
+} catch (...) {
+  return abi_exception();
+}
+
+extern "C" int32_t kzg_verify_proof_batch_group_dev(const kzg_ctx* ctx, const void* const* d_proofs48, const void* const* d_commitments48,
+                                                    const void* const* d_z32, const void* const* d_y32, const uint64_t* n_local, int32_t* ok,
+                                                    void* const* hip_streams) try {
+  if (!ctx || !ok || !d_proofs48 || !d_commitments48 || !d_z32 || !d_y32 || !n_local) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  *ok = 0;
+  const uint32_t S = 1u + (uint32_t)ctx->peers.size();
+  std::vector<GroupDevPointsShare> shares;
+  uint64_t total = 0;
+  for (uint32_t k = 0; k < S; k++) {
+    if (n_local[k] == 0) continue;
+    if (!d_proofs48[k] || !d_commitments48[k] || !d_z32[k] || !d_y32[k]) return fail(KZG_FAIL_ARGUMENT, "null device pointer for a member with items");
+    shares.push_back(GroupDevPointsShare{member_of(ctx, k), (const uint8_t*)d_proofs48[k], (const uint8_t*)d_commitments48[k], (const uint8_t*)d_z32[k],
+                                         (const uint8_t*)d_y32[k], total, n_local[k], hip_streams ? (hipStream_t)hip_streams[k] : nullptr});
+    total += n_local[k];
+  }
+  return verify_points_group_dev(ctx, shares, total, ok);
 } catch (...) {
   return abi_exception();
 }

@@ -33,11 +33,13 @@ struct kzg_verify_session {
   bool glv = false;        // n >= 32,768: both lincombs on GLV-split scalars (use_glv)
   fr_t* glv_b = nullptr;   // [2 (2n+1)]: k1 | k2 of scal
   fr_t* glv_a = nullptr;   // [2n]: k1 | k2 of the r_i
-  int32_t* stat = nullptr;   // [3n] blob / commitment / proof status
+  int32_t* stat = nullptr;   // [4n] blob / commitment / proof status; verify_proof_batch: z / commitment / proof / y status
+  unsigned long long* first4 = nullptr;  // verify_proof_batch: (index << 32) | code of the first rejected proof, commitment, z, y (k_first_errors)
   uint32_t* leaves = nullptr;  // transcript: n leaves, ceil(n / 16) mid digests, ceil(n / 256) nodes
   uint32_t* mids = nullptr;
   uint32_t* nodes = nullptr;
   uint8_t* pts48 = nullptr;  // [2n * 48] device copy of proofs || commitments (host-buffer entry points)
+  uint8_t* zy32 = nullptr;   // [2n * 32] device copy of z || y as given (host-buffer verify_proof_batch)
   uint8_t* msm_a = nullptr;  // scratch of the two lincomb MSMs (carved from buf: no allocation in phase 2)
   uint8_t* msm_b = nullptr;
   fr_t* rpow2 = nullptr;     // [64] r^(2^k)
@@ -46,6 +48,7 @@ struct kzg_verify_session {
   // decoder still runs
   int32_t* h_stat = nullptr;    // [3n]
   uint32_t* h_nodes = nullptr;  // [ceil(n / 256) * 8]
+  unsigned long long* h_first4 = nullptr;  // [4] read-back of first4
   size_t h_cap = 0;
 };
 
@@ -393,7 +396,7 @@ static void scan_first_error(const int32_t* st, uint64_t n, int32_t* idx, int32_
 
 // ---- session set-up -----------------------------------------------------------------------------------------------
 struct SessionLayout {
-  size_t o_aff, o_inf, o_z, o_y, o_scal, o_glv_b, o_glv_a, o_stat, o_leaves, o_mids, o_nodes, o_pts, o_msm_a, o_msm_b, o_rpow, o_ysum, total;
+  size_t o_aff, o_inf, o_z, o_y, o_scal, o_glv_b, o_glv_a, o_stat, o_first4, o_leaves, o_mids, o_nodes, o_pts, o_zy, o_msm_a, o_msm_b, o_rpow, o_ysum, total;
 };
 static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n) {
   SessionLayout L{};
@@ -412,11 +415,13 @@ static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n) {
   L.o_scal = take((2 * n + 1) * 32);
   L.o_glv_b = take(glv ? 2 * (2 * n + 1) * 32 : 0);
   L.o_glv_a = take(glv ? 2 * n * 32 : 0);
-  L.o_stat = take(3 * n * 4 + 4);
+  L.o_stat = take(4 * n * 4 + 4);
+  L.o_first4 = take(4 * sizeof(unsigned long long));
   L.o_leaves = take(n * 32 + 32);
   L.o_mids = take((n / 16 + 1) * 32 + 32);
   L.o_nodes = take(groups * 32 + 32);
   L.o_pts = take(2 * n * 48 + 48);
+  L.o_zy = take(2 * n * 32 + 32);
   L.o_msm_a = take((glv ? msm_var_layout(ctx, 2 * n, true) : msm_var_layout(ctx, n, false, 3 * n + 1)).total + 256);
   L.o_msm_b = take((glv ? msm_var_layout(ctx, 2 * (2 * n + 1), true) : msm_var_layout(ctx, 2 * n + 1, false, 3 * n + 1)).total + 256);
   L.o_rpow = take(64 * 32);
@@ -479,7 +484,7 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
     s->cap = want;
   }
   {
-    const size_t hneed = (3 * n + 1) * sizeof(int32_t) + ((n + 255) / 256 + 1) * 32;
+    const size_t hneed = 4 * sizeof(unsigned long long) + (3 * n + 1) * sizeof(int32_t) + ((n + 255) / 256 + 1) * 32;
     if (s->h_cap < hneed) {
       if (s->h_stat) (void)hipHostFree(s->h_stat);
       s->h_stat = nullptr;
@@ -493,6 +498,7 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
       s->h_cap = hneed + hneed / 8;
     }
     s->h_nodes = reinterpret_cast<uint32_t*>(s->h_stat + (3 * n + 1));
+    s->h_first4 = reinterpret_cast<unsigned long long*>(reinterpret_cast<uint8_t*>(s->h_stat) + align_up((3 * n + 1) * sizeof(int32_t) + ((n + 255) / 256) * 32, 8));
   }
   if (st == KZG_SESSION_STREAM) st = s->side;
   s->n = n;
@@ -506,10 +512,12 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
   s->glv_b = (fr_t*)(s->buf + L.o_glv_b);
   s->glv_a = (fr_t*)(s->buf + L.o_glv_a);
   s->stat = (int32_t*)(s->buf + L.o_stat);
+  s->first4 = (unsigned long long*)(s->buf + L.o_first4);
   s->leaves = (uint32_t*)(s->buf + L.o_leaves);
   s->mids = (uint32_t*)(s->buf + L.o_mids);
   s->nodes = (uint32_t*)(s->buf + L.o_nodes);
   s->pts48 = s->buf + L.o_pts;
+  s->zy32 = s->buf + L.o_zy;
   s->msm_a = s->buf + L.o_msm_a;
   s->msm_b = s->buf + L.o_msm_b;
   s->rpow2 = (fr_t*)(s->buf + L.o_rpow);
@@ -517,7 +525,7 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
   // generator term, cleared flags and statuses
   if (hipMemcpyAsync(s->aff + (2 * n) * 6, ctx->d_gen_affine, 96, hipMemcpyDeviceToDevice, st) != hipSuccess ||
       (s->glv && hipMemcpyAsync(s->aff + ((2 * n + 1) + 2 * n) * 6, ctx->d_gen_affine + 6, 96, hipMemcpyDeviceToDevice, st) != hipSuccess) ||  // [z^2]G
-      hipMemsetAsync(s->inf, 0, 2 * n + 1, st) != hipSuccess || hipMemsetAsync(s->stat, 0, 3 * n * 4 + 4, st) != hipSuccess) {
+      hipMemsetAsync(s->inf, 0, 2 * n + 1, st) != hipSuccess || hipMemsetAsync(s->stat, 0, 4 * n * 4 + 4, st) != hipSuccess) {
     kzg_verify_session_destroy(s);
     return fail(KZG_FAIL_HIP, "verify session init failed");
   }
@@ -1528,6 +1536,286 @@ int32_t verify_proof_single(const kzg_ctx* ctx, const uint8_t* proof48, const ui
   if (rc) return rc;
   return kzg_verify_batch_finish(ctx, partial, 1, ok);
 }
+
+// ---- Setup::verify_proof_batch (src/kzg/setup.rs:115-161) as a public batch call: n caller-supplied (proof, commitment, z, y) -------
+// Phase 2 is the blob batch's; phase 1 has neither hash nor evaluation: [decoder for all 2n points, proofs first, on the session's side
+// stream] || k_points_leaves -> k_transcript_nodes x 2 -> root.  The statuses of the four kinds live in the session's four
+// arrays -- z takes the blob slot, y the fourth -- and never cross to the host: k_first_errors runs behind the decoder on its
+// stream and 32 bytes come back.
+static void err8_clear(int32_t* err8) {
+  for (int k = 0; k < 8; k++) err8[k] = (k % 2 == 0) ? -1 : 0;
+}
+// verify_proof's parse order lifted to arrays (src/kzg/setup.rs:103-109 the way :259-271 lifts the blob call's): proofs,
+// commitments, points, evaluations
+static int32_t first_error_code4(const int32_t* err8) {
+  for (int k = 0; k < 8; k += 2)
+    if (err8[k] >= 0) return err8[k + 1];
+  return 0;
+}
+// (a) everything of phase 1 that can be enqueued at once; the node digests are on their way back when this returns
+static int32_t points_front(kzg_verify_session* s, const uint8_t* prf, const uint8_t* com, const uint8_t* z32, const uint8_t* y32) {
+  const kzg_ctx* ctx = s->ctx;
+  const uint64_t n = s->n;
+  hipStream_t st = s->st, side = s->side;
+  if (hipEventRecord(s->ev_fork, st) != hipSuccess || hipStreamWaitEvent(side, s->ev_fork, 0) != hipSuccess ||  // session initialised, inputs resident
+      hipMemsetAsync(s->first4, 0xff, 4 * sizeof(unsigned long long), side) != hipSuccess)
+    return fail(KZG_FAIL_HIP, "verify_proof_batch: fork failed");
+  {
+    ProfScope ps(ctx, PROF_DECODE, side);
+    if (fused_prep_fits(ctx, n, 2 * n))
+      launch_g1_decompress(side, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
+    else
+      launch_g1_decompress_range(side, (uint64_t)0, 2 * n, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
+  }
+  if (s->glv) hipLaunchKernelGGL(k_glv_points, dim3(blocks_for(2 * n, 64)), dim3(64), 0, side, s->aff, 2 * n, 2 * n + 1);
+  (void)hipEventRecord(s->ev_join, side);
+  const uint64_t groups = (n + 255) / 256, nmid = (n + 15) / 16;
+  hipLaunchKernelGGL(k_points_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, prf, z32, y32, n, s->z, s->y, s->stat, s->stat + 3 * n, s->leaves);
+  hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(nmid, 64)), dim3(64), 0, st, s->leaves, n, 16u, s->mids);
+  hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(groups, 64)), dim3(64), 0, st, s->mids, nmid, 16u, s->nodes);
+  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: phase 1 launch failed");
+  if (hipMemcpyAsync(s->h_nodes, s->nodes, groups * 32, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(s->ev_nodes, st) != hipSuccess)
+    return fail(KZG_FAIL_HIP, "verify_proof_batch: phase 1 readback failed");
+  return 0;
+}
+// (b) the first rejected item of each kind, behind the decoder on its stream (which also waits for k_points_leaves' two status
+//     arrays: ev_nodes was recorded after it).  err8 = {proof, commitment, z, y} x {local index, code}
+static int32_t points_status(kzg_verify_session* s, int32_t* err8) {
+  const uint64_t n = s->n;
+  hipStream_t side = s->side;
+  if (hipStreamWaitEvent(side, s->ev_nodes, 0) != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: status wait failed");
+  hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(n, 256)), dim3(256), 0, side, s->stat + 2 * n, s->stat + n, s->stat, s->stat + 3 * n, n, s->first4);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(s->h_first4, s->first4, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, side) != hipSuccess ||
+      hipEventRecord(s->ev_stat, side) != hipSuccess || hipEventSynchronize(s->ev_stat) != hipSuccess)
+    return fail(KZG_FAIL_HIP, "verify_proof_batch: status readback failed");
+  for (int k = 0; k < 4; k++) {
+    const unsigned long long w = s->h_first4[k];
+    err8[2 * k] = w == ~0ull ? -1 : (int32_t)(w >> 32);
+    err8[2 * k + 1] = w == ~0ull ? 0 : (int32_t)(uint32_t)w;
+  }
+  return 0;
+}
+static void points_drain(kzg_verify_session* s, Phase2* p2) {  // before a session with work enqueued goes back to the pool
+  (void)hipStreamSynchronize(s->st);
+  (void)hipStreamSynchronize(s->aux);
+  (void)hipStreamSynchronize(s->side);
+  if (p2 && p2->ja.owns_buf && p2->ja.buf) (void)hipFree(p2->ja.buf);
+  if (p2 && p2->jb.owns_buf && p2->jb.buf) (void)hipFree(p2->jb.buf);
+}
+
+// The single-context call.  As in verify_fused, the root, r, the scalars and both sorts are enqueued while the decoder runs, the
+// bucket kernels wait for it (both lincombs on ev_join: the decoder is ONE launch over proofs and commitments, so there is no
+// event after the proof half for lincomb A to wait on instead), and a rejected input wins over the sums.
+static int32_t verify_points_fused(kzg_verify_session* s, const uint8_t* prf, const uint8_t* com, const uint8_t* z32, const uint8_t* y32, int32_t* ok) {
+  const kzg_ctx* ctx = s->ctx;
+  TraceTimer tt(ctx->knobs.trace, "verify_proof_batch (fused phases)");
+  uint8_t root[32];
+  int32_t err8[8];
+  err8_clear(err8);
+  Phase2 p2;
+  int32_t rc = points_front(s, prf, com, z32, y32);
+  if (rc == 0) rc = p1_root(s, root);
+  tt.mark("parse + transcript, root");
+  if (rc == 0) rc = p2_scalars(s, root, 1, 0, s->n);
+  if (rc == 0) rc = p2_sort(s, p2, true);
+  if (rc == 0) rc = p2_accumulate(s, p2);
+  if (rc == 0) rc = points_status(s, err8);
+  tt.mark("decoder done, first errors");
+  const int32_t code = rc == 0 ? first_error_code4(err8) : 0;
+  if (rc == 0 && code == 0) rc = p2_finish_and_pair(s, p2, ok);
+  tt.mark("lincombs + host horner + pairing");
+  if (rc || code) {
+    points_drain(s, &p2);
+    return rc ? rc : code;
+  }
+  return 0;
+}
+
+static int32_t points_phase1(kzg_verify_session* s, const uint8_t* prf, const uint8_t* com, const uint8_t* z32, const uint8_t* y32, uint8_t* out_root32,
+                             int32_t* err8) {
+  int32_t rc = points_front(s, prf, com, z32, y32);
+  if (rc == 0) rc = p1_root(s, out_root32);
+  if (rc == 0) rc = points_status(s, err8);
+  return rc;
+}
+
+extern "C" int32_t kzg_verify_proof_phase1_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
+                                               uint64_t n, uint8_t* out_root32, int32_t* err8, kzg_verify_session** session, void* hip_stream) try {
+  if (!ctx || !out_root32 || !err8 || !session || (n && (!d_proofs48 || !d_commitments48 || !d_z32 || !d_y32)))
+    return fail(KZG_FAIL_ARGUMENT, "null argument");
+  *session = nullptr;
+  HIP_TRY(hipSetDevice(ctx->device));
+  err8_clear(err8);
+  kzg_verify_session* s = nullptr;
+  int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
+  if (rc) return rc;
+  if (n) {
+    rc = points_phase1(s, (const uint8_t*)d_proofs48, (const uint8_t*)d_commitments48, (const uint8_t*)d_z32, (const uint8_t*)d_y32, out_root32, err8);
+    if (rc) points_drain(s, nullptr);
+  } else {
+    sha256_bytes(out_root32, nullptr, 0);
+    if (hipStreamSynchronize(s->st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "verify phase 1 synchronize failed");
+  }
+  if (rc) {
+    kzg_verify_session_destroy(s);
+    return rc;
+  }
+  *session = s;
+  return 0;
+} catch (...) {
+  return abi_exception();
+}
+
+extern "C" int32_t kzg_verify_proof_batch_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
+                                              uint64_t n, int32_t* ok, void* hip_stream) try {
+  if (!ctx || !ok || (n && (!d_proofs48 || !d_commitments48 || !d_z32 || !d_y32))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  *ok = 0;
+  if (n == 0) {  // as kzg_verify_blob_proof_batch: the empty batch verifies
+    *ok = 1;
+    return 0;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  kzg_verify_session* s = nullptr;
+  int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
+  if (rc) return rc;
+  rc = verify_points_fused(s, (const uint8_t*)d_proofs48, (const uint8_t*)d_commitments48, (const uint8_t*)d_z32, (const uint8_t*)d_y32, ok);
+  kzg_verify_session_destroy(s);
+  return rc;
+} catch (...) {
+  return abi_exception();
+}
+
+// Host buffers: 160 bytes per tuple cross PCIe whole into the session's own staging (proofs || commitments, z || y) on the
+// context's verification stream; nothing of the blob calls' staging arena is used, so stage_lock is held for stage_init only.
+static int32_t points_stage_host(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                 kzg_verify_session** out) {
+  *out = nullptr;
+  {
+    std::lock_guard<std::mutex> guard(ctx->stage_lock);
+    const int32_t rc = stage_init(ctx);
+    if (rc) return rc;
+  }
+  kzg_verify_session* s = nullptr;
+  int32_t rc = session_acquire(ctx, n, ctx->verify_stream, &s);
+  if (rc) return rc;
+  if (hipMemcpyAsync(s->pts48, proofs48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+      hipMemcpyAsync(s->pts48 + n * 48, commitments48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+      hipMemcpyAsync(s->zy32, z32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+      hipMemcpyAsync(s->zy32 + n * 32, y32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess) {
+    points_drain(s, nullptr);
+    kzg_verify_session_destroy(s);
+    return fail(KZG_FAIL_HIP, "host-to-device copy failed");
+  }
+  *out = s;
+  return 0;
+}
+int32_t verify_proof_phase1_host(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                 uint8_t* out_root32, int32_t* err8, kzg_verify_session** session) {
+  *session = nullptr;
+  err8_clear(err8);
+  HIP_TRY(hipSetDevice(ctx->device));
+  kzg_verify_session* s = nullptr;
+  int32_t rc = points_stage_host(ctx, proofs48, commitments48, z32, y32, n, &s);
+  if (rc) return rc;
+  rc = points_phase1(s, s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32, out_root32, err8);
+  if (rc) {
+    points_drain(s, nullptr);
+    kzg_verify_session_destroy(s);
+    return rc;
+  }
+  *session = s;
+  return 0;
+}
+int32_t verify_proof_batch_host_single(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32,
+                                       uint64_t n, int32_t* ok) {
+  *ok = 0;
+  if (n == 1) return verify_proof_single(ctx, proofs48, commitments48, z32, y32, ok);  // one tuple: the lincombs on the host (verify_one_on_host)
+  HIP_TRY(hipSetDevice(ctx->device));
+  kzg_verify_session* s = nullptr;
+  int32_t rc = points_stage_host(ctx, proofs48, commitments48, z32, y32, n, &s);
+  if (rc) return rc;
+  rc = verify_points_fused(s, s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32, ok);
+  kzg_verify_session_destroy(s);
+  return rc;
+}
+extern "C" int32_t kzg_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32,
+                                          uint64_t n, int32_t* ok) try {
+  if (!ctx || !ok || (n && (!proofs48 || !commitments48 || !z32 || !y32))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  *ok = 0;
+  if (n == 0) {
+    *ok = 1;
+    return 0;
+  }
+  return (is_group(ctx) ? multi_verify_proof_batch : verify_proof_batch_host_single)(ctx, proofs48, commitments48, z32, y32, n, ok);
+} catch (...) {
+  return abi_exception();
+}
+
+// Device-resident shares of a group context: verify_group_dev's two rounds with the points front instead of hash and evaluation.
+int32_t verify_points_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevPointsShare>& shares, uint64_t n_total, int32_t* ok) {
+  *ok = 0;
+  const uint32_t W = (uint32_t)shares.size();
+  if (W == 0) {
+    *ok = 1;
+    return 0;
+  }
+  if (W == 1)  // one share: exactly the single-device call (one root seeds the challenge)
+    return kzg_verify_proof_batch_dev(shares[0].member, shares[0].proofs48, shares[0].commitments48, shares[0].z32, shares[0].y32, shares[0].count, ok, shares[0].st);
+  TraceTimer tt(ctx->knobs.trace, "group verify_proof_batch (device-resident)");
+  std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
+  std::vector<int32_t> err8(8 * (size_t)W);
+  for (uint32_t j = 0; j < W; j++) err8_clear(err8.data() + 8 * (size_t)j);
+  std::vector<kzg_verify_session*> sessions(W, nullptr);
+  auto release = [&]() {
+    const ErrorSnapshot keep = error_snapshot();
+    for (kzg_verify_session* s : sessions)
+      if (s) kzg_verify_session_destroy(s);
+    error_publish(keep);
+  };
+  int32_t rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
+    const GroupDevPointsShare& sh = shares[j];
+    if (hipSetDevice(sh.member->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
+    int32_t r = session_acquire(sh.member, sh.count, sh.st, &sessions[j]);
+    if (r) return r;
+    kzg_verify_session* s = sessions[j];
+    r = points_front(s, sh.proofs48, sh.commitments48, sh.z32, sh.y32);
+    if (r == 0) r = p1_root(s, roots.data() + 32 * (size_t)j);
+    return r;
+  });
+  tt.mark("round 1: parse, transcript, roots (decoders still running)");
+  if (rc) {
+    for (uint32_t j = 0; j < W; j++)  // drain the members that did enqueue before their sessions go back to the pools
+      if (sessions[j] && hipSetDevice(shares[j].member->device) == hipSuccess) points_drain(sessions[j], nullptr);
+    release();
+    return rc;
+  }
+  std::vector<int32_t> codes(W, 0);
+  rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
+    const GroupDevPointsShare& sh = shares[j];
+    kzg_verify_session* s = sessions[j];
+    if (hipSetDevice(sh.member->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
+    Phase2 p2;
+    int32_t r = p2_scalars(s, roots.data(), W, sh.first, n_total);
+    if (r == 0) r = p2_sort(s, p2, true);
+    if (r == 0) r = p2_accumulate(s, p2);
+    if (r == 0) r = points_status(s, err8.data() + 8 * (size_t)j);
+    if (r == 0) codes[j] = first_error_code4(err8.data() + 8 * (size_t)j);
+    if (r == 0 && codes[j] == 0) r = p2_finish(s, p2, partials.data() + 192 * (size_t)j);
+    if (r || codes[j]) points_drain(s, &p2);  // a rejected input's sums are discarded
+    return r;
+  });
+  tt.mark("round 2: scalars, lincombs, first errors, partial sums");
+  release();
+  if (rc) return rc;
+  std::vector<kzg::multi::Share> ms(W);
+  for (uint32_t j = 0; j < W; j++) ms[j] = kzg::multi::Share{j, shares[j].first, shares[j].count};
+  const int32_t code = kzg::multi::merged_first_error4(ms, err8.data());
+  if (code) return code;
+  rc = kzg_verify_batch_finish(ctx, partials.data(), W, ok);
+  tt.mark("sum of partials + pairing");
+  return rc;
+}
+
 
 void warm_code_object_verify() {
   hipFuncAttributes a;

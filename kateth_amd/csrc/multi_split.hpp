@@ -53,5 +53,26 @@ inline int32_t merged_first_error(const std::vector<Share>& shares, const int32_
   return 0;
 }
 
+// The same rule over the FOUR kinds of Setup::verify_proof_batch, in verify_proof's parse order (src/kzg/setup.rs:103-109: proof,
+// commitment, point, evaluation -- every proof before any commitment, and so on): err8 = {proof_idx, proof_code, commitment_idx,
+// commitment_code, z_idx, z_code, y_idx, y_code} per share, LOCAL indices (-1 = none).
+inline int32_t merged_first_error4(const std::vector<Share>& shares, const int32_t* err8) {
+  for (int kind = 0; kind < 8; kind += 2) {
+    int32_t code = 0;
+    uint64_t best = ~(uint64_t)0;
+    for (size_t j = 0; j < shares.size(); j++) {
+      const int32_t local = err8[8 * j + kind];
+      if (local < 0) continue;
+      const uint64_t g = shares[j].first + (uint64_t)local;
+      if (g < best) {
+        best = g;
+        code = err8[8 * j + kind + 1];
+      }
+    }
+    if (code) return code;
+  }
+  return 0;
+}
+
 }  // namespace multi
 }  // namespace kzg

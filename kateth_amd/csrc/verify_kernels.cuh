@@ -368,6 +368,118 @@ static __global__ __launch_bounds__(256, 8) void k_transcript_leaves(const uint8
   for (int q = 0; q < 8; q++) leaves[i * 8 + q] = s.h[q];
 }
 
+// sha256_block for a kernel that must stay small: rounds 16..63 are a ROLLED loop of three passes over sixteen unrolled rounds (the
+// schedule's rotating indices stay compile-time constants, the round constants come from a table by scalar loads), so the compiler
+// cannot expand schedule words many rounds ahead of the compression chain -- with all 64 rounds of three blocks unrolled into one
+// basic block it did, and k_transcript_leaves pays for its 64 registers with scratch.  `w` is consumed.
+__device__ __forceinline__ void sha256_block_rolled(sha256_state& s, uint32_t (&w)[16]) {
+  static constexpr uint32_t K[64] = {
+      0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
+      0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
+      0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
+      0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
+      0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
+      0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
+      0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
+      0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
+  uint32_t a = s.h[0], b = s.h[1], c = s.h[2], d = s.h[3];
+  uint32_t e = s.h[4], f = s.h[5], g = s.h[6], h = s.h[7];
+  auto round = [&](uint32_t wk) {
+    const uint32_t t1 = h + xor3(rotr32(e, 6), rotr32(e, 11), rotr32(e, 25)) + sha_ch(e, f, g) + wk;
+    const uint32_t t2 = xor3(rotr32(a, 2), rotr32(a, 13), rotr32(a, 22)) + sha_maj(a, b, c);
+    h = g; g = f; f = e; e = d + t1;
+    d = c; c = b; b = a; a = t1 + t2;
+  };
+#pragma unroll
+  for (int t = 0; t < 16; t++) round(w[t] + K[t]);
+#pragma unroll 1
+  for (int j = 16; j < 64; j += 16) {
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+      const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
+      w[t] += xor3(rotr32(w15, 7), rotr32(w15, 18), w15 >> 3) + w[(t + 9) & 15] + xor3(rotr32(w2, 17), rotr32(w2, 19), w2 >> 10);
+      round(w[t] + K[j + t]);
+    }
+  }
+  s.h[0] += a; s.h[1] += b; s.h[2] += c; s.h[3] += d;
+  s.h[4] += e; s.h[5] += f; s.h[6] += g; s.h[7] += h;
+}
+
+// Setup::verify_proof_batch's front (src/kzg/setup.rs:115-161 behind :103-109 per tuple): z_i and y_i come from the CALLER as 32
+// big-endian bytes each (16-B aligned) instead of from the hash and the evaluation kernel.  One lane per item parses both the way
+// Fr::from_be_slice does (src/bls.rs:130-139; k_fr_parse, blob_kernels.cuh: a value >= r is KZG_ERR_FF_NOT_IN_FIELD and its slot
+// is zero), writes the plain limbs k_batch_scalars reads and both status words, and hashes the transcript leaf in the same pass:
+// words 12..27 of the leaf's message are the big-endian words just loaded, so z and y are read once and there is no second
+// launch.  Like k_transcript_leaves it has to fit beside two decoder waves: 64 VGPRs -- and here without scratch
+// (sha256_block_rolled).
+static __global__ __launch_bounds__(256, 8) void k_points_leaves(const uint8_t* __restrict__ commitments48, const uint8_t* __restrict__ proofs48,
+                                                         const uint8_t* __restrict__ z32, const uint8_t* __restrict__ y32, uint64_t n,
+                                                         fr_t* __restrict__ z_plain, fr_t* __restrict__ y_plain, int32_t* __restrict__ status_z,
+                                                         int32_t* __restrict__ status_y, uint32_t* __restrict__ leaves /* n x 8 words */) {
+  issue_priority_latency();
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* c = reinterpret_cast<const uint32_t*>(commitments48 + i * 48);
+  const uint32_t* p = reinterpret_cast<const uint32_t*>(proofs48 + i * 48);
+  // parse, range check and store one scalar; v keeps the words as given (they are what the leaf binds)
+  auto take = [&](fr_t& v, const uint8_t* __restrict__ in32, fr_t* __restrict__ out_plain, int32_t* __restrict__ status) {
+    const uint4* src = reinterpret_cast<const uint4*>(in32 + i * 32);
+    const uint4 hi = src[0], lo = src[1];
+    v.v[7] = __builtin_bswap32(hi.x); v.v[6] = __builtin_bswap32(hi.y); v.v[5] = __builtin_bswap32(hi.z); v.v[4] = __builtin_bswap32(hi.w);
+    v.v[3] = __builtin_bswap32(lo.x); v.v[2] = __builtin_bswap32(lo.y); v.v[1] = __builtin_bswap32(lo.z); v.v[0] = __builtin_bswap32(lo.w);
+    const bool good = fr_is_canonical(v);
+    uint4* dst = reinterpret_cast<uint4*>(out_plain + i);
+    dst[0] = good ? make_uint4(v.v[0], v.v[1], v.v[2], v.v[3]) : make_uint4(0, 0, 0, 0);
+    dst[1] = good ? make_uint4(v.v[4], v.v[5], v.v[6], v.v[7]) : make_uint4(0, 0, 0, 0);
+    status[i] = good ? 0 : KZG_ERR_FF_NOT_IN_FIELD;
+  };
+  sha256_state s;
+  sha256_init(s);
+  uint32_t w[16];
+  fr_t v;
+  // words 0..39 of the message: C (12, byte-swapped), z (8, limbs 7..0), y (8), pi (12, byte-swapped)
+#pragma unroll
+  for (int q = 0; q < 12; q++) w[q] = __builtin_bswap32(c[q]);
+  take(v, z32, z_plain, status_z);
+#pragma unroll
+  for (int q = 0; q < 4; q++) w[12 + q] = v.v[7 - q];
+  sha256_block_rolled(s, w);
+#pragma unroll
+  for (int q = 0; q < 4; q++) w[q] = v.v[3 - q];
+  take(v, y32, y_plain, status_y);
+#pragma unroll
+  for (int q = 0; q < 8; q++) w[4 + q] = v.v[7 - q];
+#pragma unroll
+  for (int q = 0; q < 4; q++) w[12 + q] = __builtin_bswap32(p[q]);
+  sha256_block_rolled(s, w);
+#pragma unroll
+  for (int q = 0; q < 8; q++) w[q] = __builtin_bswap32(p[4 + q]);
+  w[8] = 0x80000000u;
+#pragma unroll
+  for (int q = 9; q < 15; q++) w[q] = 0;
+  w[15] = 160 * 8;
+  sha256_block_rolled(s, w);
+#pragma unroll
+  for (int q = 0; q < 8; q++) leaves[i * 8 + q] = s.h[q];
+}
+
+// The first rejected item of each of four status arrays (verify_proof_batch: proofs, commitments, z, y), found on the device: a
+// wave's lowest failing lane per array by ballot, then one 64-bit atomicMin per array and wave that has an error on
+// (index << 32) | code -- the minimum is the lowest index, its low half that item's code.  first4[k] starts as all ones
+// (= no error); the host reads back 32 bytes instead of 4 n status words.
+static __global__ __launch_bounds__(256) void k_first_errors(const int32_t* __restrict__ st0, const int32_t* __restrict__ st1, const int32_t* __restrict__ st2,
+                                                      const int32_t* __restrict__ st3, uint64_t n, unsigned long long* __restrict__ first4) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool live = i < n;
+  const int32_t code[4] = {live ? st0[i] : 0, live ? st1[i] : 0, live ? st2[i] : 0, live ? st3[i] : 0};
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const unsigned long long failing = __ballot(code[k] != 0);
+    if (failing != 0 && lane == __ffsll(failing) - 1) atomicMin(&first4[k], ((unsigned long long)i << 32) | (uint32_t)code[k]);
+  }
+}
+
 // out[g] = H(in[g * fan] .. in[min(n_in, (g + 1) * fan) - 1]) over 32-byte digests (8 big-endian word values each)
 static __global__ __launch_bounds__(64, 8) void k_transcript_nodes(const uint32_t* __restrict__ in, uint64_t n_in, uint32_t fan, uint32_t* __restrict__ nodes) {
   issue_priority_latency();

@@ -9,6 +9,7 @@
 //   blob_proof(blob, commitment)         <- src/kzg/setup.rs:177-183
 //   proof(blob, z)                       <- src/kzg/setup.rs:185-194
 //   verify_proof(proof, commitment, z, y)<- src/kzg/setup.rs:96-113
+//   verify_proof_batch(ps, cs, zs, ys)   <- src/kzg/setup.rs:115-161 behind :96-113 per tuple
 //   decompress(bytes48) -> P1            <- P1::decompress, src/bls.rs:505-531
 //   verify_blob_proof(blob, c, p)        <- src/kzg/setup.rs:208-221
 //   verify_blob_proof_batch(blobs,cs,ps) <- src/kzg/setup.rs:247-275
@@ -370,6 +371,25 @@ class Setup {
     int32_t ok = 0;
     int32_t rc = kzg_verify_blob_proof_batch(ctx_.get(), flat.data(), cs.data(), ps.data(), n, &ok);
     return finish(rc, ok, "kzg_verify_blob_proof_batch");
+  }
+
+  // Setup::verify_proof for n tuples in one call (the reference's private verify_proof_batch, src/kzg/setup.rs:115-161): the
+  // fixed-size array types make every length right, so only the four lists' sizes remain to be compared
+  bool verify_proof_batch(const std::vector<Bytes48>& proofs, const std::vector<Bytes48>& commitments, const std::vector<Bytes32>& points,
+                          const std::vector<Bytes32>& evals) const {
+    if (proofs.size() != commitments.size() || commitments.size() != points.size() || points.size() != evals.size())
+      throw std::logic_error("assertion `left == right` failed");
+    const size_t n = proofs.size();
+    std::vector<uint8_t> ps(n * 48), cs(n * 48), zs(n * 32), ys(n * 32);
+    for (size_t i = 0; i < n; i++) {
+      std::copy(proofs[i].begin(), proofs[i].end(), ps.begin() + i * 48);
+      std::copy(commitments[i].begin(), commitments[i].end(), cs.begin() + i * 48);
+      std::copy(points[i].begin(), points[i].end(), zs.begin() + i * 32);
+      std::copy(evals[i].begin(), evals[i].end(), ys.begin() + i * 32);
+    }
+    int32_t ok = 0;
+    int32_t rc = kzg_verify_proof_batch(ctx_.get(), ps.data(), cs.data(), zs.data(), ys.data(), n, &ok);
+    return finish(rc, ok, "kzg_verify_proof_batch");
   }
 
   // batch forms (contiguous buffers) for callers that already hold many blobs

@@ -9,6 +9,7 @@ Method names, argument meaning and error behaviour follow the reference:
     Setup.verify_proof(proof, commitment, z, y)  src/kzg/setup.rs:96-113
     Setup.verify_blob_proof(blob, c, p)          src/kzg/setup.rs:208-221
     Setup.verify_blob_proof_batch(blobs, cs, ps) src/kzg/setup.rs:247-275
+    Setup.verify_proof_batch(ps, cs, zs, ys)     src/kzg/setup.rs:115-161 behind :96-113 per tuple
 
 Points cross this boundary in their 48-byte compressed form (what every caller
 of the reference does next: benches/kzg.rs:25-32, src/kzg/setup.rs:341-343).
@@ -150,6 +151,13 @@ _SIGNATURES = {
     "kzg_verify_blob_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
     "kzg_verify_blob_proof": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, _i32p]),
     "kzg_verify_proof": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, _u8p, _i32p]),
+    "kzg_verify_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
+    "kzg_verify_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
+    "kzg_verify_proof_batch_group_dev": (ctypes.c_int32, [ctypes.c_void_p, _vpp, _vpp, _vpp, _vpp, _u64p, _i32p, _vpp]),
+    "kzg_verify_proof_phase1_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p],
+    ),
     "kzg_g1_decompress_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
     "kzg_evaluate_blobs": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
     "kzg_verify_phase1_dev": (
@@ -660,6 +668,49 @@ class Setup:
             raise _kzg_error(rc)
         return bool(ok.value)
 
+    def verify_proof_batch(self, proofs: Sequence[bytes], commitments: Sequence[bytes], points: Sequence[bytes], evals: Sequence[bytes]) -> bool:
+        """`Setup::verify_proof` for n tuples in one call (the reference's private `verify_proof_batch`, src/kzg/setup.rs:115-161).
+        A length mismatch is an AssertionError like verify_blob_proof_batch's; the first rejected input wins in verify_proof's
+        parse order lifted to lists: every proof, then every commitment, then every point, then every evaluation."""
+        assert len(proofs) == len(commitments), "assertion `left == right` failed"
+        assert len(commitments) == len(points), "assertion `left == right` failed"
+        assert len(points) == len(evals), "assertion `left == right` failed"
+        lists = [[_buf(v) for v in seq] for seq in (proofs, commitments, points, evals)]
+        # a wrong-length item never reaches the engine (the ABI takes n items of 48 / 32 bytes): it is the first error unless an
+        # item BEFORE it in the parse order is rejected, so only then is the engine asked -- about the items before it
+        short = None
+        for kind, (seq, width) in enumerate(zip(lists, (48, 48, 32, 32))):
+            bad = [i for i, v in enumerate(seq) if len(v) != width]
+            if bad:
+                short = (kind, bad[0])
+                break
+        if short is not None:
+            kind, at = short
+            err = KzgError(BlsError(ECGroupError("InvalidEncoding") if kind < 2 else FiniteFieldError("InvalidEncoding")))
+            # everything parsed before the short item: the kinds before `kind` whole, `kind` itself up to `at`
+            pts = b"".join(lists[0] if kind > 0 else lists[0][:at]) + b"".join([] if kind == 0 else (lists[1] if kind > 1 else lists[1][:at]))
+            if pts:
+                _, st = self.decompress_g1_batch(pts)
+                hit = [c for c in st if c]
+                if hit:
+                    raise _kzg_error(hit[0])
+            rb = _R.to_bytes(32, "big")
+            scal = ([] if kind < 2 else (lists[2] if kind > 2 else lists[2][:at])) + ([] if kind < 3 else lists[3][:at])
+            if any(v >= rb for v in scal):
+                raise _kzg_error(7)
+            raise err
+        return self.verify_proof_batch_host(b"".join(lists[0]), b"".join(lists[1]), b"".join(lists[2]), b"".join(lists[3]), len(proofs))
+
+    def verify_proof_batch_host(self, proofs, commitments, points, evals, n: int) -> bool:
+        """kzg_verify_proof_batch on n CONTIGUOUS tuples in host memory: bytes-like objects or raw host addresses (ints)"""
+        ok = ctypes.c_int32(0)
+        args = [a if isinstance(a, int) else _buf(a) for a in (proofs, commitments, points, evals)]
+        rc = self._lib.kzg_verify_proof_batch(self._h, args[0], args[1], args[2], args[3], n, ctypes.byref(ok))
+        self._check(rc, "kzg_verify_proof_batch")
+        if rc > 0:
+            raise _kzg_error(rc)
+        return bool(ok.value)
+
     def verify_blob_proof(self, blob: bytes, commitment: bytes, proof: bytes) -> bool:
         blob, commitment, proof = _buf(blob), _buf(commitment), _buf(proof)
         if len(blob) != BYTES_PER_BLOB:
@@ -728,6 +779,14 @@ class Setup:
             raise _kzg_error(rc)
         return bool(ok.value)
 
+    def verify_proof_batch_dev(self, d_proofs: int, d_commitments: int, d_points: int, d_evals: int, n: int, stream: int = 0) -> bool:
+        ok = ctypes.c_int32(0)
+        rc = self._lib.kzg_verify_proof_batch_dev(self._h, d_proofs, d_commitments, d_points, d_evals, n, ctypes.byref(ok), stream)
+        self._check(rc, "kzg_verify_proof_batch_dev")
+        if rc > 0:
+            raise _kzg_error(rc)
+        return bool(ok.value)
+
     # -- device-resident SHARDED calls on a group context: one entry per member, member k's buffers resident on member k's GPU ---
     def _per_member(self, values, what):
         m = self.members
@@ -765,6 +824,28 @@ class Setup:
         if rc > 0:
             raise _kzg_error(rc)
         return bool(ok.value)
+
+    def verify_proof_batch_group_dev(self, d_proofs, d_commitments, d_points, d_evals, n_local, streams=None) -> bool:
+        """Setup::verify_proof for the tuples of the members' resident shares (global order = member order)"""
+        ok = ctypes.c_int32(0)
+        rc = self._lib.kzg_verify_proof_batch_group_dev(self._h, self._per_member(d_proofs, "d_proofs"), self._per_member(d_commitments, "d_commitments"),
+                                                        self._per_member(d_points, "d_points"), self._per_member(d_evals, "d_evals"), self._counts(n_local),
+                                                        ctypes.byref(ok), self._streams(streams))
+        self._check(rc, "kzg_verify_proof_batch_group_dev")
+        if rc > 0:
+            raise _kzg_error(rc)
+        return bool(ok.value)
+
+    def verify_proof_phase1_dev(self, d_proofs: int, d_commitments: int, d_points: int, d_evals: int, n_local: int, stream: int = 0):
+        """-> (session handle, 32-byte transcript root, err8): phase 1 of verify_proof_batch; the session takes verify_phase2_dev,
+        verify_session_zy and verify_session_destroy like one of verify_phase1_dev"""
+        root = ctypes.create_string_buffer(32)
+        err = (ctypes.c_int32 * 8)()
+        sess = ctypes.c_void_p()
+        rc = self._lib.kzg_verify_proof_phase1_dev(self._h, d_proofs, d_commitments, d_points, d_evals, n_local, ctypes.cast(root, ctypes.c_void_p), err,
+                                                   ctypes.byref(sess), stream)
+        self._check(rc, "kzg_verify_proof_phase1_dev")
+        return sess, root.raw, list(err)
 
     def verify_phase1_dev(self, d_blobs: int, d_commitments: int, d_proofs: int, n_local: int, stream: int = 0):
         """-> (session handle, 32-byte transcript root, err6)."""
