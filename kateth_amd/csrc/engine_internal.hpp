@@ -306,22 +306,24 @@ int32_t multi_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, co
                                  int32_t* ok);
 int32_t multi_g1_decompress(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
 int32_t multi_evaluate_blobs(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
-// one member's device-resident share of a group verification (kzg_verify_blob_proof_batch_group_dev): global range [first, first + count)
+// The device-resident inputs of one batch verification call (engine_verify.hip: front_enqueue / front_status switch on `kind`).
+// Its error record is `kinds()` x {local index of the first rejected item or -1, code}, in the reference's parse order:
+//   BLOBS  (verify_blob_proof_batch): blobs, commitments48, proofs48       -> {blob, commitment, proof}   = the ABI's err6
+//   POINTS (verify_proof_batch):      proofs48, commitments48, z32, y32    -> {proof, commitment, z, y}   = the ABI's err8
+struct VerifyInputs {
+  enum Kind { BLOBS, POINTS } kind;
+  const uint8_t *blobs, *commitments48, *proofs48, *z32, *y32;
+  int kinds() const { return kind == BLOBS ? 3 : 4; }
+};
+// one member's device-resident share of a group verification (kzg_verify_*_batch_group_dev): global range [first, first + count),
+// inputs resident on member->device
 struct GroupDevShare {
   const kzg_ctx* member;
-  const uint8_t *blobs, *commitments48, *proofs48;  // resident on member->device
+  VerifyInputs in;
   uint64_t first, count;
   hipStream_t st;
 };
 int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& shares, uint64_t n_total, int32_t* ok);  // engine_verify.hip
-// the same for kzg_verify_proof_batch_group_dev
-struct GroupDevPointsShare {
-  const kzg_ctx* member;
-  const uint8_t *proofs48, *commitments48, *z32, *y32;  // resident on member->device
-  uint64_t first, count;
-  hipStream_t st;
-};
-int32_t verify_points_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevPointsShare>& shares, uint64_t n_total, int32_t* ok);  // engine_verify.hip
 int32_t stage_init(const kzg_ctx* ctx);                                             // caller holds stage_lock
 int32_t stage_reserve(const kzg_ctx* ctx, size_t arena_bytes, size_t io_bytes);   // caller holds stage_lock
 void stage_destroy(const kzg_ctx* ctx);

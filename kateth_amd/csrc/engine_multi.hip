@@ -14,7 +14,6 @@
 
 using kzg::multi::Share;
 using kzg::multi::merged_first_error;
-using kzg::multi::merged_first_error4;
 
 namespace {
 
@@ -106,88 +105,61 @@ int32_t multi_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, const uin
   return verify_proof_single(member_of(ctx, ctx->rr.fetch_add(1u, std::memory_order_relaxed) % S), proof48, commitment48, z32, y32, ok);
 }
 
-// Setup::verify_blob_proof_batch (src/kzg/setup.rs:247-275) over the members.  With one share this is exactly the
-// single-device call (one root seeds the challenge); with several the challenge is seeded by all their roots, so r differs
-// from the single-device call's while the boolean and the first-error code are the same.
+// Batch verification from host buffers over the members' shares.  `phase1(member, share, root32, err, &session)` is the single-device
+// phase 1 of one share -- verify_phase1_host or verify_proof_phase1_host -- and `kinds` the kinds of its error record.  The
+// challenge is seeded by all the shares' roots, so r differs from the single-device call's while the boolean and the
+// first-error code are the same.
+namespace {
+template <class Phase1>
+int32_t multi_verify_shares(const kzg_ctx* ctx, const std::vector<Share>& shares, uint64_t n, int kinds, int32_t* ok, Phase1&& phase1) {
+  const uint32_t W = (uint32_t)shares.size();
+  const size_t stride = 2 * (size_t)kinds;
+  std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
+  std::vector<int32_t> err(stride * W);
+  std::vector<kzg_verify_session*> sessions(W, nullptr);
+  auto release = [&]() {  // handing a session back may fail on its own: the error the caller is told about stays the first one
+    const ErrorSnapshot keep = error_snapshot();
+    for (kzg_verify_session* s : sessions)
+      if (s) kzg_verify_session_destroy(s);
+    error_publish(keep);
+  };
+  int32_t rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
+    const kzg_ctx* m = member_of(ctx, shares[j].member);
+    if (hipSetDevice(m->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
+    return phase1(m, shares[j], roots.data() + 32 * (size_t)j, err.data() + stride * j, &sessions[j]);
+  });
+  const int32_t code = rc ? 0 : merged_first_error(shares, err.data(), kinds);
+  if (rc == 0 && code == 0)
+    rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
+      return kzg_verify_phase2_dev(sessions[j], roots.data(), W, shares[j].first, n, partials.data() + 192 * (size_t)j);
+    });
+  release();
+  if (rc || code) return rc ? rc : code;
+  return kzg_verify_batch_finish(ctx, partials.data(), W, ok);
+}
+}  // namespace
+
+// Setup::verify_blob_proof_batch (src/kzg/setup.rs:247-275) over the members; one share is exactly the single-device call.
 int32_t multi_verify_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, int32_t* ok) {
   *ok = 0;
   const std::vector<Share> shares = shares_of(ctx, n);
-  const uint32_t W = (uint32_t)shares.size();
-  if (W == 1) return verify_batch_host_single(member_of(ctx, shares[0].member), blobs, commitments48, proofs48, n, ok);
-  std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
-  std::vector<int32_t> err6(6 * (size_t)W);
-  std::vector<kzg_verify_session*> sessions(W, nullptr);
-  auto release = [&]() {
-    for (kzg_verify_session* s : sessions)
-      if (s) kzg_verify_session_destroy(s);
-  };
-  int32_t rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
-    const Share& sh = shares[j];
-    const kzg_ctx* m = member_of(ctx, sh.member);
-    if (hipSetDevice(m->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
-    return verify_phase1_host(m, blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, commitments48 + sh.first * 48, proofs48 + sh.first * 48, sh.count,
-                              roots.data() + 32 * (size_t)j, err6.data() + 6 * (size_t)j, &sessions[j]);
+  if (shares.size() == 1) return verify_batch_host_single(member_of(ctx, shares[0].member), blobs, commitments48, proofs48, n, ok);
+  return multi_verify_shares(ctx, shares, n, 3, ok, [&](const kzg_ctx* m, const Share& sh, uint8_t* root32, int32_t* err6, kzg_verify_session** session) {
+    return verify_phase1_host(m, blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, commitments48 + sh.first * 48, proofs48 + sh.first * 48, sh.count, root32, err6,
+                              session);
   });
-  if (rc) {
-    const ErrorSnapshot keep = error_snapshot();
-    release();
-    error_publish(keep);
-    return rc;
-  }
-  const int32_t code = merged_first_error(shares, err6.data());
-  if (code) {
-    release();
-    return code;
-  }
-  rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
-    return kzg_verify_phase2_dev(sessions[j], roots.data(), W, shares[j].first, n, partials.data() + 192 * (size_t)j);
-  });
-  {
-    const ErrorSnapshot keep = error_snapshot();
-    release();
-    error_publish(keep);
-  }
-  if (rc) return rc;
-  return kzg_verify_batch_finish(ctx, partials.data(), W, ok);
 }
 
-// Setup::verify_proof_batch (src/kzg/setup.rs:115-161) over the members, cut like multi_verify_batch: one share is exactly the
-// single-device call; several seed the challenge with all their roots (another r, the same boolean and first-error code).
+// Setup::verify_proof_batch (src/kzg/setup.rs:115-161) over the members, cut the same way.
 int32_t multi_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
                                  int32_t* ok) {
   *ok = 0;
   const std::vector<Share> shares = shares_of(ctx, n);
-  const uint32_t W = (uint32_t)shares.size();
-  if (W == 1) return verify_proof_batch_host_single(member_of(ctx, shares[0].member), proofs48, commitments48, z32, y32, n, ok);
-  std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
-  std::vector<int32_t> err8(8 * (size_t)W);
-  std::vector<kzg_verify_session*> sessions(W, nullptr);
-  auto release = [&]() {
-    const ErrorSnapshot keep = error_snapshot();
-    for (kzg_verify_session* s : sessions)
-      if (s) kzg_verify_session_destroy(s);
-    error_publish(keep);
-  };
-  int32_t rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
-    const Share& sh = shares[j];
-    return verify_proof_phase1_host(member_of(ctx, sh.member), proofs48 + sh.first * 48, commitments48 + sh.first * 48, z32 + sh.first * 32, y32 + sh.first * 32,
-                                    sh.count, roots.data() + 32 * (size_t)j, err8.data() + 8 * (size_t)j, &sessions[j]);
+  if (shares.size() == 1) return verify_proof_batch_host_single(member_of(ctx, shares[0].member), proofs48, commitments48, z32, y32, n, ok);
+  return multi_verify_shares(ctx, shares, n, 4, ok, [&](const kzg_ctx* m, const Share& sh, uint8_t* root32, int32_t* err8, kzg_verify_session** session) {
+    return verify_proof_phase1_host(m, proofs48 + sh.first * 48, commitments48 + sh.first * 48, z32 + sh.first * 32, y32 + sh.first * 32, sh.count, root32, err8,
+                                    session);
   });
-  if (rc) {
-    release();
-    return rc;
-  }
-  const int32_t code = merged_first_error4(shares, err8.data());
-  if (code) {
-    release();
-    return code;
-  }
-  rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
-    return kzg_verify_phase2_dev(sessions[j], roots.data(), W, shares[j].first, n, partials.data() + 192 * (size_t)j);
-  });
-  release();
-  if (rc) return rc;
-  return kzg_verify_batch_finish(ctx, partials.data(), W, ok);
 }
 
 // ---- device-resident sharded calls (include/kateth_amd.h: kzg_*_group_dev) -------------------------------------------------
@@ -235,8 +207,8 @@ extern "C" int32_t kzg_verify_blob_proof_batch_group_dev(const kzg_ctx* ctx, con
   for (uint32_t k = 0; k < S; k++) {
     if (n_local[k] == 0) continue;
     if (!d_blobs[k] || !d_commitments48[k] || !d_proofs48[k]) return fail(KZG_FAIL_ARGUMENT, "null device pointer for a member with items");
-    shares.push_back(GroupDevShare{member_of(ctx, k), (const uint8_t*)d_blobs[k], (const uint8_t*)d_commitments48[k], (const uint8_t*)d_proofs48[k], total, n_local[k],
-                                   hip_streams ? (hipStream_t)hip_streams[k] : nullptr});
+    const VerifyInputs in{VerifyInputs::BLOBS, (const uint8_t*)d_blobs[k], (const uint8_t*)d_commitments48[k], (const uint8_t*)d_proofs48[k], nullptr, nullptr};
+    shares.push_back(GroupDevShare{member_of(ctx, k), in, total, n_local[k], hip_streams ? (hipStream_t)hip_streams[k] : nullptr});
     total += n_local[k];
   }
   return verify_group_dev(ctx, shares, total, ok);
@@ -250,16 +222,16 @@ extern "C" int32_t kzg_verify_proof_batch_group_dev(const kzg_ctx* ctx, const vo
   if (!ctx || !ok || !d_proofs48 || !d_commitments48 || !d_z32 || !d_y32 || !n_local) return fail(KZG_FAIL_ARGUMENT, "null argument");
   *ok = 0;
   const uint32_t S = 1u + (uint32_t)ctx->peers.size();
-  std::vector<GroupDevPointsShare> shares;
+  std::vector<GroupDevShare> shares;
   uint64_t total = 0;
   for (uint32_t k = 0; k < S; k++) {
     if (n_local[k] == 0) continue;
     if (!d_proofs48[k] || !d_commitments48[k] || !d_z32[k] || !d_y32[k]) return fail(KZG_FAIL_ARGUMENT, "null device pointer for a member with items");
-    shares.push_back(GroupDevPointsShare{member_of(ctx, k), (const uint8_t*)d_proofs48[k], (const uint8_t*)d_commitments48[k], (const uint8_t*)d_z32[k],
-                                         (const uint8_t*)d_y32[k], total, n_local[k], hip_streams ? (hipStream_t)hip_streams[k] : nullptr});
+    const VerifyInputs in{VerifyInputs::POINTS, nullptr, (const uint8_t*)d_commitments48[k], (const uint8_t*)d_proofs48[k], (const uint8_t*)d_z32[k], (const uint8_t*)d_y32[k]};
+    shares.push_back(GroupDevShare{member_of(ctx, k), in, total, n_local[k], hip_streams ? (hipStream_t)hip_streams[k] : nullptr});
     total += n_local[k];
   }
-  return verify_points_group_dev(ctx, shares, total, ok);
+  return verify_group_dev(ctx, shares, total, ok);
 } catch (...) {
   return abi_exception();
 }

@@ -68,14 +68,21 @@ void session_pool_clear(const kzg_ctx* ctx) {
   ctx->session_pool.clear();
 }
 
+// Waits for everything this use has enqueued on the session's three streams, ALWAYS all three (errors ignored: the callers are
+// on a failure path or are handing the session back).  Nothing may still touch the buffers when a session returns to the pool,
+// and nothing may still run on a Phase2's scratch when it goes out of scope.  The caller has set the session's device.
+static void session_drain(kzg_verify_session* s) {
+  (void)hipStreamSynchronize(s->st);
+  (void)hipStreamSynchronize(s->aux);
+  (void)hipStreamSynchronize(s->side);
+}
+
 // hands the session back to its context's pool (at most 8 are kept)
 extern "C" void kzg_verify_session_destroy(kzg_verify_session* s) {
   if (!s) return;
   const kzg_ctx* ctx = s->ctx;
   (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(s->st);  // nothing enqueued by this use may still touch the buffers
-  (void)hipStreamSynchronize(s->side);
-  (void)hipStreamSynchronize(s->aux);
+  session_drain(s);
   std::lock_guard<std::mutex> guard(ctx->pool_lock);
   if (ctx->session_pool.size() < 8)
     ctx->session_pool.push_back(s);
@@ -254,11 +261,20 @@ struct MsmVarJob {
   VarGeom g{};
   uint32_t nout = 0;  // points read back: W window sums, or W*c bit sums on the flat path
   uint8_t* buf = nullptr;
-  bool owns_buf = false;
+  bool owns_buf = false;  // no scratch was handed in: `buf` is this job's own allocation
   std::vector<g1_xyzz> win;
   const g1_xyzz* d_win = nullptr;
   hipStream_t st = nullptr;
   bool active = false;
+  MsmVarJob() = default;
+  MsmVarJob(const MsmVarJob&) = delete;
+  MsmVarJob& operator=(const MsmVarJob&) = delete;
+  ~MsmVarJob() { release(); }  // a job that is dropped with kernels enqueued: the owner drains its streams first
+  void release() {
+    if (owns_buf && buf) (void)hipFree(buf);
+    buf = nullptr;
+    owns_buf = false;
+  }
 };
 
 // The launch comes in two halves so that batch verification can run the first beside the point decoder:
@@ -366,8 +382,7 @@ static int32_t msm_var_finish(MsmVarJob& job, g1_xyzz& result) {
   tt.mark("kernels done + read-back");
   if (rc == 0) host_horner(result, job.win, job.g);
   tt.mark("horner");
-  if (job.owns_buf) (void)hipFree(job.buf);
-  job.buf = nullptr;
+  job.release();  // here, not at the job's end: the scratch is not held through the caller's host work
   job.active = false;
   return rc;
 }
@@ -375,12 +390,8 @@ static int32_t msm_var_finish(MsmVarJob& job, g1_xyzz& result) {
 static int32_t msm_var(const kzg_ctx* ctx, const uint4* d_points, const uint8_t* d_inf, const fr_t* d_scalars, uint64_t nterms, hipStream_t st,
                        g1_xyzz& result) {
   MsmVarJob job;
-  int32_t rc = msm_var_launch(ctx, job, d_points, d_inf, d_scalars, nterms, st);
-  if (rc) {
-    if (job.buf && job.owns_buf) (void)hipFree(job.buf);
-    return rc;
-  }
-  return msm_var_finish(job, result);
+  const int32_t rc = msm_var_launch(ctx, job, d_points, d_inf, d_scalars, nterms, st);
+  return rc ? rc : msm_var_finish(job, result);
 }
 
 static void scan_first_error(const int32_t* st, uint64_t n, int32_t* idx, int32_t* code) {
@@ -533,6 +544,33 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
   return 0;
 }
 
+// A blob call of ONE item takes its lincombs and pairing on the host (verify_one_tail) unless a test forces it through the batch
+// machinery: the entry points and the host-buffer front skip the transcript for it.
+static bool one_item_on_host(const kzg_verify_session* s) { return s->n == 1 && !s->ctx->knobs.single_via_batch; }
+
+// The point decoder beside the caller's stream.  `side` -- the session's side stream, or the caller's own under verify_serial -- waits
+// for what the caller's stream holds at the fork (ev_fork: session initialised, inputs resident) and decodes points
+// [first, first + count) of the 2n: proofs, then commitments.  `how`:
+//   DECODE_FORKED  the caller recorded ev_fork itself, earlier on its stream (phase1_items: ahead of the hash)
+//   DECODE_WHOLE   all 2n points with the one-launch decoder (k_g1_decompress) instead of a range
+//   DECODE_FINISH  nothing is decoded after this: the [z^2]-images under GLV right behind the decoder (one product per point), then ev_join
+enum : unsigned { DECODE_FORKED = 1u, DECODE_WHOLE = 2u, DECODE_FINISH = 4u };
+static void decode_on_side(kzg_verify_session* s, hipStream_t side, uint64_t first, uint64_t count, const uint8_t* prf, const uint8_t* com, unsigned how) {
+  const uint64_t n = s->n;
+  if (!(how & DECODE_FORKED)) (void)hipEventRecord(s->ev_fork, s->st);
+  (void)hipStreamWaitEvent(side, s->ev_fork, 0);
+  {
+    ProfScope ps(s->ctx, PROF_DECODE, side);
+    if (how & DECODE_WHOLE)
+      launch_g1_decompress(side, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
+    else
+      launch_g1_decompress_range(side, first, count, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
+  }
+  if (!(how & DECODE_FINISH)) return;
+  if (s->glv) hipLaunchKernelGGL(k_glv_points, dim3(blocks_for(2 * n, 64)), dim3(64), 0, side, s->aff, 2 * n, 2 * n + 1);
+  (void)hipEventRecord(s->ev_join, side);
+}
+
 // Per-item device work of items [base, base + m): Fiat-Shamir challenge z_i and evaluation y_i from blobs resident at
 // `blobs` (m blobs), enqueued on `st`.  `decode_here`: the commitments/proofs of the SAME range are decoded too (fused
 // launch for small m, the session's side stream otherwise); the caller joins ev_join.
@@ -573,22 +611,9 @@ static int32_t phase1_items(kzg_verify_session* s, const uint8_t* blobs, const u
     hipStream_t side = ctx->knobs.verify_serial ? st : s->side;
     if (beside) (void)hipEventRecord(s->ev_fork, st);  // the inputs are ready here
     launch_challenge(ctx, st, blobs, com + base * 48, m, z);  // enqueued first: its workgroups must find their SIMDs empty
-    if (beside) {
-      (void)hipStreamWaitEvent(side, s->ev_fork, 0);
-      ProfScope ps(ctx, PROF_DECODE, side);
-      launch_g1_decompress_range(side, (uint64_t)0, beside, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
-    }
-    if (decode_here) {
-      if (beside < 2 * n) {
-        (void)hipEventRecord(s->ev_fork, st);  // re-recorded: the first wait is already enqueued
-        (void)hipStreamWaitEvent(side, s->ev_fork, 0);
-        ProfScope ps(ctx, PROF_DECODE, side);
-        launch_g1_decompress_range(side, beside, 2 * n - beside, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
-      }
-      if (s->glv)  // the [z^2]-images of the 2n decoded points, right behind the decoder on its stream (one product per point)
-        hipLaunchKernelGGL(k_glv_points, dim3(blocks_for(2 * n, 64)), dim3(64), 0, side, s->aff, 2 * n, 2 * n + 1);
-      (void)hipEventRecord(s->ev_join, side);
-    }
+    if (beside) decode_on_side(s, side, 0, beside, prf, com, DECODE_FORKED | (beside == 2 * n ? DECODE_FINISH : 0u));
+    if (decode_here && beside < 2 * n)  // the rest behind the hash (ev_fork re-recorded: the first wait is already enqueued)
+      decode_on_side(s, side, beside, 2 * n - beside, prf, com, DECODE_FINISH);
   }
   bool wide_groups = m < 4096;
   if (ctx->knobs.eval_group) wide_groups = ctx->knobs.eval_group != 16;  // tests force either shape
@@ -628,56 +653,119 @@ static int32_t p1_root(kzg_verify_session* s, uint8_t* out_root32) {
   sha256_bytes(out_root32, nb.data(), nb.size());
   return 0;
 }
-// (c) read-back of the statuses and first-error scan.  The copy rides on the DECODER's stream (right behind the decoder; the
-//     blob statuses were written by the evaluation kernel, which ended before the root was read), not on the caller's: there it
-//     would queue up behind the bucket kernels of phase 2 and the host would scan 3n statuses after them instead of beside them.
-static int32_t p1_status(kzg_verify_session* s, int32_t* err6) {
-  const uint64_t n = s->n;
-  if (hipStreamWaitEvent(s->side, s->ev_join, 0) != hipSuccess ||
-      hipMemcpyAsync(s->h_stat, s->stat, 3 * n * 4, hipMemcpyDeviceToHost, s->side) != hipSuccess || hipEventRecord(s->ev_stat, s->side) != hipSuccess ||
-      hipEventSynchronize(s->ev_stat) != hipSuccess)
-    return fail(KZG_FAIL_HIP, "verify phase 1 status readback failed");
-  scan_first_error(s->h_stat, n, &err6[0], &err6[1]);
-  scan_first_error(s->h_stat + n, n, &err6[2], &err6[3]);
-  scan_first_error(s->h_stat + 2 * n, n, &err6[4], &err6[5]);
+// ---- the two kinds of call (VerifyInputs, engine_internal.hpp): what differs between them is the front and how the error record is read ----
+static VerifyInputs blob_inputs(const void* blobs, const void* commitments48, const void* proofs48) {
+  return VerifyInputs{VerifyInputs::BLOBS, (const uint8_t*)blobs, (const uint8_t*)commitments48, (const uint8_t*)proofs48, nullptr, nullptr};
+}
+static VerifyInputs point_inputs(const void* proofs48, const void* commitments48, const void* z32, const void* y32) {
+  return VerifyInputs{VerifyInputs::POINTS, nullptr, (const uint8_t*)commitments48, (const uint8_t*)proofs48, (const uint8_t*)z32, (const uint8_t*)y32};
+}
+static void err_clear(int32_t* err, int kinds) {
+  for (int k = 0; k < 2 * kinds; k++) err[k] = (k % 2 == 0) ? -1 : 0;
+}
+// first-error-wins in the reference's parse order (src/kzg/setup.rs:259-271; :103-109 lifted to arrays the same way): the first kind with an entry
+static int32_t first_error_code(const int32_t* err, int kinds) {
+  for (int k = 0; k < 2 * kinds; k += 2)
+    if (err[k] >= 0) return err[k + 1];
   return 0;
 }
-static int32_t phase1_finish(kzg_verify_session* s, const uint8_t* com, const uint8_t* prf, uint8_t* out_root32, int32_t* err6, TraceTimer& tt) {
-  int32_t rc = p1_transcript(s, com, prf);
-  if (rc == 0) rc = p1_root(s, out_root32);
-  if (rc == 0) rc = p1_status(s, err6);
-  tt.mark("gpu kernels + readback + status scan + root hash");
-  return rc;
+// Everything of phase 1 that can be enqueued at once.  When this returns z, y and the statuses are being produced, the decoder's
+// end is ev_join and the transcript's node digests are on their way back behind ev_nodes (p1_root).
+//   BLOBS:  hash, [decoder] || evaluation, transcript (phase1_items, p1_transcript)
+//   POINTS: neither hash nor evaluation: [decoder for all 2n points on the side stream] || k_points_leaves (parses z and y, their
+//           statuses in the blob slot and the fourth) -> k_transcript_nodes x 2.  The statuses never cross to the host (front_status).
+static int32_t front_enqueue(kzg_verify_session* s, const VerifyInputs& in) {
+  const kzg_ctx* ctx = s->ctx;
+  const uint64_t n = s->n;
+  hipStream_t st = s->st;
+  const uint8_t *com = in.commitments48, *prf = in.proofs48;
+  switch (in.kind) {
+    case VerifyInputs::BLOBS: {
+      const int32_t rc = phase1_items(s, in.blobs, com, prf, 0, n, st, true);
+      return rc ? rc : p1_transcript(s, com, prf);
+    }
+    case VerifyInputs::POINTS: {
+      // the decoder is ONE launch over proofs and commitments: no event after the proof half for lincomb A to wait on instead of ev_join
+      decode_on_side(s, s->side, 0, 2 * n, prf, com, DECODE_FINISH | (fused_prep_fits(ctx, n, 2 * n) ? DECODE_WHOLE : 0u));
+      if (hipMemsetAsync(s->first4, 0xff, 4 * sizeof(unsigned long long), s->side) != hipSuccess)  // for k_first_errors, later on this stream
+        return fail(KZG_FAIL_HIP, "verify_proof_batch: fork failed");
+      const uint64_t groups = (n + 255) / 256, nmid = (n + 15) / 16;
+      hipLaunchKernelGGL(k_points_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, prf, in.z32, in.y32, n, s->z, s->y, s->stat, s->stat + 3 * n, s->leaves);
+      hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(nmid, 64)), dim3(64), 0, st, s->leaves, n, 16u, s->mids);
+      hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(groups, 64)), dim3(64), 0, st, s->mids, nmid, 16u, s->nodes);
+      if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: phase 1 launch failed");
+      if (hipMemcpyAsync(s->h_nodes, s->nodes, groups * 32, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(s->ev_nodes, st) != hipSuccess)
+        return fail(KZG_FAIL_HIP, "verify_proof_batch: phase 1 readback failed");
+      return 0;
+    }
+  }
+  return fail(KZG_FAIL_ARGUMENT, "unknown kind of verification call");
+}
+// The first rejected item of each kind -> err = in.kinds() x {local index, code}.  Both ride on the DECODER's stream, right behind the
+// decoder, not on the caller's: there they would queue up behind the bucket kernels of phase 2.
+//   BLOBS:  3n status words come back and the host scans them beside the bucket kernels (the blob statuses were written by the
+//           evaluation kernel, which ended before the root was read)
+//   POINTS: k_first_errors (it also waits for k_points_leaves' two status arrays: ev_nodes was recorded after it) and 32 bytes come back
+static int32_t front_status(kzg_verify_session* s, const VerifyInputs& in, int32_t* err) {
+  const uint64_t n = s->n;
+  hipStream_t side = s->side;
+  switch (in.kind) {
+    case VerifyInputs::BLOBS:
+      if (hipStreamWaitEvent(side, s->ev_join, 0) != hipSuccess || hipMemcpyAsync(s->h_stat, s->stat, 3 * n * 4, hipMemcpyDeviceToHost, side) != hipSuccess ||
+          hipEventRecord(s->ev_stat, side) != hipSuccess || hipEventSynchronize(s->ev_stat) != hipSuccess)
+        return fail(KZG_FAIL_HIP, "verify phase 1 status readback failed");
+      for (int k = 0; k < 3; k++) scan_first_error(s->h_stat + k * n, n, &err[2 * k], &err[2 * k + 1]);
+      return 0;
+    case VerifyInputs::POINTS:
+      if (hipStreamWaitEvent(side, s->ev_nodes, 0) != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: status wait failed");
+      hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(n, 256)), dim3(256), 0, side, s->stat + 2 * n, s->stat + n, s->stat, s->stat + 3 * n, n, s->first4);
+      if (hipGetLastError() != hipSuccess || hipMemcpyAsync(s->h_first4, s->first4, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, side) != hipSuccess ||
+          hipEventRecord(s->ev_stat, side) != hipSuccess || hipEventSynchronize(s->ev_stat) != hipSuccess)
+        return fail(KZG_FAIL_HIP, "verify_proof_batch: status readback failed");
+      for (int k = 0; k < 4; k++) {
+        const unsigned long long w = s->h_first4[k];
+        err[2 * k] = w == ~0ull ? -1 : (int32_t)(w >> 32);
+        err[2 * k + 1] = w == ~0ull ? 0 : (int32_t)(uint32_t)w;
+      }
+      return 0;
+  }
+  return fail(KZG_FAIL_ARGUMENT, "unknown kind of verification call");
+}
+// Phase 1 on its own (kzg_verify_*phase1_dev): the session is acquired, the front runs to its root and error record, and a failure
+// drains the session and hands it back.  n = 0: the empty transcript's root.
+static int32_t phase1_dev(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, uint8_t* out_root32, int32_t* err, kzg_verify_session** session,
+                          hipStream_t st) {
+  *session = nullptr;
+  TraceTimer tt(ctx->knobs.trace, "phase1");
+  HIP_TRY(hipSetDevice(ctx->device));
+  err_clear(err, in.kinds());
+  kzg_verify_session* s = nullptr;
+  int32_t rc = session_acquire(ctx, n, st, &s);
+  if (rc) return rc;
+  tt.mark("session");
+  if (n) {
+    rc = front_enqueue(s, in);
+    if (rc == 0) rc = p1_root(s, out_root32);
+    if (rc == 0) rc = front_status(s, in, err);
+    tt.mark("gpu kernels + readback + first errors + root hash");
+  } else {
+    sha256_bytes(out_root32, nullptr, 0);
+    if (hipStreamSynchronize(s->st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "verify phase 1 synchronize failed");
+  }
+  if (rc) {
+    session_drain(s);
+    kzg_verify_session_destroy(s);
+    return rc;
+  }
+  *session = s;
+  return 0;
 }
 
 extern "C" int32_t kzg_verify_phase1_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_proofs48,
                                          uint64_t n, uint8_t* out_root32, int32_t* err6, kzg_verify_session** session, void* hip_stream) try {
   if (!ctx || !out_root32 || !err6 || !session || (n && (!d_blobs || !d_commitments48 || !d_proofs48)))
     return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *session = nullptr;
-  TraceTimer tt(ctx->knobs.trace, "phase1");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  for (int k = 0; k < 6; k++) err6[k] = (k % 2 == 0) ? -1 : 0;
-  kzg_verify_session* s = nullptr;
-  int32_t rc = session_acquire(ctx, n, st, &s);
-  if (rc) return rc;
-  tt.mark("session");
-  if (n) {
-    const uint8_t* com = (const uint8_t*)d_commitments48;
-    const uint8_t* prf = (const uint8_t*)d_proofs48;
-    rc = phase1_items(s, (const uint8_t*)d_blobs, com, prf, 0, n, st, true);
-    if (rc == 0) rc = phase1_finish(s, com, prf, out_root32, err6, tt);
-  } else {
-    sha256_bytes(out_root32, nullptr, 0);
-    if (hipStreamSynchronize(st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "verify phase 1 synchronize failed");
-  }
-  if (rc) {
-    kzg_verify_session_destroy(s);
-    return rc;
-  }
-  *session = s;
-  return 0;
+  return phase1_dev(ctx, blob_inputs(d_blobs, d_commitments48, d_proofs48), n, out_root32, err6, session, (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }
@@ -756,8 +844,7 @@ int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
                            int32_t* err6, kzg_verify_session** session) {
   *session = nullptr;
   TraceTimer tt(ctx->knobs.trace, "phase1(host buffers)");
-  if (err6)
-    for (int k = 0; k < 6; k++) err6[k] = (k % 2 == 0) ? -1 : 0;
+  if (err6) err_clear(err6, 3);
   std::lock_guard<std::mutex> guard(ctx->stage_lock);  // the arena and the copy/compute streams below are shared
   int32_t rc = stage_init(ctx);
   if (rc) return rc;
@@ -804,14 +891,7 @@ int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
       rc = phase1_items(s, ctx->stage, com, prf, 0, n, st, true);
     } else {
       // all points decoded once, beside the chunk pipeline
-      (void)hipEventRecord(s->ev_fork, st);
-      (void)hipStreamWaitEvent(s->side, s->ev_fork, 0);
-      {
-        ProfScope ps(ctx, PROF_DECODE, s->side);
-        launch_g1_decompress(s->side, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
-      }
-      if (s->glv) hipLaunchKernelGGL(k_glv_points, dim3(blocks_for(2 * n, 64)), dim3(64), 0, s->side, s->aff, 2 * n, 2 * n + 1);
-      (void)hipEventRecord(s->ev_join, s->side);
+      decode_on_side(s, s->side, 0, 2 * n, prf, com, DECODE_WHOLE | DECODE_FINISH);
       for (int r = 0; r < KZG_STAGE_STREAMS; r++) (void)hipStreamWaitEvent(ctx->stage_streams[r], s->ev_fork, 0);  // session initialised, points resident (all of them: the join below is over all)
       for (uint64_t k = 0; k < nchunks && rc == 0; k++) {
         const uint64_t slot = k % slots;
@@ -840,20 +920,21 @@ int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
     tt.mark("enqueue copies + per-chunk kernels");
     // err6 == null (the fused single-context call): only the transcript and its root here -- once the root is known every blob
     // has been hashed and evaluated, so the staging arena can be handed on; the statuses are read by the caller, later
-    if (err6) {
-      rc = phase1_finish(s, com, prf, out_root32, err6, tt);
-    } else if (n == 1 && !ctx->knobs.single_via_batch) {
+    if (!err6 && one_item_on_host(s)) {
       // one item: no batch challenge (r^0 = 1), hence no transcript; the arena is free once the item's kernels have run
       memset(out_root32, 0, 32);
       if (hipStreamSynchronize(st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "verify phase 1 synchronize failed");
-    } else {
-      rc = p1_transcript(s, com, prf);
-      if (rc == 0) rc = p1_root(s, out_root32);
+      break;
     }
+    rc = p1_transcript(s, com, prf);
+    if (rc == 0) rc = p1_root(s, out_root32);
+    if (rc == 0 && err6) rc = front_status(s, blob_inputs(nullptr, com, prf), err6);
+    tt.mark("gpu kernels + readback + root hash (+ status scan)");
   } while (0);
   if (rc) {
     (void)hipStreamSynchronize(ctx->stage_copy_stream);
     for (int r = 0; r < KZG_STAGE_STREAMS; r++) (void)hipStreamSynchronize(ctx->stage_streams[r]);
+    session_drain(s);
     kzg_verify_session_destroy(s);
     return rc;
   }
@@ -1044,7 +1125,6 @@ int32_t verify_one_on_host(const kzg_ctx* ctx, const uint32_t* prf24, bool prf_i
 
 }  // namespace
 
-static int32_t first_error_code(const int32_t* err6);
 // ---- phase 2 in four pieces ---------------------------------------------------------------------------------------------
 struct Phase2 {
   MsmVarJob ja, jb;
@@ -1213,10 +1293,7 @@ extern "C" int32_t kzg_verify_phase2_dev(kzg_verify_session* s, const uint8_t* r
   if (rc == 0) rc = p2_accumulate(s, p2);
   if (rc == 0) rc = p2_finish(s, p2, out192);
   tt.mark("msm A || msm B (incl. host horner)");
-  if (rc) {
-    (void)hipStreamSynchronize(s->st);
-    (void)hipStreamSynchronize(s->aux);
-  }
+  if (rc) session_drain(s);  // before p2 goes; the session stays the caller's
   return rc;
 } catch (...) {
   return abi_exception();
@@ -1250,39 +1327,34 @@ static int32_t verify_one_tail(kzg_verify_session* s, int32_t* ok) {
 // so the bucket kernels start the moment the decoder ends.  Before, all of that queued up behind it: a host round trip and
 // ~0.7 ms of short kernels on a nearly idle chip (profiles/r03/verify65536_kernel_timeline.txt).  The statuses are read after
 // the bucket kernels are enqueued; a rejected input still wins (its code is returned, the sums are discarded).
-static int32_t verify_fused(kzg_verify_session* s, const uint8_t* com, const uint8_t* prf, int32_t* ok, const uint8_t* root_done = nullptr) {
+// `in`: either kind of call; `root_done`: the host-buffer blob path, whose front ran -- and whose root was taken -- while the staging
+// arena was still locked (verify_phase1_host).
+static int32_t verify_fused(kzg_verify_session* s, const VerifyInputs& in, int32_t* ok, const char* label, const uint8_t* root_done = nullptr) {
   const kzg_ctx* ctx = s->ctx;
-  if (s->n == 1 && !ctx->knobs.single_via_batch) return verify_one_tail(s, ok);
-  TraceTimer tt(ctx->knobs.trace, "verify (fused phases)");
+  const int kinds = in.kinds();
+  TraceTimer tt(ctx->knobs.trace, label);
   uint8_t root[32];
-  int32_t err6[6];
-  for (int k = 0; k < 6; k++) err6[k] = (k % 2 == 0) ? -1 : 0;
-  Phase2 p2;
+  int32_t err[8];
+  err_clear(err, kinds);
+  Phase2 p2;  // declared before anything can fail: every failure below drains the session before p2 goes
   int32_t rc = 0;
-  if (root_done) {  // host-buffer path: transcript and root were taken while the staging arena was still locked
+  if (root_done) {
     memcpy(root, root_done, 32);
   } else {
-    rc = p1_transcript(s, com, prf);
+    rc = front_enqueue(s, in);
     if (rc == 0) rc = p1_root(s, root);
   }
-  tt.mark("hash + evaluation + transcript, root");
+  tt.mark("front + transcript, root");
   if (rc == 0) rc = p2_scalars(s, root, 1, 0, s->n);
   if (rc == 0) rc = p2_sort(s, p2, true);
   if (rc == 0) rc = p2_accumulate(s, p2);
-  if (rc == 0) rc = p1_status(s, err6);
-  tt.mark("decoder done, statuses");
-  int32_t code = 0;
-  if (rc == 0) code = first_error_code(err6);
+  if (rc == 0) rc = front_status(s, in, err);
+  tt.mark("decoder done, first errors");
+  const int32_t code = rc == 0 ? first_error_code(err, kinds) : 0;
   if (rc == 0 && code == 0) rc = p2_finish_and_pair(s, p2, ok);
   tt.mark("lincombs + host horner + pairing");
-  if (rc || code) {  // drain what is enqueued before the session goes back to the pool
-    (void)hipStreamSynchronize(s->st);
-    (void)hipStreamSynchronize(s->aux);
-    if (p2.ja.owns_buf && p2.ja.buf) (void)hipFree(p2.ja.buf);
-    if (p2.jb.owns_buf && p2.jb.buf) (void)hipFree(p2.jb.buf);
-    return rc ? rc : code;
-  }
-  return 0;
+  if (rc || code) session_drain(s);  // a rejected input wins: its code is returned, the sums are discarded
+  return rc ? rc : code;
 }
 
 // introspection: challenge z_i and evaluation y_i of items [first, first + count) of a session after phase 1
@@ -1328,14 +1400,6 @@ extern "C" int32_t kzg_verify_batch_finish(const kzg_ctx* ctx, const uint8_t* pa
   return abi_exception();
 }
 
-// first-error-wins order of the reference (src/kzg/setup.rs:259-271)
-static int32_t first_error_code(const int32_t* err6) {
-  if (err6[0] >= 0) return err6[1];
-  if (err6[2] >= 0) return err6[3];
-  if (err6[4] >= 0) return err6[5];
-  return 0;
-}
-
 extern "C" int32_t kzg_verify_blob_proof_batch_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_proofs48,
                                                    uint64_t n, int32_t* ok, void* hip_stream) try {
   if (!ctx || !ok || (n && (!d_blobs || !d_commitments48 || !d_proofs48))) return fail(KZG_FAIL_ARGUMENT, "null argument");
@@ -1348,22 +1412,25 @@ extern "C" int32_t kzg_verify_blob_proof_batch_dev(const kzg_ctx* ctx, const voi
   kzg_verify_session* s = nullptr;
   int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
   if (rc) return rc;
-  const uint8_t* com = (const uint8_t*)d_commitments48;
-  const uint8_t* prf = (const uint8_t*)d_proofs48;
-  rc = phase1_items(s, (const uint8_t*)d_blobs, com, prf, 0, n, s->st, true);
-  if (rc == 0) rc = verify_fused(s, com, prf, ok);
+  const VerifyInputs in = blob_inputs(d_blobs, d_commitments48, d_proofs48);
+  if (one_item_on_host(s)) {
+    rc = phase1_items(s, in.blobs, in.commitments48, in.proofs48, 0, 1, s->st, true);
+    if (rc == 0) rc = verify_one_tail(s, ok);
+  } else {
+    rc = verify_fused(s, in, ok, "verify (fused phases)");
+  }
   kzg_verify_session_destroy(s);
   return rc;
 } catch (...) {
   return abi_exception();
 }
 
-// Setup::verify_blob_proof_batch (src/kzg/setup.rs:223-275) over device-resident shares of a group context, phases
-// interleaved PER MEMBER as in verify_fused: round 1 enqueues hash, [decoder on the side stream] || evaluation and the
-// transcript on every member and returns the members' roots while the decoders still run; round 2 seeds ONE challenge with all
-// roots and, per member, enqueues the scalars (global powers r^i), the sorting halves of both lincombs beside the decoder, the
-// bucket kernels behind it, reads the statuses and takes the member's two partial sums.  Then the first-error merge in the
-// reference's order (src/kzg/setup.rs:259-271) and one pairing check.  Two fork/joins of pooled host threads per call.
+// Setup::verify_blob_proof_batch (src/kzg/setup.rs:223-275) or Setup::verify_proof_batch (:115-161) over device-resident shares of a
+// group context, all of one kind, phases interleaved PER MEMBER as in verify_fused: round 1 enqueues the front on every member and
+// returns the members' roots while the decoders still run; round 2 seeds ONE challenge with all roots and, per member, enqueues
+// the scalars (global powers r^i), the sorting halves of both lincombs beside the decoder, the bucket kernels behind it, reads the
+// first errors and takes the member's two partial sums.  Then the first-error merge in the reference's order over GLOBAL indices
+// (multi_split.hpp) and one pairing check.  Two fork/joins of pooled host threads per call.
 int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& shares, uint64_t n_total, int32_t* ok) {
   *ok = 0;
   const uint32_t W = (uint32_t)shares.size();
@@ -1371,12 +1438,18 @@ int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& s
     *ok = 1;
     return 0;
   }
-  if (W == 1)  // one share: exactly the single-device call (one root seeds the challenge)
-    return kzg_verify_blob_proof_batch_dev(shares[0].member, shares[0].blobs, shares[0].commitments48, shares[0].proofs48, shares[0].count, ok, shares[0].st);
-  TraceTimer tt(ctx->knobs.trace, "group verify (device-resident)");
+  const bool points = shares[0].in.kind == VerifyInputs::POINTS;
+  if (W == 1) {  // one share: exactly the single-device call (one root seeds the challenge)
+    const GroupDevShare& sh = shares[0];
+    return points ? kzg_verify_proof_batch_dev(sh.member, sh.in.proofs48, sh.in.commitments48, sh.in.z32, sh.in.y32, sh.count, ok, sh.st)
+                  : kzg_verify_blob_proof_batch_dev(sh.member, sh.in.blobs, sh.in.commitments48, sh.in.proofs48, sh.count, ok, sh.st);
+  }
+  TraceTimer tt(ctx->knobs.trace, points ? "group verify_proof_batch (device-resident)" : "group verify (device-resident)");
+  const int kinds = shares[0].in.kinds();
+  const size_t stride = 2 * (size_t)kinds;
   std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
-  std::vector<int32_t> err6(6 * (size_t)W);
-  for (size_t k = 0; k < err6.size(); k++) err6[k] = (k % 2 == 0) ? -1 : 0;
+  std::vector<int32_t> err(stride * W);
+  for (uint32_t j = 0; j < W; j++) err_clear(err.data() + stride * j, kinds);
   std::vector<kzg_verify_session*> sessions(W, nullptr);
   auto release = [&]() {
     const ErrorSnapshot keep = error_snapshot();
@@ -1388,24 +1461,14 @@ int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& s
     const GroupDevShare& sh = shares[j];
     if (hipSetDevice(sh.member->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
     int32_t r = session_acquire(sh.member, sh.count, sh.st, &sessions[j]);
-    if (r) return r;
-    kzg_verify_session* s = sessions[j];
-    r = phase1_items(s, sh.blobs, sh.commitments48, sh.proofs48, 0, sh.count, s->st, true);
-    if (r == 0) r = p1_transcript(s, sh.commitments48, sh.proofs48);
-    if (r == 0) r = p1_root(s, roots.data() + 32 * (size_t)j);
-    if (r) {
-      (void)hipStreamSynchronize(s->st);
-      (void)hipStreamSynchronize(s->side);
-    }
+    if (r == 0) r = front_enqueue(sessions[j], sh.in);
+    if (r == 0) r = p1_root(sessions[j], roots.data() + 32 * (size_t)j);
     return r;
   });
-  tt.mark("round 1: hash, evaluation, transcript, roots (decoders still running)");
+  tt.mark("round 1: front, transcript, roots (decoders still running)");
   if (rc) {
     for (uint32_t j = 0; j < W; j++)  // drain the members that did enqueue before their sessions go back to the pools
-      if (sessions[j] && hipSetDevice(shares[j].member->device) == hipSuccess) {
-        (void)hipStreamSynchronize(sessions[j]->st);
-        (void)hipStreamSynchronize(sessions[j]->side);
-      }
+      if (sessions[j] && hipSetDevice(shares[j].member->device) == hipSuccess) session_drain(sessions[j]);
     release();
     return rc;
   }
@@ -1413,30 +1476,24 @@ int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& s
   rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
     const GroupDevShare& sh = shares[j];
     kzg_verify_session* s = sessions[j];
+    int32_t* e = err.data() + stride * j;
     if (hipSetDevice(sh.member->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
     Phase2 p2;
     int32_t r = p2_scalars(s, roots.data(), W, sh.first, n_total);
     if (r == 0) r = p2_sort(s, p2, true);
     if (r == 0) r = p2_accumulate(s, p2);
-    if (r == 0) r = p1_status(s, err6.data() + 6 * (size_t)j);
-    if (r == 0) codes[j] = first_error_code(err6.data() + 6 * (size_t)j);
+    if (r == 0) r = front_status(s, sh.in, e);
+    if (r == 0) codes[j] = first_error_code(e, kinds);
     if (r == 0 && codes[j] == 0) r = p2_finish(s, p2, partials.data() + 192 * (size_t)j);
-    if (r || codes[j]) {  // drain what is enqueued before the session goes back to the pool; a rejected input's sums are discarded
-      (void)hipStreamSynchronize(s->st);
-      (void)hipStreamSynchronize(s->aux);
-      (void)hipStreamSynchronize(s->side);
-      if (p2.ja.owns_buf && p2.ja.buf) (void)hipFree(p2.ja.buf);
-      if (p2.jb.owns_buf && p2.jb.buf) (void)hipFree(p2.jb.buf);
-    }
+    if (r || codes[j]) session_drain(s);  // before p2 goes; a rejected input's sums are discarded
     return r;
   });
-  tt.mark("round 2: scalars, lincombs, statuses, partial sums");
+  tt.mark("round 2: scalars, lincombs, first errors, partial sums");
   release();
   if (rc) return rc;
-  // first-error-wins over the members' records, global indices (multi_split.hpp)
   std::vector<kzg::multi::Share> ms(W);
   for (uint32_t j = 0; j < W; j++) ms[j] = kzg::multi::Share{j, shares[j].first, shares[j].count};
-  const int32_t code = kzg::multi::merged_first_error(ms, err6.data());
+  const int32_t code = kzg::multi::merged_first_error(ms, err.data(), kinds);
   if (code) return code;
   rc = kzg_verify_batch_finish(ctx, partials.data(), W, ok);
   tt.mark("sum of partials + pairing");
@@ -1462,7 +1519,10 @@ int32_t verify_batch_host_single(const kzg_ctx* ctx, const uint8_t* blobs, const
   kzg_verify_session* s = nullptr;
   int32_t rc = verify_phase1_host(ctx, blobs, commitments48, proofs48, n, root, nullptr, &s);
   if (rc) return rc;
-  rc = verify_fused(s, s->pts48 + n * 48, s->pts48, ok, root);  // the device copies: proofs || commitments
+  if (one_item_on_host(s))
+    rc = verify_one_tail(s, ok);
+  else  // the device copies: proofs || commitments
+    rc = verify_fused(s, blob_inputs(nullptr, s->pts48 + n * 48, s->pts48), ok, "verify (fused phases)", root);
   kzg_verify_session_destroy(s);
   return rc;
 }
@@ -1538,130 +1598,13 @@ int32_t verify_proof_single(const kzg_ctx* ctx, const uint8_t* proof48, const ui
 }
 
 // ---- Setup::verify_proof_batch (src/kzg/setup.rs:115-161) as a public batch call: n caller-supplied (proof, commitment, z, y) -------
-// Phase 2 is the blob batch's; phase 1 has neither hash nor evaluation: [decoder for all 2n points, proofs first, on the session's side
-// stream] || k_points_leaves -> k_transcript_nodes x 2 -> root.  The statuses of the four kinds live in the session's four
-// arrays -- z takes the blob slot, y the fourth -- and never cross to the host: k_first_errors runs behind the decoder on its
-// stream and 32 bytes come back.
-static void err8_clear(int32_t* err8) {
-  for (int k = 0; k < 8; k++) err8[k] = (k % 2 == 0) ? -1 : 0;
-}
-// verify_proof's parse order lifted to arrays (src/kzg/setup.rs:103-109 the way :259-271 lifts the blob call's): proofs,
-// commitments, points, evaluations
-static int32_t first_error_code4(const int32_t* err8) {
-  for (int k = 0; k < 8; k += 2)
-    if (err8[k] >= 0) return err8[k + 1];
-  return 0;
-}
-// (a) everything of phase 1 that can be enqueued at once; the node digests are on their way back when this returns
-static int32_t points_front(kzg_verify_session* s, const uint8_t* prf, const uint8_t* com, const uint8_t* z32, const uint8_t* y32) {
-  const kzg_ctx* ctx = s->ctx;
-  const uint64_t n = s->n;
-  hipStream_t st = s->st, side = s->side;
-  if (hipEventRecord(s->ev_fork, st) != hipSuccess || hipStreamWaitEvent(side, s->ev_fork, 0) != hipSuccess ||  // session initialised, inputs resident
-      hipMemsetAsync(s->first4, 0xff, 4 * sizeof(unsigned long long), side) != hipSuccess)
-    return fail(KZG_FAIL_HIP, "verify_proof_batch: fork failed");
-  {
-    ProfScope ps(ctx, PROF_DECODE, side);
-    if (fused_prep_fits(ctx, n, 2 * n))
-      launch_g1_decompress(side, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
-    else
-      launch_g1_decompress_range(side, (uint64_t)0, 2 * n, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
-  }
-  if (s->glv) hipLaunchKernelGGL(k_glv_points, dim3(blocks_for(2 * n, 64)), dim3(64), 0, side, s->aff, 2 * n, 2 * n + 1);
-  (void)hipEventRecord(s->ev_join, side);
-  const uint64_t groups = (n + 255) / 256, nmid = (n + 15) / 16;
-  hipLaunchKernelGGL(k_points_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, prf, z32, y32, n, s->z, s->y, s->stat, s->stat + 3 * n, s->leaves);
-  hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(nmid, 64)), dim3(64), 0, st, s->leaves, n, 16u, s->mids);
-  hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(groups, 64)), dim3(64), 0, st, s->mids, nmid, 16u, s->nodes);
-  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: phase 1 launch failed");
-  if (hipMemcpyAsync(s->h_nodes, s->nodes, groups * 32, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(s->ev_nodes, st) != hipSuccess)
-    return fail(KZG_FAIL_HIP, "verify_proof_batch: phase 1 readback failed");
-  return 0;
-}
-// (b) the first rejected item of each kind, behind the decoder on its stream (which also waits for k_points_leaves' two status
-//     arrays: ev_nodes was recorded after it).  err8 = {proof, commitment, z, y} x {local index, code}
-static int32_t points_status(kzg_verify_session* s, int32_t* err8) {
-  const uint64_t n = s->n;
-  hipStream_t side = s->side;
-  if (hipStreamWaitEvent(side, s->ev_nodes, 0) != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: status wait failed");
-  hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(n, 256)), dim3(256), 0, side, s->stat + 2 * n, s->stat + n, s->stat, s->stat + 3 * n, n, s->first4);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(s->h_first4, s->first4, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, side) != hipSuccess ||
-      hipEventRecord(s->ev_stat, side) != hipSuccess || hipEventSynchronize(s->ev_stat) != hipSuccess)
-    return fail(KZG_FAIL_HIP, "verify_proof_batch: status readback failed");
-  for (int k = 0; k < 4; k++) {
-    const unsigned long long w = s->h_first4[k];
-    err8[2 * k] = w == ~0ull ? -1 : (int32_t)(w >> 32);
-    err8[2 * k + 1] = w == ~0ull ? 0 : (int32_t)(uint32_t)w;
-  }
-  return 0;
-}
-static void points_drain(kzg_verify_session* s, Phase2* p2) {  // before a session with work enqueued goes back to the pool
-  (void)hipStreamSynchronize(s->st);
-  (void)hipStreamSynchronize(s->aux);
-  (void)hipStreamSynchronize(s->side);
-  if (p2 && p2->ja.owns_buf && p2->ja.buf) (void)hipFree(p2->ja.buf);
-  if (p2 && p2->jb.owns_buf && p2->jb.buf) (void)hipFree(p2->jb.buf);
-}
-
-// The single-context call.  As in verify_fused, the root, r, the scalars and both sorts are enqueued while the decoder runs, the
-// bucket kernels wait for it (both lincombs on ev_join: the decoder is ONE launch over proofs and commitments, so there is no
-// event after the proof half for lincomb A to wait on instead), and a rejected input wins over the sums.
-static int32_t verify_points_fused(kzg_verify_session* s, const uint8_t* prf, const uint8_t* com, const uint8_t* z32, const uint8_t* y32, int32_t* ok) {
-  const kzg_ctx* ctx = s->ctx;
-  TraceTimer tt(ctx->knobs.trace, "verify_proof_batch (fused phases)");
-  uint8_t root[32];
-  int32_t err8[8];
-  err8_clear(err8);
-  Phase2 p2;
-  int32_t rc = points_front(s, prf, com, z32, y32);
-  if (rc == 0) rc = p1_root(s, root);
-  tt.mark("parse + transcript, root");
-  if (rc == 0) rc = p2_scalars(s, root, 1, 0, s->n);
-  if (rc == 0) rc = p2_sort(s, p2, true);
-  if (rc == 0) rc = p2_accumulate(s, p2);
-  if (rc == 0) rc = points_status(s, err8);
-  tt.mark("decoder done, first errors");
-  const int32_t code = rc == 0 ? first_error_code4(err8) : 0;
-  if (rc == 0 && code == 0) rc = p2_finish_and_pair(s, p2, ok);
-  tt.mark("lincombs + host horner + pairing");
-  if (rc || code) {
-    points_drain(s, &p2);
-    return rc ? rc : code;
-  }
-  return 0;
-}
-
-static int32_t points_phase1(kzg_verify_session* s, const uint8_t* prf, const uint8_t* com, const uint8_t* z32, const uint8_t* y32, uint8_t* out_root32,
-                             int32_t* err8) {
-  int32_t rc = points_front(s, prf, com, z32, y32);
-  if (rc == 0) rc = p1_root(s, out_root32);
-  if (rc == 0) rc = points_status(s, err8);
-  return rc;
-}
-
+// The blob batch's drivers (phase1_dev, verify_fused, verify_group_dev) over point_inputs: only the front and the reading of the
+// four-kind error record differ -- front_enqueue / front_status, POINTS.  What is here are the entry points and the host-buffer staging.
 extern "C" int32_t kzg_verify_proof_phase1_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
                                                uint64_t n, uint8_t* out_root32, int32_t* err8, kzg_verify_session** session, void* hip_stream) try {
   if (!ctx || !out_root32 || !err8 || !session || (n && (!d_proofs48 || !d_commitments48 || !d_z32 || !d_y32)))
     return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *session = nullptr;
-  HIP_TRY(hipSetDevice(ctx->device));
-  err8_clear(err8);
-  kzg_verify_session* s = nullptr;
-  int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
-  if (rc) return rc;
-  if (n) {
-    rc = points_phase1(s, (const uint8_t*)d_proofs48, (const uint8_t*)d_commitments48, (const uint8_t*)d_z32, (const uint8_t*)d_y32, out_root32, err8);
-    if (rc) points_drain(s, nullptr);
-  } else {
-    sha256_bytes(out_root32, nullptr, 0);
-    if (hipStreamSynchronize(s->st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "verify phase 1 synchronize failed");
-  }
-  if (rc) {
-    kzg_verify_session_destroy(s);
-    return rc;
-  }
-  *session = s;
-  return 0;
+  return phase1_dev(ctx, point_inputs(d_proofs48, d_commitments48, d_z32, d_y32), n, out_root32, err8, session, (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }
@@ -1678,7 +1621,7 @@ extern "C" int32_t kzg_verify_proof_batch_dev(const kzg_ctx* ctx, const void* d_
   kzg_verify_session* s = nullptr;
   int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
   if (rc) return rc;
-  rc = verify_points_fused(s, (const uint8_t*)d_proofs48, (const uint8_t*)d_commitments48, (const uint8_t*)d_z32, (const uint8_t*)d_y32, ok);
+  rc = verify_fused(s, point_inputs(d_proofs48, d_commitments48, d_z32, d_y32), ok, "verify_proof_batch (fused phases)");
   kzg_verify_session_destroy(s);
   return rc;
 } catch (...) {
@@ -1702,7 +1645,7 @@ static int32_t points_stage_host(const kzg_ctx* ctx, const uint8_t* proofs48, co
       hipMemcpyAsync(s->pts48 + n * 48, commitments48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
       hipMemcpyAsync(s->zy32, z32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess ||
       hipMemcpyAsync(s->zy32 + n * 32, y32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess) {
-    points_drain(s, nullptr);
+    session_drain(s);
     kzg_verify_session_destroy(s);
     return fail(KZG_FAIL_HIP, "host-to-device copy failed");
   }
@@ -1712,14 +1655,17 @@ static int32_t points_stage_host(const kzg_ctx* ctx, const uint8_t* proofs48, co
 int32_t verify_proof_phase1_host(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
                                  uint8_t* out_root32, int32_t* err8, kzg_verify_session** session) {
   *session = nullptr;
-  err8_clear(err8);
+  err_clear(err8, 4);
   HIP_TRY(hipSetDevice(ctx->device));
   kzg_verify_session* s = nullptr;
   int32_t rc = points_stage_host(ctx, proofs48, commitments48, z32, y32, n, &s);
   if (rc) return rc;
-  rc = points_phase1(s, s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32, out_root32, err8);
+  const VerifyInputs in = point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32);
+  rc = front_enqueue(s, in);
+  if (rc == 0) rc = p1_root(s, out_root32);
+  if (rc == 0) rc = front_status(s, in, err8);
   if (rc) {
-    points_drain(s, nullptr);
+    session_drain(s);
     kzg_verify_session_destroy(s);
     return rc;
   }
@@ -1734,7 +1680,7 @@ int32_t verify_proof_batch_host_single(const kzg_ctx* ctx, const uint8_t* proofs
   kzg_verify_session* s = nullptr;
   int32_t rc = points_stage_host(ctx, proofs48, commitments48, z32, y32, n, &s);
   if (rc) return rc;
-  rc = verify_points_fused(s, s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32, ok);
+  rc = verify_fused(s, point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32), ok, "verify_proof_batch (fused phases)");
   kzg_verify_session_destroy(s);
   return rc;
 }
@@ -1750,72 +1696,6 @@ extern "C" int32_t kzg_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* pro
 } catch (...) {
   return abi_exception();
 }
-
-// Device-resident shares of a group context: verify_group_dev's two rounds with the points front instead of hash and evaluation.
-int32_t verify_points_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevPointsShare>& shares, uint64_t n_total, int32_t* ok) {
-  *ok = 0;
-  const uint32_t W = (uint32_t)shares.size();
-  if (W == 0) {
-    *ok = 1;
-    return 0;
-  }
-  if (W == 1)  // one share: exactly the single-device call (one root seeds the challenge)
-    return kzg_verify_proof_batch_dev(shares[0].member, shares[0].proofs48, shares[0].commitments48, shares[0].z32, shares[0].y32, shares[0].count, ok, shares[0].st);
-  TraceTimer tt(ctx->knobs.trace, "group verify_proof_batch (device-resident)");
-  std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
-  std::vector<int32_t> err8(8 * (size_t)W);
-  for (uint32_t j = 0; j < W; j++) err8_clear(err8.data() + 8 * (size_t)j);
-  std::vector<kzg_verify_session*> sessions(W, nullptr);
-  auto release = [&]() {
-    const ErrorSnapshot keep = error_snapshot();
-    for (kzg_verify_session* s : sessions)
-      if (s) kzg_verify_session_destroy(s);
-    error_publish(keep);
-  };
-  int32_t rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
-    const GroupDevPointsShare& sh = shares[j];
-    if (hipSetDevice(sh.member->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
-    int32_t r = session_acquire(sh.member, sh.count, sh.st, &sessions[j]);
-    if (r) return r;
-    kzg_verify_session* s = sessions[j];
-    r = points_front(s, sh.proofs48, sh.commitments48, sh.z32, sh.y32);
-    if (r == 0) r = p1_root(s, roots.data() + 32 * (size_t)j);
-    return r;
-  });
-  tt.mark("round 1: parse, transcript, roots (decoders still running)");
-  if (rc) {
-    for (uint32_t j = 0; j < W; j++)  // drain the members that did enqueue before their sessions go back to the pools
-      if (sessions[j] && hipSetDevice(shares[j].member->device) == hipSuccess) points_drain(sessions[j], nullptr);
-    release();
-    return rc;
-  }
-  std::vector<int32_t> codes(W, 0);
-  rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
-    const GroupDevPointsShare& sh = shares[j];
-    kzg_verify_session* s = sessions[j];
-    if (hipSetDevice(sh.member->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
-    Phase2 p2;
-    int32_t r = p2_scalars(s, roots.data(), W, sh.first, n_total);
-    if (r == 0) r = p2_sort(s, p2, true);
-    if (r == 0) r = p2_accumulate(s, p2);
-    if (r == 0) r = points_status(s, err8.data() + 8 * (size_t)j);
-    if (r == 0) codes[j] = first_error_code4(err8.data() + 8 * (size_t)j);
-    if (r == 0 && codes[j] == 0) r = p2_finish(s, p2, partials.data() + 192 * (size_t)j);
-    if (r || codes[j]) points_drain(s, &p2);  // a rejected input's sums are discarded
-    return r;
-  });
-  tt.mark("round 2: scalars, lincombs, first errors, partial sums");
-  release();
-  if (rc) return rc;
-  std::vector<kzg::multi::Share> ms(W);
-  for (uint32_t j = 0; j < W; j++) ms[j] = kzg::multi::Share{j, shares[j].first, shares[j].count};
-  const int32_t code = kzg::multi::merged_first_error4(ms, err8.data());
-  if (code) return code;
-  rc = kzg_verify_batch_finish(ctx, partials.data(), W, ok);
-  tt.mark("sum of partials + pairing");
-  return rc;
-}
-
 
 void warm_code_object_verify() {
   hipFuncAttributes a;

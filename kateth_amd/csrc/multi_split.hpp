@@ -32,41 +32,24 @@ inline std::vector<Share> shares_of(uint64_t n, uint32_t members, uint32_t rotat
   return out;
 }
 
-// First-error-wins order of the reference (src/kzg/setup.rs:259-271: every blob is parsed before any commitment, every
-// commitment before any proof) from the shares' records err6 = {blob_idx, blob_code, commitment_idx, commitment_code, proof_idx,
-// proof_code} with LOCAL indices (-1 = none): the lowest GLOBAL index of the first kind that has an error.  0 = no error.
-inline int32_t merged_first_error(const std::vector<Share>& shares, const int32_t* err6) {
-  for (int kind = 0; kind < 6; kind += 2) {
+// First-error-wins order of the reference from the shares' records of `kinds` x {LOCAL index (-1 = none), code}: the lowest GLOBAL
+// index of the first kind that has an error.  0 = no error.
+//   kinds = 3, verify_blob_proof_batch (src/kzg/setup.rs:259-271: every blob is parsed before any commitment, every commitment
+//              before any proof): err6 = {blob, commitment, proof} x {idx, code}
+//   kinds = 4, verify_proof_batch in verify_proof's parse order (src/kzg/setup.rs:103-109): err8 = {proof, commitment, z, y} x {idx, code}
+// (kinds defaults to the blob call's record, so that a caller written for err6 alone still compiles)
+inline int32_t merged_first_error(const std::vector<Share>& shares, const int32_t* err, int kinds = 3) {
+  const int stride = 2 * kinds;
+  for (int kind = 0; kind < stride; kind += 2) {
     int32_t code = 0;
     uint64_t best = ~(uint64_t)0;
     for (size_t j = 0; j < shares.size(); j++) {
-      const int32_t local = err6[6 * j + kind];
+      const int32_t local = err[stride * j + kind];
       if (local < 0) continue;
       const uint64_t g = shares[j].first + (uint64_t)local;
       if (g < best) {
         best = g;
-        code = err6[6 * j + kind + 1];
-      }
-    }
-    if (code) return code;
-  }
-  return 0;
-}
-
-// The same rule over the FOUR kinds of Setup::verify_proof_batch, in verify_proof's parse order (src/kzg/setup.rs:103-109: proof,
-// commitment, point, evaluation -- every proof before any commitment, and so on): err8 = {proof_idx, proof_code, commitment_idx,
-// commitment_code, z_idx, z_code, y_idx, y_code} per share, LOCAL indices (-1 = none).
-inline int32_t merged_first_error4(const std::vector<Share>& shares, const int32_t* err8) {
-  for (int kind = 0; kind < 8; kind += 2) {
-    int32_t code = 0;
-    uint64_t best = ~(uint64_t)0;
-    for (size_t j = 0; j < shares.size(); j++) {
-      const int32_t local = err8[8 * j + kind];
-      if (local < 0) continue;
-      const uint64_t g = shares[j].first + (uint64_t)local;
-      if (g < best) {
-        best = g;
-        code = err8[8 * j + kind + 1];
+        code = err[stride * j + kind + 1];
       }
     }
     if (code) return code;

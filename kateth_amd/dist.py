@@ -20,18 +20,19 @@ def shard_range(n_total: int, rank: int, world: int) -> Tuple[int, int]:
     return first, max(0, min(per, n_total - first))
 
 
-def merge_first_error(err6_by_rank: Sequence[Sequence[int]], first_index_by_rank: Sequence[int]) -> Tuple[int, int]:
+def merge_first_error(err_by_rank: Sequence[Sequence[int]], first_index_by_rank: Sequence[int]) -> Tuple[int, int]:
     """Rebuilds the reference's first-error-wins order (src/kzg/setup.rs:259-271:
     every blob is parsed before any commitment, every commitment before any
-    proof) from the per-rank records of kzg_verify_phase1_dev.
-    Returns (code, global_index) or (0, -1)."""
-    for kind in (0, 2, 4):  # blobs, commitments, proofs
+    proof) from the per-rank records of kzg_verify_phase1_dev: (local index,
+    code) per kind, so err6 there and err8 (proofs, commitments, z, y) for
+    kzg_verify_proof_phase1_dev.  Returns (code, global_index) or (0, -1)."""
+    for kind in range(0, len(err_by_rank[0]) if err_by_rank else 0, 2):
         best = None
-        for err6, first in zip(err6_by_rank, first_index_by_rank):
-            if err6[kind] >= 0:
-                g = first + err6[kind]
+        for err, first in zip(err_by_rank, first_index_by_rank):
+            if err[kind] >= 0:
+                g = first + err[kind]
                 if best is None or g < best[1]:
-                    best = (err6[kind + 1], g)
+                    best = (err[kind + 1], g)
         if best is not None:
             return best
     return 0, -1

@@ -1,4 +1,4 @@
-// Test driver for kzg::multi::merged_first_error4 (kateth_amd/csrc/multi_split.hpp, header-only host code): every line of stdin is
+// Test driver for kzg::multi::merged_first_error with four kinds (kateth_amd/csrc/multi_split.hpp, header-only host code): every line of stdin is
 // one case -- W, then per share `first count` and its eight err8 values (LOCAL indices, -1 = none) -- and one merged code is
 // printed per case.  Built and fed by tests/test_verify_points_builder.py.
 #include <stdio.h>
@@ -19,7 +19,7 @@ int main() {
       for (int k = 0; k < 8; k++)
         if (scanf("%d", &err8[8 * j + k]) != 1) return 2;
     }
-    printf("%d\n", kzg::multi::merged_first_error4(shares, err8.data()));
+    printf("%d\n", kzg::multi::merged_first_error(shares, err8.data(), 4));
   }
   return 0;
 }

@@ -64,7 +64,7 @@ int hm_multi_shares(uint64_t n, uint32_t members, uint32_t rotate, uint64_t* out
   return (int)sh.size();
 }
 int32_t hm_multi_first_error(uint64_t n, uint32_t members, uint32_t rotate, const int32_t* err6) {
-  return kzg::multi::merged_first_error(kzg::multi::shares_of(n, members, rotate), err6);
+  return kzg::multi::merged_first_error(kzg::multi::shares_of(n, members, rotate), err6, 3);
 }
 void hm_fp_op(int op, uint8_t* out48, const uint8_t* a48, const uint8_t* b48) {
   if (op == 5) {
