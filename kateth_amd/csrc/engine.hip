@@ -229,6 +229,101 @@ int32_t ws_end(const kzg_ctx* ctx, hipStream_t st) {
   return 0;
 }
 
+// ---- host-buffer staging: the pools of the four pipelines and their slot protocol (StageRing, engine_internal.hpp); caller holds stage_lock ----
+int32_t stage_init(const kzg_ctx* ctx) {
+  if (ctx->stage_ready) return 0;
+  bool ok = hipStreamCreateWithFlags(&ctx->verify_stream, hipStreamNonBlocking) == hipSuccess &&
+            hipStreamCreateWithFlags(&ctx->stage_copy_stream, hipStreamNonBlocking) == hipSuccess;
+  for (int r = 0; r < KZG_STAGE_STREAMS && ok; r++)
+    ok = hipStreamCreateWithFlags(&ctx->stage_streams[r], hipStreamNonBlocking) == hipSuccess &&
+         hipEventCreateWithFlags(&ctx->stage_join[r], hipEventDisableTiming) == hipSuccess;
+  for (int k = 0; k < KZG_STAGE_SLOTS && ok; k++)
+    ok = hipEventCreateWithFlags(&ctx->stage_copied[k], hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&ctx->stage_done[k], hipEventDisableTiming) == hipSuccess;
+  if (!ok) {
+    stage_destroy(ctx);
+    return fail(KZG_FAIL_HIP, "staging pipeline: stream/event creation failed");
+  }
+  ctx->stage_ready = true;
+  return 0;
+}
+// the arena and the small-result pool only grow; a call that needs more than any before re-allocates
+int32_t stage_reserve(const kzg_ctx* ctx, size_t arena_bytes, size_t io_bytes) {
+  if (ctx->stage_bytes < arena_bytes) {
+    if (ctx->stage) {
+      HIP_TRY(hipDeviceSynchronize());
+      (void)hipFree(ctx->stage);
+    }
+    ctx->stage = nullptr;
+    ctx->stage_bytes = 0;
+    if (hipMalloc(&ctx->stage, arena_bytes) != hipSuccess) return fail(KZG_FAIL_HIP, "hipMalloc(staging arena) failed");
+    ctx->stage_bytes = arena_bytes;
+  }
+  if (ctx->hostio_bytes < io_bytes) {
+    if (ctx->hostio) {
+      HIP_TRY(hipDeviceSynchronize());
+      (void)hipFree(ctx->hostio);
+    }
+    ctx->hostio = nullptr;
+    ctx->hostio_bytes = 0;
+    const size_t want = io_bytes + io_bytes / 4;
+    if (hipMalloc(&ctx->hostio, want) != hipSuccess) return fail(KZG_FAIL_HIP, "hipMalloc(host i/o pool) failed");
+    ctx->hostio_bytes = want;
+  }
+  return 0;
+}
+void stage_destroy(const kzg_ctx* ctx) {
+  if (ctx->stage) (void)hipFree(ctx->stage);
+  ctx->stage = nullptr;
+  ctx->stage_bytes = 0;
+  if (ctx->hostio) (void)hipFree(ctx->hostio);
+  ctx->hostio = nullptr;
+  ctx->hostio_bytes = 0;
+  if (ctx->verify_stream) (void)hipStreamDestroy(ctx->verify_stream);
+  if (ctx->stage_copy_stream) (void)hipStreamDestroy(ctx->stage_copy_stream);
+  ctx->verify_stream = ctx->stage_copy_stream = nullptr;
+  for (int r = 0; r < KZG_STAGE_STREAMS; r++) {
+    if (ctx->stage_streams[r]) (void)hipStreamDestroy(ctx->stage_streams[r]);
+    if (ctx->stage_join[r]) (void)hipEventDestroy(ctx->stage_join[r]);
+    ctx->stage_streams[r] = nullptr;
+    ctx->stage_join[r] = nullptr;
+  }
+  for (int k = 0; k < KZG_STAGE_SLOTS; k++) {
+    if (ctx->stage_copied[k]) (void)hipEventDestroy(ctx->stage_copied[k]);
+    if (ctx->stage_done[k]) (void)hipEventDestroy(ctx->stage_done[k]);
+    ctx->stage_copied[k] = ctx->stage_done[k] = nullptr;
+  }
+  ctx->stage_ready = false;
+}
+void stage_drain(const kzg_ctx* ctx) {
+  (void)hipStreamSynchronize(ctx->stage_copy_stream);
+  for (int r = 0; r < KZG_STAGE_STREAMS; r++) (void)hipStreamSynchronize(ctx->stage_streams[r]);
+}
+int32_t stream_after(hipStream_t waiter, hipStream_t signaller, hipEvent_t ev) {
+  HIP_TRY(hipEventRecord(ev, signaller));
+  HIP_TRY(hipStreamWaitEvent(waiter, ev, 0));
+  return 0;
+}
+int32_t StageRing::open(const kzg_ctx* c, uint64_t nslots, size_t bytes_per_slot, size_t io_bytes, bool overlap_copies) {
+  ctx = c, slots = nslots, slot_bytes = bytes_per_slot, overlap = overlap_copies;
+  if (slots < 1 || slots > (uint64_t)KZG_STAGE_SLOTS) return fail(KZG_FAIL_ARGUMENT, "staging ring: slot count out of range");
+  const int32_t rc = stage_init(ctx);
+  return rc ? rc : stage_reserve(ctx, slots * slot_bytes, io_bytes);
+}
+int32_t StageRing::feed(uint64_t k, const uint8_t* host_src, size_t bytes, hipStream_t comp, uint8_t** d_chunk) {
+  const uint64_t slot = k % slots;
+  hipStream_t copy_st = overlap ? ctx->stage_copy_stream : comp;
+  if (bytes > slot_bytes) return fail(KZG_FAIL_ARGUMENT, "staging ring: chunk larger than its slot");
+  *d_chunk = ctx->stage + slot * slot_bytes;
+  if (copy_st != comp && k >= slots) HIP_TRY(hipStreamWaitEvent(copy_st, ctx->stage_done[slot], 0));
+  HIP_TRY(hipMemcpyAsync(*d_chunk, host_src, bytes, hipMemcpyHostToDevice, copy_st));
+  return copy_st != comp ? stream_after(comp, copy_st, ctx->stage_copied[slot]) : 0;
+}
+hipEvent_t StageRing::done_event(uint64_t k) const { return ctx->stage_done[k % slots]; }
+int32_t StageRing::consumed(uint64_t k, hipStream_t comp) {
+  HIP_TRY(hipEventRecord(done_event(k), comp));
+  return 0;
+}
 
 static void tables_free(CombTables& t);
 const MsmOverride* (*g_msm_override_hook)(kzg_ctx* ctx, uint32_t window_bits) = nullptr;  // set only by the test-only library (tests/window_msm)
@@ -1128,24 +1223,19 @@ int32_t commit_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_
   uint64_t max_chunk = 0;
   for (uint64_t m : plan) max_chunk = m > max_chunk ? m : max_chunk;
   // Pooled resources: the staging arena, the result buffers, the streams and the events belong to the context
-  // (stage_lock), so a steady-state call allocates nothing; the streams are ordered by events only -- the host never waits
-  // inside the loop.
+  // (stage_lock), so a steady-state call allocates nothing.
   std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
-  int32_t rc = stage_init(ctx);
+  // A call of ONE chunk (single blobs -- the drop-in's common case -- up to a few thousand) rides on one stream, copy included.
+  const bool piped = plan.size() > 1;
+  const uint64_t nslots = piped ? 2 : 1;
+  Carve io;
+  const size_t o_res = io.take((size_t)n * (out48 ? 48 : 96)), o_st = io.take((size_t)n * sizeof(int32_t));
+  StageRing ring;
+  int32_t rc = ring.open(ctx, nslots, (size_t)max_chunk * KZG_BYTES_PER_BLOB, io.off, piped);
   if (rc) return rc;
-  const uint64_t nslots = plan.size() > 1 ? 2 : 1;
-  const size_t slot_bytes = (size_t)max_chunk * KZG_BYTES_PER_BLOB;
-  const size_t out_bytes = align_up((size_t)n * (out48 ? 48 : 96), 256);
-  rc = stage_reserve(ctx, nslots * slot_bytes, out_bytes + (size_t)n * sizeof(int32_t));
-  if (rc) return rc;
-  uint8_t* d_res = ctx->hostio;
-  int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + out_bytes);
-  // A call of ONE chunk (single blobs -- the drop-in's common case -- up to a few thousand) rides on one stream, copy included:
-  // every event between two streams is a packet on one hardware queue waiting for a signal from another (~0.1 ms each with a
-  // queue per stream), and there is nothing to overlap.
-  const bool one_chunk = plan.size() == 1;
+  uint8_t* d_res = ctx->hostio + o_res;
+  int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
   hipStream_t comp[2] = {ctx->stage_streams[0], ctx->stage_streams[1]};
-  hipStream_t copy_st = one_chunk ? comp[0] : ctx->stage_copy_stream;
   std::lock_guard<std::mutex> guard(ctx->lock);  // the workspace: per slot the lane sums, the sums and the bit-plane masks of a chunk
   WsCall ws(ctx, comp[0]);
   uint64_t max_units = 1;  // launch shapes follow the table in use, which only changes under this lock
@@ -1155,52 +1245,37 @@ int32_t commit_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_
     max_units = units > max_units ? units : max_units;
   }
   do {
-    const size_t partial_bytes = align_up((size_t)max_units * 65 * sizeof(g1_xyzz), 256);
-    const size_t sums_bytes = align_up((size_t)max_chunk * sizeof(g1_xyzz), 256);
-    const size_t scratch_bytes = align_up(msm_scratch_bytes(ctx, max_chunk), 256);
-    const size_t per_slot = partial_bytes + sums_bytes + scratch_bytes;
+    Carve per_slot;
+    const size_t o_part = per_slot.take((size_t)max_units * 65 * sizeof(g1_xyzz)), o_sums = per_slot.take((size_t)max_chunk * sizeof(g1_xyzz)),
+                 o_masks = per_slot.take(msm_scratch_bytes(ctx, max_chunk));
     rc = ws.begin();
-    if (rc == 0) rc = ws_reserve(ctx, nslots * per_slot, comp[0]);
-    if (rc == 0 && !one_chunk) rc = ws_wait(ctx, comp[1]);
+    if (rc == 0) rc = ws_reserve(ctx, nslots * per_slot.off, comp[0]);
+    if (rc == 0 && piped) rc = ws_wait(ctx, comp[1]);
     if (rc) break;
-    if (hipMemsetAsync(d_status, 0, n * sizeof(int32_t), comp[0]) != hipSuccess ||
-        (!one_chunk && (hipEventRecord(ctx->stage_join[0], comp[0]) != hipSuccess || hipStreamWaitEvent(comp[1], ctx->stage_join[0], 0) != hipSuccess))) {
+    if (hipMemsetAsync(d_status, 0, n * sizeof(int32_t), comp[0]) != hipSuccess) {
       rc = fail(KZG_FAIL_HIP, "memset failed");
       break;
     }
+    if (piped) rc = stream_after(comp[1], comp[0], ctx->stage_join[0]);
     uint64_t base = 0;
     for (size_t k = 0; k < plan.size() && rc == 0; base += plan[k], k++) {
       const int slot = (int)(k & 1);  // staging slot = workspace slot = compute stream
       const uint64_t m = plan[k];
       const uint32_t splits = choose_splits(ctx, m);
       const uint32_t lpb = msm_lanes_per_blob(ctx, m, splits);
-      uint8_t* wslot = ws_ptr(ctx) + (size_t)slot * per_slot;
-      g1_xyzz* partials = reinterpret_cast<g1_xyzz*>(wslot);
-      g1_xyzz* sums = reinterpret_cast<g1_xyzz*>(wslot + partial_bytes);
-      // chunk k-2 (same slot) must have been transposed out of the staging buffer before it is overwritten
-      if (k >= 2 && hipStreamWaitEvent(copy_st, ctx->stage_done[slot], 0) != hipSuccess) {
-        rc = fail(KZG_FAIL_HIP, "stream wait failed");
-        break;
-      }
-      if (hipMemcpyAsync(ctx->stage + (size_t)slot * slot_bytes, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB,
-                         hipMemcpyHostToDevice, copy_st) != hipSuccess ||
-          (!one_chunk && (hipEventRecord(ctx->stage_copied[slot], copy_st) != hipSuccess ||
-                          hipStreamWaitEvent(comp[slot], ctx->stage_copied[slot], 0) != hipSuccess))) {
-        rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
-        break;
-      }
-      rc = msm_launch(ctx, true, ctx->stage + (size_t)slot * slot_bytes, m, d_status + base, partials, splits, lpb, wslot + partial_bytes + sums_bytes,
-                            comp[slot], ctx->stage_done[slot]);
+      uint8_t* wslot = ws_ptr(ctx) + (size_t)slot * per_slot.off;
+      g1_xyzz* partials = reinterpret_cast<g1_xyzz*>(wslot + o_part);
+      g1_xyzz* sums = reinterpret_cast<g1_xyzz*>(wslot + o_sums);
+      uint8_t* d_chunk = nullptr;
+      rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, comp[slot], &d_chunk);
+      // msm_launch records done_event(k) behind the bit-plane transposition
+      if (rc == 0) rc = msm_launch(ctx, true, d_chunk, m, d_status + base, partials, splits, lpb, wslot + o_masks, comp[slot], ring.done_event(k));
       if (rc == 0)
         rc = msm_finish(ctx, m, out48 ? d_res + base * 48 : nullptr, out_affine96 ? d_res + base * 96 : nullptr, d_status + base, partials, sums, splits, lpb,
                         comp[slot]);
     }
-    if (rc) break;
-    if (!one_chunk && (hipEventRecord(ctx->stage_join[1], comp[1]) != hipSuccess || hipStreamWaitEvent(comp[0], ctx->stage_join[1], 0) != hipSuccess)) {
-      rc = fail(KZG_FAIL_HIP, "stream join failed");
-      break;
-    }
-    rc = ws.end();
+    if (rc == 0 && piped) rc = stream_after(comp[0], comp[1], ctx->stage_join[1]);
+    if (rc == 0) rc = ws.end();
     if (rc) break;
     if (hipMemcpyAsync(out48 ? out48 : out_affine96, d_res, (size_t)n * (out48 ? 48 : 96), hipMemcpyDeviceToHost, comp[0]) != hipSuccess ||
         hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, comp[0]) != hipSuccess ||

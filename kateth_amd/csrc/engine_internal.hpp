@@ -1,4 +1,5 @@
-// Shared by the engine translation units (engine.hip, engine_proof.hip, engine_verify.hip).
+// Shared by the engine translation units (engine.hip, engine_proof.hip, engine_verify.hip).  Besides the kernels below, engine.hip owns the
+// context's pools -- the workspace slots (ws_*) and the host-buffer staging (stage_*, StageRing) -- and tears them down in kzg_ctx_destroy.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -262,9 +263,9 @@ struct kzg_ctx {
   // pooled verify sessions (device scratch + side stream + events), engine_verify.hip
   mutable std::mutex pool_lock;
   mutable std::vector<kzg_verify_session*> session_pool;
-  // host-buffer pipelines (verification: engine_verify.hip; commitments: engine.hip; proofs: engine_proof.hip), guarded by
+  // host-buffer pipelines (verification, evaluation: engine_verify.hip; commitments: engine.hip; proofs: engine_proof.hip), guarded by
   // stage_lock, so that a steady-state host-buffer call allocates nothing: a staging arena of up to
-  // KZG_STAGE_SLOTS chunk slots, a copy stream, rotating compute streams and their events; created on first use
+  // KZG_STAGE_SLOTS chunk slots, a copy stream, rotating compute streams and their events; created on first use (StageRing)
   mutable std::mutex stage_lock;
   mutable uint8_t* stage = nullptr;
   mutable size_t stage_bytes = 0;
@@ -324,9 +325,33 @@ struct GroupDevShare {
   hipStream_t st;
 };
 int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& shares, uint64_t n_total, int32_t* ok);  // engine_verify.hip
-int32_t stage_init(const kzg_ctx* ctx);                                             // caller holds stage_lock
-int32_t stage_reserve(const kzg_ctx* ctx, size_t arena_bytes, size_t io_bytes);   // caller holds stage_lock
+// ---- host-buffer staging (engine.hip), all of it with ctx->stage_lock held ----
+int32_t stage_init(const kzg_ctx* ctx);                                          // streams and events, on first use
+int32_t stage_reserve(const kzg_ctx* ctx, size_t arena_bytes, size_t io_bytes);  // the arena and the host-i/o pool only grow
+void stage_drain(const kzg_ctx* ctx);  // failure path: the host waits for the copy stream and every stage stream
 void stage_destroy(const kzg_ctx* ctx);
+// record `ev` on `signaller`, then `waiter` waits for it
+int32_t stream_after(hipStream_t waiter, hipStream_t signaller, hipEvent_t ev);
+// The slot protocol of the four host-buffer pipelines (commit_host, proof_host, verify_phase1_host, evaluate_blobs_single), stated once.
+// The caller's blobs cross PCIe in chunks through `slots` equal slots of the context's staging arena; chunk k lives in slot k % slots:
+//   feed(k)      the copy stream waits for the slot's previous consumer (done_event(k - slots), when k >= slots), copies the chunk in and
+//                records the slot's `copied` event, for which `comp` -- the stream the caller enqueues the chunk's work on -- waits;
+//   consumed(k)  records done_event(k) on `comp` behind that work.  A consumer that is done with the slot earlier records done_event(k)
+//                itself (msm_launch's scalars_consumed).
+// Streams are ordered by events only: the host never waits.  `overlap` = false (a plan of ONE chunk: nothing to overlap): the copy rides
+// on `comp` itself and stream order does it all -- every event between two streams is a packet on one hardware queue waiting for a signal
+// from another (~0.1 ms each with a queue per stream).
+// overlap = false requires a single compute stream: every feed() of the call names the same `comp`.
+struct StageRing {
+  const kzg_ctx* ctx = nullptr;
+  uint64_t slots = 1;
+  size_t slot_bytes = 0;
+  bool overlap = true;
+  int32_t open(const kzg_ctx* c, uint64_t nslots, size_t bytes_per_slot, size_t io_bytes, bool overlap_copies);  // stage_init + stage_reserve
+  int32_t feed(uint64_t k, const uint8_t* host_src, size_t bytes, hipStream_t comp, uint8_t** d_chunk);
+  hipEvent_t done_event(uint64_t k) const;
+  int32_t consumed(uint64_t k, hipStream_t comp);
+};
 
 // workspace of the call being enqueued (caller holds ctx->lock from ws_begin to ws_end)
 int32_t ws_begin(const kzg_ctx* ctx, hipStream_t st);    // takes the next slot; `st` waits for the slot's previous user
@@ -370,6 +395,10 @@ struct ProfScope {
 };
 uint32_t choose_splits(const kzg_ctx* ctx, uint64_t n);
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+struct Carve {  // hands out 256-byte aligned offsets into a pooled buffer; `off` = the bytes asked of the pool so far
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
+};
 static inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 // Every translation unit carries its kernels in a code object of its own, which the HIP runtime loads at the unit's FIRST launch --

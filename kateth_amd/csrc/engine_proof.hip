@@ -19,23 +19,18 @@ static ProofLayout proof_layout(const kzg_ctx* ctx, uint64_t n) {
   const uint64_t chunk_max = ctx->knobs.proof_chunk ? ctx->knobs.proof_chunk : 16384;
   L.cn = n < chunk_max ? n : chunk_max;
   L.splits = choose_splits(ctx, L.cn);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carve ws;
   for (int sl = 0; sl < 2; sl++) {
-    L.o_z[sl] = take(L.cn * sizeof(fr_t));
-    L.o_ir[sl] = take(2 * L.cn * sizeof(fr_t));  // per blob: 1 / prod (z - w_i) and (z^4096 - 1) / 4096
-    L.o_y[sl] = take(L.cn * sizeof(fr_t));
-    L.o_cs[sl] = take(L.cn * sizeof(int32_t));
-    L.o_q[sl] = take(L.cn * 4096 * sizeof(fr_t));
+    L.o_z[sl] = ws.take(L.cn * sizeof(fr_t));
+    L.o_ir[sl] = ws.take(2 * L.cn * sizeof(fr_t));  // per blob: 1 / prod (z - w_i) and (z^4096 - 1) / 4096
+    L.o_y[sl] = ws.take(L.cn * sizeof(fr_t));
+    L.o_cs[sl] = ws.take(L.cn * sizeof(int32_t));
+    L.o_q[sl] = ws.take(L.cn * 4096 * sizeof(fr_t));
   }
-  L.o_part = take(L.cn * L.splits * 65 * sizeof(g1_xyzz));  // 64 lane sums + 1 unit sum per (blob, split)
-  L.o_sum = take(L.cn * sizeof(g1_xyzz));
-  L.o_msm = take(msm_scratch_bytes(ctx, L.cn));
-  L.total = off;
+  L.o_part = ws.take(L.cn * L.splits * 65 * sizeof(g1_xyzz));  // 64 lane sums + 1 unit sum per (blob, split)
+  L.o_sum = ws.take(L.cn * sizeof(g1_xyzz));
+  L.o_msm = ws.take(msm_scratch_bytes(ctx, L.cn));
+  L.total = ws.off;
   return L;
 }
 
@@ -179,8 +174,6 @@ int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
-  int32_t rc = stage_init(ctx);
-  if (rc) return rc;
   constexpr uint64_t PASS = 4096;
   std::vector<uint64_t> plan;
   {
@@ -194,16 +187,11 @@ int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side
   }
   uint64_t max_pass = 0;
   for (uint64_t m : plan) max_pass = m > max_pass ? m : max_pass;
-  const uint64_t nslots = plan.size() > 1 ? 2 : 1;
-  const size_t slot_bytes = (size_t)max_pass * KZG_BYTES_PER_BLOB;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  const size_t o_side = take(n * side_bytes), o_out = take(n * 48), o_aff = take(n * 96), o_y = take(n * 32), o_st = take(n * sizeof(int32_t));
-  rc = stage_reserve(ctx, nslots * slot_bytes, off);
+  const bool piped = plan.size() > 1;  // one pass: nothing to overlap, the copy rides on the compute stream
+  Carve io;
+  const size_t o_side = io.take(n * side_bytes), o_out = io.take(n * 48), o_aff = io.take(n * 96), o_y = io.take(n * 32), o_st = io.take(n * sizeof(int32_t));
+  StageRing ring;
+  int32_t rc = ring.open(ctx, piped ? 2 : 1, (size_t)max_pass * KZG_BYTES_PER_BLOB, io.off, piped);
   if (rc) return rc;
   uint8_t* d_side = ctx->hostio + o_side;
   uint8_t* d_out = out48 ? ctx->hostio + o_out : nullptr;
@@ -211,8 +199,6 @@ int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side
   uint8_t* d_y = ctx->hostio + o_y;
   int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
   hipStream_t st = ctx->stage_streams[0];  // an idle non-blocking stream (the null stream would serialise against every blocking stream of the process)
-  const bool one_pass = plan.size() == 1;  // nothing to overlap: the copy rides on the compute stream, no event between hardware queues
-  hipStream_t copy_st = one_pass ? st : ctx->stage_copy_stream;
   std::lock_guard<std::mutex> guard(ctx->lock);
   WsCall ws(ctx, st);
   do {
@@ -226,23 +212,14 @@ int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side
     if (rc == 0) rc = ws_reserve(ctx, proof_layout(ctx, max_pass).total, st);
     uint64_t base = 0;
     for (size_t k = 0; k < plan.size() && rc == 0; base += plan[k], k++) {
-      const int slot = (int)(k & 1);
       const uint64_t m = plan[k];
-      uint8_t* d_blobs = ctx->stage + (size_t)slot * slot_bytes;
-      // pass k-2 (same slot) must be done with the staging buffer before it is overwritten
-      if (k >= 2 && hipStreamWaitEvent(copy_st, ctx->stage_done[slot], 0) != hipSuccess) {
-        rc = fail(KZG_FAIL_HIP, "stream wait failed");
-        break;
-      }
-      if (hipMemcpyAsync(d_blobs, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, hipMemcpyHostToDevice, copy_st) != hipSuccess ||
-          (!one_pass && (hipEventRecord(ctx->stage_copied[slot], copy_st) != hipSuccess || hipStreamWaitEvent(st, ctx->stage_copied[slot], 0) != hipSuccess))) {
-        rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
-        break;
-      }
-      rc = proof_dev_locked(ctx, d_blobs, side_is_commitment ? d_side + base * side_bytes : nullptr, side_is_commitment ? nullptr : d_side + base * side_bytes,
-                            m, d_out ? d_out + base * 48 : nullptr, d_aff ? d_aff + base * 96 : nullptr, out_y32 ? d_y + base * 32 : nullptr,
-                            d_status + base, st);
-      if (rc == 0 && hipEventRecord(ctx->stage_done[slot], st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "event record failed");
+      uint8_t* d_blobs = nullptr;
+      rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, st, &d_blobs);
+      if (rc == 0)
+        rc = proof_dev_locked(ctx, d_blobs, side_is_commitment ? d_side + base * side_bytes : nullptr, side_is_commitment ? nullptr : d_side + base * side_bytes,
+                              m, d_out ? d_out + base * 48 : nullptr, d_aff ? d_aff + base * 96 : nullptr, out_y32 ? d_y + base * 32 : nullptr,
+                              d_status + base, st);
+      if (rc == 0) rc = ring.consumed(k, st);
     }
     if (rc) break;
     rc = ws.end();

@@ -223,34 +223,29 @@ static MsmVarLayout msm_var_layout(const kzg_ctx* ctx, uint64_t nterms, bool glv
   if (nterms == 0) return L;
   L.g = choose_var_geom(ctx, nterms, glv, seg_total);
   L.nb = L.g.W * L.g.half;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  L.o_counts = take((size_t)(L.nb + 1) * 4);
-  L.o_offsets = take((size_t)(L.nb + 1) * 4);
-  L.o_cursors = take((size_t)(L.nb + 1) * 4);
-  L.o_entries = take((size_t)nterms * L.g.W * 4);
+  Carve pool;
+  L.o_counts = pool.take((size_t)(L.nb + 1) * 4);
+  L.o_offsets = pool.take((size_t)(L.nb + 1) * 4);
+  L.o_cursors = pool.take((size_t)(L.nb + 1) * 4);
+  L.o_entries = pool.take((size_t)nterms * L.g.W * 4);
   // split every bucket over K threads (power of two <= 64) so that a thread chains ~16 additions
   if (L.g.top_n) {  // flat path: partials only for the top window; one output point per (window, bit)
-    L.o_part = take((size_t)L.g.top_n * L.g.ktop * sizeof(g1_xyzz28));
-    L.o_bsum = take((size_t)L.nb * sizeof(g1_xyzz28));
-    L.o_win = take((size_t)L.g.W * L.g.c * sizeof(g1_xyzz));
+    L.o_part = pool.take((size_t)L.g.top_n * L.g.ktop * sizeof(g1_xyzz28));
+    L.o_bsum = pool.take((size_t)L.nb * sizeof(g1_xyzz28));
+    L.o_win = pool.take((size_t)L.g.W * L.g.c * sizeof(g1_xyzz));
     if (L.g.seg) {
       L.nseg = (uint32_t)((nterms * (uint64_t)(L.g.W - 1u) + L.g.seg - 1u) / L.g.seg);
-      L.o_seg = take((size_t)L.nseg * 2u * sizeof(g1_xyzz28));
+      L.o_seg = pool.take((size_t)L.nseg * 2u * sizeof(g1_xyzz28));
     }
-    L.total = off;
+    L.total = pool.off;
     return L;
   }
   uint64_t load = nterms / L.g.half + 1;
   while (L.K < 64 && (uint64_t)L.K * 16 < load) L.K <<= 1;
-  L.o_part = take((size_t)L.nb * L.K * sizeof(g1_xyzz28));
-  L.o_bsum = take((size_t)L.nb * sizeof(g1_xyzz28));
-  L.o_win = take((size_t)L.g.W * sizeof(g1_xyzz));
-  L.total = off;
+  L.o_part = pool.take((size_t)L.nb * L.K * sizeof(g1_xyzz28));
+  L.o_bsum = pool.take((size_t)L.nb * sizeof(g1_xyzz28));
+  L.o_win = pool.take((size_t)L.g.W * sizeof(g1_xyzz));
+  L.total = pool.off;
   return L;
 }
 
@@ -412,32 +407,27 @@ struct SessionLayout {
 static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n) {
   SessionLayout L{};
   const uint64_t groups = (n + 255) / 256;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carve pool;
   const bool glv = use_glv(ctx, n);
-  L.o_aff = take((glv ? 2 : 1) * (2 * n + 1) * 96);  // GLV: the [z^2]-images behind the points
-  L.o_inf = take(2 * n + 1);
-  L.o_z = take(n * 32 + 32);
-  L.o_y = take(n * 32 + 32);
-  L.o_scal = take((2 * n + 1) * 32);
-  L.o_glv_b = take(glv ? 2 * (2 * n + 1) * 32 : 0);
-  L.o_glv_a = take(glv ? 2 * n * 32 : 0);
-  L.o_stat = take(4 * n * 4 + 4);
-  L.o_first4 = take(4 * sizeof(unsigned long long));
-  L.o_leaves = take(n * 32 + 32);
-  L.o_mids = take((n / 16 + 1) * 32 + 32);
-  L.o_nodes = take(groups * 32 + 32);
-  L.o_pts = take(2 * n * 48 + 48);
-  L.o_zy = take(2 * n * 32 + 32);
-  L.o_msm_a = take((glv ? msm_var_layout(ctx, 2 * n, true) : msm_var_layout(ctx, n, false, 3 * n + 1)).total + 256);
-  L.o_msm_b = take((glv ? msm_var_layout(ctx, 2 * (2 * n + 1), true) : msm_var_layout(ctx, 2 * n + 1, false, 3 * n + 1)).total + 256);
-  L.o_rpow = take(64 * 32);
-  L.o_ysum = take(((n + 255) / 256 + 1) * 32);
-  L.total = off;
+  L.o_aff = pool.take((glv ? 2 : 1) * (2 * n + 1) * 96);  // GLV: the [z^2]-images behind the points
+  L.o_inf = pool.take(2 * n + 1);
+  L.o_z = pool.take(n * 32 + 32);
+  L.o_y = pool.take(n * 32 + 32);
+  L.o_scal = pool.take((2 * n + 1) * 32);
+  L.o_glv_b = pool.take(glv ? 2 * (2 * n + 1) * 32 : 0);
+  L.o_glv_a = pool.take(glv ? 2 * n * 32 : 0);
+  L.o_stat = pool.take(4 * n * 4 + 4);
+  L.o_first4 = pool.take(4 * sizeof(unsigned long long));
+  L.o_leaves = pool.take(n * 32 + 32);
+  L.o_mids = pool.take((n / 16 + 1) * 32 + 32);
+  L.o_nodes = pool.take(groups * 32 + 32);
+  L.o_pts = pool.take(2 * n * 48 + 48);
+  L.o_zy = pool.take(2 * n * 32 + 32);
+  L.o_msm_a = pool.take((glv ? msm_var_layout(ctx, 2 * n, true) : msm_var_layout(ctx, n, false, 3 * n + 1)).total + 256);
+  L.o_msm_b = pool.take((glv ? msm_var_layout(ctx, 2 * (2 * n + 1), true) : msm_var_layout(ctx, 2 * n + 1, false, 3 * n + 1)).total + 256);
+  L.o_rpow = pool.take(64 * 32);
+  L.o_ysum = pool.take(((n + 255) / 256 + 1) * 32);
+  L.total = pool.off;
   return L;
 }
 
@@ -770,72 +760,6 @@ extern "C" int32_t kzg_verify_phase1_dev(const kzg_ctx* ctx, const void* d_blobs
   return abi_exception();
 }
 
-int32_t stage_init(const kzg_ctx* ctx) {  // caller holds stage_lock
-  if (ctx->stage_ready) return 0;
-  bool ok = hipStreamCreateWithFlags(&ctx->verify_stream, hipStreamNonBlocking) == hipSuccess &&
-            hipStreamCreateWithFlags(&ctx->stage_copy_stream, hipStreamNonBlocking) == hipSuccess;
-  for (int r = 0; r < KZG_STAGE_STREAMS && ok; r++)
-    ok = hipStreamCreateWithFlags(&ctx->stage_streams[r], hipStreamNonBlocking) == hipSuccess &&
-         hipEventCreateWithFlags(&ctx->stage_join[r], hipEventDisableTiming) == hipSuccess;
-  for (int k = 0; k < KZG_STAGE_SLOTS && ok; k++)
-    ok = hipEventCreateWithFlags(&ctx->stage_copied[k], hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&ctx->stage_done[k], hipEventDisableTiming) == hipSuccess;
-  if (!ok) {
-    stage_destroy(ctx);
-    return fail(KZG_FAIL_HIP, "staging pipeline: stream/event creation failed");
-  }
-  ctx->stage_ready = true;
-  return 0;
-}
-// the arena and the small-result pool only grow; a call that needs more than any before re-allocates (caller holds stage_lock)
-int32_t stage_reserve(const kzg_ctx* ctx, size_t arena_bytes, size_t io_bytes) {
-  if (ctx->stage_bytes < arena_bytes) {
-    if (ctx->stage) {
-      HIP_TRY(hipDeviceSynchronize());
-      (void)hipFree(ctx->stage);
-    }
-    ctx->stage = nullptr;
-    ctx->stage_bytes = 0;
-    if (hipMalloc(&ctx->stage, arena_bytes) != hipSuccess) return fail(KZG_FAIL_HIP, "hipMalloc(staging arena) failed");
-    ctx->stage_bytes = arena_bytes;
-  }
-  if (ctx->hostio_bytes < io_bytes) {
-    if (ctx->hostio) {
-      HIP_TRY(hipDeviceSynchronize());
-      (void)hipFree(ctx->hostio);
-    }
-    ctx->hostio = nullptr;
-    ctx->hostio_bytes = 0;
-    const size_t want = io_bytes + io_bytes / 4;
-    if (hipMalloc(&ctx->hostio, want) != hipSuccess) return fail(KZG_FAIL_HIP, "hipMalloc(host i/o pool) failed");
-    ctx->hostio_bytes = want;
-  }
-  return 0;
-}
-void stage_destroy(const kzg_ctx* ctx) {
-  if (ctx->stage) (void)hipFree(ctx->stage);
-  ctx->stage = nullptr;
-  ctx->stage_bytes = 0;
-  if (ctx->hostio) (void)hipFree(ctx->hostio);
-  ctx->hostio = nullptr;
-  ctx->hostio_bytes = 0;
-  if (ctx->verify_stream) (void)hipStreamDestroy(ctx->verify_stream);
-  if (ctx->stage_copy_stream) (void)hipStreamDestroy(ctx->stage_copy_stream);
-  ctx->verify_stream = ctx->stage_copy_stream = nullptr;
-  for (int r = 0; r < KZG_STAGE_STREAMS; r++) {
-    if (ctx->stage_streams[r]) (void)hipStreamDestroy(ctx->stage_streams[r]);
-    if (ctx->stage_join[r]) (void)hipEventDestroy(ctx->stage_join[r]);
-    ctx->stage_streams[r] = nullptr;
-    ctx->stage_join[r] = nullptr;
-  }
-  for (int k = 0; k < KZG_STAGE_SLOTS; k++) {
-    if (ctx->stage_copied[k]) (void)hipEventDestroy(ctx->stage_copied[k]);
-    if (ctx->stage_done[k]) (void)hipEventDestroy(ctx->stage_done[k]);
-    ctx->stage_copied[k] = ctx->stage_done[k] = nullptr;
-  }
-  ctx->stage_ready = false;
-}
-
 // Host-buffer phase 1: the blobs cross PCIe in chunks through the context's staging arena (slots of `chunk` blobs) on the
 // copy stream while the per-blob kernels (challenge + evaluation are per blob) of earlier chunks run on rotating compute
 // streams -- the n * 128 KiB never have to be resident at once and the transfer overlaps the hashing.  Commitments and
@@ -846,12 +770,6 @@ int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
   TraceTimer tt(ctx->knobs.trace, "phase1(host buffers)");
   if (err6) err_clear(err6, 3);
   std::lock_guard<std::mutex> guard(ctx->stage_lock);  // the arena and the copy/compute streams below are shared
-  int32_t rc = stage_init(ctx);
-  if (rc) return rc;
-  hipStream_t st = ctx->verify_stream;
-  kzg_verify_session* s = nullptr;
-  rc = session_acquire(ctx, n, st, &s);
-  if (rc) return rc;
   // Chunk size: the SHA-256 kernel of a chunk is latency-bound (~3.7 ms whether it hashes 512 or 16,384 blobs), so chunks
   // are LARGE -- a quarter of the batch, between 512 and 4,096 blobs (512 MiB, ~9 ms of PCIe) -- and the copy of chunk k+1
   // hides the hash + evaluation of chunk k (measured with 512-blob chunks on four streams: 63 ms per 16,384 blobs, the
@@ -863,58 +781,49 @@ int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
     chunk = chunk < 512 ? 512 : (chunk > 4096 ? 4096 : chunk);
   }
   const uint64_t nchunks = (n + chunk - 1) / chunk;
-  const uint64_t slots = nchunks < KZG_STAGE_SLOTS ? nchunks : KZG_STAGE_SLOTS;
   // Compute streams the chunks rotate over: TWO.  With a hardware queue per stream (GPU_MAX_HW_QUEUES >= 8) four independent
   // chunk streams put four chunks' hash and evaluation kernels on the chip at once and the LAST chunk's latency-bound hash --
   // the call's critical path: it cannot start before its copy ends -- shares SIMDs with its predecessors' waves: 16.5 instead of
   // 15.0 ms per 4,096 triples (two or three streams: 15.0; one: 18.9; at 16,384 triples all the same, 44.2).  Round 3's four
   // streams only did well because the runtime's default of four hardware queues folded them onto fewer.
   const uint64_t nstreams = ctx->knobs.verify_streams ? ctx->knobs.verify_streams : 2;
-  const size_t slot_bytes = (size_t)chunk * KZG_BYTES_PER_BLOB;
+  StageRing ring;
+  int32_t rc = ring.open(ctx, nchunks < KZG_STAGE_SLOTS ? nchunks : KZG_STAGE_SLOTS, (size_t)chunk * KZG_BYTES_PER_BLOB, 0, nchunks > 1);
+  if (rc) return rc;
+  hipStream_t st = ctx->verify_stream;
+  kzg_verify_session* s = nullptr;
+  rc = session_acquire(ctx, n, st, &s);
+  if (rc) return rc;
   do {
-    rc = stage_reserve(ctx, slots * slot_bytes, 0);
-    if (rc) break;
     uint8_t* prf = s->pts48;
     uint8_t* com = s->pts48 + n * 48;
+    uint8_t* d_chunk = nullptr;
     if (hipMemcpyAsync(prf, proofs48, n * 48, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(com, commitments48, n * 48, hipMemcpyHostToDevice, st) != hipSuccess) {
       rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
       break;
     }
     if (nchunks == 1) {
-      // a single chunk (small batches, single items): nothing to overlap -- one copy, then the device path's launches
-      // (hash and point decoding fused in one launch: the latency-optimal shape)
-      if (hipMemcpyAsync(ctx->stage, blobs, n * (size_t)KZG_BYTES_PER_BLOB, hipMemcpyHostToDevice, st) != hipSuccess) {
-        rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
-        break;
-      }
-      rc = phase1_items(s, ctx->stage, com, prf, 0, n, st, true);
+      // a single chunk (small batches, single items): nothing to overlap -- one copy on the session's stream, then the device path's
+      // launches (hash and point decoding fused in one launch: the latency-optimal shape)
+      rc = ring.feed(0, blobs, n * (size_t)KZG_BYTES_PER_BLOB, st, &d_chunk);
+      if (rc == 0) rc = phase1_items(s, d_chunk, com, prf, 0, n, st, true);
     } else {
       // all points decoded once, beside the chunk pipeline
       decode_on_side(s, s->side, 0, 2 * n, prf, com, DECODE_WHOLE | DECODE_FINISH);
-      for (int r = 0; r < KZG_STAGE_STREAMS; r++) (void)hipStreamWaitEvent(ctx->stage_streams[r], s->ev_fork, 0);  // session initialised, points resident (all of them: the join below is over all)
+      // session initialised, points resident: decode_on_side has recorded ev_fork (all stage streams wait: the join below is over all)
+      for (int r = 0; r < KZG_STAGE_STREAMS && rc == 0; r++)
+        if (hipStreamWaitEvent(ctx->stage_streams[r], s->ev_fork, 0) != hipSuccess) rc = fail(KZG_FAIL_HIP, "stream wait failed");
       for (uint64_t k = 0; k < nchunks && rc == 0; k++) {
-        const uint64_t slot = k % slots;
         const uint64_t base = k * chunk;
         const uint64_t m = (n - base < chunk) ? (n - base) : chunk;
         hipStream_t comp = ctx->stage_streams[k % nstreams];
-        uint8_t* d_chunk = ctx->stage + slot * slot_bytes;
-        if (k >= slots) (void)hipStreamWaitEvent(ctx->stage_copy_stream, ctx->stage_done[slot], 0);  // the chunk that used this slot has been consumed
-        if (hipMemcpyAsync(d_chunk, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, hipMemcpyHostToDevice,
-                           ctx->stage_copy_stream) != hipSuccess) {
-          rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
-          break;
-        }
-        (void)hipEventRecord(ctx->stage_copied[slot], ctx->stage_copy_stream);
-        (void)hipStreamWaitEvent(comp, ctx->stage_copied[slot], 0);
-        rc = phase1_items(s, d_chunk, com, prf, base, m, comp, false);
-        (void)hipEventRecord(ctx->stage_done[slot], comp);
+        rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, comp, &d_chunk);
+        if (rc == 0) rc = phase1_items(s, d_chunk, com, prf, base, m, comp, false);
+        if (rc == 0) rc = ring.consumed(k, comp);
       }
       // join the compute streams into the session's stream
-      for (int r = 0; r < KZG_STAGE_STREAMS; r++) {
-        (void)hipEventRecord(ctx->stage_join[r], ctx->stage_streams[r]);
-        (void)hipStreamWaitEvent(st, ctx->stage_join[r], 0);
-      }
+      for (int r = 0; r < KZG_STAGE_STREAMS && rc == 0; r++) rc = stream_after(st, ctx->stage_streams[r], ctx->stage_join[r]);
     }
     if (rc) break;
     tt.mark("enqueue copies + per-chunk kernels");
@@ -932,8 +841,7 @@ int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
     tt.mark("gpu kernels + readback + root hash (+ status scan)");
   } while (0);
   if (rc) {
-    (void)hipStreamSynchronize(ctx->stage_copy_stream);
-    for (int r = 0; r < KZG_STAGE_STREAMS; r++) (void)hipStreamSynchronize(ctx->stage_streams[r]);
+    stage_drain(ctx);
     session_drain(s);
     kzg_verify_session_destroy(s);
     return rc;
@@ -986,10 +894,11 @@ int32_t g1_decompress_single(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n
   std::lock_guard<std::mutex> guard(ctx->stage_lock);  // pooled device buffers + an idle stream of the host-buffer pipelines
   int32_t rc = stage_init(ctx);
   if (rc) return rc;
-  const size_t o_out = align_up((size_t)n * 48, 256), o_st = o_out + align_up((size_t)n * 96, 256);
-  rc = stage_reserve(ctx, 0, o_st + (size_t)n * sizeof(int32_t));
+  Carve io;
+  const size_t o_in = io.take((size_t)n * 48), o_out = io.take((size_t)n * 96), o_st = io.take((size_t)n * sizeof(int32_t));
+  rc = stage_reserve(ctx, 0, io.off);
   if (rc) return rc;
-  uint8_t* d_in = ctx->hostio;
+  uint8_t* d_in = ctx->hostio + o_in;
   uint8_t* d_out = ctx->hostio + o_out;
   int32_t* d_st = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
   hipStream_t st = ctx->stage_streams[0];
@@ -1020,22 +929,20 @@ extern "C" int32_t kzg_evaluate_blobs(const kzg_ctx* ctx, const uint8_t* blobs, 
 int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status) {
   HIP_TRY(hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> guard(ctx->stage_lock);  // pooled device buffers + idle streams of the host-buffer pipelines
-  int32_t rc = stage_init(ctx);
-  if (rc) return rc;
   const uint64_t chunk = n < 2048 ? n : 2048;
   const uint64_t nchunks = (n + chunk - 1) / chunk;
-  const uint64_t slots = nchunks > 1 ? 2 : 1;
-  const size_t slot_bytes = (size_t)chunk * KZG_BYTES_PER_BLOB;
-  const size_t o_y32 = align_up((size_t)n * 32, 256), o_z = o_y32 + align_up((size_t)n * 32, 256), o_y = o_z + align_up((size_t)n * sizeof(fr_t), 256);
-  const size_t o_st = o_y + align_up((size_t)n * sizeof(fr_t), 256);
-  rc = stage_reserve(ctx, slots * slot_bytes, o_st + (size_t)n * sizeof(int32_t));
+  Carve io;
+  const size_t o_z32 = io.take((size_t)n * 32), o_y32 = io.take((size_t)n * 32), o_z = io.take((size_t)n * sizeof(fr_t)), o_y = io.take((size_t)n * sizeof(fr_t)),
+               o_st = io.take((size_t)n * sizeof(int32_t));
+  StageRing ring;  // the copy stream even for one chunk
+  int32_t rc = ring.open(ctx, nchunks > 1 ? 2 : 1, (size_t)chunk * KZG_BYTES_PER_BLOB, io.off, true);
   if (rc) return rc;
-  uint8_t* d_z32 = ctx->hostio;
+  uint8_t* d_z32 = ctx->hostio + o_z32;
   uint8_t* d_y32 = ctx->hostio + o_y32;
   fr_t* d_z = reinterpret_cast<fr_t*>(ctx->hostio + o_z);
   fr_t* d_y = reinterpret_cast<fr_t*>(ctx->hostio + o_y);
   int32_t* d_st = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
-  hipStream_t st = ctx->stage_streams[0], copy_st = ctx->stage_copy_stream;
+  hipStream_t st = ctx->stage_streams[0];
   do {
     if (hipMemcpyAsync(d_z32, z32, (size_t)n * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemsetAsync(d_st, 0, (size_t)n * sizeof(int32_t), st) != hipSuccess) {
@@ -1046,15 +953,11 @@ int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const ui
     bool wide_groups = n < 4096;
     if (ctx->knobs.eval_group) wide_groups = ctx->knobs.eval_group != 16;
     for (uint64_t k = 0; k < nchunks && rc == 0; k++) {
-      const uint64_t slot = k % slots, base = k * chunk;
+      const uint64_t base = k * chunk;
       const uint64_t m = (n - base < chunk) ? (n - base) : chunk;
-      uint8_t* d_blobs = ctx->stage + slot * slot_bytes;
-      if (k >= slots) (void)hipStreamWaitEvent(copy_st, ctx->stage_done[slot], 0);  // the chunk that used this slot has been evaluated
-      if (hipMemcpyAsync(d_blobs, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, hipMemcpyHostToDevice, copy_st) != hipSuccess ||
-          hipEventRecord(ctx->stage_copied[slot], copy_st) != hipSuccess || hipStreamWaitEvent(st, ctx->stage_copied[slot], 0) != hipSuccess) {
-        rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
-        break;
-      }
+      uint8_t* d_blobs = nullptr;
+      rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, st, &d_blobs);
+      if (rc) break;
       {
         ProfScope ps(ctx, PROF_EVAL, st);
         if (!wide_groups)
@@ -1064,7 +967,7 @@ int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const ui
           hipLaunchKernelGGL(k_eval_frac<64>, dim3((unsigned)m), dim3(64), 0, st, d_blobs, d_z + base, ctx->d_roots_brp, ctx->d_eval_tab, d_y + base,
                              d_st + base, m);
       }
-      (void)hipEventRecord(ctx->stage_done[slot], st);
+      rc = ring.consumed(k, st);
     }
     if (rc) break;
     launch_fr_store_be(st, d_y, n, d_st, d_y32);
@@ -1072,10 +975,7 @@ int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const ui
         hipMemcpyAsync(status, d_st, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
       rc = fail(KZG_FAIL_HIP, "evaluation: launch or read-back failed");
   } while (0);
-  if (rc) {
-    (void)hipStreamSynchronize(copy_st);
-    (void)hipStreamSynchronize(st);
-  }
+  if (rc) stage_drain(ctx);
   return rc;
 }
 

@@ -177,6 +177,26 @@ def test_evaluate_blobs_across_staging_chunks(engine, torch_cuda):
     assert ys2[: 2055 * 32] == y[: 2055 * 32] and ys2[2055 * 32:2056 * 32] == bytes(32) and ys2[2056 * 32:] == y[2056 * 32:2060 * 32]
 
 
+def test_evaluate_blobs_reuses_a_staging_slot(engine, torch_cuda):
+    """4,100 pairs are chunks of 2,048, 2,048 and 4 in two staging slots: the third chunk overwrites slot 0 (the smallest shape that
+    does), so its copy has to wait for the first chunk's evaluation.  Evaluated at each blob's own challenge, the results equal the
+    evaluations batch verification computed over the same device blobs, byte for byte; a non-canonical element in blob 4,097 (the
+    reused slot) is reported at its place with a zero output, and the other 4,099 results do not move"""
+    torch = torch_cuda
+    n, bad_i = 4100, 4097
+    d_blobs, d_c, d_p = _triples(engine, torch, n, 0x57A6)
+    sess, _, err6 = engine.verify_phase1_dev(d_blobs.data_ptr(), d_c.data_ptr(), d_p.data_ptr(), n)
+    z, y = engine.verify_session_zy(sess, 0, n)
+    engine.verify_session_destroy(sess)
+    hb = bytearray(d_blobs.cpu().numpy().tobytes())
+    ys, st = engine.evaluate_blobs(bytes(hb), z)
+    assert st == [0] * n and ys == y
+    hb[bad_i * 131072 + 64:bad_i * 131072 + 96] = R.to_bytes(32, "big")
+    ys2, st2 = engine.evaluate_blobs(bytes(hb), z)
+    assert st2 == [0] * bad_i + [2] + [0] * (n - bad_i - 1)
+    assert ys2[: bad_i * 32] == y[: bad_i * 32] and ys2[bad_i * 32:(bad_i + 1) * 32] == bytes(32) and ys2[(bad_i + 1) * 32:] == y[(bad_i + 1) * 32:]
+
+
 def test_point_decoder_at_batch_size_matches_the_oracle_decisions(engine):
     """P1::decompress (src/bls.rs:505-531) for 4,096 encodings in one call -- valid points, x with no square root, on-curve points
     outside the subgroup, x >= p, flag errors, infinity with stray bits: the engine's status equals the oracle's decision for

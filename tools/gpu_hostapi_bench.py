@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Host-buffer (PCIe-inclusive) throughput of the batch entry points: the caller's blobs live in host memory, as in
 kateth's byte-slice API.  Pageable memory (a Python bytes object) and pinned memory (torch pin_memory) are both timed;
-the device-resident rate of the same batch is printed beside them.  usage: gpu_hostapi_bench.py [n] [window_bits]"""
+the device-resident rate of the same batch is printed beside them; kzg_evaluate_blobs is timed over pageable memory.  usage: gpu_hostapi_bench.py [n] [window_bits]"""
 import ctypes
 import json
 import os
@@ -60,6 +60,12 @@ assert s.verify_blob_proof_batch_host(pin_b.data_ptr(), pin_c.data_ptr(), pin_p.
 rec("verify_host_pageable", timed(lambda: s.verify_blob_proof_batch_host(blobs, cs, ps, n)))
 rec("verify_host_pinned", timed(lambda: s.verify_blob_proof_batch_host(pin_b.data_ptr(), pin_c.data_ptr(), pin_p.data_ptr(), n)))
 rec("verify_dev", timed(lambda: s.verify_blob_proof_batch_dev(d_blobs.data_ptr(), d_c.data_ptr(), d_p.data_ptr(), n)))
+# Polynomial::evaluate over host buffers, each blob at its own challenge (z as batch verification computed it)
+sess, _, _ = s.verify_phase1_dev(d_blobs.data_ptr(), d_c.data_ptr(), d_p.data_ptr(), n)
+zs, ys = s.verify_session_zy(sess, 0, n)
+s.verify_session_destroy(sess)
+assert s.evaluate_blobs(blobs, zs) == (ys, [0] * n)
+rec("evaluate_host_pageable", timed(lambda: s.evaluate_blobs(blobs, zs)))
 # raw copy rates for reference
 t = timed(lambda: (d_blobs.copy_(pin_b, non_blocking=True), torch.cuda.synchronize()))
 out["h2d_pinned_GBps"] = n * 131072 / t / 1e9
