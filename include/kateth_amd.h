@@ -294,6 +294,42 @@ int32_t kzg_verify_proof_batch_group_dev(const kzg_ctx* ctx, const void* const* 
                                          const void* const* d_y32, const uint64_t* n_local, int32_t* ok, void* const* hip_streams);
 
 /*
+ * PER-ITEM VERDICTS: which items of a batch are bad.  What a caller of the reference does when Setup::verify_blob_proof_batch is
+ * false -- a loop over Setup::verify_blob_proof (src/kzg/setup.rs:208-221) or Setup::verify_proof (:96-113) -- answered from one
+ * batch call.  Inputs as kzg_verify_blob_proof_batch(_dev) / kzg_verify_proof_batch(_dev); ok_each (n bytes), status (n x int32)
+ * and ok are HOST memory in all four; the *_dev calls are synchronous like kzg_verify_*_batch_dev.
+ *   status[i]  the code kzg_verify_blob_proof / kzg_verify_proof returns for item i ALONE: 0, or the positive KZG_ERR_* of that
+ *              item's first rejected input in the single-item call's own parse order -- blob, commitment, proof
+ *              (src/kzg/setup.rs:214-217) or proof, commitment, z, y (:103-109).
+ *   ok_each[i] that call's *ok; 0 whenever status[i] != 0.
+ *   *ok        1 iff every status[i] == 0 and every ok_each[i] == 1.
+ *   n == 0     *ok = 1.  n == 1: the single-item call.
+ *   return     0, or a negative KZG_FAIL_*.  A rejected ITEM never makes the call return a positive code: it is reported in
+ *              status[], as the producers report theirs, and the other items still get their verdicts.
+ * How: one phase 1 for the whole batch.  If no item is rejected, the batch check runs first and true means every item is true.
+ * Otherwise the device computes per item A_i = [r_i] proof_i and B_i = [r_i] commitment_i + [r_i z_i] proof_i - [r_i y_i] G
+ * (r_i = r^i as in the batch check; a rejected item contributes the point at infinity), sums both level by level into a tree,
+ * and the host descends from the root spending one two-pairing check e(-A, [tau]_2) e(B, G2) == 1 per visited node: a node
+ * that passes clears its range; of a failing node the left child is checked and, if it passes, the right child fails without
+ * a check.  k false items among n cost at most 1 + 2 k ceil(log2 n) checks.  The leaf check is verify_proof_inner's equation
+ * (src/kzg/setup.rs:84-94) scaled by r_i != 0: the reference's boolean exactly.  An inner node that hides a false item passes
+ * with probability <= n / 2^255, the soundness statement of the batch call.
+ * GROUP context, host-buffer calls: the batch is cut into the same contiguous shares as kzg_verify_*_batch; each member runs
+ * the single-device call on its share as its own batch with its own challenge, writes its outputs in place, and *ok is the
+ * AND (a verdict does not depend on r: nothing is merged).  The *_dev calls act on member 0.
+ * kzg_verify_each_checks: the two-pairing checks these calls have spent on `ctx` so far (all members; measurement aid).
+ */
+int32_t kzg_verify_blob_proof_batch_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n,
+                                         uint8_t* ok_each, int32_t* status, int32_t* ok);
+int32_t kzg_verify_blob_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_proofs48, uint64_t n,
+                                             uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream);
+int32_t kzg_verify_proof_batch_each(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                    uint8_t* ok_each, int32_t* status, int32_t* ok);
+int32_t kzg_verify_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32, uint64_t n,
+                                        uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream);
+uint64_t kzg_verify_each_checks(const kzg_ctx* ctx);
+
+/*
  * DEVICE-RESIDENT sharded calls on a GROUP context (kzg_config.devices / ndev): member k's share of the batch is resident on
  * member k's GPU -- what a node keeps when blobs arrive over the network or are produced on the devices, and the only way a
  * group verifies faster than PCIe delivers (host-buffer verification tops out near 0.37 M blobs/s per GPU, device-resident
@@ -347,6 +383,17 @@ void kzg_verify_session_destroy(kzg_verify_session* session);
  * y_i (Polynomial::evaluate, src/kzg/poly.rs:10-33) phase 1 computed for items [first, first+count), 32 B big-endian each */
 int32_t kzg_verify_session_zy(kzg_verify_session* session, uint64_t first, uint64_t count, uint8_t* out_z32, uint8_t* out_y32);
 int32_t kzg_verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint64_t world, int32_t* ok);
+/*
+ * The per-item terms of a session after phase 1 and their sum trees (the device half of kzg_verify_*_batch_each, for the
+ * per-rank protocol and for tests).  kzg_verify_session_tree seeds r exactly as kzg_verify_phase2_dev does and builds, in the
+ * session, A_i and B_i of every LOCAL item with r_i = r^(first_index + i) and both sum trees; a rejected item contributes the
+ * point at infinity to both.  kzg_verify_session_tree_range returns A || B summed over the local items [lo, hi), composed
+ * from whole tree nodes, as 2 x 96 bytes in kzg_verify_phase2_dev's format: with every item accepted, the range [0, n_local)
+ * is byte for byte that call's out192 on the same session.  The tree storage (about 50 MB at 65,536 items) belongs to the
+ * session: allocated on first use, handed back to the pool with it; a caller that never asks for it pays nothing.
+ */
+int32_t kzg_verify_session_tree(kzg_verify_session* session, const uint8_t* roots32, uint64_t world, uint64_t first_index, uint64_t n_total);
+int32_t kzg_verify_session_tree_range(kzg_verify_session* session, uint64_t lo, uint64_t hi, uint8_t* out192);
 /*
  * Phase 1 of kzg_verify_proof_batch for a rank's n_local tuples (z and y from the caller instead of the hash and the
  * evaluation): err8 = {proof_idx, proof_code, commitment_idx, commitment_code, z_idx, z_code, y_idx, y_code}, LOCAL index of

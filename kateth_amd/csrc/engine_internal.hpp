@@ -263,6 +263,7 @@ struct kzg_ctx {
   // pooled verify sessions (device scratch + side stream + events), engine_verify.hip
   mutable std::mutex pool_lock;
   mutable std::vector<kzg_verify_session*> session_pool;
+  mutable std::atomic<uint64_t> each_checks{0};  // pairing checks spent by the per-item verdict calls so far (kzg_verify_each_checks)
   // host-buffer pipelines (verification, evaluation: engine_verify.hip; commitments: engine.hip; proofs: engine_proof.hip), guarded by
   // stage_lock, so that a steady-state host-buffer call allocates nothing: a staging arena of up to
   // KZG_STAGE_SLOTS chunk slots, a copy stream, rotating compute streams and their events; created on first use (StageRing)
@@ -294,6 +295,11 @@ int32_t verify_proof_batch_host_single(const kzg_ctx* ctx, const uint8_t* proofs
                                        int32_t* ok);
 int32_t verify_proof_phase1_host(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
                                  uint8_t* out_root32, int32_t* err8, kzg_verify_session** session);
+// per-item verdicts over host buffers (engine_verify.hip): one device's batch, with its own challenge
+int32_t verify_blob_each_host_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, uint8_t* ok_each,
+                                     int32_t* status, int32_t* ok);
+int32_t verify_proof_each_host_single(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                      uint8_t* ok_each, int32_t* status, int32_t* ok);
 int32_t g1_decompress_single(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
 int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
 // engine_multi.hip
@@ -305,6 +311,10 @@ int32_t multi_verify_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
 int32_t multi_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok);
 int32_t multi_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
                                  int32_t* ok);
+int32_t multi_verify_blob_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, uint8_t* ok_each,
+                               int32_t* status, int32_t* ok);
+int32_t multi_verify_proof_each(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                uint8_t* ok_each, int32_t* status, int32_t* ok);
 int32_t multi_g1_decompress(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
 int32_t multi_evaluate_blobs(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
 // The device-resident inputs of one batch verification call (engine_verify.hip: front_enqueue / front_status switch on `kind`).

@@ -162,6 +162,39 @@ int32_t multi_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, co
   });
 }
 
+// Per-item verdicts (kzg_verify_*_batch_each) over the members: the same contiguous shares, each member's share its own batch with its
+// own challenge -- an item's verdict does not depend on r, so the outputs land in place and nothing is merged but the AND.
+int32_t multi_verify_blob_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, uint8_t* ok_each,
+                               int32_t* status, int32_t* ok) {
+  *ok = 0;
+  const std::vector<Share> shares = shares_of(ctx, n);
+  std::vector<int32_t> oks(shares.size(), 0);
+  const int32_t rc = run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
+    const Share& sh = shares[j];
+    return verify_blob_each_host_single(member_of(ctx, sh.member), blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, commitments48 + sh.first * 48,
+                                        proofs48 + sh.first * 48, sh.count, ok_each + sh.first, status + sh.first, &oks[j]);
+  });
+  if (rc) return rc;
+  *ok = 1;
+  for (int32_t o : oks) *ok &= o;
+  return 0;
+}
+int32_t multi_verify_proof_each(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                uint8_t* ok_each, int32_t* status, int32_t* ok) {
+  *ok = 0;
+  const std::vector<Share> shares = shares_of(ctx, n);
+  std::vector<int32_t> oks(shares.size(), 0);
+  const int32_t rc = run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
+    const Share& sh = shares[j];
+    return verify_proof_each_host_single(member_of(ctx, sh.member), proofs48 + sh.first * 48, commitments48 + sh.first * 48, z32 + sh.first * 32,
+                                         y32 + sh.first * 32, sh.count, ok_each + sh.first, status + sh.first, &oks[j]);
+  });
+  if (rc) return rc;
+  *ok = 1;
+  for (int32_t o : oks) *ok &= o;
+  return 0;
+}
+
 // ---- device-resident sharded calls (include/kateth_amd.h: kzg_*_group_dev) -------------------------------------------------
 // Member k's share is resident on member k's GPU.  Commitments and proofs only ENQUEUE (like the *_dev calls), one pooled host
 // thread per member so that the members' launches go out side by side; nothing is gathered -- results stay where they were

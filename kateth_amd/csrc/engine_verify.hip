@@ -11,6 +11,7 @@
 #include <thread>
 #include "verify_kernels.cuh"
 #include "host_lincomb.hpp"
+#include "each_descent.hpp"
 // A verification session: device scratch for n items, a second stream (point decoding beside the evaluation kernel,
 // lincomb A beside lincomb B) and its fork/join events.  Sessions are POOLED in the context (kzg_ctx::session_pool): a
 // call takes one (growing its buffer if the batch is larger than any before), and kzg_verify_session_destroy hands it
@@ -50,11 +51,24 @@ struct kzg_verify_session {
   uint32_t* h_nodes = nullptr;  // [ceil(n / 256) * 8]
   unsigned long long* h_first4 = nullptr;  // [4] read-back of first4
   size_t h_cap = 0;
+  bool points = false;       // the front was verify_proof_batch's: the status arrays are z / commitment / proof / y
+  // per-item verdicts (kzg_verify_*_batch_each, kzg_verify_session_tree): a device allocation of its own (owned), made on first use
+  // and kept with the pooled session; carved by each_carve for the current n
+  uint8_t* tree = nullptr;
+  size_t tree_cap = 0;
+  uint64_t tree_n = 0;             // items the trees stand for; 0 = not built in this use of the session
+  int32_t* t_status = nullptr;     // [n] the single-item call's code per item (k_each_status)
+  uint32_t* t_rejected = nullptr;  // [1] how many of them are non-zero
+  g1_xyzz28* t_a = nullptr;        // both trees, level after level from the leaves (EachGeom::off)
+  g1_xyzz28* t_b = nullptr;
+  uint32_t* t_idx = nullptr;       // [EACH_GATHER] node positions of one fetch
+  g1_xyzz* t_out = nullptr;        // [2 EACH_GATHER] the fetched nodes, A and B side by side
 };
 
 static void session_free(kzg_verify_session* s) {
   if (!s) return;
   if (s->buf) (void)hipFree(s->buf);
+  if (s->tree) (void)hipFree(s->tree);
   if (s->h_stat) (void)hipHostFree(s->h_stat);
   if (s->side) (void)hipStreamDestroy(s->side);
   if (s->aux) (void)hipStreamDestroy(s->aux);
@@ -504,6 +518,8 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
   if (st == KZG_SESSION_STREAM) st = s->side;
   s->n = n;
   s->st = st;
+  s->points = false;
+  s->tree_n = 0;
   s->aff = (uint4*)(s->buf + L.o_aff);
   s->inf = s->buf + L.o_inf;
   s->z = (fr_t*)(s->buf + L.o_z);
@@ -675,6 +691,7 @@ static int32_t front_enqueue(kzg_verify_session* s, const VerifyInputs& in) {
       return rc ? rc : p1_transcript(s, com, prf);
     }
     case VerifyInputs::POINTS: {
+      s->points = true;
       // the decoder is ONE launch over proofs and commitments: no event after the proof half for lincomb A to wait on instead of ev_join
       decode_on_side(s, s->side, 0, 2 * n, prf, com, DECODE_FINISH | (fused_prep_fits(ctx, n, 2 * n) ? DECODE_WHOLE : 0u));
       if (hipMemsetAsync(s->first4, 0xff, 4 * sizeof(unsigned long long), s->side) != hipSuccess)  // for k_first_errors, later on this stream
@@ -1030,9 +1047,9 @@ struct Phase2 {
   MsmVarJob ja, jb;
 };
 // (a) r = hash_to_fr("RCKZGBATCH___V1_" || u128(4096) || u128(n_total) || roots); scalars r_i, r_i z_i, -sum r_i y_i on `st`
-static int32_t p2_scalars(kzg_verify_session* s, const uint8_t* roots32, uint64_t world, uint64_t first_index, uint64_t n_total) {
+//     p2_seed: r and its powers r^(2^k) into the session, on `st` (also the seed of the per-item terms, kzg_verify_session_tree)
+static int32_t p2_seed(kzg_verify_session* s, const uint8_t* roots32, uint64_t world, uint64_t n_total) {
   hipStream_t st = s->st;
-  const uint64_t n = s->n;
   std::vector<uint8_t> msg(48 + 32 * world);
   memcpy(msg.data(), "RCKZGBATCH___V1_", 16);
   memset(msg.data() + 16, 0, 32);
@@ -1048,8 +1065,15 @@ static int32_t p2_scalars(kzg_verify_session* s, const uint8_t* roots32, uint64_
   fr_t rpow2[64];
   rpow2[0] = r;
   for (int k = 1; k < 64; k++) fr_sqr(rpow2[k], rpow2[k - 1]);
-  const unsigned nblk = blocks_for(n, 256);
   if (hipMemcpyAsync(s->rpow2, rpow2, sizeof(rpow2), hipMemcpyHostToDevice, st) != hipSuccess) return fail(KZG_FAIL_HIP, "copy");  // pageable source: staged before the call returns
+  return 0;
+}
+static int32_t p2_scalars(kzg_verify_session* s, const uint8_t* roots32, uint64_t world, uint64_t first_index, uint64_t n_total) {
+  hipStream_t st = s->st;
+  const uint64_t n = s->n;
+  const int32_t rc = p2_seed(s, roots32, world, n_total);
+  if (rc) return rc;
+  const unsigned nblk = blocks_for(n, 256);
   hipLaunchKernelGGL(k_batch_scalars, dim3(nblk), dim3(256), 0, st, s->rpow2, s->z, s->y, n, first_index, s->scal + n, s->scal, s->ysum);
   hipLaunchKernelGGL(k_batch_ysum_finish, dim3(1), dim3(256), 0, st, s->ysum, nblk, s->scal + 2 * n);
   if (s->glv) hipLaunchKernelGGL(k_glv_split, dim3(blocks_for(2 * n + 1, 256)), dim3(256), 0, st, s->scal, n, s->glv_b, s->glv_a);
@@ -1593,6 +1617,349 @@ extern "C" int32_t kzg_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* pro
     return 0;
   }
   return (is_group(ctx) ? multi_verify_proof_batch : verify_proof_batch_host_single)(ctx, proofs48, commitments48, z32, y32, n, ok);
+} catch (...) {
+  return abi_exception();
+}
+
+// ---- per-item verdicts: kzg_verify_*_batch_each, kzg_verify_session_tree(_range) ------------------------------------------------------
+// What the reference's users do when a batch is false -- a loop over Setup::verify_blob_proof / verify_proof (src/kzg/setup.rs:208-221,
+// :96-113) -- answered from ONE phase 1: per item the single call's code (k_each_status over the session's status arrays) and its boolean.
+// Fast path: nothing rejected and the batch check true -> every item true, the terms kernel never runs.  Otherwise the per-item terms
+// A_i, B_i (k_each_terms) and their two sum trees (k_each_level) are built in the session and the host descends from the root
+// (each_descent.hpp), paying one two-pairing check per visited node: O(k log n) checks for k false items.  An inner node that hides a
+// false item passes with probability <= n / 2^255 -- the batch call's own soundness statement, per subtree.
+constexpr uint32_t EACH_GATHER = 4096;  // nodes per fetch (2 x 192 bytes each)
+struct EachGeom {
+  uint32_t height = 0;        // the root's level
+  std::vector<uint64_t> off;  // off[l]: position of level l's first node; off[height + 1] = all nodes
+};
+static EachGeom each_geom(uint64_t n) {
+  EachGeom g;
+  g.height = kzg::each::tree_height(n);
+  g.off.assign(g.height + 2, 0);
+  for (uint32_t l = 0; l <= g.height; l++) g.off[l + 1] = g.off[l] + kzg::each::level_count(n, l);
+  return g;
+}
+// the session's tree storage for its current n (about 50 MB at 65,536 items; grown on demand, freed with the session)
+static int32_t each_reserve(kzg_verify_session* s, const EachGeom& g) {
+  const uint64_t n = s->n, total = g.off[g.height + 1];
+  if (total >> 32) return fail(KZG_FAIL_ARGUMENT, "per-item verdicts: batch too large");
+  Carve c;
+  const size_t o_status = c.take(n * sizeof(int32_t)), o_rej = c.take(sizeof(uint32_t)), o_a = c.take(total * sizeof(g1_xyzz28)),
+               o_b = c.take(total * sizeof(g1_xyzz28)), o_idx = c.take(EACH_GATHER * sizeof(uint32_t)), o_out = c.take(2 * EACH_GATHER * sizeof(g1_xyzz));
+  if (s->tree_cap < c.off) {
+    if (s->tree) (void)hipFree(s->tree);
+    s->tree = nullptr;
+    s->tree_cap = 0;
+    const size_t want = c.off + c.off / 8;
+    if (hipMalloc(&s->tree, want) != hipSuccess) return fail(KZG_FAIL_HIP, "hipMalloc(per-item verdict trees) failed");
+    s->tree_cap = want;
+  }
+  s->t_status = reinterpret_cast<int32_t*>(s->tree + o_status);
+  s->t_rejected = reinterpret_cast<uint32_t*>(s->tree + o_rej);
+  s->t_a = reinterpret_cast<g1_xyzz28*>(s->tree + o_a);
+  s->t_b = reinterpret_cast<g1_xyzz28*>(s->tree + o_b);
+  s->t_idx = reinterpret_cast<uint32_t*>(s->tree + o_idx);
+  s->t_out = reinterpret_cast<g1_xyzz*>(s->tree + o_out);
+  return 0;
+}
+// per-item codes in the single-item call's parse order -- blob, commitment, proof (src/kzg/setup.rs:214-217) or proof, commitment, z, y
+// (:103-109) -- on the caller's stream, behind the front's kernels there and the decoder (ev_join)
+static int32_t each_status_enqueue(kzg_verify_session* s) {
+  const uint64_t n = s->n;
+  hipStream_t st = s->st;
+  if (hipStreamWaitEvent(st, s->ev_join, 0) != hipSuccess || hipMemsetAsync(s->t_rejected, 0, sizeof(uint32_t), st) != hipSuccess)
+    return fail(KZG_FAIL_HIP, "per-item verdicts: status enqueue failed");
+  if (s->points)
+    hipLaunchKernelGGL(k_each_status, dim3(blocks_for(n, 256)), dim3(256), 0, st, s->stat + 2 * n, s->stat + n, s->stat, s->stat + 3 * n, n, s->t_status, s->t_rejected);
+  else
+    hipLaunchKernelGGL(k_each_status, dim3(blocks_for(n, 256)), dim3(256), 0, st, s->stat, s->stat + n, s->stat + 2 * n, (const int32_t*)nullptr, n, s->t_status,
+                       s->t_rejected);
+  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "per-item verdicts: status launch failed");
+  return 0;
+}
+// terms and both trees, on the caller's stream behind each_status_enqueue and the seed (p2_seed)
+static int32_t each_build(kzg_verify_session* s, const EachGeom& g, uint64_t first_index) {
+  const uint64_t n = s->n;
+  hipStream_t st = s->st;
+  hipLaunchKernelGGL(k_each_terms, dim3(2 * blocks_for(n, 64)), dim3(64), 0, st, s->rpow2, s->z, s->y, s->aff, s->t_status, n, first_index, s->t_a, s->t_b);
+  for (uint32_t l = 0; l < g.height; l++) {
+    const uint64_t cin = g.off[l + 1] - g.off[l], cout = g.off[l + 2] - g.off[l + 1];
+    hipLaunchKernelGGL(k_each_level, dim3(blocks_for(2 * cout, 64)), dim3(64), 0, st, s->t_a + g.off[l], s->t_b + g.off[l], cin, s->t_a + g.off[l + 1],
+                       s->t_b + g.off[l + 1], cout);
+  }
+  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "per-item verdicts: tree launch failed");
+  s->tree_n = n;
+  return 0;
+}
+// nodes at `pos` (positions in the node arrays) of both trees -> out[2 k] = A's, out[2 k + 1] = B's; synchronous
+static int32_t each_fetch(kzg_verify_session* s, const std::vector<uint32_t>& pos, std::vector<g1_xyzz>& out) {
+  hipStream_t st = s->st;
+  out.resize(2 * pos.size());
+  for (size_t done = 0; done < pos.size(); done += EACH_GATHER) {
+    const uint32_t m = (uint32_t)std::min<size_t>(EACH_GATHER, pos.size() - done);
+    if (hipMemcpyAsync(s->t_idx, pos.data() + done, m * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess)
+      return fail(KZG_FAIL_HIP, "per-item verdicts: node fetch failed");
+    hipLaunchKernelGGL(k_each_gather, dim3(blocks_for(2 * (uint64_t)m, 64)), dim3(64), 0, st, s->t_a, s->t_b, s->t_idx, m, s->t_out);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out.data() + 2 * done, s->t_out, 2 * (size_t)m * sizeof(g1_xyzz), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return fail(KZG_FAIL_HIP, "per-item verdicts: node fetch failed");
+  }
+  return 0;
+}
+// The descent over the session's trees: ok_each[i] = the leaf check of item i.  A level's nodes come back in one fetch and are checked
+// side by side on the helper pool: to affine, two Miller loops, one final exponentiation each (host::verify_pairings_fixed).
+static int32_t each_descend(kzg_verify_session* s, const EachGeom& g, uint8_t* ok_each) {
+  const kzg_ctx* ctx = s->ctx;
+  TraceTimer tt(ctx->knobs.trace, "per-item verdicts: descent");
+  uint64_t checks = 0;
+  std::vector<uint32_t> pos;
+  std::vector<g1_xyzz> nodes;
+  const int32_t rc = kzg::each::descend(s->n, ok_each, [&](uint32_t level, const uint64_t* idx, size_t m, uint8_t* pass) -> int32_t {
+    pos.resize(m);
+    for (size_t k = 0; k < m; k++) pos[k] = (uint32_t)(g.off[level] + idx[k]);
+    const int32_t r = each_fetch(s, pos, nodes);
+    if (r) return r;
+    checks += m;
+    std::atomic<size_t> next{0};
+    const uint32_t hw = std::thread::hardware_concurrency();
+    const uint32_t workers = (uint32_t)std::min<size_t>(m, std::max(1u, std::min(16u, hw)));
+    return run_on_helpers(workers, [&](uint32_t) -> int32_t {
+      for (size_t k = next.fetch_add(1); k < m; k = next.fetch_add(1)) {
+        host::g1_host_affine a, b;
+        host_affine_from_xyzz(a, nodes[2 * k]);
+        host_affine_from_xyzz(b, nodes[2 * k + 1]);
+        pass[k] = host::verify_pairings_fixed(*ctx->pairing, a, b) ? 1 : 0;
+      }
+      return 0;
+    });
+  });
+  ctx->each_checks.fetch_add(checks, std::memory_order_relaxed);
+  tt.mark("done");
+  return rc;
+}
+
+extern "C" int32_t kzg_verify_session_tree(kzg_verify_session* s, const uint8_t* roots32, uint64_t world, uint64_t first_index, uint64_t n_total) try {
+  if (!s || !roots32 || world == 0) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  s->tree_n = 0;
+  if (s->n == 0) return 0;
+  const EachGeom g = each_geom(s->n);
+  int32_t rc = each_reserve(s, g);
+  if (rc == 0) rc = p2_seed(s, roots32, world, n_total);
+  if (rc == 0) rc = each_status_enqueue(s);
+  if (rc == 0) rc = each_build(s, g, first_index);
+  if (rc == 0 && hipStreamSynchronize(s->st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "per-item verdicts: tree build failed");
+  if (rc) {
+    s->tree_n = 0;
+    session_drain(s);
+  }
+  return rc;
+} catch (...) {
+  return abi_exception();
+}
+
+extern "C" int32_t kzg_verify_session_tree_range(kzg_verify_session* s, uint64_t lo, uint64_t hi, uint8_t* out192) try {
+  if (!s || !out192 || lo > hi || hi > s->n) return fail(KZG_FAIL_ARGUMENT, "bad argument");
+  if (s->n && s->tree_n != s->n) return fail(KZG_FAIL_ARGUMENT, "kzg_verify_session_tree has not been called on this session");
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  g1_xyzz A, B;
+  xyzz_set_inf(A);
+  xyzz_set_inf(B);
+  if (lo < hi) {
+    // [lo, hi) as at most 2 log2 n whole subtrees
+    const EachGeom g = each_geom(s->n);
+    std::vector<uint32_t> pos;
+    uint64_t a = lo, b = hi;
+    for (uint32_t l = 0; a < b; l++, a >>= 1, b >>= 1) {
+      if (a & 1) pos.push_back((uint32_t)(g.off[l] + a++));
+      if (b & 1) pos.push_back((uint32_t)(g.off[l] + --b));
+    }
+    std::vector<g1_xyzz> nodes;
+    const int32_t rc = each_fetch(s, pos, nodes);
+    if (rc) return rc;
+    for (size_t k = 0; k < pos.size(); k++) {
+      xyzz_add(A, nodes[2 * k]);
+      xyzz_add(B, nodes[2 * k + 1]);
+    }
+  }
+  host::g1_host_affine a, b;
+  host_affine_from_xyzz(a, A);
+  host_affine_from_xyzz(b, B);
+  host_affine_to_be96(out192, a);
+  host_affine_to_be96(out192 + 96, b);
+  return 0;
+} catch (...) {
+  return abi_exception();
+}
+
+extern "C" uint64_t kzg_verify_each_checks(const kzg_ctx* ctx) {
+  if (!ctx) return 0;
+  uint64_t total = ctx->each_checks.load(std::memory_order_relaxed);
+  for (const kzg_ctx* p : ctx->peers) total += p->each_checks.load(std::memory_order_relaxed);
+  return total;
+}
+
+// one item: the single-item call's answer in the per-item outputs
+static int32_t each_from_single(int32_t rc, int32_t one_ok, uint8_t* ok_each, int32_t* status, int32_t* ok) {
+  if (rc < 0) return rc;
+  status[0] = rc;
+  ok_each[0] = (rc == 0 && one_ok) ? 1 : 0;
+  *ok = ok_each[0];
+  return 0;
+}
+// The ending of all four calls: the session's front is enqueued and its root taken (n >= 2).
+static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, uint8_t* ok_each, int32_t* status, int32_t* ok) {
+  const uint64_t n = s->n;
+  *ok = 0;
+  const EachGeom g = each_geom(n);
+  uint32_t rejected = 0;
+  int32_t rc = each_reserve(s, g);
+  if (rc == 0) rc = each_status_enqueue(s);
+  if (rc == 0 && (hipMemcpyAsync(status, s->t_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+                  hipMemcpyAsync(&rejected, s->t_rejected, sizeof(uint32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+                  hipStreamSynchronize(s->st) != hipSuccess))
+    rc = fail(KZG_FAIL_HIP, "per-item verdicts: status read-back failed");
+  if (rc) return rc;
+  if (rejected == 0) {  // today's batch check first: true = every item true
+    Phase2 p2;
+    int32_t all = 0;
+    rc = p2_scalars(s, root, 1, 0, n);
+    if (rc == 0) rc = p2_sort(s, p2, false);
+    if (rc == 0) rc = p2_accumulate(s, p2);
+    if (rc == 0) rc = p2_finish_and_pair(s, p2, &all);
+    if (rc) {
+      session_drain(s);  // before p2 goes
+      return rc;
+    }
+    if (all) {
+      memset(ok_each, 1, n);
+      *ok = 1;
+      return 0;
+    }
+  } else {
+    rc = p2_seed(s, root, 1, n);
+  }
+  if (rc == 0) rc = each_build(s, g, 0);
+  if (rc == 0) rc = each_descend(s, g, ok_each);
+  if (rc) return rc;
+  for (uint64_t i = 0; i < n; i++)
+    if (status[i]) ok_each[i] = 0;
+  return 0;  // *ok = 0: an item was rejected, or the batch check was false
+}
+
+extern "C" int32_t kzg_verify_blob_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_proofs48, uint64_t n,
+                                                        uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream) try {
+  if (!ctx || !ok || (n && (!d_blobs || !d_commitments48 || !d_proofs48 || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  *ok = 0;
+  if (n == 0) {
+    *ok = 1;
+    return 0;
+  }
+  if (n == 1) {
+    int32_t one = 0;
+    return each_from_single(kzg_verify_blob_proof_batch_dev(ctx, d_blobs, d_commitments48, d_proofs48, 1, &one, hip_stream), one, ok_each, status, ok);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  kzg_verify_session* s = nullptr;
+  int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
+  if (rc) return rc;
+  uint8_t root[32];
+  rc = front_enqueue(s, blob_inputs(d_blobs, d_commitments48, d_proofs48));
+  if (rc == 0) rc = p1_root(s, root);
+  if (rc == 0) rc = each_finish(s, root, ok_each, status, ok);
+  if (rc) session_drain(s);
+  kzg_verify_session_destroy(s);
+  return rc;
+} catch (...) {
+  return abi_exception();
+}
+
+extern "C" int32_t kzg_verify_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
+                                                   uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream) try {
+  if (!ctx || !ok || (n && (!d_proofs48 || !d_commitments48 || !d_z32 || !d_y32 || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  *ok = 0;
+  if (n == 0) {
+    *ok = 1;
+    return 0;
+  }
+  if (n == 1) {
+    int32_t one = 0;
+    return each_from_single(kzg_verify_proof_batch_dev(ctx, d_proofs48, d_commitments48, d_z32, d_y32, 1, &one, hip_stream), one, ok_each, status, ok);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  kzg_verify_session* s = nullptr;
+  int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
+  if (rc) return rc;
+  uint8_t root[32];
+  rc = front_enqueue(s, point_inputs(d_proofs48, d_commitments48, d_z32, d_y32));
+  if (rc == 0) rc = p1_root(s, root);
+  if (rc == 0) rc = each_finish(s, root, ok_each, status, ok);
+  if (rc) session_drain(s);
+  kzg_verify_session_destroy(s);
+  return rc;
+} catch (...) {
+  return abi_exception();
+}
+
+int32_t verify_blob_each_host_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, uint8_t* ok_each,
+                                     int32_t* status, int32_t* ok) {
+  *ok = 0;
+  if (n == 1) {
+    int32_t one = 0;
+    return each_from_single(verify_batch_host_single(ctx, blobs, commitments48, proofs48, 1, &one), one, ok_each, status, ok);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  uint8_t root[32];
+  int32_t err6[6];
+  kzg_verify_session* s = nullptr;
+  int32_t rc = verify_phase1_host(ctx, blobs, commitments48, proofs48, n, root, err6, &s);
+  if (rc) return rc;
+  rc = each_finish(s, root, ok_each, status, ok);
+  if (rc) session_drain(s);
+  kzg_verify_session_destroy(s);
+  return rc;
+}
+int32_t verify_proof_each_host_single(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
+                                      uint8_t* ok_each, int32_t* status, int32_t* ok) {
+  *ok = 0;
+  if (n == 1) {
+    int32_t one = 0;
+    return each_from_single(verify_proof_single(ctx, proofs48, commitments48, z32, y32, &one), one, ok_each, status, ok);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  kzg_verify_session* s = nullptr;
+  int32_t rc = points_stage_host(ctx, proofs48, commitments48, z32, y32, n, &s);
+  if (rc) return rc;
+  uint8_t root[32];
+  rc = front_enqueue(s, point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32));
+  if (rc == 0) rc = p1_root(s, root);
+  if (rc == 0) rc = each_finish(s, root, ok_each, status, ok);
+  if (rc) session_drain(s);
+  kzg_verify_session_destroy(s);
+  return rc;
+}
+extern "C" int32_t kzg_verify_blob_proof_batch_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n,
+                                                    uint8_t* ok_each, int32_t* status, int32_t* ok) try {
+  if (!ctx || !ok || (n && (!blobs || !commitments48 || !proofs48 || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  *ok = 0;
+  if (n == 0) {
+    *ok = 1;
+    return 0;
+  }
+  return (is_group(ctx) ? multi_verify_blob_each : verify_blob_each_host_single)(ctx, blobs, commitments48, proofs48, n, ok_each, status, ok);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_verify_proof_batch_each(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32,
+                                               uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok) try {
+  if (!ctx || !ok || (n && (!proofs48 || !commitments48 || !z32 || !y32 || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  *ok = 0;
+  if (n == 0) {
+    *ok = 1;
+    return 0;
+  }
+  return (is_group(ctx) ? multi_verify_proof_each : verify_proof_each_host_single)(ctx, proofs48, commitments48, z32, y32, n, ok_each, status, ok);
 } catch (...) {
   return abi_exception();
 }

@@ -1157,5 +1157,135 @@ static __global__ __launch_bounds__(256) void k_var_bitsums(const g1_xyzz28* __r
   }
 }
 
+// ---------------------------------------------------------------------------
+// Per-item verdicts (kzg_verify_*_batch_each): the two sums of the batch check item by item, and their sum tree.
+//   A_i = [r_i] proof_i        B_i = [r_i] commitment_i + [r_i z_i] proof_i - [r_i y_i] G        r_i = r^(first_index + i)
+// e(-A_i, [tau]_2) e(B_i, G2) = 1 is verify_proof_inner's equation (src/kzg/setup.rs:84-94) scaled by r_i != 0; the sums of the
+// leaves over a range are that range's share of the batch check's two lincombs (k_batch_scalars defines the same r_i).
+// ---------------------------------------------------------------------------
+// the single-item call's first error per item: st0..st3 in that call's parse order (st3 = null: three kinds); counts the rejected
+static __global__ __launch_bounds__(256) void k_each_status(const int32_t* __restrict__ st0, const int32_t* __restrict__ st1, const int32_t* __restrict__ st2,
+                                                           const int32_t* __restrict__ st3, uint64_t n, int32_t* __restrict__ status,
+                                                           uint32_t* __restrict__ rejected) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int32_t c = st0[i];
+  if (!c) c = st1[i];
+  if (!c) c = st2[i];
+  if (!c && st3) c = st3[i];
+  status[i] = c;
+  if (c) atomicAdd(rejected, 1u);
+}
+
+// One lane per leaf; the workgroups of the first half of the grid compute the A_i (a plain double-and-add ladder over r_i), those
+// of the second half the B_i (a three-base Straus ladder without a table: one doubling per bit for all three scalars, then up to
+// three mixed additions).  The doubling is uniform over the wave, the additions are masked by the lane's own scalar bits; the
+// bases are re-read per addition (96 bytes, L2-resident) rather than held, so the loop carries the accumulator, three scalars
+// and nothing else.  Radix-2^28 point arithmetic with the complete adder behind the cheap one, as in var_bucket_chain: proof_i
+// = +-commitment_i, +-G and the identity partway through all occur.  A point at infinity is an all-zero entry and is skipped; a
+// rejected item (status != 0) writes the identity to both trees.
+static __global__ __launch_bounds__(64, 2) void k_each_terms(const fr_t* __restrict__ rpow2, const fr_t* __restrict__ z_plain, const fr_t* __restrict__ y_plain,
+                                                            const uint4* __restrict__ aff, const int32_t* __restrict__ status, uint64_t n,
+                                                            uint64_t first_index, g1_xyzz28* __restrict__ leaves_a, g1_xyzz28* __restrict__ leaves_b) {
+  const uint32_t half = gridDim.x / 2u;
+  const bool is_b = blockIdx.x >= half;  // uniform over the workgroup
+  const uint64_t i = (uint64_t)(blockIdx.x - (is_b ? half : 0u)) * 64u + threadIdx.x;
+  if (i >= n) return;
+  g1_xyzz28* out = (is_b ? leaves_b : leaves_a) + i;
+  g1_xyzz28 acc;
+  xyzz28_set_inf(acc);
+  if (status[i]) {
+    *out = acc;
+    return;
+  }
+  // scalars (plain), bit 255 first after the shift below: s0 on proof_i, s1 on commitment_i, s2 on -G
+  fr_t s0, s1, s2;
+  {
+    const uint64_t e = first_index + i;
+    fr_t r = fr_one();
+    for (int k = 0; k < 64 && (e >> k); k++)
+      if ((e >> k) & 1) fr_mul(r, r, rpow2[k]);
+    if (is_b) {
+      fr_t zm, ym, t;
+      to_mont<FrParams>(zm, z_plain[i]);
+      to_mont<FrParams>(ym, y_plain[i]);
+      fr_mul(t, r, zm);
+      from_mont<FrParams>(s0, t);
+      from_mont<FrParams>(s1, r);
+      fr_mul(t, r, ym);
+      from_mont<FrParams>(s2, t);
+    } else {
+      from_mont<FrParams>(s0, r);
+      bn_zero(s1);
+      bn_zero(s2);
+    }
+  }
+  const uint32_t nbases = is_b ? 3u : 1u;
+  // scalars are below r < 2^255: bit 255 is dropped, 255 steps
+  auto shl1 = [](fr_t& s) {
+#pragma unroll
+    for (int q = 7; q > 0; q--) s.v[q] = (s.v[q] << 1) | (s.v[q - 1] >> 31);
+    s.v[0] <<= 1;
+  };
+  shl1(s0);
+  shl1(s1);
+  shl1(s2);
+#pragma unroll 1
+  for (int step = 0; step < 255; step++) {
+    xyzz28_dbl_inl(acc);
+#pragma unroll 1
+    for (uint32_t k = 0; k < nbases; k++) {
+      const uint32_t top = k == 0 ? s0.v[7] : (k == 1 ? s1.v[7] : s2.v[7]);
+      if (!(top >> 31)) continue;
+      const uint64_t idx = k == 0 ? i : (k == 1 ? n + i : 2 * n);
+      fp_t px, py;
+      load_affine96(px, py, aff, idx);
+      if (bn_is_zero(px) && bn_is_zero(py)) continue;  // the point at infinity
+      fp28 cx, cy;
+      f28_load_entry(cx, cy, px, py, k == 2u);
+      bool done = false;
+      if (!acc.inf) done = xyzz28_madd_fast(acc, cx, cy);
+      if (!done) {
+        g1_xyzz28 tmp = acc;  // copy: the call takes addresses
+        xyzz28_madd_complete(tmp, cx, cy);
+        acc = tmp;
+      }
+    }
+    shl1(s0);
+    shl1(s1);
+    shl1(s2);
+  }
+  *out = acc;
+}
+
+// one level of both sum trees: out[j] = in[2 j] + in[2 j + 1], a missing sibling being the identity; lanes [0, cnt_out) take
+// tree A, lanes [cnt_out, 2 cnt_out) tree B.  Complete additions: equal and opposite nodes occur for batches with repeated items.
+static __global__ __launch_bounds__(64) void k_each_level(const g1_xyzz28* __restrict__ in_a, const g1_xyzz28* __restrict__ in_b, uint64_t cnt_in,
+                                                         g1_xyzz28* __restrict__ out_a, g1_xyzz28* __restrict__ out_b, uint64_t cnt_out) {
+  const uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= 2 * cnt_out) return;
+  const bool b = id >= cnt_out;
+  const uint64_t j = b ? id - cnt_out : id;
+  const g1_xyzz28* in = b ? in_b : in_a;
+  g1_xyzz28 acc = in[2 * j];
+  if (2 * j + 1 < cnt_in) {
+    const g1_xyzz28 other = in[2 * j + 1];
+    xyzz28_add_complete_inl<true>(acc, other);
+  }
+  (b ? out_b : out_a)[j] = acc;
+}
+
+// nodes idx[k] (positions in the trees' node arrays) of both trees, side by side: out[2 k] = A's, out[2 k + 1] = B's, in the
+// 12 x 32-limb format the host computes in
+static __global__ __launch_bounds__(64) void k_each_gather(const g1_xyzz28* __restrict__ tree_a, const g1_xyzz28* __restrict__ tree_b,
+                                                          const uint32_t* __restrict__ idx, uint32_t m, g1_xyzz* __restrict__ out) {
+  const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= 2u * m) return;
+  const g1_xyzz28 node = ((id & 1u) ? tree_b : tree_a)[idx[id >> 1]];
+  g1_xyzz o;
+  xyzz28_to_xyzz(o, node);
+  out[id] = o;
+}
+
 #endif
 }  // namespace kzg

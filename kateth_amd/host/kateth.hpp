@@ -392,6 +392,59 @@ class Setup {
     return finish(rc, ok, "kzg_verify_proof_batch");
   }
 
+  // Per-item verdicts: entry i is what verify_blob_proof / verify_proof returns for item i alone -- `ok`, or with status != 0 the
+  // ErrorKind that call throws (reported in place, never thrown: the other items keep their verdicts).
+  struct Verdict {
+    bool ok;
+    int32_t status;
+  };
+  std::vector<Verdict> verify_blob_proof_batch_each(const std::vector<const uint8_t*>& blobs, const std::vector<size_t>& blob_lens,
+                                                    const std::vector<Bytes48>& commitments, const std::vector<Bytes48>& proofs) const {
+    if (blobs.size() != commitments.size() || commitments.size() != proofs.size() || blobs.size() != blob_lens.size())
+      throw std::logic_error("assertion `left == right` failed");
+    const size_t n = blobs.size();
+    // a short blob never reaches the engine: its slot takes the zero blob with commitment = proof = infinity, its verdict InvalidLen
+    std::vector<uint8_t> flat(n * BLOB_BYTES, 0), cs(n * 48), ps(n * 48), ok_each(n);
+    std::vector<int32_t> status(n);
+    for (size_t i = 0; i < n; i++) {
+      const bool whole = blob_lens[i] == BLOB_BYTES;
+      if (whole) std::copy(blobs[i], blobs[i] + BLOB_BYTES, flat.begin() + i * BLOB_BYTES);
+      Bytes48 inf{};
+      inf[0] = 0xC0;
+      const Bytes48& c = whole ? commitments[i] : inf;
+      const Bytes48& p = whole ? proofs[i] : inf;
+      std::copy(c.begin(), c.end(), cs.begin() + i * 48);
+      std::copy(p.begin(), p.end(), ps.begin() + i * 48);
+    }
+    int32_t ok = 0;
+    check(kzg_verify_blob_proof_batch_each(ctx_.get(), flat.data(), cs.data(), ps.data(), n, ok_each.data(), status.data(), &ok),
+          "kzg_verify_blob_proof_batch_each");
+    std::vector<Verdict> out(n);
+    for (size_t i = 0; i < n; i++)
+      out[i] = blob_lens[i] == BLOB_BYTES ? Verdict{ok_each[i] != 0, status[i]} : Verdict{false, static_cast<int32_t>(ErrorKind::BlobInvalidLen)};
+    return out;
+  }
+  std::vector<Verdict> verify_proof_batch_each(const std::vector<Bytes48>& proofs, const std::vector<Bytes48>& commitments,
+                                               const std::vector<Bytes32>& points, const std::vector<Bytes32>& evals) const {
+    if (proofs.size() != commitments.size() || commitments.size() != points.size() || points.size() != evals.size())
+      throw std::logic_error("assertion `left == right` failed");
+    const size_t n = proofs.size();
+    std::vector<uint8_t> ps(n * 48), cs(n * 48), zs(n * 32), ys(n * 32), ok_each(n);
+    std::vector<int32_t> status(n);
+    for (size_t i = 0; i < n; i++) {
+      std::copy(proofs[i].begin(), proofs[i].end(), ps.begin() + i * 48);
+      std::copy(commitments[i].begin(), commitments[i].end(), cs.begin() + i * 48);
+      std::copy(points[i].begin(), points[i].end(), zs.begin() + i * 32);
+      std::copy(evals[i].begin(), evals[i].end(), ys.begin() + i * 32);
+    }
+    int32_t ok = 0;
+    check(kzg_verify_proof_batch_each(ctx_.get(), ps.data(), cs.data(), zs.data(), ys.data(), n, ok_each.data(), status.data(), &ok),
+          "kzg_verify_proof_batch_each");
+    std::vector<Verdict> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = Verdict{ok_each[i] != 0, status[i]};
+    return out;
+  }
+
   // batch forms (contiguous buffers) for callers that already hold many blobs
   void blob_to_commitment_batch(const uint8_t* blobs, size_t n, uint8_t* out48, int32_t* status) const {
     check(kzg_blob_to_commitment_batch(ctx_.get(), blobs, n, out48, status), "kzg_blob_to_commitment_batch");

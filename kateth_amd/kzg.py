@@ -21,7 +21,7 @@ from __future__ import annotations
 import ctypes
 import json
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 BYTES_PER_BLOB = 131072
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -158,6 +158,19 @@ _SIGNATURES = {
         ctypes.c_int32,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p],
     ),
+    "kzg_verify_blob_proof_batch_each": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p, _i32p]),
+    "kzg_verify_blob_proof_batch_each_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p, _i32p, ctypes.c_void_p],
+    ),
+    "kzg_verify_proof_batch_each": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p, _i32p]),
+    "kzg_verify_proof_batch_each_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p, _i32p, ctypes.c_void_p],
+    ),
+    "kzg_verify_each_checks": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "kzg_verify_session_tree": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]),
+    "kzg_verify_session_tree_range": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, _u8p]),
     "kzg_g1_decompress_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
     "kzg_evaluate_blobs": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
     "kzg_verify_phase1_dev": (
@@ -751,6 +764,73 @@ class Setup:
             raise _kzg_error(rc)
         return bool(ok.value)
 
+    # -- per-item verdicts: what a loop over verify_blob_proof / verify_proof would return or raise, from one batch call ---
+    def _each_result(self, rc: int, what: str, n: int, ok_each, status, ok) -> Tuple[List[bool], List[int], bool]:
+        self._check(rc, what)
+        if rc > 0:  # the ABI reports rejected items in status[], never as the call's code
+            raise EngineError("%s returned %d" % (what, rc))
+        return [bool(b) for b in ok_each.raw[:n]], list(status[:n]), bool(ok.value)
+
+    def verify_blob_proof_batch_each_host(self, blobs, commitments, proofs, n: int):
+        """kzg_verify_blob_proof_batch_each on n CONTIGUOUS items in host memory -> (ok_each, status, ok)"""
+        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
+        args = [a if isinstance(a, int) else _buf(a) for a in (blobs, commitments, proofs)]
+        rc = self._lib.kzg_verify_blob_proof_batch_each(self._h, args[0], args[1], args[2], n, ctypes.cast(ok_each, ctypes.c_void_p), status, ctypes.byref(ok))
+        return self._each_result(rc, "kzg_verify_blob_proof_batch_each", n, ok_each, status, ok)
+
+    def verify_proof_batch_each_host(self, proofs, commitments, points, evals, n: int):
+        """kzg_verify_proof_batch_each on n CONTIGUOUS tuples in host memory -> (ok_each, status, ok)"""
+        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
+        args = [a if isinstance(a, int) else _buf(a) for a in (proofs, commitments, points, evals)]
+        rc = self._lib.kzg_verify_proof_batch_each(self._h, args[0], args[1], args[2], args[3], n, ctypes.cast(ok_each, ctypes.c_void_p), status, ctypes.byref(ok))
+        return self._each_result(rc, "kzg_verify_proof_batch_each", n, ok_each, status, ok)
+
+    @staticmethod
+    def _each_list(n, early, ok_each, status):
+        """entry i: the wrong-length item's error, else the engine's verdict for it"""
+        return [early[i] if i in early else (_kzg_error(status[i]) if status[i] else ok_each[i]) for i in range(n)]
+
+    def verify_blob_proof_batch_each(self, blobs: Sequence[bytes], commitments: Sequence[bytes], proofs: Sequence[bytes]) -> List[Union[bool, KzgError]]:
+        """Entry i is what `verify_blob_proof(blobs[i], commitments[i], proofs[i])` returns -- or the KzgError it raises, RETURNED in
+        the list.  A wrong-length item gets that call's length error (blob first, then commitment, then proof) and a valid
+        placeholder goes to the engine in its slot.  Length mismatches between the lists are AssertionErrors, as in the batch call."""
+        assert len(blobs) == len(commitments), "assertion `left == right` failed"
+        assert len(commitments) == len(proofs), "assertion `left == right` failed"
+        n = len(blobs)
+        items = [(_buf(b), _buf(c), _buf(p)) for b, c, p in zip(blobs, commitments, proofs)]
+        early = {}
+        for i, (b, c, p) in enumerate(items):
+            if len(b) != BYTES_PER_BLOB:
+                early[i] = KzgError(BlobError("InvalidLen"))
+            elif len(c) != 48 or len(p) != 48:
+                early[i] = KzgError(BlsError(ECGroupError("InvalidEncoding")))
+        inf48 = bytes([0xC0]) + bytes(47)
+        placeholder = (bytes(BYTES_PER_BLOB), inf48, inf48)  # the zero polynomial, committed to and opened by the point at infinity
+        sent = [placeholder if i in early else it for i, it in enumerate(items)]
+        ok_each, status, _ = self.verify_blob_proof_batch_each_host(b"".join(s[0] for s in sent), b"".join(s[1] for s in sent), b"".join(s[2] for s in sent), n)
+        return self._each_list(n, early, ok_each, status)
+
+    def verify_proof_batch_each(self, proofs: Sequence[bytes], commitments: Sequence[bytes], points: Sequence[bytes],
+                                evals: Sequence[bytes]) -> List[Union[bool, KzgError]]:
+        """Entry i is what `verify_proof(proofs[i], commitments[i], points[i], evals[i])` returns -- or the KzgError it raises,
+        RETURNED in the list (verify_proof's own order: point lengths before scalar lengths, then the engine's parse order)."""
+        assert len(proofs) == len(commitments), "assertion `left == right` failed"
+        assert len(commitments) == len(points), "assertion `left == right` failed"
+        assert len(points) == len(evals), "assertion `left == right` failed"
+        n = len(proofs)
+        items = [tuple(_buf(v) for v in t) for t in zip(proofs, commitments, points, evals)]
+        early = {}
+        for i, (p, c, z, y) in enumerate(items):
+            if len(p) != 48 or len(c) != 48:
+                early[i] = KzgError(BlsError(ECGroupError("InvalidEncoding")))
+            elif len(z) != 32 or len(y) != 32:
+                early[i] = KzgError(BlsError(FiniteFieldError("InvalidEncoding")))
+        inf48 = bytes([0xC0]) + bytes(47)
+        placeholder = (inf48, inf48, bytes(32), bytes(32))  # the zero polynomial opened at 0
+        sent = [placeholder if i in early else it for i, it in enumerate(items)]
+        ok_each, status, _ = self.verify_proof_batch_each_host(*[b"".join(s[k] for s in sent) for k in range(4)], n)
+        return self._each_list(n, early, ok_each, status)
+
     def verify_blob_proof_batch_host(self, blobs, commitments, proofs, n: int) -> bool:
         """kzg_verify_blob_proof_batch on n CONTIGUOUS items in host memory: bytes-like objects or raw host addresses
         (ints, e.g. the data_ptr() of a pinned tensor -- pinned memory crosses PCIe at the full rate)."""
@@ -786,6 +866,24 @@ class Setup:
         if rc > 0:
             raise _kzg_error(rc)
         return bool(ok.value)
+
+    def verify_blob_proof_batch_each_dev(self, d_blobs: int, d_commitments: int, d_proofs: int, n: int, stream: int = 0):
+        """-> (ok_each: List[bool], status: List[int], ok: bool); synchronous, results in host memory"""
+        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
+        rc = self._lib.kzg_verify_blob_proof_batch_each_dev(self._h, d_blobs, d_commitments, d_proofs, n, ctypes.cast(ok_each, ctypes.c_void_p), status,
+                                                            ctypes.byref(ok), stream)
+        return self._each_result(rc, "kzg_verify_blob_proof_batch_each_dev", n, ok_each, status, ok)
+
+    def verify_proof_batch_each_dev(self, d_proofs: int, d_commitments: int, d_points: int, d_evals: int, n: int, stream: int = 0):
+        """-> (ok_each: List[bool], status: List[int], ok: bool); synchronous, results in host memory"""
+        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
+        rc = self._lib.kzg_verify_proof_batch_each_dev(self._h, d_proofs, d_commitments, d_points, d_evals, n, ctypes.cast(ok_each, ctypes.c_void_p), status,
+                                                       ctypes.byref(ok), stream)
+        return self._each_result(rc, "kzg_verify_proof_batch_each_dev", n, ok_each, status, ok)
+
+    def verify_each_checks(self) -> int:
+        """two-pairing checks the per-item verdict calls have spent on this context so far"""
+        return int(self._lib.kzg_verify_each_checks(self._h))
 
     # -- device-resident SHARDED calls on a group context: one entry per member, member k's buffers resident on member k's GPU ---
     def _per_member(self, values, what):
@@ -860,6 +958,18 @@ class Setup:
         out = ctypes.create_string_buffer(192)
         rc = self._lib.kzg_verify_phase2_dev(session, _buf(roots), len(roots) // 32, first_index, n_total, ctypes.cast(out, ctypes.c_void_p))
         self._check(rc, "kzg_verify_phase2_dev")
+        return out.raw
+
+    def verify_session_tree(self, session, roots: bytes, first_index: int, n_total: int):
+        """builds the per-item terms and their sum trees in a phase-1 session (r seeded as verify_phase2_dev seeds it)"""
+        rc = self._lib.kzg_verify_session_tree(session, _buf(roots), len(roots) // 32, first_index, n_total)
+        self._check(rc, "kzg_verify_session_tree")
+
+    def verify_session_tree_range(self, session, lo: int, hi: int) -> bytes:
+        """A || B summed over the session's local items [lo, hi), 192 bytes in verify_phase2_dev's format"""
+        out = ctypes.create_string_buffer(192)
+        rc = self._lib.kzg_verify_session_tree_range(session, lo, hi, ctypes.cast(out, ctypes.c_void_p))
+        self._check(rc, "kzg_verify_session_tree_range")
         return out.raw
 
     def verify_session_zy(self, session, first: int, count: int):
