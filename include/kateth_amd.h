@@ -318,6 +318,9 @@ int32_t kzg_verify_proof_batch_group_dev(const kzg_ctx* ctx, const void* const* 
  * the single-device call on its share as its own batch with its own challenge, writes its outputs in place, and *ok is the
  * AND (a verdict does not depend on r: nothing is merged).  The *_dev calls act on member 0.
  * kzg_verify_each_checks: the two-pairing checks these calls have spent on `ctx` so far (all members; measurement aid).
+ * kzg_ctx_sessions_created: the verification sessions `ctx` and its members have ever constructed.  Every verification call takes a
+ * pooled session and returns it on every exit, so calls made one at a time stop creating sessions after the first of each route; a
+ * session that regrows its buffer is not a new one (measurement aid).
  */
 int32_t kzg_verify_blob_proof_batch_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n,
                                          uint8_t* ok_each, int32_t* status, int32_t* ok);
@@ -328,6 +331,7 @@ int32_t kzg_verify_proof_batch_each(const kzg_ctx* ctx, const uint8_t* proofs48,
 int32_t kzg_verify_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32, uint64_t n,
                                         uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream);
 uint64_t kzg_verify_each_checks(const kzg_ctx* ctx);
+uint64_t kzg_ctx_sessions_created(const kzg_ctx* ctx);
 
 /*
  * DEVICE-RESIDENT sharded calls on a GROUP context (kzg_config.devices / ndev): member k's share of the batch is resident on

@@ -264,6 +264,7 @@ struct kzg_ctx {
   mutable std::mutex pool_lock;
   mutable std::vector<kzg_verify_session*> session_pool;
   mutable std::atomic<uint64_t> each_checks{0};  // pairing checks spent by the per-item verdict calls so far (kzg_verify_each_checks)
+  mutable std::atomic<uint64_t> sessions_created{0};  // sessions constructed so far; a steady state creates none (kzg_ctx_sessions_created)
   // host-buffer pipelines (verification, evaluation: engine_verify.hip; commitments: engine.hip; proofs: engine_proof.hip), guarded by
   // stage_lock, so that a steady-state host-buffer call allocates nothing: a staging arena of up to
   // KZG_STAGE_SLOTS chunk slots, a copy stream, rotating compute streams and their events; created on first use (StageRing)
@@ -285,21 +286,7 @@ int32_t ctx_create_single(const uint8_t* g1_lagrange, const uint8_t* g2_monomial
 int32_t commit_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out48, uint8_t* out_affine96, int32_t* status);    // engine.hip
 int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side, size_t side_bytes, bool side_is_commitment, uint64_t n, uint8_t* out48,
                    uint8_t* out_affine96, uint8_t* out_y32, int32_t* status);  // engine_proof.hip
-int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, uint8_t* out_root32,
-                           int32_t* err6, kzg_verify_session** session);  // engine_verify.hip
-int32_t verify_batch_host_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, int32_t* ok);
 int32_t verify_proof_single(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok);
-// Setup::verify_proof_batch over host buffers (engine_verify.hip): the whole call on one device, and its phase 1 alone (err8 = {proof, commitment, z, y} x {local
-// index, code}) for a group's shares
-int32_t verify_proof_batch_host_single(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
-                                       int32_t* ok);
-int32_t verify_proof_phase1_host(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
-                                 uint8_t* out_root32, int32_t* err8, kzg_verify_session** session);
-// per-item verdicts over host buffers (engine_verify.hip): one device's batch, with its own challenge
-int32_t verify_blob_each_host_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, uint8_t* ok_each,
-                                     int32_t* status, int32_t* ok);
-int32_t verify_proof_each_host_single(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
-                                      uint8_t* ok_each, int32_t* status, int32_t* ok);
 int32_t g1_decompress_single(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
 int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
 // engine_multi.hip
@@ -307,25 +294,43 @@ int32_t group_create(const uint8_t* g1_lagrange, const uint8_t* g2_monomial, con
 int32_t multi_commit(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out48, uint8_t* out_affine96, int32_t* status);
 int32_t multi_proof(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side, size_t side_bytes, bool side_is_commitment, uint64_t n, uint8_t* out48,
                     uint8_t* out_affine96, uint8_t* out_y32, int32_t* status);
-int32_t multi_verify_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, int32_t* ok);
 int32_t multi_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok);
-int32_t multi_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
-                                 int32_t* ok);
-int32_t multi_verify_blob_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, uint8_t* ok_each,
-                               int32_t* status, int32_t* ok);
-int32_t multi_verify_proof_each(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
-                                uint8_t* ok_each, int32_t* status, int32_t* ok);
 int32_t multi_g1_decompress(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
 int32_t multi_evaluate_blobs(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
-// The device-resident inputs of one batch verification call (engine_verify.hip: front_enqueue / front_status switch on `kind`).
-// Its error record is `kinds()` x {local index of the first rejected item or -1, code}, in the reference's parse order:
+// The inputs of one batch verification call (engine_verify.hip: front_enqueue / front_status switch on `kind`), in the caller's host
+// buffers (`on_host`) or device-resident.  Its error record is `kinds()` x {local index of the first rejected item or -1, code}, in the
+// reference's parse order:
 //   BLOBS  (verify_blob_proof_batch): blobs, commitments48, proofs48       -> {blob, commitment, proof}   = the ABI's err6
 //   POINTS (verify_proof_batch):      proofs48, commitments48, z32, y32    -> {proof, commitment, z, y}   = the ABI's err8
 struct VerifyInputs {
   enum Kind { BLOBS, POINTS } kind;
   const uint8_t *blobs, *commitments48, *proofs48, *z32, *y32;
+  bool on_host;
   int kinds() const { return kind == BLOBS ? 3 : 4; }
+  bool any_null() const { return !commitments48 || !proofs48 || (kind == BLOBS ? !blobs : (!z32 || !y32)); }
+  VerifyInputs advanced(uint64_t first) const {  // the same inputs from item `first` on
+    return VerifyInputs{kind, blobs ? blobs + first * (size_t)KZG_BYTES_PER_BLOB : nullptr, commitments48 + first * 48, proofs48 + first * 48,
+                        z32 ? z32 + first * 32 : nullptr, y32 ? y32 + first * 32 : nullptr, on_host};
+  }
 };
+static inline VerifyInputs blob_inputs(const void* blobs, const void* commitments48, const void* proofs48, bool on_host) {
+  return VerifyInputs{VerifyInputs::BLOBS, (const uint8_t*)blobs, (const uint8_t*)commitments48, (const uint8_t*)proofs48, nullptr, nullptr, on_host};
+}
+static inline VerifyInputs point_inputs(const void* proofs48, const void* commitments48, const void* z32, const void* y32, bool on_host) {
+  return VerifyInputs{VerifyInputs::POINTS, nullptr, (const uint8_t*)commitments48, (const uint8_t*)proofs48, (const uint8_t*)z32, (const uint8_t*)y32, on_host};
+}
+// the wanted ending of a batch call: one boolean (no VerifyEach), or the per-item verdicts of kzg_verify_*_batch_each beside it
+struct VerifyEach {
+  uint8_t* ok_each;
+  int32_t* status;
+};
+// The single-device batch call behind every route -- {blobs, points} x {host buffers, device pointers} x {one boolean, per-item verdicts};
+// n >= 1, `st`: the caller's stream of the device routes -- and phase 1 alone, whose session becomes the caller's (engine_verify.hip).
+int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, const VerifyEach* each, int32_t* ok);
+int32_t verify_phase1(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, uint8_t* out_root32, int32_t* err, kzg_verify_session** session);
+// the same over a group's members, from host buffers (engine_multi.hip)
+int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, int32_t* ok);
+int32_t multi_verify_each(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, const VerifyEach& each, int32_t* ok);
 // one member's device-resident share of a group verification (kzg_verify_*_batch_group_dev): global range [first, first + count),
 // inputs resident on member->device
 struct GroupDevShare {

@@ -105,89 +105,49 @@ int32_t multi_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, const uin
   return verify_proof_single(member_of(ctx, ctx->rr.fetch_add(1u, std::memory_order_relaxed) % S), proof48, commitment48, z32, y32, ok);
 }
 
-// Batch verification from host buffers over the members' shares.  `phase1(member, share, root32, err, &session)` is the single-device
-// phase 1 of one share -- verify_phase1_host or verify_proof_phase1_host -- and `kinds` the kinds of its error record.  The
-// challenge is seeded by all the shares' roots, so r differs from the single-device call's while the boolean and the
-// first-error code are the same.
-namespace {
-template <class Phase1>
-int32_t multi_verify_shares(const kzg_ctx* ctx, const std::vector<Share>& shares, uint64_t n, int kinds, int32_t* ok, Phase1&& phase1) {
+// Setup::verify_blob_proof_batch (src/kzg/setup.rs:247-275) or Setup::verify_proof_batch (:115-161) from host buffers over the members'
+// shares; one share is exactly the single-device call on that member.  Otherwise every share runs the single-device phase 1
+// (verify_phase1) on its member; the challenge is seeded by all the shares' roots, so r differs from the single-device call's while the
+// boolean and the first-error code are the same.
+int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, int32_t* ok) {
+  *ok = 0;
+  const std::vector<Share> shares = shares_of(ctx, n);
+  if (shares.size() == 1) return verify_batch_single(member_of(ctx, shares[0].member), in, n, nullptr, nullptr, ok);
   const uint32_t W = (uint32_t)shares.size();
+  const int kinds = in.kinds();
   const size_t stride = 2 * (size_t)kinds;
   std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
   std::vector<int32_t> err(stride * W);
-  std::vector<kzg_verify_session*> sessions(W, nullptr);
-  auto release = [&]() {  // handing a session back may fail on its own: the error the caller is told about stays the first one
-    const ErrorSnapshot keep = error_snapshot();
-    for (kzg_verify_session* s : sessions)
-      if (s) kzg_verify_session_destroy(s);
-    error_publish(keep);
-  };
+  std::vector<kzg_verify_session*> sessions(W, nullptr);  // phase 1 hands them to this call
   int32_t rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
     const kzg_ctx* m = member_of(ctx, shares[j].member);
     if (hipSetDevice(m->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
-    return phase1(m, shares[j], roots.data() + 32 * (size_t)j, err.data() + stride * j, &sessions[j]);
+    return verify_phase1(m, in.advanced(shares[j].first), shares[j].count, nullptr, roots.data() + 32 * (size_t)j, err.data() + stride * j, &sessions[j]);
   });
   const int32_t code = rc ? 0 : merged_first_error(shares, err.data(), kinds);
   if (rc == 0 && code == 0)
     rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
       return kzg_verify_phase2_dev(sessions[j], roots.data(), W, shares[j].first, n, partials.data() + 192 * (size_t)j);
     });
-  release();
+  {  // handing a session back may fail on its own: the error the caller is told about stays the first one
+    const ErrorSnapshot keep = error_snapshot();
+    for (kzg_verify_session* s : sessions) kzg_verify_session_destroy(s);
+    error_publish(keep);
+  }
   if (rc || code) return rc ? rc : code;
   return kzg_verify_batch_finish(ctx, partials.data(), W, ok);
-}
-}  // namespace
-
-// Setup::verify_blob_proof_batch (src/kzg/setup.rs:247-275) over the members; one share is exactly the single-device call.
-int32_t multi_verify_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, int32_t* ok) {
-  *ok = 0;
-  const std::vector<Share> shares = shares_of(ctx, n);
-  if (shares.size() == 1) return verify_batch_host_single(member_of(ctx, shares[0].member), blobs, commitments48, proofs48, n, ok);
-  return multi_verify_shares(ctx, shares, n, 3, ok, [&](const kzg_ctx* m, const Share& sh, uint8_t* root32, int32_t* err6, kzg_verify_session** session) {
-    return verify_phase1_host(m, blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, commitments48 + sh.first * 48, proofs48 + sh.first * 48, sh.count, root32, err6,
-                              session);
-  });
-}
-
-// Setup::verify_proof_batch (src/kzg/setup.rs:115-161) over the members, cut the same way.
-int32_t multi_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
-                                 int32_t* ok) {
-  *ok = 0;
-  const std::vector<Share> shares = shares_of(ctx, n);
-  if (shares.size() == 1) return verify_proof_batch_host_single(member_of(ctx, shares[0].member), proofs48, commitments48, z32, y32, n, ok);
-  return multi_verify_shares(ctx, shares, n, 4, ok, [&](const kzg_ctx* m, const Share& sh, uint8_t* root32, int32_t* err8, kzg_verify_session** session) {
-    return verify_proof_phase1_host(m, proofs48 + sh.first * 48, commitments48 + sh.first * 48, z32 + sh.first * 32, y32 + sh.first * 32, sh.count, root32, err8,
-                                    session);
-  });
 }
 
 // Per-item verdicts (kzg_verify_*_batch_each) over the members: the same contiguous shares, each member's share its own batch with its
 // own challenge -- an item's verdict does not depend on r, so the outputs land in place and nothing is merged but the AND.
-int32_t multi_verify_blob_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, uint8_t* ok_each,
-                               int32_t* status, int32_t* ok) {
+int32_t multi_verify_each(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, const VerifyEach& each, int32_t* ok) {
   *ok = 0;
   const std::vector<Share> shares = shares_of(ctx, n);
   std::vector<int32_t> oks(shares.size(), 0);
   const int32_t rc = run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
     const Share& sh = shares[j];
-    return verify_blob_each_host_single(member_of(ctx, sh.member), blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, commitments48 + sh.first * 48,
-                                        proofs48 + sh.first * 48, sh.count, ok_each + sh.first, status + sh.first, &oks[j]);
-  });
-  if (rc) return rc;
-  *ok = 1;
-  for (int32_t o : oks) *ok &= o;
-  return 0;
-}
-int32_t multi_verify_proof_each(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
-                                uint8_t* ok_each, int32_t* status, int32_t* ok) {
-  *ok = 0;
-  const std::vector<Share> shares = shares_of(ctx, n);
-  std::vector<int32_t> oks(shares.size(), 0);
-  const int32_t rc = run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
-    const Share& sh = shares[j];
-    return verify_proof_each_host_single(member_of(ctx, sh.member), proofs48 + sh.first * 48, commitments48 + sh.first * 48, z32 + sh.first * 32,
-                                         y32 + sh.first * 32, sh.count, ok_each + sh.first, status + sh.first, &oks[j]);
+    const VerifyEach out{each.ok_each + sh.first, each.status + sh.first};
+    return verify_batch_single(member_of(ctx, sh.member), in.advanced(sh.first), sh.count, nullptr, &out, &oks[j]);
   });
   if (rc) return rc;
   *ok = 1;
@@ -230,21 +190,30 @@ extern "C" int32_t kzg_compute_blob_proof_batch_group_dev(const kzg_ctx* ctx, co
   return abi_exception();
 }
 
-extern "C" int32_t kzg_verify_blob_proof_batch_group_dev(const kzg_ctx* ctx, const void* const* d_blobs, const void* const* d_commitments48,
-                                                         const void* const* d_proofs48, const uint64_t* n_local, int32_t* ok, void* const* hip_streams) try {
-  if (!ctx || !ok || !d_blobs || !d_commitments48 || !d_proofs48 || !n_local) return fail(KZG_FAIL_ARGUMENT, "null argument");
+// the GroupDevShare list of the two *_group_dev calls: member k's pointers (an array the kind does not have is null) and its global range
+namespace {
+int32_t verify_group_shares(const kzg_ctx* ctx, VerifyInputs::Kind kind, const void* const* blobs, const void* const* commitments48, const void* const* proofs48,
+                            const void* const* z32, const void* const* y32, const uint64_t* n_local, void* const* hip_streams, int32_t* ok) {
   *ok = 0;
   const uint32_t S = 1u + (uint32_t)ctx->peers.size();
+  auto at = [](const void* const* a, uint32_t k) { return a ? (const uint8_t*)a[k] : nullptr; };
   std::vector<GroupDevShare> shares;
   uint64_t total = 0;
   for (uint32_t k = 0; k < S; k++) {
     if (n_local[k] == 0) continue;
-    if (!d_blobs[k] || !d_commitments48[k] || !d_proofs48[k]) return fail(KZG_FAIL_ARGUMENT, "null device pointer for a member with items");
-    const VerifyInputs in{VerifyInputs::BLOBS, (const uint8_t*)d_blobs[k], (const uint8_t*)d_commitments48[k], (const uint8_t*)d_proofs48[k], nullptr, nullptr};
+    const VerifyInputs in{kind, at(blobs, k), at(commitments48, k), at(proofs48, k), at(z32, k), at(y32, k), false};
+    if (in.any_null()) return fail(KZG_FAIL_ARGUMENT, "null device pointer for a member with items");
     shares.push_back(GroupDevShare{member_of(ctx, k), in, total, n_local[k], hip_streams ? (hipStream_t)hip_streams[k] : nullptr});
     total += n_local[k];
   }
   return verify_group_dev(ctx, shares, total, ok);
+}
+}  // namespace
+
+extern "C" int32_t kzg_verify_blob_proof_batch_group_dev(const kzg_ctx* ctx, const void* const* d_blobs, const void* const* d_commitments48,
+                                                         const void* const* d_proofs48, const uint64_t* n_local, int32_t* ok, void* const* hip_streams) try {
+  if (!ctx || !ok || !d_blobs || !d_commitments48 || !d_proofs48 || !n_local) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return verify_group_shares(ctx, VerifyInputs::BLOBS, d_blobs, d_commitments48, d_proofs48, nullptr, nullptr, n_local, hip_streams, ok);
 } catch (...) {
   return abi_exception();
 }
@@ -253,18 +222,7 @@ extern "C" int32_t kzg_verify_proof_batch_group_dev(const kzg_ctx* ctx, const vo
                                                     const void* const* d_z32, const void* const* d_y32, const uint64_t* n_local, int32_t* ok,
                                                     void* const* hip_streams) try {
   if (!ctx || !ok || !d_proofs48 || !d_commitments48 || !d_z32 || !d_y32 || !n_local) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *ok = 0;
-  const uint32_t S = 1u + (uint32_t)ctx->peers.size();
-  std::vector<GroupDevShare> shares;
-  uint64_t total = 0;
-  for (uint32_t k = 0; k < S; k++) {
-    if (n_local[k] == 0) continue;
-    if (!d_proofs48[k] || !d_commitments48[k] || !d_z32[k] || !d_y32[k]) return fail(KZG_FAIL_ARGUMENT, "null device pointer for a member with items");
-    const VerifyInputs in{VerifyInputs::POINTS, nullptr, (const uint8_t*)d_commitments48[k], (const uint8_t*)d_proofs48[k], (const uint8_t*)d_z32[k], (const uint8_t*)d_y32[k]};
-    shares.push_back(GroupDevShare{member_of(ctx, k), in, total, n_local[k], hip_streams ? (hipStream_t)hip_streams[k] : nullptr});
-    total += n_local[k];
-  }
-  return verify_group_dev(ctx, shares, total, ok);
+  return verify_group_shares(ctx, VerifyInputs::POINTS, nullptr, d_commitments48, d_proofs48, d_z32, d_y32, n_local, hip_streams, ok);
 } catch (...) {
   return abi_exception();
 }

@@ -82,9 +82,9 @@ void session_pool_clear(const kzg_ctx* ctx) {
   ctx->session_pool.clear();
 }
 
-// Waits for everything this use has enqueued on the session's three streams, ALWAYS all three (errors ignored: the callers are
-// on a failure path or are handing the session back).  Nothing may still touch the buffers when a session returns to the pool,
-// and nothing may still run on a Phase2's scratch when it goes out of scope.  The caller has set the session's device.
+// Waits for everything this use has enqueued on the session's three streams, ALWAYS all three (errors ignored).  Two rules, each
+// stated once in code: nothing runs on a session when it re-enters the pool (kzg_verify_session_destroy, reached through SessionUse),
+// and nothing runs on a Phase2's scratch when it goes (~Phase2).  The caller has set the session's device.
 static void session_drain(kzg_verify_session* s) {
   (void)hipStreamSynchronize(s->st);
   (void)hipStreamSynchronize(s->aux);
@@ -103,6 +103,25 @@ extern "C" void kzg_verify_session_destroy(kzg_verify_session* s) {
   else
     session_free(s);
 }
+
+// The session of ONE use: whatever way the owner leaves -- a result, an error code, a HIP_TRY -- the session goes back to the pool,
+// drained.  release(): phase 1 on its own hands the session to the caller, who ends it with kzg_verify_session_destroy.
+struct SessionUse {
+  kzg_verify_session* s = nullptr;
+  SessionUse() = default;
+  SessionUse(const SessionUse&) = delete;
+  SessionUse& operator=(const SessionUse&) = delete;
+  ~SessionUse() { reset(); }
+  void reset() {
+    kzg_verify_session_destroy(s);
+    s = nullptr;
+  }
+  kzg_verify_session* release() {
+    kzg_verify_session* out = s;
+    s = nullptr;
+    return out;
+  }
+};
 
 // Window sizes.  Up to 32,767 terms: c = 8 (32 windows whose TOP window is full -- top raw digit 7 bits, all 128 signed
 // buckets used; with e.g. c = 12 the top window has 8 distinct digits and a few buckets receive n/8 points each, a serial
@@ -278,7 +297,7 @@ struct MsmVarJob {
   MsmVarJob() = default;
   MsmVarJob(const MsmVarJob&) = delete;
   MsmVarJob& operator=(const MsmVarJob&) = delete;
-  ~MsmVarJob() { release(); }  // a job that is dropped with kernels enqueued: the owner drains its streams first
+  ~MsmVarJob() { release(); }  // a job that is dropped with kernels enqueued: its owner has drained the streams (~Phase2)
   void release() {
     if (owns_buf && buf) (void)hipFree(buf);
     buf = nullptr;
@@ -472,6 +491,7 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
     s = new (std::nothrow) kzg_verify_session();
     if (!s) return fail(KZG_FAIL_ARGUMENT, "out of host memory");
     s->ctx = ctx;
+    ctx->sessions_created.fetch_add(1, std::memory_order_relaxed);
     // the side stream carries the point decoder (long per-lane chains) next to the evaluation kernel's flood of short waves:
     // highest queue priority, so that its workgroups are placed first when both kernels become runnable
     int prio_least = 0, prio_greatest = 0;
@@ -660,11 +680,11 @@ static int32_t p1_root(kzg_verify_session* s, uint8_t* out_root32) {
   return 0;
 }
 // ---- the two kinds of call (VerifyInputs, engine_internal.hpp): what differs between them is the front and how the error record is read ----
-static VerifyInputs blob_inputs(const void* blobs, const void* commitments48, const void* proofs48) {
-  return VerifyInputs{VerifyInputs::BLOBS, (const uint8_t*)blobs, (const uint8_t*)commitments48, (const uint8_t*)proofs48, nullptr, nullptr};
-}
-static VerifyInputs point_inputs(const void* proofs48, const void* commitments48, const void* z32, const void* y32) {
-  return VerifyInputs{VerifyInputs::POINTS, nullptr, (const uint8_t*)commitments48, (const uint8_t*)proofs48, (const uint8_t*)z32, (const uint8_t*)y32};
+// the device copies of a host-buffer call in its session: proofs || commitments, z || y (the blobs pass through the staging arena)
+static VerifyInputs staged_inputs(const kzg_verify_session* s, VerifyInputs::Kind kind) {
+  const uint64_t n = s->n;
+  return kind == VerifyInputs::BLOBS ? blob_inputs(nullptr, s->pts48 + n * 48, s->pts48, false)
+                                     : point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32, false);
 }
 static void err_clear(int32_t* err, int kinds) {
   for (int k = 0; k < 2 * kinds; k++) err[k] = (k % 2 == 0) ? -1 : 0;
@@ -738,41 +758,11 @@ static int32_t front_status(kzg_verify_session* s, const VerifyInputs& in, int32
   }
   return fail(KZG_FAIL_ARGUMENT, "unknown kind of verification call");
 }
-// Phase 1 on its own (kzg_verify_*phase1_dev): the session is acquired, the front runs to its root and error record, and a failure
-// drains the session and hands it back.  n = 0: the empty transcript's root.
-static int32_t phase1_dev(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, uint8_t* out_root32, int32_t* err, kzg_verify_session** session,
-                          hipStream_t st) {
-  *session = nullptr;
-  TraceTimer tt(ctx->knobs.trace, "phase1");
-  HIP_TRY(hipSetDevice(ctx->device));
-  err_clear(err, in.kinds());
-  kzg_verify_session* s = nullptr;
-  int32_t rc = session_acquire(ctx, n, st, &s);
-  if (rc) return rc;
-  tt.mark("session");
-  if (n) {
-    rc = front_enqueue(s, in);
-    if (rc == 0) rc = p1_root(s, out_root32);
-    if (rc == 0) rc = front_status(s, in, err);
-    tt.mark("gpu kernels + readback + first errors + root hash");
-  } else {
-    sha256_bytes(out_root32, nullptr, 0);
-    if (hipStreamSynchronize(s->st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "verify phase 1 synchronize failed");
-  }
-  if (rc) {
-    session_drain(s);
-    kzg_verify_session_destroy(s);
-    return rc;
-  }
-  *session = s;
-  return 0;
-}
-
 extern "C" int32_t kzg_verify_phase1_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_proofs48,
                                          uint64_t n, uint8_t* out_root32, int32_t* err6, kzg_verify_session** session, void* hip_stream) try {
-  if (!ctx || !out_root32 || !err6 || !session || (n && (!d_blobs || !d_commitments48 || !d_proofs48)))
-    return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return phase1_dev(ctx, blob_inputs(d_blobs, d_commitments48, d_proofs48), n, out_root32, err6, session, (hipStream_t)hip_stream);
+  const VerifyInputs in = blob_inputs(d_blobs, d_commitments48, d_proofs48, false);
+  if (!ctx || !out_root32 || !err6 || !session || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return verify_phase1(ctx, in, n, (hipStream_t)hip_stream, out_root32, err6, session);
 } catch (...) {
   return abi_exception();
 }
@@ -781,8 +771,8 @@ extern "C" int32_t kzg_verify_phase1_dev(const kzg_ctx* ctx, const void* d_blobs
 // copy stream while the per-blob kernels (challenge + evaluation are per blob) of earlier chunks run on rotating compute
 // streams -- the n * 128 KiB never have to be resident at once and the transfer overlaps the hashing.  Commitments and
 // proofs (96 B per item) are copied whole and decoded once on the session's side stream.
-int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, uint8_t* out_root32,
-                           int32_t* err6, kzg_verify_session** session) {
+static int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n,
+                                  uint8_t* out_root32, int32_t* err6, kzg_verify_session** session) {
   *session = nullptr;
   TraceTimer tt(ctx->knobs.trace, "phase1(host buffers)");
   if (err6) err_clear(err6, 3);
@@ -808,9 +798,10 @@ int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
   int32_t rc = ring.open(ctx, nchunks < KZG_STAGE_SLOTS ? nchunks : KZG_STAGE_SLOTS, (size_t)chunk * KZG_BYTES_PER_BLOB, 0, nchunks > 1);
   if (rc) return rc;
   hipStream_t st = ctx->verify_stream;
-  kzg_verify_session* s = nullptr;
-  rc = session_acquire(ctx, n, st, &s);
+  SessionUse use;  // declared behind the lock: a failed call's session is drained and pooled before the arena is handed on
+  rc = session_acquire(ctx, n, st, &use.s);
   if (rc) return rc;
+  kzg_verify_session* s = use.s;
   do {
     uint8_t* prf = s->pts48;
     uint8_t* com = s->pts48 + n * 48;
@@ -854,16 +845,65 @@ int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8
     }
     rc = p1_transcript(s, com, prf);
     if (rc == 0) rc = p1_root(s, out_root32);
-    if (rc == 0 && err6) rc = front_status(s, blob_inputs(nullptr, com, prf), err6);
+    if (rc == 0 && err6) rc = front_status(s, staged_inputs(s, VerifyInputs::BLOBS), err6);
     tt.mark("gpu kernels + readback + root hash (+ status scan)");
   } while (0);
   if (rc) {
-    stage_drain(ctx);
-    session_drain(s);
-    kzg_verify_session_destroy(s);
+    stage_drain(ctx);  // the chunk kernels on the arena's own streams, which no session drains
     return rc;
   }
-  *session = s;
+  *session = use.release();
+  return 0;
+}
+
+// Host points: 160 bytes per tuple cross PCIe whole into the session's own staging (proofs || commitments, z || y) on the
+// context's verification stream; nothing of the blob calls' staging arena is used, so stage_lock is held for stage_init only.
+static int32_t points_stage_host(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, kzg_verify_session** out) {
+  *out = nullptr;
+  {
+    std::lock_guard<std::mutex> guard(ctx->stage_lock);
+    const int32_t rc = stage_init(ctx);
+    if (rc) return rc;
+  }
+  SessionUse use;
+  const int32_t rc = session_acquire(ctx, n, ctx->verify_stream, &use.s);
+  if (rc) return rc;
+  kzg_verify_session* s = use.s;
+  if (hipMemcpyAsync(s->pts48, in.proofs48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+      hipMemcpyAsync(s->pts48 + n * 48, in.commitments48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+      hipMemcpyAsync(s->zy32, in.z32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+      hipMemcpyAsync(s->zy32 + n * 32, in.y32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess)
+    return fail(KZG_FAIL_HIP, "host-to-device copy failed");
+  *out = use.release();
+  return 0;
+}
+
+// Phase 1 on its own, behind kzg_verify_*phase1_dev and the host-buffer shares of a group: a session with device-resident inputs comes
+// to be, the front runs to its root and error record, and the session becomes the caller's.  n = 0: the empty transcript's root.
+int32_t verify_phase1(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, uint8_t* out_root32, int32_t* err, kzg_verify_session** session) {
+  *session = nullptr;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (in.on_host && in.kind == VerifyInputs::BLOBS)  // through the staging arena: front and root while stage_lock is held
+    return verify_phase1_host(ctx, in.blobs, in.commitments48, in.proofs48, n, out_root32, err, session);
+  TraceTimer tt(ctx->knobs.trace, "phase1");
+  err_clear(err, in.kinds());
+  SessionUse use;
+  int32_t rc = in.on_host ? points_stage_host(ctx, in, n, &use.s) : session_acquire(ctx, n, st, &use.s);
+  if (rc) return rc;
+  kzg_verify_session* s = use.s;
+  tt.mark("session");
+  if (n) {
+    const VerifyInputs dev = in.on_host ? staged_inputs(s, in.kind) : in;
+    rc = front_enqueue(s, dev);
+    if (rc == 0) rc = p1_root(s, out_root32);
+    if (rc == 0) rc = front_status(s, dev, err);
+    tt.mark("gpu kernels + readback + first errors + root hash");
+  } else {
+    sha256_bytes(out_root32, nullptr, 0);
+    if (hipStreamSynchronize(s->st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "verify phase 1 synchronize failed");
+  }
+  if (rc) return rc;
+  *session = use.release();
   return 0;
 }
 
@@ -1043,8 +1083,15 @@ int32_t verify_one_on_host(const kzg_ctx* ctx, const uint32_t* prf24, bool prf_i
 }  // namespace
 
 // ---- phase 2 in four pieces ---------------------------------------------------------------------------------------------
+// The two lincomb jobs of one phase 2 on session `s`.  A Phase2 that goes while a job is still active -- an error return, a rejected
+// input whose sums are discarded -- drains the session first: nothing runs on its scratch when it goes.
 struct Phase2 {
+  kzg_verify_session* s;
   MsmVarJob ja, jb;
+  explicit Phase2(kzg_verify_session* session) : s(session) {}
+  ~Phase2() {
+    if (ja.active || jb.active) session_drain(s);
+  }
 };
 // (a) r = hash_to_fr("RCKZGBATCH___V1_" || u128(4096) || u128(n_total) || roots); scalars r_i, r_i z_i, -sum r_i y_i on `st`
 //     p2_seed: r and its powers r^(2^k) into the session, on `st` (also the seed of the per-item terms, kzg_verify_session_tree)
@@ -1210,14 +1257,13 @@ extern "C" int32_t kzg_verify_phase2_dev(kzg_verify_session* s, const uint8_t* r
     memset(out192, 0, 192);  // A = B = infinity
     return 0;
   }
-  Phase2 p2;
+  Phase2 p2(s);
   int32_t rc = p2_scalars(s, roots32, world, first_index, n_total);
   tt.mark("seed + scalars enqueue");
   if (rc == 0) rc = p2_sort(s, p2, false);
   if (rc == 0) rc = p2_accumulate(s, p2);
   if (rc == 0) rc = p2_finish(s, p2, out192);
   tt.mark("msm A || msm B (incl. host horner)");
-  if (rc) session_drain(s);  // before p2 goes; the session stays the caller's
   return rc;
 } catch (...) {
   return abi_exception();
@@ -1260,7 +1306,7 @@ static int32_t verify_fused(kzg_verify_session* s, const VerifyInputs& in, int32
   uint8_t root[32];
   int32_t err[8];
   err_clear(err, kinds);
-  Phase2 p2;  // declared before anything can fail: every failure below drains the session before p2 goes
+  Phase2 p2(s);
   int32_t rc = 0;
   if (root_done) {
     memcpy(root, root_done, 32);
@@ -1277,8 +1323,7 @@ static int32_t verify_fused(kzg_verify_session* s, const VerifyInputs& in, int32
   const int32_t code = rc == 0 ? first_error_code(err, kinds) : 0;
   if (rc == 0 && code == 0) rc = p2_finish_and_pair(s, p2, ok);
   tt.mark("lincombs + host horner + pairing");
-  if (rc || code) session_drain(s);  // a rejected input wins: its code is returned, the sums are discarded
-  return rc ? rc : code;
+  return rc ? rc : code;  // a rejected input wins: its code is returned, the sums are discarded
 }
 
 // introspection: challenge z_i and evaluation y_i of items [first, first + count) of a session after phase 1
@@ -1324,27 +1369,17 @@ extern "C" int32_t kzg_verify_batch_finish(const kzg_ctx* ctx, const uint8_t* pa
   return abi_exception();
 }
 
+// The answer every batch entry point gives before anything else is looked at: the empty batch verifies (reference quirk Q4).
+static int32_t empty_batch(int32_t* ok) {
+  *ok = 1;
+  return 0;
+}
+
 extern "C" int32_t kzg_verify_blob_proof_batch_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_proofs48,
                                                    uint64_t n, int32_t* ok, void* hip_stream) try {
-  if (!ctx || !ok || (n && (!d_blobs || !d_commitments48 || !d_proofs48))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *ok = 0;
-  if (n == 0) {  // reference quirk Q4: the spec answer for an empty batch is true
-    *ok = 1;
-    return 0;
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  kzg_verify_session* s = nullptr;
-  int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
-  if (rc) return rc;
-  const VerifyInputs in = blob_inputs(d_blobs, d_commitments48, d_proofs48);
-  if (one_item_on_host(s)) {
-    rc = phase1_items(s, in.blobs, in.commitments48, in.proofs48, 0, 1, s->st, true);
-    if (rc == 0) rc = verify_one_tail(s, ok);
-  } else {
-    rc = verify_fused(s, in, ok, "verify (fused phases)");
-  }
-  kzg_verify_session_destroy(s);
-  return rc;
+  const VerifyInputs in = blob_inputs(d_blobs, d_commitments48, d_proofs48, false);
+  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, nullptr, ok) : empty_batch(ok);
 } catch (...) {
   return abi_exception();
 }
@@ -1358,58 +1393,48 @@ extern "C" int32_t kzg_verify_blob_proof_batch_dev(const kzg_ctx* ctx, const voi
 int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& shares, uint64_t n_total, int32_t* ok) {
   *ok = 0;
   const uint32_t W = (uint32_t)shares.size();
-  if (W == 0) {  // reference quirk Q4: the empty batch verifies
-    *ok = 1;
-    return 0;
-  }
+  if (W == 0) return empty_batch(ok);
   const bool points = shares[0].in.kind == VerifyInputs::POINTS;
-  if (W == 1) {  // one share: exactly the single-device call (one root seeds the challenge)
-    const GroupDevShare& sh = shares[0];
-    return points ? kzg_verify_proof_batch_dev(sh.member, sh.in.proofs48, sh.in.commitments48, sh.in.z32, sh.in.y32, sh.count, ok, sh.st)
-                  : kzg_verify_blob_proof_batch_dev(sh.member, sh.in.blobs, sh.in.commitments48, sh.in.proofs48, sh.count, ok, sh.st);
-  }
+  // one share: exactly the single-device call (one root seeds the challenge)
+  if (W == 1) return verify_batch_single(shares[0].member, shares[0].in, shares[0].count, shares[0].st, nullptr, ok);
   TraceTimer tt(ctx->knobs.trace, points ? "group verify_proof_batch (device-resident)" : "group verify (device-resident)");
   const int kinds = shares[0].in.kinds();
   const size_t stride = 2 * (size_t)kinds;
   std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
   std::vector<int32_t> err(stride * W);
   for (uint32_t j = 0; j < W; j++) err_clear(err.data() + stride * j, kinds);
-  std::vector<kzg_verify_session*> sessions(W, nullptr);
-  auto release = [&]() {
+  std::vector<SessionUse> uses(W);
+  auto release = [&]() {  // handing a session back may fail on its own: the error the caller is told about stays the first one
     const ErrorSnapshot keep = error_snapshot();
-    for (kzg_verify_session* s : sessions)
-      if (s) kzg_verify_session_destroy(s);
+    for (SessionUse& u : uses) u.reset();
     error_publish(keep);
   };
   int32_t rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
     const GroupDevShare& sh = shares[j];
     if (hipSetDevice(sh.member->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
-    int32_t r = session_acquire(sh.member, sh.count, sh.st, &sessions[j]);
-    if (r == 0) r = front_enqueue(sessions[j], sh.in);
-    if (r == 0) r = p1_root(sessions[j], roots.data() + 32 * (size_t)j);
+    int32_t r = session_acquire(sh.member, sh.count, sh.st, &uses[j].s);
+    if (r == 0) r = front_enqueue(uses[j].s, sh.in);
+    if (r == 0) r = p1_root(uses[j].s, roots.data() + 32 * (size_t)j);
     return r;
   });
   tt.mark("round 1: front, transcript, roots (decoders still running)");
   if (rc) {
-    for (uint32_t j = 0; j < W; j++)  // drain the members that did enqueue before their sessions go back to the pools
-      if (sessions[j] && hipSetDevice(shares[j].member->device) == hipSuccess) session_drain(sessions[j]);
     release();
     return rc;
   }
   std::vector<int32_t> codes(W, 0);
   rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
     const GroupDevShare& sh = shares[j];
-    kzg_verify_session* s = sessions[j];
+    kzg_verify_session* s = uses[j].s;
     int32_t* e = err.data() + stride * j;
     if (hipSetDevice(sh.member->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
-    Phase2 p2;
+    Phase2 p2(s);
     int32_t r = p2_scalars(s, roots.data(), W, sh.first, n_total);
     if (r == 0) r = p2_sort(s, p2, true);
     if (r == 0) r = p2_accumulate(s, p2);
     if (r == 0) r = front_status(s, sh.in, e);
     if (r == 0) codes[j] = first_error_code(e, kinds);
-    if (r == 0 && codes[j] == 0) r = p2_finish(s, p2, partials.data() + 192 * (size_t)j);
-    if (r || codes[j]) session_drain(s);  // before p2 goes; a rejected input's sums are discarded
+    if (r == 0 && codes[j] == 0) r = p2_finish(s, p2, partials.data() + 192 * (size_t)j);  // a rejected input's sums are discarded
     return r;
   });
   tt.mark("round 2: scalars, lincombs, first errors, partial sums");
@@ -1426,29 +1451,12 @@ int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& s
 
 extern "C" int32_t kzg_verify_blob_proof_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48,
                                                uint64_t n, int32_t* ok) try {
-  if (!ctx || !ok || (n && (!blobs || !commitments48 || !proofs48))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *ok = 0;
-  if (n == 0) {
-    *ok = 1;
-    return 0;
-  }
-  return (is_group(ctx) ? multi_verify_batch : verify_batch_host_single)(ctx, blobs, commitments48, proofs48, n, ok);
+  const VerifyInputs in = blob_inputs(blobs, commitments48, proofs48, true);
+  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return empty_batch(ok);
+  return is_group(ctx) ? multi_verify_batch(ctx, in, n, ok) : verify_batch_single(ctx, in, n, nullptr, nullptr, ok);
 } catch (...) {
   return abi_exception();
-}
-int32_t verify_batch_host_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, int32_t* ok) {
-  *ok = 0;
-  HIP_TRY(hipSetDevice(ctx->device));
-  uint8_t root[32];
-  kzg_verify_session* s = nullptr;
-  int32_t rc = verify_phase1_host(ctx, blobs, commitments48, proofs48, n, root, nullptr, &s);
-  if (rc) return rc;
-  if (one_item_on_host(s))
-    rc = verify_one_tail(s, ok);
-  else  // the device copies: proofs || commitments
-    rc = verify_fused(s, blob_inputs(nullptr, s->pts48 + n * 48, s->pts48), ok, "verify (fused phases)", root);
-  kzg_verify_session_destroy(s);
-  return rc;
 }
 
 // Setup::verify_blob_proof (src/kzg/setup.rs:208-221): a batch of one (the random
@@ -1473,15 +1481,12 @@ extern "C" int32_t kzg_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, 
 int32_t verify_proof_single(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok) {
   *ok = 0;
   HIP_TRY(hipSetDevice(ctx->device));
-  kzg_verify_session* s = nullptr;
-  hipStream_t st = nullptr;
-  {
-    // a private stream per call would cost a creation; the session's own stream carries the whole single-item call
-    int32_t rc0 = session_acquire(ctx, 1, KZG_SESSION_STREAM, &s);
-    if (rc0) return rc0;
-    st = s->st;
-  }
-  int32_t rc = 0;
+  SessionUse use;
+  // a private stream per call would cost a creation; the session's own stream carries the whole single-item call
+  int32_t rc = session_acquire(ctx, 1, KZG_SESSION_STREAM, &use.s);
+  if (rc) return rc;
+  kzg_verify_session* s = use.s;
+  hipStream_t st = s->st;
   int32_t h_stat[2] = {0, 0};
   uint32_t h_aff[48];  // proof, commitment as decoded
   uint8_t h_inf[2] = {0, 0};
@@ -1507,116 +1512,44 @@ int32_t verify_proof_single(const kzg_ctx* ctx, const uint8_t* proof48, const ui
     if (hipMemcpyAsync(s->z, &zy[0], 32, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(s->y, &zy[1], 32, hipMemcpyHostToDevice, st) != hipSuccess) { rc = fail(KZG_FAIL_HIP, "copy"); break; }
   } while (0);
-  if (rc == 0 && !ctx->knobs.single_via_batch) {
-    kzg_verify_session_destroy(s);
-    return verify_one_on_host(ctx, h_aff, h_inf[0] != 0, h_aff + 24, h_inf[1] != 0, zy[0], zy[1], ok);
-  }
   uint8_t partial[192];
-  if (rc == 0) {
+  if (rc == 0 && ctx->knobs.single_via_batch) {
     const uint8_t root[32] = {0};
     rc = kzg_verify_phase2_dev(s, root, 1, 0, 1, partial);
   }
-  kzg_verify_session_destroy(s);
+  use.reset();  // the host's part needs no session
   if (rc) return rc;
+  if (!ctx->knobs.single_via_batch) return verify_one_on_host(ctx, h_aff, h_inf[0] != 0, h_aff + 24, h_inf[1] != 0, zy[0], zy[1], ok);
   return kzg_verify_batch_finish(ctx, partial, 1, ok);
 }
 
 // ---- Setup::verify_proof_batch (src/kzg/setup.rs:115-161) as a public batch call: n caller-supplied (proof, commitment, z, y) -------
-// The blob batch's drivers (phase1_dev, verify_fused, verify_group_dev) over point_inputs: only the front and the reading of the
-// four-kind error record differ -- front_enqueue / front_status, POINTS.  What is here are the entry points and the host-buffer staging.
+// The blob batch's drivers (verify_batch_single, verify_phase1, verify_fused, verify_group_dev) over point_inputs: only the front and the
+// reading of the four-kind error record differ -- front_enqueue / front_status, POINTS.
 extern "C" int32_t kzg_verify_proof_phase1_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
                                                uint64_t n, uint8_t* out_root32, int32_t* err8, kzg_verify_session** session, void* hip_stream) try {
-  if (!ctx || !out_root32 || !err8 || !session || (n && (!d_proofs48 || !d_commitments48 || !d_z32 || !d_y32)))
-    return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return phase1_dev(ctx, point_inputs(d_proofs48, d_commitments48, d_z32, d_y32), n, out_root32, err8, session, (hipStream_t)hip_stream);
+  const VerifyInputs in = point_inputs(d_proofs48, d_commitments48, d_z32, d_y32, false);
+  if (!ctx || !out_root32 || !err8 || !session || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return verify_phase1(ctx, in, n, (hipStream_t)hip_stream, out_root32, err8, session);
 } catch (...) {
   return abi_exception();
 }
 
 extern "C" int32_t kzg_verify_proof_batch_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
                                               uint64_t n, int32_t* ok, void* hip_stream) try {
-  if (!ctx || !ok || (n && (!d_proofs48 || !d_commitments48 || !d_z32 || !d_y32))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *ok = 0;
-  if (n == 0) {  // as kzg_verify_blob_proof_batch: the empty batch verifies
-    *ok = 1;
-    return 0;
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  kzg_verify_session* s = nullptr;
-  int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
-  if (rc) return rc;
-  rc = verify_fused(s, point_inputs(d_proofs48, d_commitments48, d_z32, d_y32), ok, "verify_proof_batch (fused phases)");
-  kzg_verify_session_destroy(s);
-  return rc;
+  const VerifyInputs in = point_inputs(d_proofs48, d_commitments48, d_z32, d_y32, false);
+  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, nullptr, ok) : empty_batch(ok);
 } catch (...) {
   return abi_exception();
 }
 
-// Host buffers: 160 bytes per tuple cross PCIe whole into the session's own staging (proofs || commitments, z || y) on the
-// context's verification stream; nothing of the blob calls' staging arena is used, so stage_lock is held for stage_init only.
-static int32_t points_stage_host(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
-                                 kzg_verify_session** out) {
-  *out = nullptr;
-  {
-    std::lock_guard<std::mutex> guard(ctx->stage_lock);
-    const int32_t rc = stage_init(ctx);
-    if (rc) return rc;
-  }
-  kzg_verify_session* s = nullptr;
-  int32_t rc = session_acquire(ctx, n, ctx->verify_stream, &s);
-  if (rc) return rc;
-  if (hipMemcpyAsync(s->pts48, proofs48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-      hipMemcpyAsync(s->pts48 + n * 48, commitments48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-      hipMemcpyAsync(s->zy32, z32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-      hipMemcpyAsync(s->zy32 + n * 32, y32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess) {
-    session_drain(s);
-    kzg_verify_session_destroy(s);
-    return fail(KZG_FAIL_HIP, "host-to-device copy failed");
-  }
-  *out = s;
-  return 0;
-}
-int32_t verify_proof_phase1_host(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
-                                 uint8_t* out_root32, int32_t* err8, kzg_verify_session** session) {
-  *session = nullptr;
-  err_clear(err8, 4);
-  HIP_TRY(hipSetDevice(ctx->device));
-  kzg_verify_session* s = nullptr;
-  int32_t rc = points_stage_host(ctx, proofs48, commitments48, z32, y32, n, &s);
-  if (rc) return rc;
-  const VerifyInputs in = point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32);
-  rc = front_enqueue(s, in);
-  if (rc == 0) rc = p1_root(s, out_root32);
-  if (rc == 0) rc = front_status(s, in, err8);
-  if (rc) {
-    session_drain(s);
-    kzg_verify_session_destroy(s);
-    return rc;
-  }
-  *session = s;
-  return 0;
-}
-int32_t verify_proof_batch_host_single(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32,
-                                       uint64_t n, int32_t* ok) {
-  *ok = 0;
-  if (n == 1) return verify_proof_single(ctx, proofs48, commitments48, z32, y32, ok);  // one tuple: the lincombs on the host (verify_one_on_host)
-  HIP_TRY(hipSetDevice(ctx->device));
-  kzg_verify_session* s = nullptr;
-  int32_t rc = points_stage_host(ctx, proofs48, commitments48, z32, y32, n, &s);
-  if (rc) return rc;
-  rc = verify_fused(s, point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32), ok, "verify_proof_batch (fused phases)");
-  kzg_verify_session_destroy(s);
-  return rc;
-}
 extern "C" int32_t kzg_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32,
                                           uint64_t n, int32_t* ok) try {
-  if (!ctx || !ok || (n && (!proofs48 || !commitments48 || !z32 || !y32))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *ok = 0;
-  if (n == 0) {
-    *ok = 1;
-    return 0;
-  }
-  return (is_group(ctx) ? multi_verify_proof_batch : verify_proof_batch_host_single)(ctx, proofs48, commitments48, z32, y32, n, ok);
+  const VerifyInputs in = point_inputs(proofs48, commitments48, z32, y32, true);
+  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return empty_batch(ok);
+  return is_group(ctx) ? multi_verify_batch(ctx, in, n, ok) : verify_batch_single(ctx, in, n, nullptr, nullptr, ok);
 } catch (...) {
   return abi_exception();
 }
@@ -1750,10 +1683,7 @@ extern "C" int32_t kzg_verify_session_tree(kzg_verify_session* s, const uint8_t*
   if (rc == 0) rc = each_status_enqueue(s);
   if (rc == 0) rc = each_build(s, g, first_index);
   if (rc == 0 && hipStreamSynchronize(s->st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "per-item verdicts: tree build failed");
-  if (rc) {
-    s->tree_n = 0;
-    session_drain(s);
-  }
+  if (rc) s->tree_n = 0;
   return rc;
 } catch (...) {
   return abi_exception();
@@ -1799,41 +1729,36 @@ extern "C" uint64_t kzg_verify_each_checks(const kzg_ctx* ctx) {
   for (const kzg_ctx* p : ctx->peers) total += p->each_checks.load(std::memory_order_relaxed);
   return total;
 }
-
-// one item: the single-item call's answer in the per-item outputs
-static int32_t each_from_single(int32_t rc, int32_t one_ok, uint8_t* ok_each, int32_t* status, int32_t* ok) {
-  if (rc < 0) return rc;
-  status[0] = rc;
-  ok_each[0] = (rc == 0 && one_ok) ? 1 : 0;
-  *ok = ok_each[0];
-  return 0;
+extern "C" uint64_t kzg_ctx_sessions_created(const kzg_ctx* ctx) {
+  if (!ctx) return 0;
+  uint64_t total = ctx->sessions_created.load(std::memory_order_relaxed);
+  for (const kzg_ctx* p : ctx->peers) total += p->sessions_created.load(std::memory_order_relaxed);
+  return total;
 }
-// The ending of all four calls: the session's front is enqueued and its root taken (n >= 2).
-static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, uint8_t* ok_each, int32_t* status, int32_t* ok) {
+
+// The ending of the per-item calls: the session's front is enqueued and its root taken (n >= 2).
+static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, const VerifyEach& out, int32_t* ok) {
   const uint64_t n = s->n;
   *ok = 0;
   const EachGeom g = each_geom(n);
   uint32_t rejected = 0;
   int32_t rc = each_reserve(s, g);
   if (rc == 0) rc = each_status_enqueue(s);
-  if (rc == 0 && (hipMemcpyAsync(status, s->t_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+  if (rc == 0 && (hipMemcpyAsync(out.status, s->t_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
                   hipMemcpyAsync(&rejected, s->t_rejected, sizeof(uint32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
                   hipStreamSynchronize(s->st) != hipSuccess))
     rc = fail(KZG_FAIL_HIP, "per-item verdicts: status read-back failed");
   if (rc) return rc;
   if (rejected == 0) {  // today's batch check first: true = every item true
-    Phase2 p2;
+    Phase2 p2(s);
     int32_t all = 0;
     rc = p2_scalars(s, root, 1, 0, n);
     if (rc == 0) rc = p2_sort(s, p2, false);
     if (rc == 0) rc = p2_accumulate(s, p2);
     if (rc == 0) rc = p2_finish_and_pair(s, p2, &all);
-    if (rc) {
-      session_drain(s);  // before p2 goes
-      return rc;
-    }
+    if (rc) return rc;
     if (all) {
-      memset(ok_each, 1, n);
+      memset(out.ok_each, 1, n);
       *ok = 1;
       return 0;
     }
@@ -1841,125 +1766,90 @@ static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, uint8_t* 
     rc = p2_seed(s, root, 1, n);
   }
   if (rc == 0) rc = each_build(s, g, 0);
-  if (rc == 0) rc = each_descend(s, g, ok_each);
+  if (rc == 0) rc = each_descend(s, g, out.ok_each);
   if (rc) return rc;
   for (uint64_t i = 0; i < n; i++)
-    if (status[i]) ok_each[i] = 0;
+    if (out.status[i]) out.ok_each[i] = 0;
   return 0;  // *ok = 0: an item was rejected, or the batch check was false
+}
+
+// The single-device batch call (engine_internal.hpp).  What differs between the routes: how the session with device-resident inputs
+// comes to be, the single-item shortcuts, and the ending.
+int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, const VerifyEach* each, int32_t* ok) {
+  *ok = 0;
+  const bool blobs = in.kind == VerifyInputs::BLOBS;
+  if (each && n == 1) {  // per-item verdicts of one item: the boolean call's answer in the per-item outputs
+    int32_t one = 0;
+    const int32_t rc = verify_batch_single(ctx, in, 1, st, nullptr, &one);
+    if (rc < 0) return rc;
+    each->status[0] = rc;
+    *ok = each->ok_each[0] = (rc == 0 && one) ? 1 : 0;
+    return 0;
+  }
+  // one tuple from host buffers: z and y parsed on the host, the lincombs there too (verify_one_on_host)
+  if (n == 1 && in.on_host && !blobs) return verify_proof_single(ctx, in.proofs48, in.commitments48, in.z32, in.y32, ok);
+  HIP_TRY(hipSetDevice(ctx->device));
+  SessionUse use;
+  uint8_t root[32];
+  int32_t err6[6];
+  // Host blobs pass through the staging arena, so their front runs -- and the root is taken -- while it is locked.  The per-item
+  // ending asks for the statuses there although each_finish reads its own: kept as it was, a candidate for removal.
+  const bool front_done = in.on_host && blobs;
+  int32_t rc = front_done   ? verify_phase1_host(ctx, in.blobs, in.commitments48, in.proofs48, n, root, each ? err6 : nullptr, &use.s)
+               : in.on_host ? points_stage_host(ctx, in, n, &use.s)
+                            : session_acquire(ctx, n, st, &use.s);
+  if (rc) return rc;
+  kzg_verify_session* s = use.s;
+  const VerifyInputs dev = in.on_host ? staged_inputs(s, in.kind) : in;
+  if (blobs && one_item_on_host(s)) {  // no transcript: the item's kernels, then the host (verify_one_tail)
+    if (!front_done) rc = phase1_items(s, dev.blobs, dev.commitments48, dev.proofs48, 0, 1, s->st, true);
+    return rc ? rc : verify_one_tail(s, ok);
+  }
+  if (!each) return verify_fused(s, dev, ok, blobs ? "verify (fused phases)" : "verify_proof_batch (fused phases)", front_done ? root : nullptr);
+  if (!front_done) {
+    rc = front_enqueue(s, dev);
+    if (rc == 0) rc = p1_root(s, root);
+  }
+  return rc ? rc : each_finish(s, root, *each, ok);
 }
 
 extern "C" int32_t kzg_verify_blob_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_proofs48, uint64_t n,
                                                         uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream) try {
-  if (!ctx || !ok || (n && (!d_blobs || !d_commitments48 || !d_proofs48 || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *ok = 0;
-  if (n == 0) {
-    *ok = 1;
-    return 0;
-  }
-  if (n == 1) {
-    int32_t one = 0;
-    return each_from_single(kzg_verify_blob_proof_batch_dev(ctx, d_blobs, d_commitments48, d_proofs48, 1, &one, hip_stream), one, ok_each, status, ok);
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  kzg_verify_session* s = nullptr;
-  int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
-  if (rc) return rc;
-  uint8_t root[32];
-  rc = front_enqueue(s, blob_inputs(d_blobs, d_commitments48, d_proofs48));
-  if (rc == 0) rc = p1_root(s, root);
-  if (rc == 0) rc = each_finish(s, root, ok_each, status, ok);
-  if (rc) session_drain(s);
-  kzg_verify_session_destroy(s);
-  return rc;
+  const VerifyInputs in = blob_inputs(d_blobs, d_commitments48, d_proofs48, false);
+  const VerifyEach each{ok_each, status};
+  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, &each, ok) : empty_batch(ok);
 } catch (...) {
   return abi_exception();
 }
 
 extern "C" int32_t kzg_verify_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
                                                    uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream) try {
-  if (!ctx || !ok || (n && (!d_proofs48 || !d_commitments48 || !d_z32 || !d_y32 || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *ok = 0;
-  if (n == 0) {
-    *ok = 1;
-    return 0;
-  }
-  if (n == 1) {
-    int32_t one = 0;
-    return each_from_single(kzg_verify_proof_batch_dev(ctx, d_proofs48, d_commitments48, d_z32, d_y32, 1, &one, hip_stream), one, ok_each, status, ok);
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  kzg_verify_session* s = nullptr;
-  int32_t rc = session_acquire(ctx, n, (hipStream_t)hip_stream, &s);
-  if (rc) return rc;
-  uint8_t root[32];
-  rc = front_enqueue(s, point_inputs(d_proofs48, d_commitments48, d_z32, d_y32));
-  if (rc == 0) rc = p1_root(s, root);
-  if (rc == 0) rc = each_finish(s, root, ok_each, status, ok);
-  if (rc) session_drain(s);
-  kzg_verify_session_destroy(s);
-  return rc;
+  const VerifyInputs in = point_inputs(d_proofs48, d_commitments48, d_z32, d_y32, false);
+  const VerifyEach each{ok_each, status};
+  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, &each, ok) : empty_batch(ok);
 } catch (...) {
   return abi_exception();
 }
 
-int32_t verify_blob_each_host_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n, uint8_t* ok_each,
-                                     int32_t* status, int32_t* ok) {
-  *ok = 0;
-  if (n == 1) {
-    int32_t one = 0;
-    return each_from_single(verify_batch_host_single(ctx, blobs, commitments48, proofs48, 1, &one), one, ok_each, status, ok);
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  uint8_t root[32];
-  int32_t err6[6];
-  kzg_verify_session* s = nullptr;
-  int32_t rc = verify_phase1_host(ctx, blobs, commitments48, proofs48, n, root, err6, &s);
-  if (rc) return rc;
-  rc = each_finish(s, root, ok_each, status, ok);
-  if (rc) session_drain(s);
-  kzg_verify_session_destroy(s);
-  return rc;
-}
-int32_t verify_proof_each_host_single(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32, uint64_t n,
-                                      uint8_t* ok_each, int32_t* status, int32_t* ok) {
-  *ok = 0;
-  if (n == 1) {
-    int32_t one = 0;
-    return each_from_single(verify_proof_single(ctx, proofs48, commitments48, z32, y32, &one), one, ok_each, status, ok);
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  kzg_verify_session* s = nullptr;
-  int32_t rc = points_stage_host(ctx, proofs48, commitments48, z32, y32, n, &s);
-  if (rc) return rc;
-  uint8_t root[32];
-  rc = front_enqueue(s, point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32));
-  if (rc == 0) rc = p1_root(s, root);
-  if (rc == 0) rc = each_finish(s, root, ok_each, status, ok);
-  if (rc) session_drain(s);
-  kzg_verify_session_destroy(s);
-  return rc;
-}
 extern "C" int32_t kzg_verify_blob_proof_batch_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n,
                                                     uint8_t* ok_each, int32_t* status, int32_t* ok) try {
-  if (!ctx || !ok || (n && (!blobs || !commitments48 || !proofs48 || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *ok = 0;
-  if (n == 0) {
-    *ok = 1;
-    return 0;
-  }
-  return (is_group(ctx) ? multi_verify_blob_each : verify_blob_each_host_single)(ctx, blobs, commitments48, proofs48, n, ok_each, status, ok);
+  const VerifyInputs in = blob_inputs(blobs, commitments48, proofs48, true);
+  const VerifyEach each{ok_each, status};
+  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return empty_batch(ok);
+  return is_group(ctx) ? multi_verify_each(ctx, in, n, each, ok) : verify_batch_single(ctx, in, n, nullptr, &each, ok);
 } catch (...) {
   return abi_exception();
 }
 extern "C" int32_t kzg_verify_proof_batch_each(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32,
                                                uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok) try {
-  if (!ctx || !ok || (n && (!proofs48 || !commitments48 || !z32 || !y32 || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  *ok = 0;
-  if (n == 0) {
-    *ok = 1;
-    return 0;
-  }
-  return (is_group(ctx) ? multi_verify_proof_each : verify_proof_each_host_single)(ctx, proofs48, commitments48, z32, y32, n, ok_each, status, ok);
+  const VerifyInputs in = point_inputs(proofs48, commitments48, z32, y32, true);
+  const VerifyEach each{ok_each, status};
+  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return empty_batch(ok);
+  return is_group(ctx) ? multi_verify_each(ctx, in, n, each, ok) : verify_batch_single(ctx, in, n, nullptr, &each, ok);
 } catch (...) {
   return abi_exception();
 }

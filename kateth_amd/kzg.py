@@ -169,6 +169,7 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p, _i32p, ctypes.c_void_p],
     ),
     "kzg_verify_each_checks": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "kzg_ctx_sessions_created": (ctypes.c_uint64, [ctypes.c_void_p]),
     "kzg_verify_session_tree": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]),
     "kzg_verify_session_tree_range": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, _u8p]),
     "kzg_g1_decompress_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
@@ -884,6 +885,10 @@ class Setup:
     def verify_each_checks(self) -> int:
         """two-pairing checks the per-item verdict calls have spent on this context so far"""
         return int(self._lib.kzg_verify_each_checks(self._h))
+
+    def sessions_created(self) -> int:
+        """verification sessions this context and its members have ever constructed (a steady state creates none)"""
+        return int(self._lib.kzg_ctx_sessions_created(self._h))
 
     # -- device-resident SHARDED calls on a group context: one entry per member, member k's buffers resident on member k's GPU ---
     def _per_member(self, values, what):

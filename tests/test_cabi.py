@@ -34,7 +34,7 @@ def test_header_and_library_agree(lib):
     from kateth_amd import kzg
 
     declared = declared_functions()
-    assert "kzg_blob_to_commitment_batch" in declared and "kzg_verify_blob_proof_batch" in declared
+    assert "kzg_blob_to_commitment_batch" in declared and "kzg_verify_blob_proof_batch" in declared and "kzg_ctx_sessions_created" in declared
     out = subprocess.check_output(["nm", "-D", "--defined-only", kzg.library_path()], text=True)
     exported = sorted(set(re.findall(r"\bT (kzg_[a-z0-9_]+)\b", out)))
     assert exported == declared, (set(declared) ^ set(exported))

@@ -65,6 +65,7 @@ def test_null_context_is_an_argument_error_not_a_crash(lib):
     assert lib.kzg_verify_proof_batch_dev(None, None, None, None, None, 0, ctypes.byref(ok), None) == -1
     assert lib.kzg_verify_proof_batch_group_dev(None, None, None, None, None, None, ctypes.byref(ok), None) == -1
     assert lib.kzg_verify_proof_phase1_dev(None, None, None, None, None, 0, None, None, None, None) == -1
+    assert lib.kzg_ctx_sessions_created(None) == 0
 
 
 def test_mirror_checks_lengths_before_the_engine():

@@ -8,8 +8,10 @@ kzg_verify_session_tree / kzg_verify_session_tree_range.
    constructed truth and n calls of kzg_verify_proof.
 3. REJECTIONS beside verdicts: status[] carries the single call's first error, the other items keep their verdicts.
 4. BLOB triples against kzg_verify_blob_proof and the oracle.
-5. The same answers by every route: host buffers, *_dev, a group context, the Python mirror (wrong-length items included), n = 0.
+5. The same answers by every route: host buffers, *_dev, a group context, the Python mirror (wrong-length items included), n = 0;
+   blob triples by the same routes.
 6. DEGENERATE points: infinity, repeated and opposite points in one tree.
+7. The POOL: after one call of every route, no route and no exit creates a session (kzg_ctx_sessions_created).
 
 Shapes: ragged trees (3, 65, 257), one wave and its edge (64, 65), a lone leaf (1, 2)."""
 import ctypes
@@ -23,6 +25,7 @@ from conftest import TRUSTED_SETUP  # noqa: E402
 
 import verify_exact as vx  # noqa: E402
 import verify_points as vp  # noqa: E402
+import verify_routes as vr  # noqa: E402
 from oracle.pyref import bls  # noqa: E402
 
 R = vp.R
@@ -392,7 +395,8 @@ def _mirror(got):
     return ok_each, status
 
 
-def test_every_route_gives_the_same_verdicts(engine, group3, torch_cuda, linear, mixed65):
+def test_every_route_gives_the_same_verdicts(engine, group3, torch_cuda, linear, mixed65, blobs257):
+    _blob_triples_by_every_route(engine, group3, torch_cuda, blobs257)
     n = 65
     two, done = _spoiled(linear.arrays(n), n, "commitment", [31, 32])
     assert done == [31, 32]
@@ -428,6 +432,91 @@ def test_every_route_gives_the_same_verdicts(engine, group3, torch_cuda, linear,
         ok = ctypes.c_int32(-1)
         assert e._lib.kzg_verify_blob_proof_batch_each_dev(e._h, None, None, None, 0, None, None, ctypes.byref(ok), None) == 0 and ok.value == 1
     assert engine.verify_proof_batch_each([], [], [], []) == [] and engine.verify_blob_proof_batch_each([], [], []) == []
+
+
+@pytest.fixture(scope="module")
+def blobs257(engine, torch_cuda):
+    return vr.blob_arrays(engine, torch_cuda, N_MAX)
+
+
+def _rejected_blobs(arrays):
+    """one rejected item of each kind: a blob element = r at 10, an off-curve commitment at 50, a proof outside the group at 200
+    -> (arrays, status); a batch call answers the blob's code, blobs being parsed first"""
+    blobs, coms, proofs = arrays
+    bad, B = _bad_points(), vr.BLOB_BYTES
+    blobs = vr.put(blobs, 10, B, vr.put(blobs[10 * B:11 * B], 77, 32, R.to_bytes(32, "big")))
+    return (blobs, vr.put(coms, 50, 48, bad[4]), vr.put(proofs, 200, 48, bad[5])), {10: 2, 50: 4, 200: 5}
+
+
+def _rejected_points(arrays):
+    """an off-curve commitment at 50, a proof outside the group at 200, z = r at 10, y = r at 20; a batch call answers the proof's code"""
+    prf, com, zb, yb = arrays
+    bad, rb = _bad_points(), R.to_bytes(32, "big")
+    return (vp.put(prf, 200, 48, bad[5]), vp.put(com, 50, 48, bad[4]), vp.put(zb, 10, 32, rb), vp.put(yb, 20, 32, rb)), {10: 7, 20: 7, 50: 4, 200: 5}
+
+
+def _blob_triples_by_every_route(engine, group3, torch_cuda, blobs257):
+    """the per-item blob routes -- host, device, group host, member 0 of the group -- against each other"""
+    n = 65
+    blobs, coms, proofs = (a[:w * n] for a, w in zip(blobs257, vr.WIDTHS["blobs"]))
+    swapped = vr.put(vr.put(proofs, 31, 48, proofs[48 * 32:48 * 33]), 32, 48, proofs[48 * 31:48 * 32])
+    bad = _bad_points()
+    mixed = (vr.put(blobs, 10, vr.BLOB_BYTES, vr.put(blobs[10 * vr.BLOB_BYTES:11 * vr.BLOB_BYTES], 77, 32, R.to_bytes(32, "big"))), vr.put(coms, 9, 48, bad[4]), swapped)
+    status = [2 if i == 10 else 4 if i == 9 else 0 for i in range(n)]
+    for arrays, want in (((blobs, coms, proofs), (0, [1] * n, [0] * n, 1)), ((blobs, coms, swapped), (0, [0 if i in (31, 32) else 1 for i in range(n)], [0] * n, 0)),
+                         (mixed, (0, [0 if i in (9, 10, 31, 32) else 1 for i in range(n)], status, 0))):
+        got = {name: call() for name, call in vr.each_routes(engine, group3, vr.Inputs(torch_cuda, "blobs", arrays, n)).items()}
+        assert len(got) == 4 and all(v == want for v in got.values()), got
+
+
+# ---- 7. the pool ------------------------------------------------------------------------------------------------------------------
+def test_sessions_return_to_the_pool_on_every_exit(engine, group3, torch_cuda, linear, blobs257):
+    """Every route, one call at a time from this thread.  The first round of valid calls at n = 257 -- a second 256-item transcript
+    group, more than one share per member -- creates every session a route ever holds at once; after it no shape and no exit (true,
+    false with the per-item descent, a rejected item of each kind, phase 1 abandoned) creates another.  A session that a path failed
+    to hand back would be missing from the pool at the next call, which would then construct one: the count is exact."""
+    n = N_MAX
+
+    def every_route(kind, arrays, m):
+        x = vr.Inputs(torch_cuda, kind, arrays, m)
+        boolean = {name: call() for name, call in vr.boolean_routes(engine, group3, x).items()}
+        boolean["group dev, an idle member"] = vr.group_dev(group3, x, [m - m // 2, 0, m // 2])
+        assert vr.phases(engine, x, [(0, m)], finish=False) == (0, None)  # phase 1, then kzg_verify_session_destroy
+        each = {name: call() for name, call in vr.each_routes(engine, group3, x).items()}
+        return boolean, each
+
+    def expect(got, want_boolean, want_each, label):
+        boolean, each = got
+        assert all(v == want_boolean for v in boolean.values()), (label, boolean)
+        assert all(v == want_each for v in each.values()), (label, {k: (v[0], v[3], [i for i, o in enumerate(v[1]) if not o], [s for s in v[2] if s]) for k, v in each.items()})
+
+    def verdicts(m, false=(), status=None):
+        status = status or {}
+        return 0, [0 if i in false or i in status else 1 for i in range(m)], [status.get(i, 0) for i in range(m)], 0 if false or status else 1
+
+    valid = {"points": linear.arrays(n), "blobs": blobs257}
+    for kind in ("points", "blobs"):
+        expect(every_route(kind, valid[kind], n), (0, 1), verdicts(n), (kind, "warm-up"))
+    created = (engine.sessions_created(), group3.sessions_created())
+    assert created[0] >= 2 and created[1] >= 3, created  # two shares on one context; a session per member
+
+    spoiled_points, done = _spoiled(valid["points"], n, "y+1", [100])
+    assert done == [100]
+    blobs, coms, proofs = blobs257
+    shapes = {
+        "points": [(spoiled_points, (0, 0), verdicts(n, false=[100]))],
+        "blobs": [((blobs, coms, vr.put(proofs, 100, 48, proofs[48 * 101:48 * 102])), (0, 0), verdicts(n, false=[100]))],
+    }
+    bad, status = _rejected_points(valid["points"])
+    shapes["points"].append((bad, (5, 0), verdicts(n, status=status)))
+    bad, status = _rejected_blobs(blobs257)
+    shapes["blobs"].append((bad, (2, 0), verdicts(n, status=status)))
+    for kind in ("points", "blobs"):
+        for m in (1, 2, n):
+            expect(every_route(kind, valid[kind], m), (0, 1), verdicts(m), (kind, m))
+        for arrays, want_boolean, want_each in shapes[kind]:
+            expect(every_route(kind, arrays, n), want_boolean, want_each, (kind, want_boolean))
+    assert (engine.sessions_created(), group3.sessions_created()) == created
 
 
 def test_descent_spends_pairings_only_where_a_subtree_fails(engine, torch_cuda, linear):

@@ -17,6 +17,7 @@ from conftest import TRUSTED_SETUP  # noqa: E402
 
 import verify_exact as vx  # noqa: E402
 import verify_points as vp  # noqa: E402
+import verify_routes as vr  # noqa: E402
 from oracle.pyref import bls  # noqa: E402
 
 R = vp.R
@@ -414,6 +415,22 @@ def test_every_route_gives_the_same_answer(engine, group3, linear, torch_cuda):
     ok = ctypes.c_int32(-1)
     none = group3._per_member([0, 0, 0], "share")
     assert group3._lib.kzg_verify_proof_batch_group_dev(group3._h, none, none, none, none, group3._counts([0, 0, 0]), ctypes.byref(ok), None) == 0 and ok.value == 1
+    # the blob routes -- host, device, group host, group device, phase 1 -> phase 2 -> finish -- and the point routes through the same
+    # callers (verify_routes.py), phases included: two swapped proofs make a false batch; a blob element = r (code 2) wins over an
+    # off-curve commitment (code 4) earlier in the batch, blobs being parsed first
+    n = 33
+    blobs, coms, proofs = vr.blob_arrays(engine, torch_cuda, n)
+    swapped = vr.put(vr.put(proofs, 3, 48, proofs[48 * 4:48 * 5]), 4, 48, proofs[48 * 3:48 * 4])
+    bad_blob = vr.put(blobs, 20, vr.BLOB_BYTES, vr.put(blobs[20 * vr.BLOB_BYTES:21 * vr.BLOB_BYTES], 77, 32, BAD_SCALARS["r"]))
+    cases = [("blobs", "valid", (blobs, coms, proofs), (0, 1)), ("blobs", "false", (blobs, coms, swapped), (0, 0)),
+             ("blobs", "rejected", (bad_blob, vr.put(coms, 5, 48, bad[4]), proofs), (2, 0)),
+             ("points", "valid", tuple(a[:w * n] for a, w in zip(valid, WIDTH)), (0, 1)), ("points", "rejected", tuple(a[:w * n] for a, w in zip(rejected, WIDTH)), (7, 0))]
+    for kind, label, arrays, want in cases:
+        x = vr.Inputs(torch_cuda, kind, arrays, n)
+        got = {name: call() for name, call in vr.boolean_routes(engine, group3, x).items()}
+        assert len(got) == 7 and all(v == want for v in got.values()), (kind, label, got)
+    ok = ctypes.c_int32(-1)
+    assert group3._lib.kzg_verify_blob_proof_batch_group_dev(group3._h, none, none, none, group3._counts([0, 0, 0]), ctypes.byref(ok), None) == 0 and ok.value == 1
 
 
 def test_python_mirror_raises_the_reference_errors(engine, linear):
