@@ -176,105 +176,219 @@ KZG_HD void f30_mul_core_c(fp30& r, const fp30& a, const fp30& b, const fp30& c,
 #include "mac30_asm.cuh"  // mad30_chain: v_mad_i64_i32 chains (generated, tools/gen_mac_asm.py)
 namespace kzg {
 
+// KZG_FP30_HOST_ATOMS (tests/hostmath_atoms only): the CPU build takes the device version below as well, with the C fallback of
+// every generated statement, so that a CPU test runs f30_prod::step and f30_run2 THEMSELVES against f30_mul_core_c.
 #if defined(__HIP_DEVICE_COMPILE__)
+#define KZG_F30_ATOM_FENCE() __builtin_amdgcn_sched_barrier(0)
+#else
+#define KZG_F30_ATOM_FENCE() ((void)0)
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) || defined(KZG_FP30_HOST_ATOMS)
 // Device version: every column is issued as explicit v_mad_i64_i32 chains that START from the carry of the previous column
 // (rdx_mont.cuh has the reasons).  Same arithmetic as f30_mul_core_c, which the CPU tests run.
-template <bool SQR, bool TWO, int C0, int C1, bool UFORM, int K>
-KZG_HD void f30_column(int64_t& A, int32_t* q, fp30& r, const fp30& a, const int32_t* a2, const fp30& b, const fp30& c, const fp30& d,
-                       const fp30& inj0, const fp30& inj1) {
-  constexpr int N_ = F30_N;
-  constexpr int i0 = (K < N_) ? 0 : K - N_ + 1;
-  constexpr int i1 = (K < N_) ? K : N_ - 1;
-  constexpr int cnt = i1 - i0 + 1;
-  if constexpr (SQR) {
-    constexpr int last_pair = (K - 1) / 2;
-    constexpr int npairs = (K >= 1 && last_pair >= i0) ? last_pair - i0 + 1 : 0;
-    constexpr int diag = (K % 2 == 0) ? 1 : 0;
-    int32_t xs[npairs + diag], ys[npairs + diag];
-    KZG_UNROLL_FULL
-    for (int t = 0; t < npairs; t++) {
-      xs[t] = a2[i0 + t];
-      ys[t] = a.l[K - i0 - t];
-    }
-    if constexpr (diag) {
-      xs[npairs] = a.l[K / 2];
-      ys[npairs] = a.l[K / 2];
-    }
-    mad30_chain<npairs + diag, false>::run(A, xs, ys);
-  } else {
-    int32_t xs[cnt], ys[cnt];
-    KZG_UNROLL_FULL
-    for (int t = 0; t < cnt; t++) {
-      xs[t] = a.l[i0 + t];
-      ys[t] = b.l[K - i0 - t];
-    }
-    mad30_chain<cnt, false>::run(A, xs, ys);
-  }
-  if constexpr (TWO) {
-    int32_t xs[cnt], ys[cnt];
-    KZG_UNROLL_FULL
-    for (int t = 0; t < cnt; t++) {
-      xs[t] = c.l[i0 + t];
-      ys[t] = d.l[K - i0 - t];
-    }
-    mad30_chain<cnt, false>::run(A, xs, ys);
-  }
-  if constexpr (K < N_) {
-    if constexpr (K > 0) {
-      int32_t qs[K], ps[K];
+// One product in flight: its operands, the column accumulator and the quotient digits.  step<K, PH>() issues phase PH of column
+// K, so that a caller can advance TWO independent products phase by phase (f30_run2).
+template <bool SQR, bool TWO, int C0 = 0, int C1 = 0, bool UFORM = false>
+struct f30_prod {
+  static constexpr bool kSqr = SQR, kTwo = TWO, kUform = UFORM;
+  static constexpr int PHASES = 6, COLS = 2 * F30_N - 1;
+  static constexpr int NINJ = (C0 != 0 ? 1 : 0) + (C1 != 0 ? 1 : 0);
+  fp30& r;
+  const fp30& a;
+  const fp30& b;
+  const fp30& c;
+  const fp30& d;
+  const fp30& inj0;
+  const fp30& inj1;
+  int64_t A;
+  uint64_t cy;  // takes the multiply-adds' carry-out, never read (mac30_asm.cuh)
+  uint32_t t;
+  int32_t top;
+  int32_t q[F30_N];
+  int32_t a2[F30_N];
+  KZG_HD f30_prod(fp30& r_, const fp30& a_, const fp30& b_, const fp30& c_, const fp30& d_, const fp30& i0_, const fp30& i1_)
+      : r(r_), a(a_), b(b_), c(c_), d(d_), inj0(i0_), inj1(i1_), A(0), cy(0), t(0), top(0) {
+    if (SQR) {
       KZG_UNROLL_FULL
-      for (int t = 0; t < K; t++) {
-        qs[t] = q[t];
-        ps[t] = f30_p(K - t);
+      for (int i = 0; i < F30_N; i++) a2[i] = a.l[i] << 1;
+    }
+    // the injected values' limb 12 joins the carry out of column 24 (read before r.l[12] is written: r may alias)
+    if (C0 != 0) top += C0 * inj0.l[F30_N - 1];
+    if (C1 != 0) top += C1 * inj1.l[F30_N - 1];
+  }
+  static constexpr int cnt_of(int K) { return K < F30_N ? K + 1 : COLS - K; }
+  // columns 1..13 open with the previous column's q * p(0) multiply-add and its shift (mad30_fold)
+  static constexpr bool folds(int K) { return K >= 1 && K <= F30_N; }
+  // a double product's two chains as ONE statement where its operand list allows
+  static constexpr bool pq_merged(int K) { return 2 * cnt_of(K) <= (folds(K) ? 13 : 14); }
+  // length of column K's product statement and of its reduction chain (injected limbs at its end from column 13 on)
+  static constexpr int k1_of(int K) {
+    if (SQR) {
+      const int i0 = K < F30_N ? 0 : K - F30_N + 1, last_pair = (K - 1) / 2;
+      return ((K >= 1 && last_pair >= i0) ? last_pair - i0 + 1 : 0) + (K % 2 == 0 ? 1 : 0);
+    }
+    return TWO ? 2 * cnt_of(K) : cnt_of(K);
+  }
+  static constexpr int k2_of(int K) { return K < F30_N ? K : cnt_of(K) + NINJ; }
+  // the product and the reduction chain as ONE statement where its operand list allows (tools/gen_mac_asm.py, merged30)
+  static constexpr bool col_merged(int K) {
+    return K > 0 && (!TWO || pq_merged(K)) && 2 + (folds(K) ? 2 : 0) + 2 * k1_of(K) + 2 * k2_of(K) <= 30;
+  }
+  // the atoms of column K (tools/gen_mac_asm.py, atoms30, is the same table and computes the pair schedules from it)
+  static constexpr bool has(int K, int PH) {
+    return PH == 0 ? true : PH == 1 ? (TWO && !pq_merged(K)) : PH == 2 ? (K > 0 && !col_merged(K)) : PH == 3 ? true : PH == 4 ? (K < F30_N || !UFORM) : K >= F30_N;
+  }
+  template <int K>
+  KZG_HD void reduction_operands(int32_t* qs, int32_t* ps) {
+    constexpr int N_ = F30_N;
+    if constexpr (K < N_) {
+      KZG_UNROLL_FULL
+      for (int t_ = 0; t_ < K; t_++) {
+        qs[t_] = q[t_];
+        ps[t_] = f30_p(K - t_);
       }
-      mad30_chain<K, true>::run(A, qs, ps);
-    }
-    q[K] = f30_sbfe((uint32_t)A * (uint32_t)KZG_FP30_INV);
-    const int32_t p0 = f30_p(0);
-    mad30_chain<1, true>::run(A, &q[K], &p0);
-    A >>= 30;
-  } else {
-    constexpr int ninj = (C0 != 0 ? 1 : 0) + (C1 != 0 ? 1 : 0);  // injected limbs ride at the end of the reduction chain
-    int32_t qs[cnt + ninj], ps[cnt + ninj];
-    KZG_UNROLL_FULL
-    for (int t = 0; t < cnt; t++) {
-      qs[t] = q[i0 + t];
-      ps[t] = f30_p(K - i0 - t);
-    }
-    if constexpr (C0 != 0) {
-      qs[cnt] = inj0.l[K - N_];
-      ps[cnt] = C0;
-    }
-    if constexpr (C1 != 0) {
-      qs[cnt + ninj - 1] = inj1.l[K - N_];
-      ps[cnt + ninj - 1] = C1;
-    }
-    mad30_chain<cnt + ninj, true>::run(A, qs, ps);
-    if constexpr (UFORM) {
-      r.l[K - N_] = (int32_t)((uint32_t)A & F30_MASK);
-      A >>= 30;
     } else {
-      r.l[K - N_] = f30_sbfe((uint32_t)A);
-      A = (A + (int64_t)F30_H) >> 30;
+      constexpr int i0 = K - N_ + 1, cnt = cnt_of(K);
+      KZG_UNROLL_FULL
+      for (int t_ = 0; t_ < cnt; t_++) {
+        qs[t_] = q[i0 + t_];
+        ps[t_] = f30_p(K - i0 - t_);
+      }
+      if constexpr (C0 != 0) {  // injected limbs ride at the end of the reduction chain
+        qs[cnt] = inj0.l[K - N_];
+        ps[cnt] = C0;
+      }
+      if constexpr (C1 != 0) {
+        qs[cnt + NINJ - 1] = inj1.l[K - N_];
+        ps[cnt + NINJ - 1] = C1;
+      }
     }
   }
-  if constexpr (K + 1 < 2 * N_ - 1) f30_column<SQR, TWO, C0, C1, UFORM, K + 1>(A, q, r, a, a2, b, c, d, inj0, inj1);
+  template <int K, int L>
+  KZG_HD void product_chain(const int32_t* xs, const int32_t* ys) {
+    if constexpr (col_merged(K)) {
+      static_assert(L == k1_of(K), "product statement length");
+      int32_t qs[k2_of(K)], ps[k2_of(K)];
+      reduction_operands<K>(qs, ps);
+      mad30_col<folds(K), L, k2_of(K)>::run(A, cy, folds(K) ? q[K - 1] : 0, f30_p(0), xs, ys, qs, ps);
+    } else if constexpr (folds(K)) {
+      mad30_fold<L>::run(A, cy, q[K - 1], f30_p(0), xs, ys);
+    } else {
+      mad30_chain<L, false>::run(A, cy, xs, ys);
+    }
+  }
+  template <int K, int PH>
+  KZG_HD void step() {
+    constexpr int N_ = F30_N;
+    constexpr int i0 = (K < N_) ? 0 : K - N_ + 1;
+    constexpr int cnt = cnt_of(K);
+    if constexpr (PH == 0) {
+      if constexpr (SQR) {
+        constexpr int last_pair = (K - 1) / 2;
+        constexpr int npairs = (K >= 1 && last_pair >= i0) ? last_pair - i0 + 1 : 0;
+        constexpr int diag = (K % 2 == 0) ? 1 : 0;
+        int32_t xs[npairs + diag], ys[npairs + diag];
+        KZG_UNROLL_FULL
+        for (int t_ = 0; t_ < npairs; t_++) {
+          xs[t_] = a2[i0 + t_];
+          ys[t_] = a.l[K - i0 - t_];
+        }
+        if constexpr (diag) {
+          xs[npairs] = a.l[K / 2];
+          ys[npairs] = a.l[K / 2];
+        }
+        product_chain<K, npairs + diag>(xs, ys);
+      } else if constexpr (TWO && pq_merged(K)) {
+        int32_t xs[2 * cnt], ys[2 * cnt];
+        KZG_UNROLL_FULL
+        for (int t_ = 0; t_ < cnt; t_++) {
+          xs[t_] = a.l[i0 + t_];
+          ys[t_] = b.l[K - i0 - t_];
+          xs[cnt + t_] = c.l[i0 + t_];
+          ys[cnt + t_] = d.l[K - i0 - t_];
+        }
+        product_chain<K, 2 * cnt>(xs, ys);
+      } else {
+        int32_t xs[cnt], ys[cnt];
+        KZG_UNROLL_FULL
+        for (int t_ = 0; t_ < cnt; t_++) {
+          xs[t_] = a.l[i0 + t_];
+          ys[t_] = b.l[K - i0 - t_];
+        }
+        product_chain<K, cnt>(xs, ys);
+      }
+    } else if constexpr (PH == 1) {
+      int32_t xs[cnt], ys[cnt];
+      KZG_UNROLL_FULL
+      for (int t_ = 0; t_ < cnt; t_++) {
+        xs[t_] = c.l[i0 + t_];
+        ys[t_] = d.l[K - i0 - t_];
+      }
+      mad30_chain<cnt, false>::run(A, cy, xs, ys);
+    } else if constexpr (PH == 2) {
+      int32_t qs[k2_of(K)], ps[k2_of(K)];
+      reduction_operands<K>(qs, ps);
+      mad30_chain<k2_of(K), true>::run(A, cy, qs, ps);
+    } else if constexpr (PH == 3) {
+      if constexpr (K < N_) {
+        t = (uint32_t)A * ((uint32_t)KZG_FP30_INV << 2);  // the quotient digit's two instructions are two atoms: each can separate
+      } else if constexpr (UFORM) {
+        r.l[K - N_] = (int32_t)((uint32_t)A & F30_MASK);
+      } else {
+        r.l[K - N_] = f30_sbfe((uint32_t)A);  // r may alias an operand: limb K-13 of every operand was last read in column K-1
+      }
+    } else if constexpr (PH == 4) {
+      if constexpr (K < N_)
+        q[K] = (int32_t)t >> 2;  // = f30_sbfe(A * INV).  q[K] * p(0) and the exact shift open the next column's statement
+      else
+        A += (int64_t)F30_H;
+    } else {
+      A >>= 30;
+    }
+  }
+  KZG_HD void finish() { r.l[F30_N - 1] = (int32_t)A + top; }  // column 25 holds only the carry
+};
+// the atom after (K, PH), as K * PHASES + PH; COLS * PHASES when there is none
+template <class P>
+constexpr int f30_next_atom(int at) {
+  for (at++; at < P::COLS * P::PHASES; at++)
+    if (P::has(at / P::PHASES, at % P::PHASES)) return at;
+  return at;
+}
+template <int AT, class PA>
+KZG_HD void f30_run1(PA& x) {
+  if constexpr (AT < PA::COLS * PA::PHASES) {
+    x.template step<AT / PA::PHASES, AT % PA::PHASES>();
+    f30_run1<f30_next_atom<PA>(AT)>(x);
+  } else {
+    x.finish();
+  }
+}
+// Two INDEPENDENT products, atom by atom in the generated order (mac30_asm.cuh, f30_sched): wherever it can be arranged, a
+// compiler-generated instruction of one product stands between a statement of the other and the next reader of its accumulator,
+// which is what spares the wait state.  The scheduling barriers keep the compiler from undoing the order; they emit nothing.
+template <int I, int ATA, int ATB, class S, class PA, class PB>
+KZG_HD void f30_run2(PA& x, PB& y) {
+  if constexpr (I < S::LEN) {
+    if constexpr (S::pick[I] == '0') {
+      x.template step<ATA / PA::PHASES, ATA % PA::PHASES>();
+      KZG_F30_ATOM_FENCE();
+      f30_run2<I + 1, f30_next_atom<PA>(ATA), ATB, S>(x, y);
+    } else {
+      y.template step<ATB / PB::PHASES, ATB % PB::PHASES>();
+      KZG_F30_ATOM_FENCE();
+      f30_run2<I + 1, ATA, f30_next_atom<PB>(ATB), S>(x, y);
+    }
+  } else {
+    static_assert(ATA == PA::COLS * PA::PHASES && ATB == PB::COLS * PB::PHASES, "the schedule issues every atom of both products");
+    x.finish();
+    y.finish();
+  }
 }
 template <bool SQR, bool TWO, int C0 = 0, int C1 = 0, bool UFORM = false>
 KZG_HD void f30_mul_core(fp30& r, const fp30& a, const fp30& b, const fp30& c, const fp30& d, const fp30& inj0, const fp30& inj1) {
-  constexpr int N_ = F30_N;
-  int32_t q[N_];
-  int32_t a2[N_];
-  if (SQR) {
-    KZG_UNROLL_FULL
-    for (int i = 0; i < N_; i++) a2[i] = a.l[i] << 1;
-  }
-  int32_t top = 0;  // the injected values' limb 12 joins the carry out of column 24 (read before r.l[12] is written: r may alias)
-  if (C0 != 0) top += C0 * inj0.l[N_ - 1];
-  if (C1 != 0) top += C1 * inj1.l[N_ - 1];
-  int64_t A = 0;
-  f30_column<SQR, TWO, C0, C1, UFORM, 0>(A, q, r, a, a2, b, c, d, inj0, inj1);
-  r.l[N_ - 1] = (int32_t)A + top;  // column 25 holds only the carry
+  f30_prod<SQR, TWO, C0, C1, UFORM> x(r, a, b, c, d, inj0, inj1);
+  f30_run1<0>(x);
 }
 #else
 template <bool SQR, bool TWO, int C0 = 0, int C1 = 0, bool UFORM = false>
@@ -282,6 +396,21 @@ KZG_HD void f30_mul_core(fp30& r, const fp30& a, const fp30& b, const fp30& c, c
   f30_mul_core_c<SQR, TWO, C0, C1, UFORM>(r, a, b, c, d, inj0, inj1);
 }
 #endif
+// two independent products side by side: ra = (a b [+ ...]) ..., rb likewise.  No result may alias an operand of the OTHER product.
+template <bool SQRA, bool TWOA, int C0A, int C1A, bool UA, bool SQRB, bool TWOB, int C0B, int C1B, bool UB>
+KZG_HD void f30_mul_core2(fp30& ra, const fp30& aa, const fp30& ba, const fp30& ca, const fp30& da, const fp30& i0a, const fp30& i1a,
+                          fp30& rb, const fp30& ab, const fp30& bb, const fp30& cb, const fp30& db, const fp30& i0b, const fp30& i1b) {
+#if defined(__HIP_DEVICE_COMPILE__) || defined(KZG_FP30_HOST_ATOMS)
+  using PA = f30_prod<SQRA, TWOA, C0A, C1A, UA>;
+  using PB = f30_prod<SQRB, TWOB, C0B, C1B, UB>;
+  PA x(ra, aa, ba, ca, da, i0a, i1a);
+  PB y(rb, ab, bb, cb, db, i0b, i1b);
+  f30_run2<0, 0, 0, f30_sched<SQRA, TWOA, PA::NINJ, UA, SQRB, TWOB, PB::NINJ, UB>>(x, y);
+#else
+  f30_mul_core_c<SQRA, TWOA, C0A, C1A, UA>(ra, aa, ba, ca, da, i0a, i1a);
+  f30_mul_core_c<SQRB, TWOB, C0B, C1B, UB>(rb, ab, bb, cb, db, i0b, i1b);
+#endif
+}
 
 KZG_HD void f30_mul(fp30& r, const fp30& a, const fp30& b) { f30_mul_core<false, false>(r, a, b, a, b, a, a); }   // C x C or L x C
 KZG_HD void f30_sqr(fp30& r, const fp30& a) { f30_mul_core<true, false>(r, a, a, a, a, a, a); }                   // C
@@ -526,18 +655,18 @@ KZG_HD void xyzz30_mdbl(g1_xyzz30& p, const fp30& x, const fp30& y) {
 //   P = X2 ZZ1 - X1,  R = Y2 ZZZ1 - Y1,  V = R^2 - PPP - 3 Q = X3 - Q;   X3 = V + Q (L-form: only ever a product's first operand
 //   or an injected value);  -Y3 = R V + Y1 PPP as ONE reduction: the raw result is the negated sum, the flag says so.
 KZG_HD bool xyzz30_madd_fast(g1_xyzz30& p, const fp30& x2, const fp30& y2) {
-  fp30 u, r, pp, ppp, v;
+  fp30 u, r, pp, ppp, qq, v;
   f30_mul_inj<-1>(u, x2, p.zz, p.x);        // P (|P| < 3.9 p)
   if (f30_maybe_zero(u)) return false;
-  f30_mul_inj<-1>(r, y2, p.zzz, p.y);       // R
-  f30_sqr(pp, u);                           // PP
-  f30_mul(ppp, u, pp);                      // PPP
-  f30_mul_u(p.zz, p.zz, pp);                // ZZ3   (U-form: ZZ only ever meets a table entry's x and PP)
-  f30_mul_u(p.zzz, p.zzz, ppp);             // ZZZ3  (U-form: ZZZ only ever meets a table entry's y and PPP)
-  f30_mul(pp, p.x, pp);                     // Q = X1 PP (L x C; X1 and PP are dead from here)
-  f30_sqr_inj2<-1, -3>(v, r, ppp, pp);      // V = X3 - Q (|V| < 2.7 p)
-  f30_add(p.x, v, pp);                      // X3
-  f30_mul2(p.y, r, v, p.y, ppp);            // -Y3
+  f30_mul_core2<true, false, 0, 0, false, false, false, -1, 0, false>(pp, u, u, u, u, u, u,               // PP
+                                                                      r, y2, p.zzz, y2, p.zzz, p.y, p.y);  // R
+  f30_mul_core2<false, false, 0, 0, false, false, false, 0, 0, false>(ppp, u, pp, u, pp, u, u,          // PPP
+                                                                      qq, p.x, pp, p.x, pp, u, u);     // Q = X1 PP (L x C)
+  f30_mul_core2<true, false, -1, -3, false, false, false, 0, 0, true>(v, r, r, r, r, ppp, qq,            // V = X3 - Q (|V| < 2.7 p)
+                                                                      p.zz, p.zz, pp, p.zz, pp, u, u);  // ZZ3 (U-form)
+  f30_add(p.x, v, qq);                      // X3
+  f30_mul_core2<false, true, 0, 0, false, false, false, 0, 0, true>(p.y, r, v, p.y, ppp, u, u,                  // -Y3
+                                                                    p.zzz, p.zzz, ppp, p.zzz, ppp, u, u);      // ZZZ3 (U-form)
   p.yneg ^= 1u;
   return true;
 }
