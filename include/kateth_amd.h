@@ -241,6 +241,31 @@ int32_t kzg_compute_blob_proof_batch(const kzg_ctx* ctx, const uint8_t* blobs, c
 int32_t kzg_compute_blob_proof_batch_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, uint64_t n, void* d_out48, void* d_status, void* hip_stream);
 
 /*
+ * The blob sidecar of n blobs in one call: Setup::blob_to_commitment (src/kzg/setup.rs:167-171) followed by Setup::blob_proof
+ * (:177-183) on the same blob, plus EIP-4844's kzg_to_versioned_hash of each commitment.  The blobs cross PCIe once, and the
+ * proof's challenge hashes the commitments the device has just written (nothing is decoded or subgroup-checked again).
+ *   blobs                  : n * 131072 bytes
+ *   out_commitments48      : n * 48 bytes        out_proofs48 : n * 48 bytes
+ *   out_versioned_hashes32 : n * 32 bytes, or NULL = not wanted
+ *   status                 : n * int32 ; 0 or KZG_ERR_BLOB_INVALID_FIELD_ELEMENT per blob
+ * Outputs: out_commitments48, out_proofs48 and status equal, byte for byte, what kzg_blob_to_commitment_batch followed by
+ *   kzg_compute_blob_proof_batch(blobs, those commitments) write.  A rejected blob gets 48 + 48 + 32 zero bytes.
+ * Versioned hash: for an accepted blob 0x01 || SHA-256(commitment48)[1:32]; the point at infinity (c0 00 ...) is hashed like any
+ *   other commitment.
+ * Bounds: nothing beyond n items is written; n == 0 returns 0.
+ * Null pointers: a null required pointer with n > 0 returns KZG_FAIL_ARGUMENT; only the versioned-hash pointer may be null.
+ * The *_dev form takes HIP device pointers resident on ctx's device (16-byte aligned), enqueues on `hip_stream` and returns without
+ *   synchronising, like the other producer *_dev calls; it takes a workspace slot of its own, so calls on different streams run
+ *   side by side.
+ * Group contexts: the host-buffer call cuts the batch into the same contiguous shares as kzg_compute_blob_proof_batch; the *_dev
+ *   call acts on member 0.
+ */
+int32_t kzg_blob_sidecar_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48,
+                               uint8_t* out_versioned_hashes32 /* may be NULL */, int32_t* status);
+int32_t kzg_blob_sidecar_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_commitments48, void* d_out_proofs48,
+                                   void* d_out_versioned_hashes32 /* may be NULL */, void* d_status, void* hip_stream);
+
+/*
  * Replaces Setup::proof for n (blob, z) pairs (src/kzg/setup.rs:185-194):
  *   z32 : n * 32 bytes big-endian ; out_proof48 : n * 48 ; out_y32 : n * 32
  *   status : per item 0, KZG_ERR_BLOB_*, KZG_ERR_FF_NOT_IN_FIELD for z

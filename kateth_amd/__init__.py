@@ -26,6 +26,7 @@ from .kzg import (  # noqa: F401,E402
     LoadSetupError,
     Setup,
     library_path,
+    versioned_hash,
 )
 
 __all__ = [
@@ -40,4 +41,5 @@ __all__ = [
     "LoadSetupError",
     "BYTES_PER_BLOB",
     "library_path",
+    "versioned_hash",
 ]

@@ -193,6 +193,23 @@ static __global__ __launch_bounds__(256) void k_fr_store_be(const fr_t* __restri
   o[1] = make_uint4(__builtin_bswap32(v.v[3]), __builtin_bswap32(v.v[2]), __builtin_bswap32(v.v[1]), __builtin_bswap32(v.v[0]));
 }
 
+// kzg_to_versioned_hash (EIP-4844) of n commitments, one lane each: 0x01 || SHA-256(commitment48)[1:32]; an item whose status is
+// non-zero gets 32 zero bytes
+static __global__ __launch_bounds__(256) void k_versioned_hash(const uint8_t* __restrict__ commitments48, uint64_t n, const int32_t* __restrict__ status,
+                                                               uint8_t* __restrict__ out32) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t h[8];
+  versioned_hash_words(commitments48 + i * 48, h);
+  if (status[i] != 0) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) h[q] = 0;
+  }
+  uint4* o = reinterpret_cast<uint4*>(out32 + i * 32);
+  o[0] = make_uint4(__builtin_bswap32(h[0]), __builtin_bswap32(h[1]), __builtin_bswap32(h[2]), __builtin_bswap32(h[3]));
+  o[1] = make_uint4(__builtin_bswap32(h[4]), __builtin_bswap32(h[5]), __builtin_bswap32(h[6]), __builtin_bswap32(h[7]));
+}
+
 #endif  // __HIPCC__
 
 }  // namespace kzg

@@ -67,6 +67,10 @@ void launch_fr_store_be(hipStream_t st, const fr_t* plain, uint64_t n, const int
   if (n == 0) return;
   hipLaunchKernelGGL(k_fr_store_be, dim3(blocks_for(n, 256)), dim3(256), 0, st, plain, n, status, out32);
 }
+void launch_versioned_hash(hipStream_t st, const uint8_t* commitments48, uint64_t n, const int32_t* status, uint8_t* out32) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_versioned_hash, dim3(blocks_for(n, 256)), dim3(256), 0, st, commitments48, n, status, out32);
+}
 void launch_synth_blobs(hipStream_t st, uint64_t seed, uint64_t first_index, uint64_t n, uint8_t* d_blobs) {
   const uint64_t elems = n * 4096;
   if (elems == 0) return;

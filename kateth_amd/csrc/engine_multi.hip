@@ -82,6 +82,16 @@ int32_t multi_proof(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* sid
   });
 }
 
+int32_t multi_sidecar(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48, uint8_t* out_versioned_hashes32,
+                      int32_t* status) {
+  const std::vector<Share> shares = shares_of(ctx, n);
+  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
+    const Share& sh = shares[j];
+    return sidecar_host(member_of(ctx, sh.member), blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, sh.count, out_commitments48 + sh.first * 48,
+                        out_proofs48 + sh.first * 48, out_versioned_hashes32 ? out_versioned_hashes32 + sh.first * 32 : nullptr, status + sh.first);
+  });
+}
+
 int32_t multi_g1_decompress(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status) {
   const std::vector<Share> shares = shares_of(ctx, n);
   return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {

@@ -1,4 +1,6 @@
 // compute_blob_kzg_proof / compute_kzg_proof entry points
+#include <algorithm>
+
 #include "engine_internal.hpp"
 #include "poly_kernels.cuh"  // this translation unit owns the quotient / evaluation kernels of the proof path
 
@@ -169,22 +171,24 @@ extern "C" int32_t kzg_compute_blob_proof_batch_dev(const kzg_ctx* ctx, const vo
 // streams, every chunk's MSM as one wave per SIMD: 44.7 ms at 4,096 but 170 ms at 16,384 -- the short kernels of later chunks
 // (k_poly: 8-wave workgroups of 126 VGPRs) find no register space beside two resident MSM chunks (2 x 232 VGPRs per SIMD)
 // and wait for a whole chunk to drain, so the pipeline degenerates to two-deep serial passes.
+static std::vector<uint64_t> proof_host_plan(uint64_t n) {
+  constexpr uint64_t PASS = 4096;
+  std::vector<uint64_t> plan;
+  uint64_t rest = n;
+  if (n > PASS + 1024) {  // a short first pass only where later passes can hide behind it (measured: at 4,096 blobs two passes cost what they save)
+    plan.push_back(1024);
+    rest -= 1024;
+  }
+  for (; rest > PASS; rest -= PASS) plan.push_back(PASS);
+  if (rest) plan.push_back(rest);
+  return plan;
+}
 int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side, size_t side_bytes, bool side_is_commitment, uint64_t n,
                           uint8_t* out48, uint8_t* out_affine96, uint8_t* out_y32, int32_t* status) {
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(ctx->device));
   std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
-  constexpr uint64_t PASS = 4096;
-  std::vector<uint64_t> plan;
-  {
-    uint64_t rest = n;
-    if (n > PASS + 1024) {  // a short first pass only where later passes can hide behind it (measured: at 4,096 blobs two passes cost what they save)
-      plan.push_back(1024);
-      rest -= 1024;
-    }
-    for (; rest > PASS; rest -= PASS) plan.push_back(PASS);
-    if (rest) plan.push_back(rest);
-  }
+  const std::vector<uint64_t> plan = proof_host_plan(n);
   uint64_t max_pass = 0;
   for (uint64_t m : plan) max_pass = m > max_pass ? m : max_pass;
   const bool piped = plan.size() > 1;  // one pass: nothing to overlap, the copy rides on the compute stream
@@ -260,6 +264,132 @@ extern "C" int32_t kzg_compute_proof_batch_affine(const kzg_ctx* ctx, const uint
                                                   uint8_t* out_y32, int32_t* status) try {
   if (!ctx || (n && (!blobs || !z32 || !out_proof_affine96 || !out_y32 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
   return (is_group(ctx) ? multi_proof : proof_host)(ctx, blobs, z32, 32, false, n, nullptr, out_proof_affine96, out_y32, status);
+} catch (...) {
+  return abi_exception();
+}
+
+// ---------------------------------------------------------------------------
+// blob sidecar: commitment, blob proof and versioned hash of every blob in one call
+// ---------------------------------------------------------------------------
+// Setup::blob_to_commitment, then Setup::blob_proof with that commitment, then kzg_to_versioned_hash, for n blobs resident on the
+// device.  Chunks and workspace are proof_layout's (preparation slot 0 only); a chunk's two MSMs have the same shape and follow each
+// other on `st`, so they share the lane sums, the sums and the bit-plane masks.  The challenge hashes the commitments the device has
+// just written: they are valid by construction, so nothing is decoded and no commitment status is merged.
+static int32_t sidecar_dev_locked(const kzg_ctx* ctx, const uint8_t* d_blobs, uint64_t n, uint8_t* d_out_commitments48, uint8_t* d_out_proofs48, uint8_t* d_out_vh32,
+                                  int32_t* d_status, hipStream_t st) {
+  if (n == 0) return 0;
+  const ProofLayout L = proof_layout(ctx, n);
+  const uint64_t cn = L.cn;
+  int32_t rc = ws_reserve(ctx, L.total, st);
+  if (rc) return rc;
+  uint8_t* ws = ws_ptr(ctx);
+  fr_t* z = reinterpret_cast<fr_t*>(ws + L.o_z[0]);
+  fr_t* y = reinterpret_cast<fr_t*>(ws + L.o_y[0]);
+  fr_t* invr = reinterpret_cast<fr_t*>(ws + L.o_ir[0]);
+  fr_t* q = reinterpret_cast<fr_t*>(ws + L.o_q[0]);
+  g1_xyzz* partials = reinterpret_cast<g1_xyzz*>(ws + L.o_part);
+  g1_xyzz* sums = reinterpret_cast<g1_xyzz*>(ws + L.o_sum);
+  HIP_TRY(hipMemsetAsync(d_status, 0, n * sizeof(int32_t), st));
+  for (uint64_t base = 0; base < n; base += cn) {
+    const uint64_t m = (n - base < cn) ? (n - base) : cn;
+    const uint8_t* blobs = d_blobs + base * (uint64_t)KZG_BYTES_PER_BLOB;
+    uint8_t* com = d_out_commitments48 + base * 48;
+    rc = msm_pipeline(ctx, true, blobs, m, com, nullptr, d_status + base, partials, sums, L.splits, ws + L.o_msm, st);
+    if (rc) return rc;
+    launch_challenge(ctx, st, blobs, com, m, z);
+    {
+      ProfScope ps(ctx, PROF_POLY, st);
+      hipLaunchKernelGGL(k_poly_root_inverse, dim3(blocks_for(m, 64)), dim3(64), 0, st, z, m, invr);
+      hipLaunchKernelGGL(k_poly<true>, dim3((unsigned)m), dim3(512), 0, st, blobs, z, ctx->d_roots_brp, invr, y, q, d_status + base);
+    }
+    rc = msm_pipeline(ctx, false, reinterpret_cast<const uint8_t*>(q), m, d_out_proofs48 + base * 48, nullptr, d_status + base, partials, sums, L.splits,
+                      ws + L.o_msm, st);
+    if (rc) return rc;
+    if (d_out_vh32) launch_versioned_hash(st, com, m, d_status + base, d_out_vh32 + base * 32);
+  }
+  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "sidecar pipeline launch failed");
+  return 0;
+}
+
+extern "C" int32_t kzg_blob_sidecar_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_commitments48, void* d_out_proofs48,
+                                              void* d_out_versioned_hashes32, void* d_status, void* hip_stream) try {
+  if (!ctx || (n && (!d_blobs || !d_out_commitments48 || !d_out_proofs48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> guard(ctx->lock);
+  hipStream_t st = (hipStream_t)hip_stream;
+  WsCall ws(ctx, st);
+  int32_t rc = ws.begin();
+  if (rc == 0)
+    rc = sidecar_dev_locked(ctx, (const uint8_t*)d_blobs, n, (uint8_t*)d_out_commitments48, (uint8_t*)d_out_proofs48, (uint8_t*)d_out_versioned_hashes32,
+                            (int32_t*)d_status, st);
+  if (rc == 0) rc = ws.end();
+  return rc;
+} catch (...) {
+  return abi_exception();
+}
+
+// Host-buffer form, after proof_host: the blobs cross PCIe ONCE, in passes through the staging ring, and every pass goes through
+// sidecar_dev_locked; the three results and the statuses come back through the host-i/o pool.  A staging slot is free again only
+// when the pass's quotient kernel has read the blobs -- commit_host's release behind the bit-plane transposition would be too
+// early here -- so consumed(k) follows the pass's whole enqueue.  Passes: proof_host's plan, or KATETH_AMD_SIDECAR_PASS blobs each.
+int32_t sidecar_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48, uint8_t* out_versioned_hashes32,
+                     int32_t* status) {
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
+  std::vector<uint64_t> plan;
+  if (ctx->knobs.sidecar_pass)
+    for (uint64_t rest = n; rest; rest -= plan.back()) plan.push_back(rest < ctx->knobs.sidecar_pass ? rest : ctx->knobs.sidecar_pass);
+  else
+    plan = proof_host_plan(n);
+  uint64_t max_pass = 0;
+  for (uint64_t m : plan) max_pass = m > max_pass ? m : max_pass;
+  const bool piped = plan.size() > 1;
+  Carve io;
+  const size_t o_com = io.take(n * 48), o_prf = io.take(n * 48), o_vh = io.take(n * 32), o_st = io.take(n * sizeof(int32_t));
+  StageRing ring;
+  int32_t rc = ring.open(ctx, piped ? 2 : 1, (size_t)max_pass * KZG_BYTES_PER_BLOB, io.off, piped);
+  if (rc) return rc;
+  uint8_t* d_com = ctx->hostio + o_com;
+  uint8_t* d_prf = ctx->hostio + o_prf;
+  uint8_t* d_vh = out_versioned_hashes32 ? ctx->hostio + o_vh : nullptr;
+  int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
+  hipStream_t st = ctx->stage_streams[0];
+  std::lock_guard<std::mutex> guard(ctx->lock);
+  WsCall ws(ctx, st);
+  do {
+    // one workspace slot for all passes, sized BEFORE anything is in flight for the pass that asks most (a short last pass may take
+    // more splits, and so more lane sums, than a full one): growing it between passes would free memory under the pipeline
+    rc = ws.begin();
+    size_t need = 0;
+    for (uint64_t m : plan) need = std::max(need, proof_layout(ctx, m).total);
+    if (rc == 0) rc = ws_reserve(ctx, need, st);
+    uint64_t base = 0;
+    for (size_t k = 0; k < plan.size() && rc == 0; base += plan[k], k++) {
+      const uint64_t m = plan[k];
+      uint8_t* d_blobs = nullptr;
+      rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, st, &d_blobs);
+      if (rc == 0) rc = sidecar_dev_locked(ctx, d_blobs, m, d_com + base * 48, d_prf + base * 48, d_vh ? d_vh + base * 32 : nullptr, d_status + base, st);
+      if (rc == 0) rc = ring.consumed(k, st);
+    }
+    if (rc) break;
+    rc = ws.end();
+    if (rc) break;
+    if (hipMemcpyAsync(out_commitments48, d_com, n * 48, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(out_proofs48, d_prf, n * 48, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (d_vh && hipMemcpyAsync(out_versioned_hashes32, d_vh, n * 32, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
+  } while (0);
+  if (rc) (void)hipDeviceSynchronize();
+  return rc;
+}
+
+extern "C" int32_t kzg_blob_sidecar_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48,
+                                          uint8_t* out_versioned_hashes32, int32_t* status) try {
+  if (!ctx || (n && (!blobs || !out_commitments48 || !out_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return (is_group(ctx) ? multi_sidecar : sidecar_host)(ctx, blobs, n, out_commitments48, out_proofs48, out_versioned_hashes32, status);
 } catch (...) {
   return abi_exception();
 }

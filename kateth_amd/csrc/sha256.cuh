@@ -112,6 +112,24 @@ KZG_HD void sha256_block(sha256_state& s, const uint32_t* win) {
   s.h[7] += h;
 }
 
+// EIP-4844's kzg_to_versioned_hash of one 48-byte commitment as 8 big-endian words: 0x01 || SHA-256(com)[1:32].  The message is one
+// block -- 12 words of commitment, the padding bit, the bit length 384 -- and the digest's first byte gives way to the version.
+KZG_HD void versioned_hash_words(const uint8_t com[48], uint32_t out[8]) {
+  uint32_t w[16];
+#pragma unroll
+  for (int i = 0; i < 12; i++)
+    w[i] = ((uint32_t)com[4 * i] << 24) | ((uint32_t)com[4 * i + 1] << 16) | ((uint32_t)com[4 * i + 2] << 8) | (uint32_t)com[4 * i + 3];
+  w[12] = 0x80000000u;
+  w[13] = 0;
+  w[14] = 0;
+  w[15] = 384;
+  sha256_state s;
+  sha256_init(s);
+  sha256_block(s, w);
+#pragma unroll
+  for (int i = 0; i < 8; i++) out[i] = s.h[i];
+  out[0] = (out[0] & 0x00ffffffu) | 0x01000000u;
+}
 
 #if defined(__HIPCC__)
 // ---- SHA-256 split over two cooperating waves (latency-bound hashing of few long messages) ------------------

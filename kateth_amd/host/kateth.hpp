@@ -276,6 +276,21 @@ class Setup {
     return out;
   }
 
+  // blob_to_commitment, then blob_proof on the same blob, then EIP-4844's kzg_to_versioned_hash (0x01 || SHA-256(commitment)[1:32]),
+  // in one call: the blob is uploaded once
+  struct Sidecar {
+    Bytes48 commitment, proof;
+    Bytes32 versioned_hash;
+  };
+  Sidecar blob_sidecar(const uint8_t* blob, size_t len) const {
+    if (len != BLOB_BYTES) throw Error(ErrorKind::BlobInvalidLen);
+    Sidecar out{};
+    int32_t status = 0;
+    check(kzg_blob_sidecar_batch(ctx_.get(), blob, 1, out.commitment.data(), out.proof.data(), out.versioned_hash.data(), &status), "kzg_blob_sidecar_batch");
+    if (status) throw Error(static_cast<ErrorKind>(status));
+    return out;
+  }
+
   // (proof, y)
   std::pair<Bytes48, Bytes32> proof(const uint8_t* blob, size_t len, const Bytes32& point) const {
     if (len != BLOB_BYTES) throw Error(ErrorKind::BlobInvalidLen);
@@ -451,6 +466,11 @@ class Setup {
   }
   void blob_proof_batch(const uint8_t* blobs, const uint8_t* commitments48, size_t n, uint8_t* out48, int32_t* status) const {
     check(kzg_compute_blob_proof_batch(ctx_.get(), blobs, commitments48, n, out48, status), "kzg_compute_blob_proof_batch");
+  }
+
+  // out_versioned_hashes32 may be null (not wanted)
+  void blob_sidecar_batch(const uint8_t* blobs, size_t n, uint8_t* out_commitments48, uint8_t* out_proofs48, uint8_t* out_versioned_hashes32, int32_t* status) const {
+    check(kzg_blob_sidecar_batch(ctx_.get(), blobs, n, out_commitments48, out_proofs48, out_versioned_hashes32, status), "kzg_blob_sidecar_batch");
   }
 
   const kzg_ctx* raw() const { return ctx_.get(); }

@@ -5,6 +5,7 @@ Method names, argument meaning and error behaviour follow the reference:
     Setup.load_json(path)                        src/kzg/setup.rs:46-82
     Setup.blob_to_commitment(blob)               src/kzg/setup.rs:167-171   (+ compress, src/bls.rs:491-503)
     Setup.blob_proof(blob, commitment48)         src/kzg/setup.rs:177-183
+    Setup.blob_sidecar(blob)                     :167-171 then :177-183 on the same blob, + EIP-4844 kzg_to_versioned_hash
     Setup.proof(blob, z32)                       src/kzg/setup.rs:185-194
     Setup.verify_proof(proof, commitment, z, y)  src/kzg/setup.rs:96-113
     Setup.verify_blob_proof(blob, c, p)          src/kzg/setup.rs:208-221
@@ -146,6 +147,11 @@ _SIGNATURES = {
     "kzg_compute_proof_batch_affine": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
     "kzg_compute_blob_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
     "kzg_compute_blob_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kzg_blob_sidecar_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, _i32p]),
+    "kzg_blob_sidecar_batch_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "kzg_compute_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
     "kzg_verify_blob_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
     "kzg_verify_blob_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
@@ -265,6 +271,16 @@ def _buf(data) -> bytes:
     if hasattr(data, "to_bytes") and not isinstance(data, int):  # a Blob
         return data.to_bytes()
     return bytes(bytearray(data))
+
+
+def versioned_hash(commitment48) -> bytes:
+    """EIP-4844's `kzg_to_versioned_hash`: 0x01 || SHA-256(commitment48)[1:32], on the host (hashlib; no GPU, no library)."""
+    import hashlib
+
+    commitment48 = _buf(commitment48)
+    if len(commitment48) != 48:
+        raise ValueError("a commitment is 48 bytes")
+    return b"\x01" + hashlib.sha256(commitment48).digest()[1:]
 
 
 def _has_noncanonical_element(blob: bytes) -> bool:
@@ -518,6 +534,20 @@ class Setup:
         self._check(rc, "kzg_compute_blob_proof_batch")
         return out.raw, list(status)
 
+    def blob_sidecar_batch(self, blobs: bytes, n: Optional[int] = None):
+        """n concatenated blobs -> (n*48 bytes of commitments, n*48 bytes of blob proofs, n*32 bytes of versioned hashes, [status]):
+        `blob_to_commitment`, then `blob_proof` on the same blob, then EIP-4844's `kzg_to_versioned_hash`, the blobs uploaded once."""
+        blobs = _buf(blobs)
+        n = len(blobs) // BYTES_PER_BLOB if n is None else n
+        if len(blobs) != n * BYTES_PER_BLOB:
+            raise BlobError("InvalidLen")
+        coms, proofs, hashes = ctypes.create_string_buffer(48 * n), ctypes.create_string_buffer(48 * n), ctypes.create_string_buffer(32 * n)
+        status = (ctypes.c_int32 * n)()
+        rc = self._lib.kzg_blob_sidecar_batch(self._h, blobs, n, ctypes.cast(coms, ctypes.c_void_p), ctypes.cast(proofs, ctypes.c_void_p),
+                                              ctypes.cast(hashes, ctypes.c_void_p), status)
+        self._check(rc, "kzg_blob_sidecar_batch")
+        return coms.raw, proofs.raw, hashes.raw, list(status)
+
     def compute_proof_batch(self, blobs: bytes, zs: bytes):
         blobs, zs = _buf(blobs), _buf(zs)
         n = len(zs) // 32
@@ -607,6 +637,16 @@ class Setup:
         if status[0]:
             raise error_from_status(status[0])
         return out
+
+    def blob_sidecar(self, blob: bytes) -> Tuple[bytes, bytes, bytes]:
+        """(commitment48, proof48, versioned_hash32) of one blob; raises what `blob_to_commitment` raises."""
+        blob = _buf(blob)
+        if len(blob) != BYTES_PER_BLOB:
+            raise BlobError("InvalidLen")
+        coms, proofs, hashes, status = self.blob_sidecar_batch(blob, 1)
+        if status[0]:
+            raise error_from_status(status[0])
+        return coms, proofs, hashes
 
     def blob_proof(self, blob: bytes, commitment: bytes) -> bytes:
         """`Setup::blob_proof` + `compress` (kzg::Error on bad input)."""
@@ -851,6 +891,11 @@ class Setup:
     def compute_blob_proof_batch_dev(self, d_blobs: int, d_commitments: int, n: int, d_out48: int, d_status: int, stream: int = 0):
         rc = self._lib.kzg_compute_blob_proof_batch_dev(self._h, d_blobs, d_commitments, n, d_out48, d_status, stream)
         self._check(rc, "kzg_compute_blob_proof_batch_dev")
+
+    def blob_sidecar_batch_dev(self, d_blobs: int, n: int, d_commitments: int, d_proofs: int, d_versioned_hashes: int, d_status: int, stream: int = 0):
+        """d_versioned_hashes = 0: no hashes wanted"""
+        rc = self._lib.kzg_blob_sidecar_batch_dev(self._h, d_blobs, n, d_commitments, d_proofs, d_versioned_hashes or None, d_status, stream)
+        self._check(rc, "kzg_blob_sidecar_batch_dev")
 
     def verify_blob_proof_batch_dev(self, d_blobs: int, d_commitments: int, d_proofs: int, n: int, stream: int = 0) -> bool:
         ok = ctypes.c_int32(0)
