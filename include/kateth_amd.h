@@ -53,6 +53,9 @@ extern "C" {
 #define KZG_BYTES_PER_G2 96       /* P2::COMPRESSED, src/bls.rs:569 */
 #define KZG_SETUP_G1_POINTS 4096  /* Setup<4096, 65>, benches/kzg.rs:12 */
 #define KZG_SETUP_G2_POINTS 65
+#define KZG_CELLS_PER_EXT_BLOB 128     /* EIP-7594: the blob extended to 8192 elements, cut into cells */
+#define KZG_FIELD_ELEMENTS_PER_CELL 64
+#define KZG_BYTES_PER_CELL 2048
 
 /* per-item / per-call rejection codes; they rebuild the reference's enums */
 #define KZG_OK 0
@@ -264,6 +267,27 @@ int32_t kzg_blob_sidecar_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_
                                uint8_t* out_versioned_hashes32 /* may be NULL */, int32_t* status);
 int32_t kzg_blob_sidecar_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_commitments48, void* d_out_proofs48,
                                    void* d_out_versioned_hashes32 /* may be NULL */, void* d_status, void* hip_stream);
+
+/*
+ * The cells of n blobs (EIP-7594, PeerDAS): compute_cells of specs/fulu/polynomial-commitments-sampling.md, which is c-kzg-4844's
+ * compute_cells_and_kzg_proofs(cells, NULL, blob).  The blob's polynomial p -- the one Polynomial::evaluate reads
+ * (src/kzg/poly.rs:10-33) -- is evaluated at the 8192 powers of omega_8192 = 7^((r-1)/8192), in bit-reversed order: E[j] = blob
+ * element j and E[4096 + j] = p(omega_8192 * roots_brp[j]) for j < 4096.  Cell c is E[64 c .. 64 c + 63], 32 bytes big-endian
+ * canonical per element.
+ *   blobs     : n * 131072 bytes
+ *   out_cells : n * 128 * 2048 bytes; cells 0..63 of an accepted blob are the blob, byte for byte
+ *   status    : n * int32 ; 0 or KZG_ERR_BLOB_INVALID_FIELD_ELEMENT per blob.  A rejected blob gets 262144 zero bytes.
+ * Not here: cell proofs (they need the monomial G1 setup and FK20), cell verification and cell recovery.
+ * Bounds: nothing beyond n items is written; n == 0 returns 0.  A null pointer with n > 0 returns KZG_FAIL_ARGUMENT.
+ * The *_dev form takes HIP device pointers resident on ctx's device (16-byte aligned), enqueues one kernel on `hip_stream` and returns
+ *   without synchronising; it needs no workspace and takes no lock, so calls on different streams run side by side.
+ * The host-buffer form streams the blobs through the staging ring in passes (KATETH_AMD_CELLS_PASS blobs each), downloads the
+ *   extension half only and copies cells 0..63 from the caller's own blob.
+ * Group contexts: the host-buffer call cuts the batch into the same contiguous shares as kzg_blob_to_commitment_batch; the *_dev
+ *   call acts on member 0.
+ */
+int32_t kzg_compute_cells_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells /* n * 128 * 2048 */, int32_t* status);
+int32_t kzg_compute_cells_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_cells, void* d_status, void* hip_stream);
 
 /*
  * Replaces Setup::proof for n (blob, z) pairs (src/kzg/setup.rs:185-194):

@@ -16,6 +16,9 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 from .kzg import (  # noqa: F401,E402
     BYTES_PER_BLOB,
+    BYTES_PER_CELL,
+    CELLS_PER_EXT_BLOB,
+    FIELD_ELEMENTS_PER_CELL,
     P1,
     Blob,
     BlobError,
@@ -40,6 +43,9 @@ __all__ = [
     "KzgError",
     "LoadSetupError",
     "BYTES_PER_BLOB",
+    "CELLS_PER_EXT_BLOB",
+    "FIELD_ELEMENTS_PER_CELL",
+    "BYTES_PER_CELL",
     "library_path",
     "versioned_hash",
 ]

@@ -1,0 +1,85 @@
+// compute_cells (EIP-7594): the blob extension kernel (compiled once: engine_proof.hip owns this header).  Replaces
+// compute_cells of specs/fulu/polynomial-commitments-sampling.md = c-kzg-4844's compute_cells_and_kzg_proofs(cells, NULL, blob).
+#pragma once
+#include "cells_math.cuh"
+#include "issue_fair.cuh"
+#include "scalar_load.cuh"
+
+namespace kzg {
+#if defined(__HIPCC__)
+
+// One 512-thread workgroup per blob, the grid loops over the blobs.  The blob is read from HBM once (16-byte big-endian loads, element
+// i 512 + t: a wave reads 2 KiB in a row), range-checked as it arrives, and kept in LDS as eight word planes (131,072 B static, the
+// whole CU: one workgroup = two waves per SIMD) through the seven steps of cells_math.cuh.  Once the whole blob is known to be canonical
+// cells 0..63 are stored from the image -- global memory is not read a second time -- and the extension half leaves through the image
+// too, so that all stores are as coalesced as the loads.  No global scratch.
+// A blob with an element >= r: status KZG_ERR_BLOB_INVALID_FIELD_ELEMENT and 262,144 zero bytes.
+// Shape: 512 threads x 8 elements, four image round trips per transform (seven barriers in all: the two middle passes share one).
+// LDS lets one workgroup live on a CU, i.e. two waves per SIMD, so a wave may use 256 VGPRs -- a 1,024-thread workgroup (4 elements
+// per thread, six round trips per transform) would have to stay within 128.
+// hipcc -Rpass-analysis=kernel-resource-usage (gfx950, ROCm 7): 256 VGPRs, 0 AGPRs, 106 SGPRs (6 spilled to VGPR lanes), scratch 0,
+// LDS 131,076 B static (above 64 KiB without any launch attribute), occupancy 2 waves per SIMD.
+static __global__ __launch_bounds__(CELLS_THREADS) void k_compute_cells(const uint8_t* __restrict__ blobs, uint64_t n, const uint32_t* __restrict__ tab,
+                                                                     uint8_t* __restrict__ out_cells, int32_t* __restrict__ status) {
+  __shared__ uint32_t img[CELLS_IMAGE_DWORDS];
+  __shared__ int sh_bad;
+  for (uint64_t b = blockIdx.x; b < n; b += gridDim.x) {
+    // opaque per blob: otherwise every address of the load and store phases is computed once, ahead of the blob loop, and kept in
+    // registers through the steps (256 VGPRs and spills)
+    uint32_t t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    const uint4* in = reinterpret_cast<const uint4*>(blobs + b * 131072ull);
+    uint4* out = reinterpret_cast<uint4*>(out_cells + b * 262144ull);
+    // the image as 4096 x 32 big-endian bytes, coalesced like the loads, to out[first ..]
+    auto store_half = [&](uint32_t first) {
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        const uint32_t e = (uint32_t)i * CELLS_THREADS + t;
+        fr_t v;
+        cells_get(v, img, e);
+        out[first + 2 * e] = make_uint4(__builtin_bswap32(v.v[7]), __builtin_bswap32(v.v[6]), __builtin_bswap32(v.v[5]), __builtin_bswap32(v.v[4]));
+        out[first + 2 * e + 1] = make_uint4(__builtin_bswap32(v.v[3]), __builtin_bswap32(v.v[2]), __builtin_bswap32(v.v[1]), __builtin_bswap32(v.v[0]));
+      }
+    };
+    if (t == 0) sh_bad = 0;
+    __syncthreads();  // also: the previous blob's last reads of the image are done
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const uint32_t e = (uint32_t)i * CELLS_THREADS + t;
+      const uint4 w0 = in[2 * e], w1 = in[2 * e + 1];
+      fr_t v;
+      v.v[7] = __builtin_bswap32(w0.x);
+      v.v[6] = __builtin_bswap32(w0.y);
+      v.v[5] = __builtin_bswap32(w0.z);
+      v.v[4] = __builtin_bswap32(w0.w);
+      v.v[3] = __builtin_bswap32(w1.x);
+      v.v[2] = __builtin_bswap32(w1.y);
+      v.v[1] = __builtin_bswap32(w1.z);
+      v.v[0] = __builtin_bswap32(w1.w);
+      bad |= !fr_is_canonical(v);
+      cells_put(img, e, v);
+    }
+    if (bad) sh_bad = 1;
+    __syncthreads();
+    if (sh_bad) {  // block-uniform
+      const uint4 zero = make_uint4(0, 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 32; i++) out[(uint32_t)i * CELLS_THREADS + t] = zero;
+      if (t == 0) status[b] = KZG_ERR_BLOB_INVALID_FIELD_ELEMENT;
+      __syncthreads();  // every wave has read sh_bad before thread 0 clears it for the next blob
+      continue;
+    }
+    store_half(0);  // cells 0..63: the blob itself
+    if (t == 0) status[b] = 0;
+#pragma unroll 1
+    for (int k = 0; k < CELLS_STEPS; k++) {
+      cells_step(img, tab, t, k);
+      __syncthreads();
+    }
+    store_half(8192);  // cells 64..127
+  }
+}
+
+#endif
+}  // namespace kzg

@@ -476,6 +476,7 @@ EnvKnobs read_env_knobs() {
     if (const char* e = getenv("KATETH_AMD_HOST_FP")) host_fp_force_portable() = std::string(e) == "portable";  // measurement aid: the host's Fp products without mulx / adx
     if (const char* e = getenv("KATETH_AMD_PROOF_CHUNK")) k.proof_chunk = (uint64_t)atoll(e) > 0 ? (uint64_t)atoll(e) : 0;
     if (const char* e = getenv("KATETH_AMD_SIDECAR_PASS")) k.sidecar_pass = (uint64_t)atoll(e) > 0 ? (uint64_t)atoll(e) : 0;
+    if (const char* e = getenv("KATETH_AMD_CELLS_PASS")) k.cells_pass = (uint64_t)atoll(e) > 0 ? (uint64_t)atoll(e) : 0;
     if (const char* e = getenv("KATETH_AMD_PROOF_OVERLAP")) k.proof_overlap = atoi(e) != 0;
     if (const char* e = getenv("KATETH_AMD_EVAL_GROUP")) k.eval_group = atoi(e);
     k.verify_serial = getenv("KATETH_AMD_VERIFY_SERIAL") != nullptr;
@@ -541,6 +542,7 @@ extern "C" void kzg_ctx_destroy(kzg_ctx* ctx) {
   if (ctx->d_bases_brp) (void)hipFree(ctx->d_bases_brp);
   if (ctx->d_roots_brp) (void)hipFree(ctx->d_roots_brp);
   if (ctx->d_eval_tab) (void)hipFree(ctx->d_eval_tab);
+  if (ctx->d_cells_tab) (void)hipFree(ctx->d_cells_tab);
   if (ctx->d_gen_affine) (void)hipFree(ctx->d_gen_affine);
   if (ctx->d_comb_k) (void)hipFree(ctx->d_comb_k);
   if (ctx->d_comb_k_lat) (void)hipFree(ctx->d_comb_k_lat);
@@ -816,6 +818,8 @@ static int32_t ctx_build(kzg_ctx* ctx, const uint8_t* g1_lagrange, const uint8_t
   hipLaunchKernelGGL(k_setup_roots, dim3(64), dim3(64), 0, st, ctx->d_roots_brp);
   HIP_TRY(hipMalloc(&ctx->d_eval_tab, (size_t)EVAL_TAB_HEXES * EVAL_TAB_DWORDS * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_setup_eval_tab, dim3(EVAL_TAB_HEXES / 64), dim3(64), 0, st, ctx->d_roots_brp, ctx->d_eval_tab);
+  HIP_TRY(hipMalloc(&ctx->d_cells_tab, (size_t)CELLS_TAB_ENTRIES * CELLS_TAB_ENTRY * sizeof(uint32_t)));
+  hipLaunchKernelGGL(k_setup_cells_tab, dim3(CELLS_TAB_ENTRIES / 64), dim3(64), 0, st, ctx->d_cells_tab);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   tt.mark("roots + evaluation table");

@@ -92,6 +92,15 @@ int32_t multi_sidecar(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint
   });
 }
 
+int32_t multi_cells(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status) {
+  const std::vector<Share> shares = shares_of(ctx, n);
+  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
+    const Share& sh = shares[j];
+    return cells_host(member_of(ctx, sh.member), blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, sh.count,
+                      out_cells + sh.first * (size_t)KZG_CELLS_PER_EXT_BLOB * KZG_BYTES_PER_CELL, status + sh.first);
+  });
+}
+
 int32_t multi_g1_decompress(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status) {
   const std::vector<Share> shares = shares_of(ctx, n);
   return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {

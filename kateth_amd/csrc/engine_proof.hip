@@ -3,6 +3,7 @@
 
 #include "engine_internal.hpp"
 #include "poly_kernels.cuh"  // this translation unit owns the quotient / evaluation kernels of the proof path
+#include "cells_kernels.cuh"  // ... and the blob extension kernel of compute_cells
 
 __global__ __launch_bounds__(256) void k_merge_status(int32_t* __restrict__ primary, const int32_t* __restrict__ secondary, uint64_t n) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -390,6 +391,79 @@ extern "C" int32_t kzg_blob_sidecar_batch(const kzg_ctx* ctx, const uint8_t* blo
                                           uint8_t* out_versioned_hashes32, int32_t* status) try {
   if (!ctx || (n && (!blobs || !out_commitments48 || !out_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
   return (is_group(ctx) ? multi_sidecar : sidecar_host)(ctx, blobs, n, out_commitments48, out_proofs48, out_versioned_hashes32, status);
+} catch (...) {
+  return abi_exception();
+}
+
+// ---------------------------------------------------------------------------
+// compute_cells (EIP-7594): the 128 cells of every blob
+// ---------------------------------------------------------------------------
+// One launch, one workgroup per CU looping over the blobs (a workgroup holds its blob in all of the CU's LDS it may claim, so a
+// larger grid would only queue).  The kernel writes every output byte and every status: nothing is cleared first.
+static int32_t cells_enqueue(const kzg_ctx* ctx, const uint8_t* d_blobs, uint64_t n, uint8_t* d_out_cells, int32_t* d_status, hipStream_t st) {
+  const unsigned grid = (unsigned)std::min<uint64_t>(n, ctx->num_cus);
+  hipLaunchKernelGGL(k_compute_cells, dim3(grid), dim3(CELLS_THREADS), 0, st, d_blobs, n, ctx->d_cells_tab, d_out_cells, d_status);
+  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "compute_cells launch failed");
+  return 0;
+}
+
+extern "C" int32_t kzg_compute_cells_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_cells, void* d_status, void* hip_stream) try {
+  if (!ctx || (n && (!d_blobs || !d_out_cells || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return cells_enqueue(ctx, (const uint8_t*)d_blobs, n, (uint8_t*)d_out_cells, (int32_t*)d_status, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+
+// Host-buffer form.  PCIe is this call's limit (128 KiB up and 256 KiB down per blob), so only the extension half comes back: cells
+// 0..63 of an accepted blob ARE the caller's blob and are copied on the host.  Passes of KATETH_AMD_CELLS_PASS blobs (default 512)
+// through the staging ring; a slot holds a pass's blobs and, behind them, its 256 KiB of cells per blob, and is free again when the
+// pass's download has been enqueued behind its kernel.
+constexpr size_t CELLS_BYTES_PER_BLOB = (size_t)KZG_CELLS_PER_EXT_BLOB * KZG_BYTES_PER_CELL;
+int32_t cells_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status) {
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
+  const uint64_t pass = std::min<uint64_t>(n, ctx->knobs.cells_pass ? ctx->knobs.cells_pass : 512);
+  const uint64_t passes = (n + pass - 1) / pass;
+  const bool piped = passes > 1;
+  Carve io;
+  const size_t o_st = io.take(n * sizeof(int32_t));
+  StageRing ring;
+  int32_t rc = ring.open(ctx, piped ? 2 : 1, (size_t)pass * (KZG_BYTES_PER_BLOB + CELLS_BYTES_PER_BLOB), io.off, piped);
+  if (rc) return rc;
+  int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
+  hipStream_t st = ctx->stage_streams[0];
+  for (uint64_t k = 0; k < passes && rc == 0; k++) {
+    const uint64_t base = k * pass, m = std::min<uint64_t>(pass, n - base);
+    uint8_t* d_blobs = nullptr;
+    rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, st, &d_blobs);
+    uint8_t* d_cells = d_blobs + pass * (size_t)KZG_BYTES_PER_BLOB;
+    if (rc == 0) rc = cells_enqueue(ctx, d_blobs, m, d_cells, d_status + base, st);
+    if (rc == 0 && hipMemcpy2DAsync(out_cells + base * CELLS_BYTES_PER_BLOB + KZG_BYTES_PER_BLOB, CELLS_BYTES_PER_BLOB, d_cells + KZG_BYTES_PER_BLOB,
+                                    CELLS_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB, m, hipMemcpyDeviceToHost, st) != hipSuccess)
+      rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
+    if (rc == 0) rc = ring.consumed(k, st);
+  }
+  if (rc == 0 && (hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+    rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
+  if (rc) {
+    (void)hipDeviceSynchronize();
+    return rc;
+  }
+  for (uint64_t i = 0; i < n; i++) {
+    if (status[i] == 0)
+      memcpy(out_cells + i * CELLS_BYTES_PER_BLOB, blobs + i * (size_t)KZG_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB);
+    else
+      memset(out_cells + i * CELLS_BYTES_PER_BLOB, 0, KZG_BYTES_PER_BLOB);
+  }
+  return 0;
+}
+
+extern "C" int32_t kzg_compute_cells_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status) try {
+  if (!ctx || (n && (!blobs || !out_cells || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return (is_group(ctx) ? multi_cells : cells_host)(ctx, blobs, n, out_cells, status);
 } catch (...) {
   return abi_exception();
 }

@@ -1,6 +1,7 @@
 // Context-creation kernels: what Setup::load_json does after parsing
 // (src/kzg/setup.rs:52-81) plus the batch normaliser of the fixed-base table build (msm_comb.cuh).
 #pragma once
+#include "cells_math.cuh"
 #include "fp30.cuh"
 #include "fr29.cuh"
 #include "msm_fixed.cuh"
@@ -195,6 +196,16 @@ static __global__ __launch_bounds__(64) void k_setup_roots(fr_t* __restrict__ ro
     if ((t >> bit) & 1u) fr_mul(acc, acc, w);
   }
   roots_brp[bitrev12(t)] = acc;
+}
+
+// one thread per entry of compute_cells' twiddle table (layout and entry function: cells_math.cuh)
+static __global__ __launch_bounds__(64) void k_setup_cells_tab(uint32_t* __restrict__ cells_tab) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= CELLS_TAB_ENTRIES) return;
+  uint32_t e[CELLS_TAB_ENTRY];
+  cells_tab_entry(i, e);
+#pragma unroll
+  for (int q = 0; q < CELLS_TAB_ENTRY; q++) cells_tab[(uint64_t)i * CELLS_TAB_ENTRY + q] = e[q];
 }
 
 #endif

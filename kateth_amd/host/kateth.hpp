@@ -291,6 +291,18 @@ class Setup {
     return out;
   }
 
+  // compute_cells (EIP-7594, specs/fulu/polynomial-commitments-sampling.md): the blob extended to 8192 evaluations, as 128 cells of
+  // 2,048 bytes in one buffer; cells 0..63 are the blob itself.  Cell proofs, verification and recovery are not part of the engine.
+  static constexpr size_t CELLS_PER_EXT_BLOB = KZG_CELLS_PER_EXT_BLOB, FIELD_ELEMENTS_PER_CELL = KZG_FIELD_ELEMENTS_PER_CELL, BYTES_PER_CELL = KZG_BYTES_PER_CELL;
+  std::vector<uint8_t> compute_cells(const uint8_t* blob, size_t len) const {
+    if (len != BLOB_BYTES) throw Error(ErrorKind::BlobInvalidLen);
+    std::vector<uint8_t> out(CELLS_PER_EXT_BLOB * BYTES_PER_CELL);
+    int32_t status = 0;
+    check(kzg_compute_cells_batch(ctx_.get(), blob, 1, out.data(), &status), "kzg_compute_cells_batch");
+    if (status) throw Error(static_cast<ErrorKind>(status));
+    return out;
+  }
+
   // (proof, y)
   std::pair<Bytes48, Bytes32> proof(const uint8_t* blob, size_t len, const Bytes32& point) const {
     if (len != BLOB_BYTES) throw Error(ErrorKind::BlobInvalidLen);
@@ -471,6 +483,11 @@ class Setup {
   // out_versioned_hashes32 may be null (not wanted)
   void blob_sidecar_batch(const uint8_t* blobs, size_t n, uint8_t* out_commitments48, uint8_t* out_proofs48, uint8_t* out_versioned_hashes32, int32_t* status) const {
     check(kzg_blob_sidecar_batch(ctx_.get(), blobs, n, out_commitments48, out_proofs48, out_versioned_hashes32, status), "kzg_blob_sidecar_batch");
+  }
+
+  // out_cells: n * 128 * 2048 bytes
+  void compute_cells_batch(const uint8_t* blobs, size_t n, uint8_t* out_cells, int32_t* status) const {
+    check(kzg_compute_cells_batch(ctx_.get(), blobs, n, out_cells, status), "kzg_compute_cells_batch");
   }
 
   const kzg_ctx* raw() const { return ctx_.get(); }

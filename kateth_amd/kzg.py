@@ -6,6 +6,7 @@ Method names, argument meaning and error behaviour follow the reference:
     Setup.blob_to_commitment(blob)               src/kzg/setup.rs:167-171   (+ compress, src/bls.rs:491-503)
     Setup.blob_proof(blob, commitment48)         src/kzg/setup.rs:177-183
     Setup.blob_sidecar(blob)                     :167-171 then :177-183 on the same blob, + EIP-4844 kzg_to_versioned_hash
+    Setup.compute_cells(blob)                    EIP-7594 compute_cells (specs/fulu/polynomial-commitments-sampling.md)
     Setup.proof(blob, z32)                       src/kzg/setup.rs:185-194
     Setup.verify_proof(proof, commitment, z, y)  src/kzg/setup.rs:96-113
     Setup.verify_blob_proof(blob, c, p)          src/kzg/setup.rs:208-221
@@ -25,6 +26,9 @@ import os
 from typing import List, Optional, Sequence, Tuple, Union
 
 BYTES_PER_BLOB = 131072
+CELLS_PER_EXT_BLOB = 128  # EIP-7594
+FIELD_ELEMENTS_PER_CELL = 64
+BYTES_PER_CELL = 2048
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -152,6 +156,8 @@ _SIGNATURES = {
         ctypes.c_int32,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "kzg_compute_cells_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
+    "kzg_compute_cells_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kzg_compute_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
     "kzg_verify_blob_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
     "kzg_verify_blob_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
@@ -548,6 +554,19 @@ class Setup:
         self._check(rc, "kzg_blob_sidecar_batch")
         return coms.raw, proofs.raw, hashes.raw, list(status)
 
+    def compute_cells_batch(self, blobs: bytes, n: Optional[int] = None):
+        """n concatenated blobs -> (n * 128 * 2048 bytes of cells, [status]): EIP-7594's `compute_cells` per blob.  Cells 0..63 of an
+        accepted blob are the blob itself; a rejected blob gets zero bytes."""
+        blobs = _buf(blobs)
+        n = len(blobs) // BYTES_PER_BLOB if n is None else n
+        if len(blobs) != n * BYTES_PER_BLOB:
+            raise BlobError("InvalidLen")
+        out = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * n)
+        status = (ctypes.c_int32 * n)()
+        rc = self._lib.kzg_compute_cells_batch(self._h, blobs, n, ctypes.cast(out, ctypes.c_void_p), status)
+        self._check(rc, "kzg_compute_cells_batch")
+        return out.raw, list(status)
+
     def compute_proof_batch(self, blobs: bytes, zs: bytes):
         blobs, zs = _buf(blobs), _buf(zs)
         n = len(zs) // 32
@@ -647,6 +666,16 @@ class Setup:
         if status[0]:
             raise error_from_status(status[0])
         return coms, proofs, hashes
+
+    def compute_cells(self, blob: bytes) -> List[bytes]:
+        """`compute_cells` (EIP-7594): the 128 cells of one blob, 2,048 bytes each; raises what `blob_to_commitment` raises."""
+        blob = _buf(blob)
+        if len(blob) != BYTES_PER_BLOB:
+            raise BlobError("InvalidLen")
+        out, status = self.compute_cells_batch(blob, 1)
+        if status[0]:
+            raise error_from_status(status[0])
+        return [out[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
 
     def blob_proof(self, blob: bytes, commitment: bytes) -> bytes:
         """`Setup::blob_proof` + `compress` (kzg::Error on bad input)."""
@@ -896,6 +925,11 @@ class Setup:
         """d_versioned_hashes = 0: no hashes wanted"""
         rc = self._lib.kzg_blob_sidecar_batch_dev(self._h, d_blobs, n, d_commitments, d_proofs, d_versioned_hashes or None, d_status, stream)
         self._check(rc, "kzg_blob_sidecar_batch_dev")
+
+    def compute_cells_batch_dev(self, d_blobs: int, n: int, d_out_cells: int, d_status: int, stream: int = 0):
+        """n blobs resident on the device -> n * 128 * 2048 bytes of cells and n int32 statuses; enqueues on `stream` and returns"""
+        rc = self._lib.kzg_compute_cells_batch_dev(self._h, d_blobs, n, d_out_cells, d_status, stream)
+        self._check(rc, "kzg_compute_cells_batch_dev")
 
     def verify_blob_proof_batch_dev(self, d_blobs: int, d_commitments: int, d_proofs: int, n: int, stream: int = 0) -> bool:
         ok = ctypes.c_int32(0)
