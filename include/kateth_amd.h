@@ -66,6 +66,9 @@ extern "C" {
 #define KZG_ERR_EC_NOT_IN_GROUP 5            /* ECGroupError::NotInGroup           src/bls.rs:30  */
 #define KZG_ERR_FF_INVALID_ENCODING 6        /* FiniteFieldError::InvalidEncoding  src/bls.rs:23  */
 #define KZG_ERR_FF_NOT_IN_FIELD 7            /* FiniteFieldError::NotInFiniteField src/bls.rs:24  */
+/* kzg_recover_cells_batch only; the reference has no cell recovery */
+#define KZG_ERR_CELLS_NOT_ENOUGH 8           /* fewer than 64 cells present */
+#define KZG_ERR_CELLS_INCONSISTENT 9         /* the present cells are not the evaluations of one polynomial of degree < 4096 */
 
 #define KZG_FAIL_ARGUMENT (-1)
 #define KZG_FAIL_HIP (-2)
@@ -277,7 +280,7 @@ int32_t kzg_blob_sidecar_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint
  *   blobs     : n * 131072 bytes
  *   out_cells : n * 128 * 2048 bytes; cells 0..63 of an accepted blob are the blob, byte for byte
  *   status    : n * int32 ; 0 or KZG_ERR_BLOB_INVALID_FIELD_ELEMENT per blob.  A rejected blob gets 262144 zero bytes.
- * Not here: cell proofs (they need the monomial G1 setup and FK20), cell verification and cell recovery.
+ * Not here: cell proofs (they need the monomial G1 setup and FK20) and cell verification; cell recovery is kzg_recover_cells_batch.
  * Bounds: nothing beyond n items is written; n == 0 returns 0.  A null pointer with n > 0 returns KZG_FAIL_ARGUMENT.
  * The *_dev form takes HIP device pointers resident on ctx's device (16-byte aligned), enqueues one kernel on `hip_stream` and returns
  *   without synchronising; it needs no workspace and takes no lock, so calls on different streams run side by side.
@@ -288,6 +291,40 @@ int32_t kzg_blob_sidecar_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint
  */
 int32_t kzg_compute_cells_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells /* n * 128 * 2048 */, int32_t* status);
 int32_t kzg_compute_cells_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_cells, void* d_status, void* hip_stream);
+
+/*
+ * The missing cells of n cell sets (EIP-7594, PeerDAS): the cells half of recover_cells_and_kzg_proofs of
+ * specs/fulu/polynomial-commitments-sampling.md (c-kzg-4844's recover_cells_and_kzg_proofs without its proofs).  A node that holds at
+ * least 64 of a blob's 128 cells rebuilds the others: the present elements determine the polynomial p of degree < 4096, and the
+ * absent cells are its evaluations, as kzg_compute_cells_batch would give them.
+ *   cells     : n * 128 * 2048 bytes, laid out like kzg_compute_cells_batch's output: cell c of an item at byte 2048 c
+ *   present   : n * 16 bytes, a 128-bit mask per item: cell c is present iff bit (c & 7), least significant first, of byte (c >> 3)
+ *               is set.  The bytes of an absent cell are never read: they may be anything, non-canonical garbage included.
+ *   out_cells : n * 128 * 2048 bytes; for an accepted item all 128 cells, the present ones byte for byte as they came
+ *   status    : n * int32 ; per item 0 or, in this order of precedence,
+ *               KZG_ERR_CELLS_NOT_ENOUGH            fewer than 64 cells present
+ *               KZG_ERR_BLOB_INVALID_FIELD_ELEMENT  an element >= r in a present cell
+ *               KZG_ERR_CELLS_INCONSISTENT          the recovered polynomial disagrees with a present element
+ *               A rejected item gets 262144 zero bytes; its neighbours are untouched.
+ * The consistency check is an ADDITION to the specification: recover_polynomialcoeff truncates silently when the present cells do not
+ *   lie on one polynomial of degree < 4096, so what it returns then depends on the algorithm.  Here every present element is compared
+ *   with the recovered polynomial as the result is stored, which makes the call well-defined.  With exactly 64 cells present every
+ *   input is consistent; the check can fire from 65 cells on.
+ * out_cells must not overlap cells.  The kernel uses an item's own output region as scratch before the final stores: while a call
+ *   is in flight the region holds intermediate values.
+ * Not here: the proofs half of recovery (it needs the monomial G1 setup and FK20, like cell proofs).
+ * Bounds: nothing beyond n items is written; n == 0 returns 0.  A null pointer with n > 0 returns KZG_FAIL_ARGUMENT.
+ * The *_dev form takes HIP device pointers resident on ctx's device (16-byte aligned), enqueues one kernel on `hip_stream` and returns
+ *   without synchronising; it needs no workspace and takes no lock, so calls on different streams run side by side.
+ * The host-buffer form streams the cell sets through the staging ring in passes (KATETH_AMD_CELLS_PASS items each); every pass
+ *   uploads and downloads whole cell sets.
+ * Group contexts: the host-buffer call cuts the batch into the same contiguous shares as kzg_blob_to_commitment_batch; the *_dev
+ *   call acts on member 0.
+ */
+int32_t kzg_recover_cells_batch(const kzg_ctx* ctx, const uint8_t* cells /* n * 128 * 2048 */, const uint8_t* present /* n * 16 */, uint64_t n,
+                                uint8_t* out_cells /* n * 128 * 2048 */, int32_t* status);
+int32_t kzg_recover_cells_batch_dev(const kzg_ctx* ctx, const void* d_cells, const void* d_present, uint64_t n, void* d_out_cells, void* d_status,
+                                    void* hip_stream);
 
 /*
  * Replaces Setup::proof for n (blob, z) pairs (src/kzg/setup.rs:185-194):

@@ -23,6 +23,7 @@ from .kzg import (  # noqa: F401,E402
     Blob,
     BlobError,
     BlsError,
+    CellsError,
     ECGroupError,
     FiniteFieldError,
     KzgError,
@@ -41,6 +42,7 @@ __all__ = [
     "ECGroupError",
     "FiniteFieldError",
     "KzgError",
+    "CellsError",
     "LoadSetupError",
     "BYTES_PER_BLOB",
     "CELLS_PER_EXT_BLOB",

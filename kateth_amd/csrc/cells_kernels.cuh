@@ -1,7 +1,9 @@
 // compute_cells (EIP-7594): the blob extension kernel (compiled once: engine_proof.hip owns this header).  Replaces
 // compute_cells of specs/fulu/polynomial-commitments-sampling.md = c-kzg-4844's compute_cells_and_kzg_proofs(cells, NULL, blob).
+// recover_cells: k_recover_cells below replaces the cells half of recover_cells_and_kzg_proofs.
 #pragma once
 #include "cells_math.cuh"
+#include "recover_math.cuh"
 #include "issue_fair.cuh"
 #include "scalar_load.cuh"
 
@@ -78,6 +80,79 @@ static __global__ __launch_bounds__(CELLS_THREADS) void k_compute_cells(const ui
       __syncthreads();
     }
     store_half(8192);  // cells 64..127
+  }
+}
+
+// recover_cells: one 512-thread workgroup per cell set, the grid loops over the sets; the steps are those of recover_math.cuh, on the
+// same LDS image as k_compute_cells, followed by that kernel's own seven steps for cells 64..127.  Global traffic per accepted item:
+// the present cells are read twice (to be scaled into the image, and to be compared with at the end), 128 KiB go to the item's own
+// output region and come back (the stash of steps 3 and 7: every thread reads what it wrote itself, so no fence is needed), and the
+// 256 KiB of the result are written once.  The bytes of an absent cell are never read.
+// Status, in this order: fewer than 64 cells present -> KZG_ERR_CELLS_NOT_ENOUGH; a present element >= r ->
+// KZG_ERR_BLOB_INVALID_FIELD_ELEMENT; the recovered polynomial differs from a present element -> KZG_ERR_CELLS_INCONSISTENT.  A
+// rejected item gets 262,144 zero bytes -- after the barrier that ends its last step, so they land on top of what was stored before.
+// LDS: the image, 6,912 B of Z_c / P_u, the mask and the flag.
+static __global__ __launch_bounds__(CELLS_THREADS) void k_recover_cells(const uint8_t* __restrict__ cells, const uint8_t* __restrict__ present, uint64_t n,
+                                                                     const uint32_t* __restrict__ tab, const uint32_t* __restrict__ rtab,
+                                                                     uint8_t* __restrict__ out_cells, int32_t* __restrict__ status) {
+  __shared__ uint32_t img[CELLS_IMAGE_DWORDS];
+  __shared__ uint32_t zs[RECOVER_ZS_DWORDS];
+  __shared__ uint32_t mask[4];
+  __shared__ int sh_bad;
+  for (uint64_t b = blockIdx.x; b < n; b += gridDim.x) {
+    uint32_t t = threadIdx.x;  // opaque per item, as in k_compute_cells
+    asm volatile("" : "+v"(t));
+    const uint8_t* in = cells + b * 262144ull;
+    uint8_t* out = out_cells + b * 262144ull;
+    if (t < 4) mask[t] = reinterpret_cast<const uint32_t*>(present + b * 16ull)[t];
+    if (t == 0) sh_bad = 0;
+    __syncthreads();  // also: the previous item's last reads of the image are done
+    if (recover_count(mask) < RECOVER_MIN_CELLS) {  // block-uniform
+      if (t == 0) sh_bad = KZG_ERR_CELLS_NOT_ENOUGH;
+    } else {
+      recover_prep_partial(img, rtab, mask, t);
+      __syncthreads();
+      recover_prep_combine(zs, img, t);
+      __syncthreads();
+#pragma unroll 1
+      for (int k = 0; k < RECOVER_STEPS; k++) {
+        if (k == 0 || k == 4) {
+          uint32_t tl = t;  // opaque again: the addresses of a load or store phase are not to be computed ahead of the loop and kept
+          asm volatile("" : "+v"(tl));
+          if (recover_load_half(img, zs, in, mask, tl, (uint32_t)k >> 2)) sh_bad = KZG_ERR_BLOB_INVALID_FIELD_ELEMENT;
+          __syncthreads();
+          if (sh_bad) break;  // block-uniform
+        }
+        recover_step(img, zs, reinterpret_cast<uint32_t*>(out), tab, rtab, t, k);
+        __syncthreads();
+      }
+      if (sh_bad == 0) {
+#pragma unroll 1
+        for (uint32_t half = 0; half < 2; half++) {
+          if (half) {
+#pragma unroll 1
+            for (int k = 0; k < CELLS_STEPS; k++) {
+              cells_step(img, tab, t, k);
+              __syncthreads();
+            }
+          }
+          uint32_t ts = t;
+          asm volatile("" : "+v"(ts));
+          if (recover_store_half(img, in, out, mask, ts, half)) sh_bad = KZG_ERR_CELLS_INCONSISTENT;
+          __syncthreads();
+        }
+      }
+    }
+    __syncthreads();
+    const int code = sh_bad;
+    if (code) {
+      uint4* z = reinterpret_cast<uint4*>(out);
+      const uint4 zero = make_uint4(0, 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 32; i++) z[(uint32_t)i * CELLS_THREADS + t] = zero;
+    }
+    if (t == 0) status[b] = code;
+    __syncthreads();  // every wave has read mask and sh_bad before the next item replaces them
   }
 }
 

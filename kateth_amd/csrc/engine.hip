@@ -543,6 +543,7 @@ extern "C" void kzg_ctx_destroy(kzg_ctx* ctx) {
   if (ctx->d_roots_brp) (void)hipFree(ctx->d_roots_brp);
   if (ctx->d_eval_tab) (void)hipFree(ctx->d_eval_tab);
   if (ctx->d_cells_tab) (void)hipFree(ctx->d_cells_tab);
+  if (ctx->d_recover_tab) (void)hipFree(ctx->d_recover_tab);
   if (ctx->d_gen_affine) (void)hipFree(ctx->d_gen_affine);
   if (ctx->d_comb_k) (void)hipFree(ctx->d_comb_k);
   if (ctx->d_comb_k_lat) (void)hipFree(ctx->d_comb_k_lat);
@@ -820,6 +821,8 @@ static int32_t ctx_build(kzg_ctx* ctx, const uint8_t* g1_lagrange, const uint8_t
   hipLaunchKernelGGL(k_setup_eval_tab, dim3(EVAL_TAB_HEXES / 64), dim3(64), 0, st, ctx->d_roots_brp, ctx->d_eval_tab);
   HIP_TRY(hipMalloc(&ctx->d_cells_tab, (size_t)CELLS_TAB_ENTRIES * CELLS_TAB_ENTRY * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_setup_cells_tab, dim3(CELLS_TAB_ENTRIES / 64), dim3(64), 0, st, ctx->d_cells_tab);
+  HIP_TRY(hipMalloc(&ctx->d_recover_tab, (size_t)RECOVER_TAB_ENTRIES * CELLS_TAB_ENTRY * sizeof(uint32_t)));
+  hipLaunchKernelGGL(k_setup_recover_tab, dim3(RECOVER_TAB_ENTRIES / 64), dim3(64), 0, st, ctx->d_recover_tab);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   tt.mark("roots + evaluation table");

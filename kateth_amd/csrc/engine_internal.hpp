@@ -136,7 +136,7 @@ struct EnvKnobs {
   uint32_t msm_splits = 0;       // KATETH_AMD_MSM_SPLITS: force the (blob, split) decomposition of the fixed-base MSM (power of two <= 64; 0 = automatic)
   uint64_t challenge_split_max = 0;  // KATETH_AMD_CHALLENGE_SPLIT_MAX: largest batch hashed by the two-wave SHA-256 kernel (0 = default)
   uint64_t sidecar_pass = 0;     // KATETH_AMD_SIDECAR_PASS: blobs per staging pass of kzg_blob_sidecar_batch (0 = the plan of the host-buffer proof call)
-  uint64_t cells_pass = 0;       // KATETH_AMD_CELLS_PASS: blobs per staging pass of kzg_compute_cells_batch (0 = default)
+  uint64_t cells_pass = 0;       // KATETH_AMD_CELLS_PASS: items per staging pass of kzg_compute_cells_batch and kzg_recover_cells_batch (0 = default)
 };
 EnvKnobs read_env_knobs();
 
@@ -236,6 +236,7 @@ struct kzg_ctx {
   fr_t* d_roots_brp = nullptr;   // 4096 roots of unity, Montgomery, BRP order
   uint32_t* d_eval_tab = nullptr;  // 256 hexes x twenty 9-limb slots in radix-2^29 limbs (layout: fr29.cuh; k_eval_frac, verify_kernels.cuh)
   uint32_t* d_cells_tab = nullptr;  // compute_cells' twiddles: 12,288 entries of twelve dwords (layout: cells_math.cuh; k_compute_cells, cells_kernels.cuh)
+  uint32_t* d_recover_tab = nullptr;  // recover_cells' twists, omega_128 powers and coset points: 12,480 such entries (layout: recover_math.cuh; k_recover_cells)
   uint4* d_gen_affine = nullptr; // G1 generator and its [z^2]-image (GLV cross-check path), affine, 2^392-Montgomery (2 x 96 B): a term of batch verification's second lincomb
   host::pairing_ctx* pairing = nullptr;  // host: Frobenius constants + Miller lines of G2 and [tau]_2
   uint64_t table_bytes = 0;
@@ -292,6 +293,7 @@ int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side
 int32_t sidecar_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48, uint8_t* out_versioned_hashes32,
                      int32_t* status);  // engine_proof.hip
 int32_t cells_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status);  // engine_proof.hip
+int32_t recover_host(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status);  // engine_proof.hip
 int32_t verify_proof_single(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok);
 int32_t g1_decompress_single(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
 int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
@@ -303,6 +305,7 @@ int32_t multi_proof(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* sid
 int32_t multi_sidecar(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48, uint8_t* out_versioned_hashes32,
                       int32_t* status);
 int32_t multi_cells(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status);
+int32_t multi_recover(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status);
 int32_t multi_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok);
 int32_t multi_g1_decompress(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
 int32_t multi_evaluate_blobs(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);

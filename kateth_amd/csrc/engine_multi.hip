@@ -101,6 +101,16 @@ int32_t multi_cells(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_
   });
 }
 
+int32_t multi_recover(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status) {
+  const std::vector<Share> shares = shares_of(ctx, n);
+  constexpr size_t set_bytes = (size_t)KZG_CELLS_PER_EXT_BLOB * KZG_BYTES_PER_CELL;
+  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
+    const Share& sh = shares[j];
+    return recover_host(member_of(ctx, sh.member), cells + sh.first * set_bytes, present + sh.first * 16, sh.count, out_cells + sh.first * set_bytes,
+                        status + sh.first);
+  });
+}
+
 int32_t multi_g1_decompress(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status) {
   const std::vector<Share> shares = shares_of(ctx, n);
   return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {

@@ -468,6 +468,74 @@ extern "C" int32_t kzg_compute_cells_batch(const kzg_ctx* ctx, const uint8_t* bl
   return abi_exception();
 }
 
+// ---------------------------------------------------------------------------
+// recover_cells (EIP-7594): the absent cells of every cell set
+// ---------------------------------------------------------------------------
+// One launch shaped like compute_cells'.  The kernel writes every output byte and every status.
+static int32_t recover_enqueue(const kzg_ctx* ctx, const uint8_t* d_cells, const uint8_t* d_present, uint64_t n, uint8_t* d_out_cells, int32_t* d_status,
+                               hipStream_t st) {
+  const unsigned grid = (unsigned)std::min<uint64_t>(n, ctx->num_cus);
+  hipLaunchKernelGGL(k_recover_cells, dim3(grid), dim3(CELLS_THREADS), 0, st, d_cells, d_present, n, ctx->d_cells_tab, ctx->d_recover_tab, d_out_cells,
+                     d_status);
+  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "recover_cells launch failed");
+  return 0;
+}
+
+extern "C" int32_t kzg_recover_cells_batch_dev(const kzg_ctx* ctx, const void* d_cells, const void* d_present, uint64_t n, void* d_out_cells, void* d_status,
+                                               void* hip_stream) try {
+  if (!ctx || (n && (!d_cells || !d_present || !d_out_cells || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return recover_enqueue(ctx, (const uint8_t*)d_cells, (const uint8_t*)d_present, n, (uint8_t*)d_out_cells, (int32_t*)d_status, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+
+// Host-buffer form: whole cell sets up and whole cell sets down (256 KiB each way per item), in passes of KATETH_AMD_CELLS_PASS items
+// (default 256) through the staging ring; a slot holds a pass's input and, behind it, its output.  The masks of the whole call go up
+// once, next to the statuses.
+int32_t recover_host(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status) {
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
+  const uint64_t pass = std::min<uint64_t>(n, ctx->knobs.cells_pass ? ctx->knobs.cells_pass : 256);
+  const uint64_t passes = (n + pass - 1) / pass;
+  const bool piped = passes > 1;
+  Carve io;
+  const size_t o_st = io.take(n * sizeof(int32_t)), o_mask = io.take(n * 16);
+  StageRing ring;
+  int32_t rc = ring.open(ctx, piped ? 2 : 1, (size_t)pass * 2 * CELLS_BYTES_PER_BLOB, io.off, piped);
+  if (rc) return rc;
+  int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
+  uint8_t* d_present = ctx->hostio + o_mask;
+  hipStream_t st = ctx->stage_streams[0];
+  if (hipMemcpyAsync(d_present, present, n * 16, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
+  for (uint64_t k = 0; k < passes && rc == 0; k++) {
+    const uint64_t base = k * pass, m = std::min<uint64_t>(pass, n - base);
+    uint8_t* d_cells = nullptr;
+    rc = ring.feed(k, cells + base * CELLS_BYTES_PER_BLOB, m * CELLS_BYTES_PER_BLOB, st, &d_cells);
+    uint8_t* d_out = d_cells + pass * CELLS_BYTES_PER_BLOB;
+    if (rc == 0) rc = recover_enqueue(ctx, d_cells, d_present + base * 16, m, d_out, d_status + base, st);
+    if (rc == 0 && hipMemcpyAsync(out_cells + base * CELLS_BYTES_PER_BLOB, d_out, m * CELLS_BYTES_PER_BLOB, hipMemcpyDeviceToHost, st) != hipSuccess)
+      rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
+    if (rc == 0) rc = ring.consumed(k, st);
+  }
+  if (rc == 0 && (hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+    rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
+  if (rc) {
+    (void)hipDeviceSynchronize();
+    return rc;
+  }
+  return 0;
+}
+
+extern "C" int32_t kzg_recover_cells_batch(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status) try {
+  if (!ctx || (n && (!cells || !present || !out_cells || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return (is_group(ctx) ? multi_recover : recover_host)(ctx, cells, present, n, out_cells, status);
+} catch (...) {
+  return abi_exception();
+}
+
 void warm_code_object_proof() {
   hipFuncAttributes a;
   (void)hipFuncGetAttributes(&a, (const void*)k_poly_root_inverse);

@@ -2,6 +2,7 @@
 // (src/kzg/setup.rs:52-81) plus the batch normaliser of the fixed-base table build (msm_comb.cuh).
 #pragma once
 #include "cells_math.cuh"
+#include "recover_math.cuh"
 #include "fp30.cuh"
 #include "fr29.cuh"
 #include "msm_fixed.cuh"
@@ -206,6 +207,16 @@ static __global__ __launch_bounds__(64) void k_setup_cells_tab(uint32_t* __restr
   cells_tab_entry(i, e);
 #pragma unroll
   for (int q = 0; q < CELLS_TAB_ENTRY; q++) cells_tab[(uint64_t)i * CELLS_TAB_ENTRY + q] = e[q];
+}
+
+// the same for recover_cells' tables (recover_math.cuh)
+static __global__ __launch_bounds__(64) void k_setup_recover_tab(uint32_t* __restrict__ recover_tab) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= RECOVER_TAB_ENTRIES) return;
+  uint32_t e[CELLS_TAB_ENTRY];
+  recover_tab_entry(i, e);
+#pragma unroll
+  for (int q = 0; q < CELLS_TAB_ENTRY; q++) recover_tab[(uint64_t)i * CELLS_TAB_ENTRY + q] = e[q];
 }
 
 #endif

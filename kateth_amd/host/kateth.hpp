@@ -26,6 +26,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -48,6 +49,8 @@ enum class ErrorKind : int32_t {
   ECGroupNotInGroup = KZG_ERR_EC_NOT_IN_GROUP,                   // src/bls.rs:30
   FiniteFieldInvalidEncoding = KZG_ERR_FF_INVALID_ENCODING,      // src/bls.rs:23
   FiniteFieldNotInFiniteField = KZG_ERR_FF_NOT_IN_FIELD,         // src/bls.rs:24
+  CellsNotEnough = KZG_ERR_CELLS_NOT_ENOUGH,                     // recover_cells: fewer than 64 cells
+  CellsInconsistent = KZG_ERR_CELLS_INCONSISTENT,                // recover_cells: the cells do not lie on one polynomial of degree < 4096
 };
 
 class Error : public std::runtime_error {
@@ -292,13 +295,35 @@ class Setup {
   }
 
   // compute_cells (EIP-7594, specs/fulu/polynomial-commitments-sampling.md): the blob extended to 8192 evaluations, as 128 cells of
-  // 2,048 bytes in one buffer; cells 0..63 are the blob itself.  Cell proofs, verification and recovery are not part of the engine.
+  // 2,048 bytes in one buffer; cells 0..63 are the blob itself.  Cell proofs, cell verification and the proofs half of recovery are not
+  // part of the engine.
   static constexpr size_t CELLS_PER_EXT_BLOB = KZG_CELLS_PER_EXT_BLOB, FIELD_ELEMENTS_PER_CELL = KZG_FIELD_ELEMENTS_PER_CELL, BYTES_PER_CELL = KZG_BYTES_PER_CELL;
   std::vector<uint8_t> compute_cells(const uint8_t* blob, size_t len) const {
     if (len != BLOB_BYTES) throw Error(ErrorKind::BlobInvalidLen);
     std::vector<uint8_t> out(CELLS_PER_EXT_BLOB * BYTES_PER_CELL);
     int32_t status = 0;
     check(kzg_compute_cells_batch(ctx_.get(), blob, 1, out.data(), &status), "kzg_compute_cells_batch");
+    if (status) throw Error(static_cast<ErrorKind>(status));
+    return out;
+  }
+
+  // recover_cells: the cells half of the spec's recover_cells_and_kzg_proofs.  cell_indices: 64..128 strictly ascending indices < 128;
+  // cells: the cells of those indices, concatenated (2,048 bytes each).  Returns all 128 cells in one buffer.  Beyond the spec, cells that
+  // do not lie on one polynomial of degree < 4096 are rejected (ErrorKind::CellsInconsistent) instead of giving an arbitrary result.
+  std::vector<uint8_t> recover_cells(const std::vector<uint64_t>& cell_indices, const uint8_t* cells, size_t len) const {
+    const size_t m = cell_indices.size();
+    if (len != m * BYTES_PER_CELL || m > CELLS_PER_EXT_BLOB) throw std::invalid_argument("recover_cells: one 2048-byte cell per index, at most 128");
+    if (m < CELLS_PER_EXT_BLOB / 2) throw Error(ErrorKind::CellsNotEnough);
+    std::vector<uint8_t> in(CELLS_PER_EXT_BLOB * BYTES_PER_CELL), out(CELLS_PER_EXT_BLOB * BYTES_PER_CELL);
+    std::array<uint8_t, 16> present{};
+    for (size_t i = 0; i < m; i++) {
+      const uint64_t c = cell_indices[i];
+      if (c >= CELLS_PER_EXT_BLOB || (i && c <= cell_indices[i - 1])) throw std::invalid_argument("recover_cells: indices must be < 128 and strictly ascending");
+      std::memcpy(in.data() + c * BYTES_PER_CELL, cells + i * BYTES_PER_CELL, BYTES_PER_CELL);
+      present[c >> 3] |= static_cast<uint8_t>(1u << (c & 7));
+    }
+    int32_t status = 0;
+    check(kzg_recover_cells_batch(ctx_.get(), in.data(), present.data(), 1, out.data(), &status), "kzg_recover_cells_batch");
     if (status) throw Error(static_cast<ErrorKind>(status));
     return out;
   }
@@ -488,6 +513,11 @@ class Setup {
   // out_cells: n * 128 * 2048 bytes
   void compute_cells_batch(const uint8_t* blobs, size_t n, uint8_t* out_cells, int32_t* status) const {
     check(kzg_compute_cells_batch(ctx_.get(), blobs, n, out_cells, status), "kzg_compute_cells_batch");
+  }
+
+  // cells, out_cells: n * 128 * 2048 bytes (they must not overlap); present: n * 16 bytes, bit c & 7 of byte c >> 3 = cell c
+  void recover_cells_batch(const uint8_t* cells, const uint8_t* present, size_t n, uint8_t* out_cells, int32_t* status) const {
+    check(kzg_recover_cells_batch(ctx_.get(), cells, present, n, out_cells, status), "kzg_recover_cells_batch");
   }
 
   const kzg_ctx* raw() const { return ctx_.get(); }

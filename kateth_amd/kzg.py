@@ -7,6 +7,7 @@ Method names, argument meaning and error behaviour follow the reference:
     Setup.blob_proof(blob, commitment48)         src/kzg/setup.rs:177-183
     Setup.blob_sidecar(blob)                     :167-171 then :177-183 on the same blob, + EIP-4844 kzg_to_versioned_hash
     Setup.compute_cells(blob)                    EIP-7594 compute_cells (specs/fulu/polynomial-commitments-sampling.md)
+    Setup.recover_cells(cell_indices, cells)     EIP-7594 recover_cells_and_kzg_proofs, its cells half (same document)
     Setup.proof(blob, z32)                       src/kzg/setup.rs:185-194
     Setup.verify_proof(proof, commitment, z, y)  src/kzg/setup.rs:96-113
     Setup.verify_blob_proof(blob, c, p)          src/kzg/setup.rs:208-221
@@ -73,6 +74,14 @@ class LoadSetupError(Exception):
     pass
 
 
+class CellsError(Exception):
+    """rejections of `recover_cells` (EIP-7594); the reference has no counterpart."""
+
+    def __init__(self, kind: str):
+        super().__init__("cells::Error::" + kind)
+        self.kind = kind
+
+
 class EngineError(RuntimeError):
     """negative return from the C ABI: HIP / argument / device failure."""
 
@@ -85,6 +94,8 @@ _STATUS = {
     5: lambda: ECGroupError("NotInGroup"),
     6: lambda: FiniteFieldError("InvalidEncoding"),
     7: lambda: FiniteFieldError("NotInFiniteField"),
+    8: lambda: CellsError("NotEnoughCells"),
+    9: lambda: CellsError("Inconsistent"),
 }
 
 
@@ -158,6 +169,11 @@ _SIGNATURES = {
     ),
     "kzg_compute_cells_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
     "kzg_compute_cells_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kzg_recover_cells_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
+    "kzg_recover_cells_batch_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "kzg_compute_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
     "kzg_verify_blob_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
     "kzg_verify_blob_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
@@ -567,6 +583,21 @@ class Setup:
         self._check(rc, "kzg_compute_cells_batch")
         return out.raw, list(status)
 
+    def recover_cells_batch(self, cells: bytes, present: bytes, n: Optional[int] = None):
+        """n cell sets (128 * 2048 bytes each, laid out like `compute_cells_batch`'s output) and n 16-byte masks (cell c present iff bit
+        c & 7 of byte c >> 3) -> (n * 128 * 2048 bytes of cells, [status]).  Absent cells may hold anything.  Status 8: fewer than 64
+        cells present; 2: a present element >= r; 9: the present cells do not lie on one polynomial of degree < 4096 (a check the spec
+        does not make).  A rejected item gets zero bytes."""
+        cells, present = _buf(cells), _buf(present)
+        n = len(present) // 16 if n is None else n
+        if len(cells) != n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL or len(present) != n * 16:
+            raise ValueError("recover_cells_batch: n * 262144 bytes of cells and n * 16 bytes of mask")
+        out = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * n)
+        status = (ctypes.c_int32 * n)()
+        rc = self._lib.kzg_recover_cells_batch(self._h, cells, present, n, ctypes.cast(out, ctypes.c_void_p), status)
+        self._check(rc, "kzg_recover_cells_batch")
+        return out.raw, list(status)
+
     def compute_proof_batch(self, blobs: bytes, zs: bytes):
         blobs, zs = _buf(blobs), _buf(zs)
         n = len(zs) // 32
@@ -673,6 +704,32 @@ class Setup:
         if len(blob) != BYTES_PER_BLOB:
             raise BlobError("InvalidLen")
         out, status = self.compute_cells_batch(blob, 1)
+        if status[0]:
+            raise error_from_status(status[0])
+        return [out[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
+
+    def recover_cells(self, cell_indices: Sequence[int], cells: Sequence[bytes]) -> List[bytes]:
+        """The cells half of `recover_cells_and_kzg_proofs` (EIP-7594): all 128 cells from at least 64 of them.  As the spec asserts:
+        one cell per index, 64..128 of them, every index < 128, indices strictly ascending, every cell 2,048 bytes (ValueError).
+        Raises BlobError InvalidFieldElement for an element >= r and, beyond the spec, CellsError Inconsistent when the cells do not lie
+        on one polynomial of degree < 4096."""
+        cell_indices = [int(c) for c in cell_indices]
+        cells = [_buf(c) for c in cells]
+        if len(cell_indices) != len(cells):
+            raise ValueError("recover_cells: %d indices for %d cells" % (len(cell_indices), len(cells)))
+        if not CELLS_PER_EXT_BLOB // 2 <= len(cell_indices) <= CELLS_PER_EXT_BLOB:
+            raise ValueError("recover_cells: %d cells, need 64..128" % len(cell_indices))
+        if any(not 0 <= c < CELLS_PER_EXT_BLOB for c in cell_indices):
+            raise ValueError("recover_cells: cell index out of range")
+        if any(a >= b for a, b in zip(cell_indices, cell_indices[1:])):
+            raise ValueError("recover_cells: cell indices must be strictly ascending")
+        if any(len(c) != BYTES_PER_CELL for c in cells):
+            raise ValueError("recover_cells: a cell is %d bytes" % BYTES_PER_CELL)
+        flat, mask = bytearray(CELLS_PER_EXT_BLOB * BYTES_PER_CELL), bytearray(16)
+        for c, cell in zip(cell_indices, cells):
+            flat[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] = cell
+            mask[c >> 3] |= 1 << (c & 7)
+        out, status = self.recover_cells_batch(bytes(flat), bytes(mask), 1)
         if status[0]:
             raise error_from_status(status[0])
         return [out[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
@@ -930,6 +987,12 @@ class Setup:
         """n blobs resident on the device -> n * 128 * 2048 bytes of cells and n int32 statuses; enqueues on `stream` and returns"""
         rc = self._lib.kzg_compute_cells_batch_dev(self._h, d_blobs, n, d_out_cells, d_status, stream)
         self._check(rc, "kzg_compute_cells_batch_dev")
+
+    def recover_cells_batch_dev(self, d_cells: int, d_present: int, n: int, d_out_cells: int, d_status: int, stream: int = 0):
+        """n cell sets and n 16-byte masks resident on the device -> n * 128 * 2048 bytes of cells and n int32 statuses; enqueues on
+        `stream` and returns.  `d_out_cells` must not overlap `d_cells`."""
+        rc = self._lib.kzg_recover_cells_batch_dev(self._h, d_cells, d_present, n, d_out_cells, d_status, stream)
+        self._check(rc, "kzg_recover_cells_batch_dev")
 
     def verify_blob_proof_batch_dev(self, d_blobs: int, d_commitments: int, d_proofs: int, n: int, stream: int = 0) -> bool:
         ok = ctypes.c_int32(0)
