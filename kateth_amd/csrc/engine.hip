@@ -229,7 +229,8 @@ int32_t ws_end(const kzg_ctx* ctx, hipStream_t st) {
   return 0;
 }
 
-// ---- host-buffer staging: the pools of the four pipelines and their slot protocol (StageRing, engine_internal.hpp); caller holds stage_lock ----
+// ---- host-buffer staging: the pools of the host-buffer pipelines, their slot protocol (StageRing) and the producer calls' driver (HostCall), both
+// described in engine_internal.hpp; caller holds stage_lock ----
 int32_t stage_init(const kzg_ctx* ctx) {
   if (ctx->stage_ready) return 0;
   bool ok = hipStreamCreateWithFlags(&ctx->verify_stream, hipStreamNonBlocking) == hipSuccess &&
@@ -323,6 +324,31 @@ hipEvent_t StageRing::done_event(uint64_t k) const { return ctx->stage_done[k % 
 int32_t StageRing::consumed(uint64_t k, hipStream_t comp) {
   HIP_TRY(hipEventRecord(done_event(k), comp));
   return 0;
+}
+
+int32_t HostCall::open(std::vector<uint64_t> passes_plan, size_t item_slot_bytes, bool overlap) {
+  plan = std::move(passes_plan);
+  for (uint64_t m : plan) max_pass = m > max_pass ? m : max_pass;
+  int32_t rc = too_many ? fail(KZG_FAIL_ARGUMENT, "host call: too many arrays") : 0;
+  if (rc == 0 && hipSetDevice(ctx->device) != hipSuccess) rc = fail(KZG_FAIL_HIP, "hipSetDevice failed");
+  if (rc) return close(rc);
+  stage_guard = std::unique_lock<std::mutex>(ctx->stage_lock);
+  rc = ring.open(ctx, plan.size() > 1 ? 2 : 1, (size_t)max_pass * item_slot_bytes, io.off, overlap);
+  if (rc) return close(rc);
+  opened = true;
+  st = ctx->stage_streams[0];
+  for (int a = 0; a < count && rc == 0; a++)
+    if (arrays[a].kind == UP && hipMemcpyAsync(dev(a), arrays[a].host, arrays[a].bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+      rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
+  return rc ? close(rc) : 0;
+}
+int32_t HostCall::close(int32_t rc) {
+  for (int a = 0; a < count && rc == 0; a++)
+    if (arrays[a].kind == DOWN && hipMemcpyAsync(arrays[a].host, dev(a), arrays[a].bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+      rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
+  if (rc == 0 && hipStreamSynchronize(st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
+  if (rc) (void)hipDeviceSynchronize();
+  return rc;
 }
 
 static void tables_free(CombTables& t);
@@ -1224,25 +1250,20 @@ static std::vector<uint64_t> commit_host_plan(uint64_t n) {
 }
 
 int32_t commit_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out48, uint8_t* out_affine96, int32_t* status) {
-  if (!ctx || (n && (!blobs || (!out48 && !out_affine96) || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
   if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(ctx->device));
-  const std::vector<uint64_t> plan = commit_host_plan(n);
-  uint64_t max_chunk = 0;
-  for (uint64_t m : plan) max_chunk = m > max_chunk ? m : max_chunk;
   // Pooled resources: the staging arena, the result buffers, the streams and the events belong to the context
   // (stage_lock), so a steady-state call allocates nothing.
-  std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
+  HostCall hc(ctx);
+  const int a_res = hc.download(out48 ? out48 : out_affine96, (size_t)n * (out48 ? 48 : 96)), a_st = hc.download(status, n * sizeof(int32_t));
   // A call of ONE chunk (single blobs -- the drop-in's common case -- up to a few thousand) rides on one stream, copy included.
+  int32_t rc = hc.open(commit_host_plan(n), KZG_BYTES_PER_BLOB);
+  if (rc) return rc;
+  const std::vector<uint64_t>& plan = hc.plan;
+  const uint64_t max_chunk = hc.max_pass;
   const bool piped = plan.size() > 1;
   const uint64_t nslots = piped ? 2 : 1;
-  Carve io;
-  const size_t o_res = io.take((size_t)n * (out48 ? 48 : 96)), o_st = io.take((size_t)n * sizeof(int32_t));
-  StageRing ring;
-  int32_t rc = ring.open(ctx, nslots, (size_t)max_chunk * KZG_BYTES_PER_BLOB, io.off, piped);
-  if (rc) return rc;
-  uint8_t* d_res = ctx->hostio + o_res;
-  int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
+  uint8_t* d_res = hc.dev(a_res);
+  int32_t* d_status = hc.dev<int32_t>(a_st);
   hipStream_t comp[2] = {ctx->stage_streams[0], ctx->stage_streams[1]};
   std::lock_guard<std::mutex> guard(ctx->lock);  // the workspace: per slot the lane sums, the sums and the bit-plane masks of a chunk
   WsCall ws(ctx, comp[0]);
@@ -1252,59 +1273,49 @@ int32_t commit_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_
     const uint64_t units = msm_units(m, sp, msm_lanes_per_blob(ctx, m, sp));
     max_units = units > max_units ? units : max_units;
   }
-  do {
-    Carve per_slot;
-    const size_t o_part = per_slot.take((size_t)max_units * 65 * sizeof(g1_xyzz)), o_sums = per_slot.take((size_t)max_chunk * sizeof(g1_xyzz)),
-                 o_masks = per_slot.take(msm_scratch_bytes(ctx, max_chunk));
-    rc = ws.begin();
-    if (rc == 0) rc = ws_reserve(ctx, nslots * per_slot.off, comp[0]);
-    if (rc == 0 && piped) rc = ws_wait(ctx, comp[1]);
-    if (rc) break;
-    if (hipMemsetAsync(d_status, 0, n * sizeof(int32_t), comp[0]) != hipSuccess) {
-      rc = fail(KZG_FAIL_HIP, "memset failed");
-      break;
-    }
-    if (piped) rc = stream_after(comp[1], comp[0], ctx->stage_join[0]);
-    uint64_t base = 0;
-    for (size_t k = 0; k < plan.size() && rc == 0; base += plan[k], k++) {
-      const int slot = (int)(k & 1);  // staging slot = workspace slot = compute stream
-      const uint64_t m = plan[k];
-      const uint32_t splits = choose_splits(ctx, m);
-      const uint32_t lpb = msm_lanes_per_blob(ctx, m, splits);
-      uint8_t* wslot = ws_ptr(ctx) + (size_t)slot * per_slot.off;
-      g1_xyzz* partials = reinterpret_cast<g1_xyzz*>(wslot + o_part);
-      g1_xyzz* sums = reinterpret_cast<g1_xyzz*>(wslot + o_sums);
-      uint8_t* d_chunk = nullptr;
-      rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, comp[slot], &d_chunk);
-      // msm_launch records done_event(k) behind the bit-plane transposition
-      if (rc == 0) rc = msm_launch(ctx, true, d_chunk, m, d_status + base, partials, splits, lpb, wslot + o_masks, comp[slot], ring.done_event(k));
-      if (rc == 0)
-        rc = msm_finish(ctx, m, out48 ? d_res + base * 48 : nullptr, out_affine96 ? d_res + base * 96 : nullptr, d_status + base, partials, sums, splits, lpb,
-                        comp[slot]);
-    }
-    if (rc == 0 && piped) rc = stream_after(comp[0], comp[1], ctx->stage_join[1]);
-    if (rc == 0) rc = ws.end();
-    if (rc) break;
-    if (hipMemcpyAsync(out48 ? out48 : out_affine96, d_res, (size_t)n * (out48 ? 48 : 96), hipMemcpyDeviceToHost, comp[0]) != hipSuccess ||
-        hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, comp[0]) != hipSuccess ||
-        hipStreamSynchronize(comp[0]) != hipSuccess)
-      rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
-  } while (0);
-  if (rc) (void)hipDeviceSynchronize();
-  return rc;
+  Carve per_slot;
+  const size_t o_part = per_slot.take((size_t)max_units * 65 * sizeof(g1_xyzz)), o_sums = per_slot.take((size_t)max_chunk * sizeof(g1_xyzz)),
+               o_masks = per_slot.take(msm_scratch_bytes(ctx, max_chunk));
+  rc = ws.begin();
+  if (rc == 0) rc = ws_reserve(ctx, nslots * per_slot.off, comp[0]);
+  if (rc == 0 && piped) rc = ws_wait(ctx, comp[1]);
+  if (rc == 0 && hipMemsetAsync(d_status, 0, n * sizeof(int32_t), comp[0]) != hipSuccess) rc = fail(KZG_FAIL_HIP, "memset failed");
+  if (rc == 0 && piped) rc = stream_after(comp[1], comp[0], ctx->stage_join[0]);
+  uint64_t base = 0;
+  for (size_t k = 0; k < plan.size() && rc == 0; base += plan[k], k++) {
+    const int slot = (int)(k & 1);  // staging slot = workspace slot = compute stream
+    const uint64_t m = plan[k];
+    const uint32_t splits = choose_splits(ctx, m);
+    const uint32_t lpb = msm_lanes_per_blob(ctx, m, splits);
+    uint8_t* wslot = ws_ptr(ctx) + (size_t)slot * per_slot.off;
+    g1_xyzz* partials = reinterpret_cast<g1_xyzz*>(wslot + o_part);
+    g1_xyzz* sums = reinterpret_cast<g1_xyzz*>(wslot + o_sums);
+    uint8_t* d_chunk = nullptr;
+    rc = hc.ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, comp[slot], &d_chunk);
+    // msm_launch records done_event(k) behind the bit-plane transposition
+    if (rc == 0) rc = msm_launch(ctx, true, d_chunk, m, d_status + base, partials, splits, lpb, wslot + o_masks, comp[slot], hc.ring.done_event(k));
+    if (rc == 0)
+      rc = msm_finish(ctx, m, out48 ? d_res + base * 48 : nullptr, out_affine96 ? d_res + base * 96 : nullptr, d_status + base, partials, sums, splits, lpb,
+                      comp[slot]);
+  }
+  if (rc == 0 && piped) rc = stream_after(comp[0], comp[1], ctx->stage_join[1]);
+  if (rc == 0) rc = ws.end();
+  return hc.close(rc);
 }
 
 extern "C" int32_t kzg_blob_to_commitment_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out48, int32_t* status) try {
-  if (n && !out48) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (is_group(ctx)) return multi_commit(ctx, blobs, n, out48, nullptr, status);
-  return commit_host(ctx, blobs, n, out48, nullptr, status);
+  if (!ctx || (n && (!blobs || !out48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
+    return commit_host(m, blobs + first * (size_t)KZG_BYTES_PER_BLOB, count, out48 + first * 48, nullptr, status + first);
+  });
 } catch (...) {
   return abi_exception();
 }
 extern "C" int32_t kzg_blob_to_commitment_batch_affine(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_affine96, int32_t* status) try {
-  if (n && !out_affine96) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (is_group(ctx)) return multi_commit(ctx, blobs, n, nullptr, out_affine96, status);
-  return commit_host(ctx, blobs, n, nullptr, out_affine96, status);
+  if (!ctx || (n && (!blobs || !out_affine96 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
+    return commit_host(m, blobs + first * (size_t)KZG_BYTES_PER_BLOB, count, nullptr, out_affine96 + first * 96, status + first);
+  });
 } catch (...) {
   return abi_exception();
 }

@@ -1,5 +1,6 @@
-// Shared by the engine translation units (engine.hip, engine_proof.hip, engine_verify.hip).  Besides the kernels below, engine.hip owns the
-// context's pools -- the workspace slots (ws_*) and the host-buffer staging (stage_*, StageRing) -- and tears them down in kzg_ctx_destroy.
+// Shared by the engine translation units (engine.hip, engine_blob.hip, engine_proof.hip, engine_verify.hip, engine_multi.hip).  Besides the
+// kernels below, engine.hip owns the context's pools -- the workspace slots (ws_*) and the host-buffer staging (stage_*, StageRing, and the
+// HostCall driver that every host-buffer producer call runs through) -- and tears them down in kzg_ctx_destroy.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -283,9 +284,10 @@ struct kzg_ctx {
 };
 void session_pool_clear(const kzg_ctx* ctx);
 
-// ---- single-device implementations behind the host-buffer entry points; the extern "C" wrappers hand GROUP contexts to
-// engine_multi.hip, which shards a batch over the members and calls these per member ----
+// ---- single-device implementations behind the host-buffer entry points.  The extern "C" producers reach them through on_members, which
+// hands a group's call to engine_multi.hip; the verification calls shard over a group in engine_multi.hip (multi_verify_*) ----
 static inline bool is_group(const kzg_ctx* ctx) { return ctx && !ctx->peers.empty(); }
+constexpr size_t KZG_BYTES_PER_CELL_SET = (size_t)KZG_CELLS_PER_EXT_BLOB * KZG_BYTES_PER_CELL;  // the 128 cells of one extended blob
 int32_t ctx_create_single(const uint8_t* g1_lagrange, const uint8_t* g2_monomial, const kzg_config* cfg, int device, kzg_ctx** out);  // engine.hip
 int32_t commit_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out48, uint8_t* out_affine96, int32_t* status);    // engine.hip
 int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side, size_t side_bytes, bool side_is_commitment, uint64_t n, uint8_t* out48,
@@ -299,16 +301,17 @@ int32_t g1_decompress_single(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n
 int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
 // engine_multi.hip
 int32_t group_create(const uint8_t* g1_lagrange, const uint8_t* g2_monomial, const kzg_config* cfg, kzg_ctx** out);
-int32_t multi_commit(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out48, uint8_t* out_affine96, int32_t* status);
-int32_t multi_proof(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side, size_t side_bytes, bool side_is_commitment, uint64_t n, uint8_t* out48,
-                    uint8_t* out_affine96, uint8_t* out_y32, int32_t* status);
-int32_t multi_sidecar(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48, uint8_t* out_versioned_hashes32,
-                      int32_t* status);
-int32_t multi_cells(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status);
-int32_t multi_recover(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status);
 int32_t multi_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok);
-int32_t multi_g1_decompress(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
-int32_t multi_evaluate_blobs(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
+// The member dispatch of the producer calls: fn(member, first, count) once per share of the n items, each share on its member's own host
+// thread, the first failing share's code and text returned (run_on_helpers); a call of fewer items than members starts at a rotating
+// member.  `fn` advances the caller's pointers to item `first` and calls the single-device implementation on `member`.  A single-device
+// context is its own only member: fn(ctx, 0, n) on the calling thread, with no shares, no helper thread and no allocation.
+using MemberCall = std::function<int32_t(const kzg_ctx* member, uint64_t first, uint64_t count)>;
+int32_t on_group_members(const kzg_ctx* ctx, uint64_t n, const MemberCall& fn);
+template <class Fn>
+static inline int32_t on_members(const kzg_ctx* ctx, uint64_t n, Fn&& fn) {
+  return is_group(ctx) ? on_group_members(ctx, n, std::ref(fn)) : fn(ctx, (uint64_t)0, n);
+}
 // The inputs of one batch verification call (engine_verify.hip: front_enqueue / front_status switch on `kind`), in the caller's host
 // buffers (`on_host`) or device-resident.  Its error record is `kinds()` x {local index of the first rejected item or -1, code}, in the
 // reference's parse order:
@@ -352,14 +355,20 @@ struct GroupDevShare {
   hipStream_t st;
 };
 int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& shares, uint64_t n_total, int32_t* ok);  // engine_verify.hip
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+struct Carve {  // hands out 256-byte aligned offsets into a pooled buffer; `off` = the bytes asked of the pool so far
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
+};
 // ---- host-buffer staging (engine.hip), all of it with ctx->stage_lock held ----
 int32_t stage_init(const kzg_ctx* ctx);                                          // streams and events, on first use
 int32_t stage_reserve(const kzg_ctx* ctx, size_t arena_bytes, size_t io_bytes);  // the arena and the host-i/o pool only grow
-void stage_drain(const kzg_ctx* ctx);  // failure path: the host waits for the copy stream and every stage stream
+void stage_drain(const kzg_ctx* ctx);  // verify_phase1_host's failure path: the host waits for the copy stream and every stage stream
 void stage_destroy(const kzg_ctx* ctx);
 // record `ev` on `signaller`, then `waiter` waits for it
 int32_t stream_after(hipStream_t waiter, hipStream_t signaller, hipEvent_t ev);
-// The slot protocol of the four host-buffer pipelines (commit_host, proof_host, verify_phase1_host, evaluate_blobs_single), stated once.
+// The slot protocol of the host-buffer pipelines, stated once.  Its users are HostCall (below: the seven producer calls) and
+// verify_phase1_host (engine_verify.hip).
 // The caller's blobs cross PCIe in chunks through `slots` equal slots of the context's staging arena; chunk k lives in slot k % slots:
 //   feed(k)      the copy stream waits for the slot's previous consumer (done_event(k - slots), when k >= slots), copies the chunk in and
 //                records the slot's `copied` event, for which `comp` -- the stream the caller enqueues the chunk's work on -- waits;
@@ -379,6 +388,85 @@ struct StageRing {
   hipEvent_t done_event(uint64_t k) const;
   int32_t consumed(uint64_t k, hipStream_t comp);
 };
+
+// The driver of a host-buffer producer call on one device (commit_host; proof_host, sidecar_host, cells_host, recover_host; evaluate_blobs_single,
+// g1_decompress_single), which owns the call's StageRing:
+//   upload / download / scratch   register the call's small per-item arrays in the host-i/o pool by host pointer and byte count, BEFORE the
+//                                 pools are sized; the statuses are one more downloaded array.  A null host pointer (an output the caller does
+//                                 not want) registers nothing: its handle resolves to a null device pointer and nothing is copied.
+//   open(plan, item_slot_bytes)   hipSetDevice, stage_lock (held until the driver goes out of scope), the pools -- slots of the largest pass x
+//                                 item_slot_bytes, two when the plan has more than one pass, which is also when copies overlap unless `overlap` says
+//                                 otherwise -- and the uploads, enqueued on `st`.  An empty plan opens no arena.
+//   dev(handle)                   the array's device pointer, resolved at the time of the call and null before open(): opening may move the pools.
+//   passes(src, item_bytes, body) per pass k of m items from item `base` on: feed(k), body(k, base, m, d_chunk), consumed(k); stops at the first
+//                                 non-zero code.  The body enqueues on `st`; the slot is released behind all of it.
+//   close(rc)                     the one exit of the call, `rc` = the code of the steps since open(): the downloads and the synchronisation of `st`,
+//                                 or, after any failure (its own included), a wait for the whole device -- copies into and out of the caller's buffers
+//                                 may be in flight -- and the first code, its text untouched.  A failing open() has taken this exit already.
+// Workspaces and ctx->lock are the caller's business, between open() and close().  commit_host runs its two-stream loop on `ring` itself.
+struct HostCall {
+  const kzg_ctx* ctx;
+  StageRing ring;
+  hipStream_t st = nullptr;    // stage_streams[0], from open() on: an idle non-blocking stream (the null stream would serialise against every
+                               // blocking stream of the process)
+  std::vector<uint64_t> plan;  // items per pass
+  uint64_t max_pass = 0;
+  explicit HostCall(const kzg_ctx* c) : ctx(c) {}
+  int upload(const void* host, size_t bytes) { return add(UP, const_cast<void*>(host), bytes); }
+  int download(void* host, size_t bytes) { return add(DOWN, host, bytes); }
+  int scratch(size_t bytes) { return add(SCRATCH, nullptr, bytes); }
+  template <class T = uint8_t>
+  T* dev(int handle) const {
+    return opened && handle >= 0 ? reinterpret_cast<T*>(ctx->hostio + arrays[handle].off) : nullptr;
+  }
+  int32_t open(std::vector<uint64_t> passes_plan, size_t item_slot_bytes, bool overlap);
+  int32_t open(std::vector<uint64_t> passes_plan, size_t item_slot_bytes) {
+    const bool piped = passes_plan.size() > 1;
+    return open(std::move(passes_plan), item_slot_bytes, piped);
+  }
+  template <class Body>
+  int32_t passes(const uint8_t* src, size_t item_bytes, Body&& body) {
+    int32_t rc = 0;
+    uint64_t base = 0;
+    for (size_t k = 0; k < plan.size() && rc == 0; base += plan[k], k++) {
+      uint8_t* d_chunk = nullptr;
+      rc = ring.feed(k, src + base * item_bytes, plan[k] * item_bytes, st, &d_chunk);
+      if (rc == 0) rc = body(k, base, plan[k], d_chunk);
+      if (rc == 0) rc = ring.consumed(k, st);
+    }
+    return rc;
+  }
+  int32_t close(int32_t rc);
+
+ private:
+  enum Kind { UP, DOWN, SCRATCH };
+  struct Array {
+    Kind kind;
+    void* host;
+    size_t bytes, off;
+  };
+  static constexpr int MAX_ARRAYS = 8;
+  Array arrays[MAX_ARRAYS];
+  int count = 0;
+  bool opened = false, too_many = false;  // more than MAX_ARRAYS registrations: open() refuses
+  Carve io;
+  std::unique_lock<std::mutex> stage_guard;
+  int add(Kind kind, void* host, size_t bytes) {
+    if (kind != SCRATCH && !host) return -1;
+    if (count == MAX_ARRAYS) {
+      too_many = true;
+      return -1;
+    }
+    arrays[count] = Array{kind, host, bytes, io.take(bytes)};
+    return count++;
+  }
+};
+// passes of `pass` items and a shorter last one
+static inline std::vector<uint64_t> even_plan(uint64_t n, uint64_t pass) {
+  std::vector<uint64_t> plan;
+  for (uint64_t rest = n; rest; rest -= plan.back()) plan.push_back(rest < pass ? rest : pass);
+  return plan;
+}
 
 // workspace of the call being enqueued (caller holds ctx->lock from ws_begin to ws_end)
 int32_t ws_begin(const kzg_ctx* ctx, hipStream_t st);    // takes the next slot; `st` waits for the slot's previous user
@@ -421,11 +509,6 @@ struct ProfScope {
   }
 };
 uint32_t choose_splits(const kzg_ctx* ctx, uint64_t n);
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-struct Carve {  // hands out 256-byte aligned offsets into a pooled buffer; `off` = the bytes asked of the pool so far
-  size_t off = 0;
-  size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
-};
 static inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 // Every translation unit carries its kernels in a code object of its own, which the HIP runtime loads at the unit's FIRST launch --

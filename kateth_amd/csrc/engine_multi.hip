@@ -4,7 +4,8 @@
 // holding the full tables (the setup is 4096 + 65 points: replicated, never sharded).  Blobs are independent in all three
 // operations (the reference walks them one by one: src/kzg/setup.rs:235-242), so the host-buffer entry points cut a batch
 // into contiguous ranges, one per member, run the single-device implementation of each range on a host thread of its own and
-// let it write straight into the caller's buffers: no collective, no gather.  The only cross-member step is the end of batch
+// let it write straight into the caller's buffers: no collective, no gather (on_members, engine_internal.hpp: the producer's
+// own lambda advances its pointers to the range).  The only cross-member step is the end of batch
 // verification (src/kzg/setup.rs:152-160): every member returns its transcript root and first-error records, the roots of
 // ALL members seed the batch challenge, every member returns its two partial sums with GLOBAL powers r^i, and one member sums
 // the partials and runs the single pairing check -- the same phase1 / roots / phase2 / finish protocol that
@@ -61,71 +62,9 @@ int32_t group_create(const uint8_t* g1_lagrange, const uint8_t* g2_monomial, con
   return 0;
 }
 
-int32_t multi_commit(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out48, uint8_t* out_affine96, int32_t* status) {
-  if (!ctx || (n && (!blobs || (!out48 && !out_affine96) || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+int32_t on_group_members(const kzg_ctx* ctx, uint64_t n, const MemberCall& fn) {
   const std::vector<Share> shares = shares_of(ctx, n);
-  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
-    const Share& sh = shares[j];
-    return commit_host(member_of(ctx, sh.member), blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, sh.count, out48 ? out48 + sh.first * 48 : nullptr,
-                       out_affine96 ? out_affine96 + sh.first * 96 : nullptr, status + sh.first);
-  });
-}
-
-int32_t multi_proof(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side, size_t side_bytes, bool side_is_commitment, uint64_t n, uint8_t* out48,
-                    uint8_t* out_affine96, uint8_t* out_y32, int32_t* status) {
-  const std::vector<Share> shares = shares_of(ctx, n);
-  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
-    const Share& sh = shares[j];
-    return proof_host(member_of(ctx, sh.member), blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, side + sh.first * side_bytes, side_bytes, side_is_commitment,
-                      sh.count, out48 ? out48 + sh.first * 48 : nullptr, out_affine96 ? out_affine96 + sh.first * 96 : nullptr,
-                      out_y32 ? out_y32 + sh.first * 32 : nullptr, status + sh.first);
-  });
-}
-
-int32_t multi_sidecar(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48, uint8_t* out_versioned_hashes32,
-                      int32_t* status) {
-  const std::vector<Share> shares = shares_of(ctx, n);
-  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
-    const Share& sh = shares[j];
-    return sidecar_host(member_of(ctx, sh.member), blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, sh.count, out_commitments48 + sh.first * 48,
-                        out_proofs48 + sh.first * 48, out_versioned_hashes32 ? out_versioned_hashes32 + sh.first * 32 : nullptr, status + sh.first);
-  });
-}
-
-int32_t multi_cells(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status) {
-  const std::vector<Share> shares = shares_of(ctx, n);
-  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
-    const Share& sh = shares[j];
-    return cells_host(member_of(ctx, sh.member), blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, sh.count,
-                      out_cells + sh.first * (size_t)KZG_CELLS_PER_EXT_BLOB * KZG_BYTES_PER_CELL, status + sh.first);
-  });
-}
-
-int32_t multi_recover(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status) {
-  const std::vector<Share> shares = shares_of(ctx, n);
-  constexpr size_t set_bytes = (size_t)KZG_CELLS_PER_EXT_BLOB * KZG_BYTES_PER_CELL;
-  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
-    const Share& sh = shares[j];
-    return recover_host(member_of(ctx, sh.member), cells + sh.first * set_bytes, present + sh.first * 16, sh.count, out_cells + sh.first * set_bytes,
-                        status + sh.first);
-  });
-}
-
-int32_t multi_g1_decompress(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status) {
-  const std::vector<Share> shares = shares_of(ctx, n);
-  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
-    const Share& sh = shares[j];
-    return g1_decompress_single(member_of(ctx, sh.member), in48 + sh.first * 48, sh.count, out_affine96 + sh.first * 96, status + sh.first);
-  });
-}
-
-int32_t multi_evaluate_blobs(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status) {
-  const std::vector<Share> shares = shares_of(ctx, n);
-  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
-    const Share& sh = shares[j];
-    return evaluate_blobs_single(member_of(ctx, sh.member), blobs + sh.first * (size_t)KZG_BYTES_PER_BLOB, z32 + sh.first * 32, sh.count, out_y32 + sh.first * 32,
-                                 status + sh.first);
-  });
+  return run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t { return fn(member_of(ctx, shares[j].member), shares[j].first, shares[j].count); });
 }
 
 // Setup::verify_proof (src/kzg/setup.rs:96-113) is one item: any member serves it

@@ -187,69 +187,49 @@ static std::vector<uint64_t> proof_host_plan(uint64_t n) {
 int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side, size_t side_bytes, bool side_is_commitment, uint64_t n,
                           uint8_t* out48, uint8_t* out_affine96, uint8_t* out_y32, int32_t* status) {
   if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
-  const std::vector<uint64_t> plan = proof_host_plan(n);
-  uint64_t max_pass = 0;
-  for (uint64_t m : plan) max_pass = m > max_pass ? m : max_pass;
-  const bool piped = plan.size() > 1;  // one pass: nothing to overlap, the copy rides on the compute stream
-  Carve io;
-  const size_t o_side = io.take(n * side_bytes), o_out = io.take(n * 48), o_aff = io.take(n * 96), o_y = io.take(n * 32), o_st = io.take(n * sizeof(int32_t));
-  StageRing ring;
-  int32_t rc = ring.open(ctx, piped ? 2 : 1, (size_t)max_pass * KZG_BYTES_PER_BLOB, io.off, piped);
+  HostCall hc(ctx);
+  const int a_side = hc.upload(side, n * side_bytes), a_out = hc.download(out48, n * 48), a_aff = hc.download(out_affine96, n * 96),
+            a_y = hc.download(out_y32, n * 32), a_st = hc.download(status, n * sizeof(int32_t));
+  int32_t rc = hc.open(proof_host_plan(n), KZG_BYTES_PER_BLOB);  // one pass: nothing to overlap, the copy rides on the compute stream
   if (rc) return rc;
-  uint8_t* d_side = ctx->hostio + o_side;
-  uint8_t* d_out = out48 ? ctx->hostio + o_out : nullptr;
-  uint8_t* d_aff = out_affine96 ? ctx->hostio + o_aff : nullptr;
-  uint8_t* d_y = ctx->hostio + o_y;
-  int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
-  hipStream_t st = ctx->stage_streams[0];  // an idle non-blocking stream (the null stream would serialise against every blocking stream of the process)
+  uint8_t *d_side = hc.dev(a_side), *d_out = hc.dev(a_out), *d_aff = hc.dev(a_aff), *d_y = hc.dev(a_y);
+  int32_t* d_status = hc.dev<int32_t>(a_st);
   std::lock_guard<std::mutex> guard(ctx->lock);
-  WsCall ws(ctx, st);
-  do {
-    if (hipMemcpyAsync(d_side, side, n * side_bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
-      rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
-      break;
-    }
-    // one workspace slot for all passes (they follow each other on `st`), sized for the largest pass BEFORE anything is in
-    // flight: growing it between passes would free memory under the pipeline
-    rc = ws.begin();
-    if (rc == 0) rc = ws_reserve(ctx, proof_layout(ctx, max_pass).total, st);
-    uint64_t base = 0;
-    for (size_t k = 0; k < plan.size() && rc == 0; base += plan[k], k++) {
-      const uint64_t m = plan[k];
-      uint8_t* d_blobs = nullptr;
-      rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, st, &d_blobs);
-      if (rc == 0)
-        rc = proof_dev_locked(ctx, d_blobs, side_is_commitment ? d_side + base * side_bytes : nullptr, side_is_commitment ? nullptr : d_side + base * side_bytes,
-                              m, d_out ? d_out + base * 48 : nullptr, d_aff ? d_aff + base * 96 : nullptr, out_y32 ? d_y + base * 32 : nullptr,
-                              d_status + base, st);
-      if (rc == 0) rc = ring.consumed(k, st);
-    }
-    if (rc) break;
-    rc = ws.end();
-    if (rc) break;
-    if ((out48 && hipMemcpyAsync(out48, d_out, n * 48, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        (out_affine96 && hipMemcpyAsync(out_affine96, d_aff, n * 96, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        (out_y32 && hipMemcpyAsync(out_y32, d_y, n * 32, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
-  } while (0);
-  if (rc) (void)hipDeviceSynchronize();
-  return rc;
+  WsCall ws(ctx, hc.st);
+  // one workspace slot for all passes (they follow each other on the call's stream), sized for the largest pass BEFORE anything is in
+  // flight: growing it between passes would free memory under the pipeline
+  rc = ws.begin();
+  if (rc == 0) rc = ws_reserve(ctx, proof_layout(ctx, hc.max_pass).total, hc.st);
+  if (rc == 0)
+    rc = hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
+      return proof_dev_locked(ctx, d_blobs, side_is_commitment ? d_side + base * side_bytes : nullptr, side_is_commitment ? nullptr : d_side + base * side_bytes, m,
+                              d_out ? d_out + base * 48 : nullptr, d_aff ? d_aff + base * 96 : nullptr, d_y ? d_y + base * 32 : nullptr, d_status + base, hc.st);
+    });
+  if (rc == 0) rc = ws.end();
+  return hc.close(rc);
 }
 
+// the four host-buffer proof calls: `side` is the commitments (48 bytes per item) or the evaluation points (32)
+static int32_t proof_on_members(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side, bool side_is_commitment, uint64_t n, uint8_t* out48,
+                                uint8_t* out_affine96, uint8_t* out_y32, int32_t* status) {
+  const size_t side_bytes = side_is_commitment ? 48 : 32;
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
+    return proof_host(m, blobs + first * (size_t)KZG_BYTES_PER_BLOB, side + first * side_bytes, side_bytes, side_is_commitment, count,
+                      out48 ? out48 + first * 48 : nullptr, out_affine96 ? out_affine96 + first * 96 : nullptr, out_y32 ? out_y32 + first * 32 : nullptr,
+                      status + first);
+  });
+}
 extern "C" int32_t kzg_compute_blob_proof_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, uint64_t n,
                                                 uint8_t* out48, int32_t* status) try {
   if (!ctx || (n && (!blobs || !commitments48 || !out48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return (is_group(ctx) ? multi_proof : proof_host)(ctx, blobs, commitments48, 48, true, n, out48, nullptr, nullptr, status);
+  return proof_on_members(ctx, blobs, commitments48, true, n, out48, nullptr, nullptr, status);
 } catch (...) {
   return abi_exception();
 }
 extern "C" int32_t kzg_compute_blob_proof_batch_affine(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, uint64_t n,
                                                        uint8_t* out_affine96, int32_t* status) try {
   if (!ctx || (n && (!blobs || !commitments48 || !out_affine96 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return (is_group(ctx) ? multi_proof : proof_host)(ctx, blobs, commitments48, 48, true, n, nullptr, out_affine96, nullptr, status);
+  return proof_on_members(ctx, blobs, commitments48, true, n, nullptr, out_affine96, nullptr, status);
 } catch (...) {
   return abi_exception();
 }
@@ -257,14 +237,14 @@ extern "C" int32_t kzg_compute_blob_proof_batch_affine(const kzg_ctx* ctx, const
 extern "C" int32_t kzg_compute_proof_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_proof48,
                                            uint8_t* out_y32, int32_t* status) try {
   if (!ctx || (n && (!blobs || !z32 || !out_proof48 || !out_y32 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return (is_group(ctx) ? multi_proof : proof_host)(ctx, blobs, z32, 32, false, n, out_proof48, nullptr, out_y32, status);
+  return proof_on_members(ctx, blobs, z32, false, n, out_proof48, nullptr, out_y32, status);
 } catch (...) {
   return abi_exception();
 }
 extern "C" int32_t kzg_compute_proof_batch_affine(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_proof_affine96,
                                                   uint8_t* out_y32, int32_t* status) try {
   if (!ctx || (n && (!blobs || !z32 || !out_proof_affine96 || !out_y32 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return (is_group(ctx) ? multi_proof : proof_host)(ctx, blobs, z32, 32, false, n, nullptr, out_proof_affine96, out_y32, status);
+  return proof_on_members(ctx, blobs, z32, false, n, nullptr, out_proof_affine96, out_y32, status);
 } catch (...) {
   return abi_exception();
 }
@@ -337,60 +317,36 @@ extern "C" int32_t kzg_blob_sidecar_batch_dev(const kzg_ctx* ctx, const void* d_
 int32_t sidecar_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48, uint8_t* out_versioned_hashes32,
                      int32_t* status) {
   if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
-  std::vector<uint64_t> plan;
-  if (ctx->knobs.sidecar_pass)
-    for (uint64_t rest = n; rest; rest -= plan.back()) plan.push_back(rest < ctx->knobs.sidecar_pass ? rest : ctx->knobs.sidecar_pass);
-  else
-    plan = proof_host_plan(n);
-  uint64_t max_pass = 0;
-  for (uint64_t m : plan) max_pass = m > max_pass ? m : max_pass;
-  const bool piped = plan.size() > 1;
-  Carve io;
-  const size_t o_com = io.take(n * 48), o_prf = io.take(n * 48), o_vh = io.take(n * 32), o_st = io.take(n * sizeof(int32_t));
-  StageRing ring;
-  int32_t rc = ring.open(ctx, piped ? 2 : 1, (size_t)max_pass * KZG_BYTES_PER_BLOB, io.off, piped);
+  HostCall hc(ctx);
+  const int a_com = hc.download(out_commitments48, n * 48), a_prf = hc.download(out_proofs48, n * 48), a_vh = hc.download(out_versioned_hashes32, n * 32),
+            a_st = hc.download(status, n * sizeof(int32_t));
+  int32_t rc = hc.open(ctx->knobs.sidecar_pass ? even_plan(n, ctx->knobs.sidecar_pass) : proof_host_plan(n), KZG_BYTES_PER_BLOB);
   if (rc) return rc;
-  uint8_t* d_com = ctx->hostio + o_com;
-  uint8_t* d_prf = ctx->hostio + o_prf;
-  uint8_t* d_vh = out_versioned_hashes32 ? ctx->hostio + o_vh : nullptr;
-  int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
-  hipStream_t st = ctx->stage_streams[0];
+  uint8_t *d_com = hc.dev(a_com), *d_prf = hc.dev(a_prf), *d_vh = hc.dev(a_vh);
+  int32_t* d_status = hc.dev<int32_t>(a_st);
   std::lock_guard<std::mutex> guard(ctx->lock);
-  WsCall ws(ctx, st);
-  do {
-    // one workspace slot for all passes, sized BEFORE anything is in flight for the pass that asks most (a short last pass may take
-    // more splits, and so more lane sums, than a full one): growing it between passes would free memory under the pipeline
-    rc = ws.begin();
-    size_t need = 0;
-    for (uint64_t m : plan) need = std::max(need, proof_layout(ctx, m).total);
-    if (rc == 0) rc = ws_reserve(ctx, need, st);
-    uint64_t base = 0;
-    for (size_t k = 0; k < plan.size() && rc == 0; base += plan[k], k++) {
-      const uint64_t m = plan[k];
-      uint8_t* d_blobs = nullptr;
-      rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, st, &d_blobs);
-      if (rc == 0) rc = sidecar_dev_locked(ctx, d_blobs, m, d_com + base * 48, d_prf + base * 48, d_vh ? d_vh + base * 32 : nullptr, d_status + base, st);
-      if (rc == 0) rc = ring.consumed(k, st);
-    }
-    if (rc) break;
-    rc = ws.end();
-    if (rc) break;
-    if (hipMemcpyAsync(out_commitments48, d_com, n * 48, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(out_proofs48, d_prf, n * 48, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (d_vh && hipMemcpyAsync(out_versioned_hashes32, d_vh, n * 32, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
-  } while (0);
-  if (rc) (void)hipDeviceSynchronize();
-  return rc;
+  WsCall ws(ctx, hc.st);
+  // one workspace slot for all passes, sized BEFORE anything is in flight for the pass that asks most (a short last pass may take
+  // more splits, and so more lane sums, than a full one): growing it between passes would free memory under the pipeline
+  rc = ws.begin();
+  size_t need = 0;
+  for (uint64_t m : hc.plan) need = std::max(need, proof_layout(ctx, m).total);
+  if (rc == 0) rc = ws_reserve(ctx, need, hc.st);
+  if (rc == 0)
+    rc = hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
+      return sidecar_dev_locked(ctx, d_blobs, m, d_com + base * 48, d_prf + base * 48, d_vh ? d_vh + base * 32 : nullptr, d_status + base, hc.st);
+    });
+  if (rc == 0) rc = ws.end();
+  return hc.close(rc);
 }
 
 extern "C" int32_t kzg_blob_sidecar_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48,
                                           uint8_t* out_versioned_hashes32, int32_t* status) try {
   if (!ctx || (n && (!blobs || !out_commitments48 || !out_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return (is_group(ctx) ? multi_sidecar : sidecar_host)(ctx, blobs, n, out_commitments48, out_proofs48, out_versioned_hashes32, status);
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
+    return sidecar_host(m, blobs + first * (size_t)KZG_BYTES_PER_BLOB, count, out_commitments48 + first * 48, out_proofs48 + first * 48,
+                        out_versioned_hashes32 ? out_versioned_hashes32 + first * 32 : nullptr, status + first);
+  });
 } catch (...) {
   return abi_exception();
 }
@@ -420,50 +376,37 @@ extern "C" int32_t kzg_compute_cells_batch_dev(const kzg_ctx* ctx, const void* d
 // 0..63 of an accepted blob ARE the caller's blob and are copied on the host.  Passes of KATETH_AMD_CELLS_PASS blobs (default 512)
 // through the staging ring; a slot holds a pass's blobs and, behind them, its 256 KiB of cells per blob, and is free again when the
 // pass's download has been enqueued behind its kernel.
-constexpr size_t CELLS_BYTES_PER_BLOB = (size_t)KZG_CELLS_PER_EXT_BLOB * KZG_BYTES_PER_CELL;
 int32_t cells_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status) {
   if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
-  const uint64_t pass = std::min<uint64_t>(n, ctx->knobs.cells_pass ? ctx->knobs.cells_pass : 512);
-  const uint64_t passes = (n + pass - 1) / pass;
-  const bool piped = passes > 1;
-  Carve io;
-  const size_t o_st = io.take(n * sizeof(int32_t));
-  StageRing ring;
-  int32_t rc = ring.open(ctx, piped ? 2 : 1, (size_t)pass * (KZG_BYTES_PER_BLOB + CELLS_BYTES_PER_BLOB), io.off, piped);
+  HostCall hc(ctx);
+  const int a_st = hc.download(status, n * sizeof(int32_t));
+  int32_t rc = hc.open(even_plan(n, ctx->knobs.cells_pass ? ctx->knobs.cells_pass : 512), KZG_BYTES_PER_BLOB + KZG_BYTES_PER_CELL_SET);
   if (rc) return rc;
-  int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
-  hipStream_t st = ctx->stage_streams[0];
-  for (uint64_t k = 0; k < passes && rc == 0; k++) {
-    const uint64_t base = k * pass, m = std::min<uint64_t>(pass, n - base);
-    uint8_t* d_blobs = nullptr;
-    rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, st, &d_blobs);
-    uint8_t* d_cells = d_blobs + pass * (size_t)KZG_BYTES_PER_BLOB;
-    if (rc == 0) rc = cells_enqueue(ctx, d_blobs, m, d_cells, d_status + base, st);
-    if (rc == 0 && hipMemcpy2DAsync(out_cells + base * CELLS_BYTES_PER_BLOB + KZG_BYTES_PER_BLOB, CELLS_BYTES_PER_BLOB, d_cells + KZG_BYTES_PER_BLOB,
-                                    CELLS_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB, m, hipMemcpyDeviceToHost, st) != hipSuccess)
-      rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
-    if (rc == 0) rc = ring.consumed(k, st);
-  }
-  if (rc == 0 && (hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
-    rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
-  if (rc) {
-    (void)hipDeviceSynchronize();
-    return rc;
-  }
+  int32_t* d_status = hc.dev<int32_t>(a_st);
+  rc = hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
+    uint8_t* d_cells = d_blobs + hc.max_pass * (size_t)KZG_BYTES_PER_BLOB;
+    const int32_t e = cells_enqueue(ctx, d_blobs, m, d_cells, d_status + base, hc.st);
+    if (e == 0 && hipMemcpy2DAsync(out_cells + base * KZG_BYTES_PER_CELL_SET + KZG_BYTES_PER_BLOB, KZG_BYTES_PER_CELL_SET, d_cells + KZG_BYTES_PER_BLOB,
+                                    KZG_BYTES_PER_CELL_SET, KZG_BYTES_PER_BLOB, m, hipMemcpyDeviceToHost, hc.st) != hipSuccess)
+      return fail(KZG_FAIL_HIP, "device-to-host copy failed");
+    return e;
+  });
+  rc = hc.close(rc);
+  if (rc) return rc;
   for (uint64_t i = 0; i < n; i++) {
     if (status[i] == 0)
-      memcpy(out_cells + i * CELLS_BYTES_PER_BLOB, blobs + i * (size_t)KZG_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB);
+      memcpy(out_cells + i * KZG_BYTES_PER_CELL_SET, blobs + i * (size_t)KZG_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB);
     else
-      memset(out_cells + i * CELLS_BYTES_PER_BLOB, 0, KZG_BYTES_PER_BLOB);
+      memset(out_cells + i * KZG_BYTES_PER_CELL_SET, 0, KZG_BYTES_PER_BLOB);
   }
   return 0;
 }
 
 extern "C" int32_t kzg_compute_cells_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status) try {
   if (!ctx || (n && (!blobs || !out_cells || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return (is_group(ctx) ? multi_cells : cells_host)(ctx, blobs, n, out_cells, status);
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
+    return cells_host(m, blobs + first * (size_t)KZG_BYTES_PER_BLOB, count, out_cells + first * KZG_BYTES_PER_CELL_SET, status + first);
+  });
 } catch (...) {
   return abi_exception();
 }
@@ -496,42 +439,27 @@ extern "C" int32_t kzg_recover_cells_batch_dev(const kzg_ctx* ctx, const void* d
 // once, next to the statuses.
 int32_t recover_host(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status) {
   if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> stage_guard(ctx->stage_lock);
-  const uint64_t pass = std::min<uint64_t>(n, ctx->knobs.cells_pass ? ctx->knobs.cells_pass : 256);
-  const uint64_t passes = (n + pass - 1) / pass;
-  const bool piped = passes > 1;
-  Carve io;
-  const size_t o_st = io.take(n * sizeof(int32_t)), o_mask = io.take(n * 16);
-  StageRing ring;
-  int32_t rc = ring.open(ctx, piped ? 2 : 1, (size_t)pass * 2 * CELLS_BYTES_PER_BLOB, io.off, piped);
+  HostCall hc(ctx);
+  const int a_mask = hc.upload(present, n * 16), a_st = hc.download(status, n * sizeof(int32_t));
+  int32_t rc = hc.open(even_plan(n, ctx->knobs.cells_pass ? ctx->knobs.cells_pass : 256), 2 * KZG_BYTES_PER_CELL_SET);
   if (rc) return rc;
-  int32_t* d_status = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
-  uint8_t* d_present = ctx->hostio + o_mask;
-  hipStream_t st = ctx->stage_streams[0];
-  if (hipMemcpyAsync(d_present, present, n * 16, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
-  for (uint64_t k = 0; k < passes && rc == 0; k++) {
-    const uint64_t base = k * pass, m = std::min<uint64_t>(pass, n - base);
-    uint8_t* d_cells = nullptr;
-    rc = ring.feed(k, cells + base * CELLS_BYTES_PER_BLOB, m * CELLS_BYTES_PER_BLOB, st, &d_cells);
-    uint8_t* d_out = d_cells + pass * CELLS_BYTES_PER_BLOB;
-    if (rc == 0) rc = recover_enqueue(ctx, d_cells, d_present + base * 16, m, d_out, d_status + base, st);
-    if (rc == 0 && hipMemcpyAsync(out_cells + base * CELLS_BYTES_PER_BLOB, d_out, m * CELLS_BYTES_PER_BLOB, hipMemcpyDeviceToHost, st) != hipSuccess)
-      rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
-    if (rc == 0) rc = ring.consumed(k, st);
-  }
-  if (rc == 0 && (hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
-    rc = fail(KZG_FAIL_HIP, "device-to-host copy failed");
-  if (rc) {
-    (void)hipDeviceSynchronize();
-    return rc;
-  }
-  return 0;
+  const uint8_t* d_present = hc.dev(a_mask);
+  int32_t* d_status = hc.dev<int32_t>(a_st);
+  rc = hc.passes(cells, KZG_BYTES_PER_CELL_SET, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_cells) {
+    uint8_t* d_out = d_cells + hc.max_pass * KZG_BYTES_PER_CELL_SET;
+    const int32_t e = recover_enqueue(ctx, d_cells, d_present + base * 16, m, d_out, d_status + base, hc.st);
+    if (e == 0 && hipMemcpyAsync(out_cells + base * KZG_BYTES_PER_CELL_SET, d_out, m * KZG_BYTES_PER_CELL_SET, hipMemcpyDeviceToHost, hc.st) != hipSuccess)
+      return fail(KZG_FAIL_HIP, "device-to-host copy failed");
+    return e;
+  });
+  return hc.close(rc);
 }
 
 extern "C" int32_t kzg_recover_cells_batch(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status) try {
   if (!ctx || (n && (!cells || !present || !out_cells || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return (is_group(ctx) ? multi_recover : recover_host)(ctx, cells, present, n, out_cells, status);
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
+    return recover_host(m, cells + first * KZG_BYTES_PER_CELL_SET, present + first * 16, count, out_cells + first * KZG_BYTES_PER_CELL_SET, status + first);
+  });
 } catch (...) {
   return abi_exception();
 }

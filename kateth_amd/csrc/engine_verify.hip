@@ -941,34 +941,25 @@ __global__ __launch_bounds__(64) void k_g1_decompress_public(const uint8_t* __re
 
 extern "C" int32_t kzg_g1_decompress_batch(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status) try {
   if (!ctx || (n && (!in48 || !out_affine96 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return 0;
-  return (is_group(ctx) ? multi_g1_decompress : g1_decompress_single)(ctx, in48, n, out_affine96, status);
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
+    return g1_decompress_single(m, in48 + first * 48, count, out_affine96 + first * 96, status + first);
+  });
 } catch (...) {
   return abi_exception();
 }
+// pooled device buffers and an idle stream of the host-buffer pipelines; nothing crosses the staging arena
 int32_t g1_decompress_single(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status) {
-  HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> guard(ctx->stage_lock);  // pooled device buffers + an idle stream of the host-buffer pipelines
-  int32_t rc = stage_init(ctx);
+  if (n == 0) return 0;
+  HostCall hc(ctx);
+  const int a_in = hc.upload(in48, (size_t)n * 48), a_out = hc.download(out_affine96, (size_t)n * 96), a_st = hc.download(status, (size_t)n * sizeof(int32_t));
+  int32_t rc = hc.open({}, 0);
   if (rc) return rc;
-  Carve io;
-  const size_t o_in = io.take((size_t)n * 48), o_out = io.take((size_t)n * 96), o_st = io.take((size_t)n * sizeof(int32_t));
-  rc = stage_reserve(ctx, 0, io.off);
-  if (rc) return rc;
-  uint8_t* d_in = ctx->hostio + o_in;
-  uint8_t* d_out = ctx->hostio + o_out;
-  int32_t* d_st = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
-  hipStream_t st = ctx->stage_streams[0];
-  HIP_TRY(hipMemcpyAsync(d_in, in48, (size_t)n * 48, hipMemcpyHostToDevice, st));
   {
-    ProfScope ps(ctx, PROF_DECODE, st);
-    hipLaunchKernelGGL(k_g1_decompress_public, dim3(blocks_for(n, 64)), dim3(64), 0, st, d_in, n, d_out, d_st);
+    ProfScope ps(ctx, PROF_DECODE, hc.st);
+    hipLaunchKernelGGL(k_g1_decompress_public, dim3(blocks_for(n, 64)), dim3(64), 0, hc.st, hc.dev(a_in), n, hc.dev(a_out), hc.dev<int32_t>(a_st));
   }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out_affine96, d_out, (size_t)n * 96, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(status, d_st, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return 0;
+  if (hipGetLastError() != hipSuccess) rc = fail(KZG_FAIL_HIP, "point decoding: launch failed");
+  return hc.close(rc);
 }
 
 // Polynomial::evaluate (src/kzg/poly.rs:10-33) for n (blob, z) pairs from host buffers, through the evaluation kernel of the
@@ -976,64 +967,43 @@ int32_t g1_decompress_single(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n
 // reaches k_eval_frac only through this entry point.)
 extern "C" int32_t kzg_evaluate_blobs(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status) try {
   if (!ctx || (n && (!blobs || !z32 || !out_y32 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return 0;
-  return (is_group(ctx) ? multi_evaluate_blobs : evaluate_blobs_single)(ctx, blobs, z32, n, out_y32, status);
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
+    return evaluate_blobs_single(m, blobs + first * (size_t)KZG_BYTES_PER_BLOB, z32 + first * 32, count, out_y32 + first * 32, status + first);
+  });
 } catch (...) {
   return abi_exception();
 }
 // The blobs cross PCIe through the staging arena in chunks of up to 2,048 (two slots: the copy of chunk k+1 beside the
-// evaluation of chunk k); only z, y and the statuses live in the small host-i/o pool, so a large call pins nothing.
+// evaluation of chunk k; the copy stream even for one chunk); only z, y and the statuses live in the small host-i/o pool, so a
+// large call pins nothing.
 int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status) {
-  HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> guard(ctx->stage_lock);  // pooled device buffers + idle streams of the host-buffer pipelines
-  const uint64_t chunk = n < 2048 ? n : 2048;
-  const uint64_t nchunks = (n + chunk - 1) / chunk;
-  Carve io;
-  const size_t o_z32 = io.take((size_t)n * 32), o_y32 = io.take((size_t)n * 32), o_z = io.take((size_t)n * sizeof(fr_t)), o_y = io.take((size_t)n * sizeof(fr_t)),
-               o_st = io.take((size_t)n * sizeof(int32_t));
-  StageRing ring;  // the copy stream even for one chunk
-  int32_t rc = ring.open(ctx, nchunks > 1 ? 2 : 1, (size_t)chunk * KZG_BYTES_PER_BLOB, io.off, true);
+  if (n == 0) return 0;
+  HostCall hc(ctx);
+  const int a_z32 = hc.upload(z32, (size_t)n * 32), a_y32 = hc.download(out_y32, (size_t)n * 32), a_z = hc.scratch((size_t)n * sizeof(fr_t)),
+            a_y = hc.scratch((size_t)n * sizeof(fr_t)), a_st = hc.download(status, (size_t)n * sizeof(int32_t));
+  int32_t rc = hc.open(even_plan(n, 2048), KZG_BYTES_PER_BLOB, true);
   if (rc) return rc;
-  uint8_t* d_z32 = ctx->hostio + o_z32;
-  uint8_t* d_y32 = ctx->hostio + o_y32;
-  fr_t* d_z = reinterpret_cast<fr_t*>(ctx->hostio + o_z);
-  fr_t* d_y = reinterpret_cast<fr_t*>(ctx->hostio + o_y);
-  int32_t* d_st = reinterpret_cast<int32_t*>(ctx->hostio + o_st);
-  hipStream_t st = ctx->stage_streams[0];
-  do {
-    if (hipMemcpyAsync(d_z32, z32, (size_t)n * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(d_st, 0, (size_t)n * sizeof(int32_t), st) != hipSuccess) {
-      rc = fail(KZG_FAIL_HIP, "host-to-device copy failed");
-      break;
-    }
-    launch_fr_parse(st, d_z32, n, d_z, d_st);
-    bool wide_groups = n < 4096;
-    if (ctx->knobs.eval_group) wide_groups = ctx->knobs.eval_group != 16;
-    for (uint64_t k = 0; k < nchunks && rc == 0; k++) {
-      const uint64_t base = k * chunk;
-      const uint64_t m = (n - base < chunk) ? (n - base) : chunk;
-      uint8_t* d_blobs = nullptr;
-      rc = ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, st, &d_blobs);
-      if (rc) break;
-      {
-        ProfScope ps(ctx, PROF_EVAL, st);
-        if (!wide_groups)
-          hipLaunchKernelGGL(k_eval_frac<16>, dim3(blocks_for(m, 4)), dim3(64), 0, st, d_blobs, d_z + base, ctx->d_roots_brp, ctx->d_eval_tab, d_y + base,
-                             d_st + base, m);
-        else
-          hipLaunchKernelGGL(k_eval_frac<64>, dim3((unsigned)m), dim3(64), 0, st, d_blobs, d_z + base, ctx->d_roots_brp, ctx->d_eval_tab, d_y + base,
-                             d_st + base, m);
-      }
-      rc = ring.consumed(k, st);
-    }
-    if (rc) break;
-    launch_fr_store_be(st, d_y, n, d_st, d_y32);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out_y32, d_y32, (size_t)n * 32, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(status, d_st, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      rc = fail(KZG_FAIL_HIP, "evaluation: launch or read-back failed");
-  } while (0);
-  if (rc) stage_drain(ctx);
-  return rc;
+  fr_t *d_z = hc.dev<fr_t>(a_z), *d_y = hc.dev<fr_t>(a_y);
+  int32_t* d_st = hc.dev<int32_t>(a_st);
+  hipStream_t st = hc.st;
+  if (hipMemsetAsync(d_st, 0, (size_t)n * sizeof(int32_t), st) != hipSuccess) return hc.close(fail(KZG_FAIL_HIP, "memset failed"));
+  launch_fr_parse(st, hc.dev(a_z32), n, d_z, d_st);
+  bool wide_groups = n < 4096;
+  if (ctx->knobs.eval_group) wide_groups = ctx->knobs.eval_group != 16;
+  rc = hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
+    ProfScope ps(ctx, PROF_EVAL, st);
+    if (!wide_groups)
+      hipLaunchKernelGGL(k_eval_frac<16>, dim3(blocks_for(m, 4)), dim3(64), 0, st, d_blobs, d_z + base, ctx->d_roots_brp, ctx->d_eval_tab, d_y + base, d_st + base,
+                         m);
+    else
+      hipLaunchKernelGGL(k_eval_frac<64>, dim3((unsigned)m), dim3(64), 0, st, d_blobs, d_z + base, ctx->d_roots_brp, ctx->d_eval_tab, d_y + base, d_st + base, m);
+    return 0;
+  });
+  if (rc == 0) {
+    launch_fr_store_be(st, d_y, n, d_st, hc.dev(a_y32));
+    if (hipGetLastError() != hipSuccess) rc = fail(KZG_FAIL_HIP, "evaluation: launch failed");
+  }
+  return hc.close(rc);
 }
 
 // ---- ONE item: the lincombs on the host ---------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Host-buffer (PCIe-inclusive) throughput of the batch entry points: the caller's blobs live in host memory, as in
 kateth's byte-slice API.  Pageable memory (a Python bytes object) and pinned memory (torch pin_memory) are both timed;
-the device-resident rate of the same batch is printed beside them; kzg_evaluate_blobs is timed over pageable memory.  usage: gpu_hostapi_bench.py [n] [window_bits]"""
+the device-resident rate of the same batch is printed beside them; kzg_evaluate_blobs, the sidecar call, compute_cells, recover_cells
+(the last two on min(n, 1024) items: 256 KiB down, or up and down, per item) and the point decoder are timed over pageable memory.
+usage: gpu_hostapi_bench.py [n] [window_bits]"""
 import ctypes
 import json
 import os
@@ -45,8 +47,8 @@ def timed(fn, reps=3):
     return (time.perf_counter() - t0) / reps
 
 
-def rec(name, t):
-    out[name + "_ms"], out[name + "_blobs_per_s"] = 1e3 * t, n / t
+def rec(name, t, items=n):
+    out[name + "_ms"], out[name + "_blobs_per_s"] = 1e3 * t, items / t
 
 
 rec("commit_host_pageable", timed(lambda: s.blob_to_commitment_batch(blobs, n)))
@@ -66,6 +68,35 @@ zs, ys = s.verify_session_zy(sess, 0, n)
 s.verify_session_destroy(sess)
 assert s.evaluate_blobs(blobs, zs) == (ys, [0] * n)
 rec("evaluate_host_pageable", timed(lambda: s.evaluate_blobs(blobs, zs)))
+# the sidecar call: commitments and blob proofs as the two device calls above gave them
+got = s.blob_sidecar_batch(blobs, n)
+assert got[0] == cs and got[1] == ps and not any(got[3])
+rec("sidecar_host_pageable", timed(lambda: s.blob_sidecar_batch(blobs, n)))
+# compute_cells and recover_cells (every even cell present) on m items: at least two staging passes at the default pass sizes from m = 1,024 on
+m = min(n, 1024)
+SET = 2 * 131072
+d_cells = torch.empty(m * SET, dtype=torch.uint8, device="cuda")
+s.compute_cells_batch_dev(d_blobs.data_ptr(), m, d_cells.data_ptr(), d_st.data_ptr())
+torch.cuda.synchronize()
+cells = d_cells.cpu().numpy().tobytes()
+assert s.compute_cells_batch(blobs[: m * 131072], m) == (cells, [0] * m)
+rec("cells_host_pageable", timed(lambda: s.compute_cells_batch(blobs[: m * 131072], m)), m)
+masks = bytes([0x55]) * (16 * m)
+d_masks = torch.frombuffer(bytearray(masks), dtype=torch.uint8).cuda()
+d_rec = torch.empty(m * SET, dtype=torch.uint8, device="cuda")
+s.recover_cells_batch_dev(d_cells.data_ptr(), d_masks.data_ptr(), m, d_rec.data_ptr(), d_st.data_ptr())
+torch.cuda.synchronize()
+assert d_rec.cpu().numpy().tobytes() == cells and not d_st[:m].any().item()
+assert s.recover_cells_batch(cells, masks, m) == (cells, [0] * m)
+rec("recover_host_pageable", timed(lambda: s.recover_cells_batch(cells, masks, m)), m)
+del d_cells, d_rec, cells
+# the point decoder on the n commitments, through the C ABI with the caller's buffers allocated once (there is no device-resident form: the
+# decoded points are compressed again on the host)
+pts, pst = s.decompress_g1_batch(cs)
+assert not any(pst) and all(pts[i].compress() == cs[48 * i: 48 * i + 48] for i in range(0, n, 61))
+aff, ast = (ctypes.c_uint8 * (96 * n))(), (ctypes.c_int32 * n)()
+rec("decompress_host_pageable", timed(lambda: s._lib.kzg_g1_decompress_batch(s._h, cs, n, aff, ast)))
+assert bytes(aff) == b"".join(p.affine for p in pts)
 # raw copy rates for reference
 t = timed(lambda: (d_blobs.copy_(pin_b, non_blocking=True), torch.cuda.synchronize()))
 out["h2d_pinned_GBps"] = n * 131072 / t / 1e9
