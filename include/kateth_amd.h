@@ -56,6 +56,7 @@ extern "C" {
 #define KZG_CELLS_PER_EXT_BLOB 128     /* EIP-7594: the blob extended to 8192 elements, cut into cells */
 #define KZG_FIELD_ELEMENTS_PER_CELL 64
 #define KZG_BYTES_PER_CELL 2048
+#define KZG_G1_MONOMIAL_POINTS 64      /* the monomial G1 points [tau^j]_1, j < 64, a context derives on first use (kzg_ctx_g1_monomial) */
 
 /* per-item / per-call rejection codes; they rebuild the reference's enums */
 #define KZG_OK 0
@@ -69,6 +70,8 @@ extern "C" {
 /* kzg_recover_cells_batch only; the reference has no cell recovery */
 #define KZG_ERR_CELLS_NOT_ENOUGH 8           /* fewer than 64 cells present */
 #define KZG_ERR_CELLS_INCONSISTENT 9         /* the present cells are not the evaluations of one polynomial of degree < 4096 */
+/* kzg_verify_cell_proof_batch only */
+#define KZG_ERR_CELL_INDEX 10                /* a cell index >= 128 */
 
 #define KZG_FAIL_ARGUMENT (-1)
 #define KZG_FAIL_HIP (-2)
@@ -280,7 +283,8 @@ int32_t kzg_blob_sidecar_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint
  *   blobs     : n * 131072 bytes
  *   out_cells : n * 128 * 2048 bytes; cells 0..63 of an accepted blob are the blob, byte for byte
  *   status    : n * int32 ; 0 or KZG_ERR_BLOB_INVALID_FIELD_ELEMENT per blob.  A rejected blob gets 262144 zero bytes.
- * Not here: cell proofs (they need the monomial G1 setup and FK20) and cell verification; cell recovery is kzg_recover_cells_batch.
+ * Not here: cell proofs (they need FK20; the first 64 monomial G1 points exist, kzg_ctx_g1_monomial).  Cell recovery is
+ *   kzg_recover_cells_batch, cell verification kzg_verify_cell_proof_batch.
  * Bounds: nothing beyond n items is written; n == 0 returns 0.  A null pointer with n > 0 returns KZG_FAIL_ARGUMENT.
  * The *_dev form takes HIP device pointers resident on ctx's device (16-byte aligned), enqueues one kernel on `hip_stream` and returns
  *   without synchronising; it needs no workspace and takes no lock, so calls on different streams run side by side.
@@ -312,7 +316,8 @@ int32_t kzg_compute_cells_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uin
  *   input is consistent; the check can fire from 65 cells on.
  * out_cells must not overlap cells.  The kernel uses an item's own output region as scratch before the final stores: while a call
  *   is in flight the region holds intermediate values.
- * Not here: the proofs half of recovery (it needs the monomial G1 setup and FK20, like cell proofs).
+ * Not here: the proofs half of recovery (it needs FK20 over the full monomial G1 setup, like cell proofs; a context derives the first 64
+ *   of those points, kzg_ctx_g1_monomial).
  * Bounds: nothing beyond n items is written; n == 0 returns 0.  A null pointer with n > 0 returns KZG_FAIL_ARGUMENT.
  * The *_dev form takes HIP device pointers resident on ctx's device (16-byte aligned), enqueues one kernel on `hip_stream` and returns
  *   without synchronising; it needs no workspace and takes no lock, so calls on different streams run side by side.
@@ -378,6 +383,53 @@ int32_t kzg_verify_proof_batch_dev(const kzg_ctx* ctx, const void* d_proofs48, c
                                    int32_t* ok, void* hip_stream);
 int32_t kzg_verify_proof_batch_group_dev(const kzg_ctx* ctx, const void* const* d_proofs48, const void* const* d_commitments48, const void* const* d_z32,
                                          const void* const* d_y32, const uint64_t* n_local, int32_t* ok, void* const* hip_streams);
+
+/*
+ * Introspection: the 48-byte encodings of the monomial G1 setup points [tau^j]_1, first <= j < first + count, first + count <= 64.
+ * A Setup<4096, 65> file carries the Lagrange form only; the context derives these 64 on the device as the commitments of the
+ * blobs of X^j (element i = roots_brp[i]^j) through its own commitment path, on whichever table stands then -- ONCE, in its first
+ * kzg_verify_cell_proof_batch[_dev] or kzg_ctx_g1_monomial call (64 commitments, about a millisecond), not in kzg_ctx_create: a
+ * context that never verifies cells launches nothing for them.  Point 0 is the G1 generator.  They are the fixed terms of cell
+ * verification's second lincomb; a group context's members each derive and hold a copy (this call reads member 0's).
+ */
+int32_t kzg_ctx_g1_monomial(const kzg_ctx* ctx, uint32_t first, uint32_t count, uint8_t* out48);
+
+/*
+ * verify_cell_kzg_proof_batch of specs/fulu/polynomial-commitments-sampling.md (EIP-7594, PeerDAS) with c-kzg-4844's argument shape:
+ * n (commitment, cell index, cell, proof) tuples, ONE commitment per cell (a caller with many cells of one blob repeats it; the same
+ * tuple may occur more than once).  Every array has n items, contiguous: 48 bytes per point, a uint64 per index, 2048 bytes per cell
+ * (64 elements, 32 bytes big-endian each, as kzg_compute_cells_batch lays a cell out).  Device pointers (*_dev) are resident on ctx's
+ * device and 16-byte aligned; the calls are synchronous like kzg_verify_proof_batch_dev (they return the boolean); hip_stream = NULL
+ * is the default stream.
+ *   Cell c holds p(h_c w64^brp6(i)), i < 64, with h_c = omega_8192^brp7(c) (coset_shift_for_cell).  With I_k the polynomial of degree
+ *   < 64 through cell k and r the challenge:
+ *   *ok = 1  iff  e(sum r^k proof_k, [tau^64]_2) ==
+ *                 e(sum r^k commitment_k + sum r^k h_k^64 proof_k - sum_{j<64} S_j [tau^j]_1, G2),   S = sum_k r^k I_k,
+ *            i.e. kzg_verify_proof_batch's check with z_k = h_k^64, y_k = 0, 64 monomial terms in place of the generator term and
+ *            g2_monomial[64] in place of g2_monomial[1].  r is the ENGINE's challenge, bound to every input like the blob and points
+ *            batches' (deviations Q1 / Q2): leaf k of the transcript tree = SHA-256(commitment48 || cell_index as 8 bytes big-endian
+ *            || cell 2048 || proof48), and the seed message starts with the spec's cell domain "RCKZGCBATCH__V1_", so a cells root
+ *            never reproduces a blob batch's r.  The boolean is therefore the spec's, up to the 2^-255 soundness error of the random
+ *            combination; the transcript is not r-for-r the spec's.
+ *   n == 0   *ok = 1.  A null required pointer with n > 0 returns KZG_FAIL_ARGUMENT.
+ *   rejected inputs: the positive code of the FIRST rejected input, *ok = 0.  First = the spec's order of assertions lifted to
+ *            arrays the way the other batch calls lift theirs: every cell index before any commitment, every commitment before any
+ *            cell, every cell before any proof; the lowest index within the first kind that has an error.
+ *              1. cell index >= 128                 KZG_ERR_CELL_INDEX
+ *              2. commitment                        KZG_ERR_EC_* as kzg_g1_decompress_batch reports them
+ *              3. cell: an element >= r             KZG_ERR_BLOB_INVALID_FIELD_ELEMENT
+ *              4. proof                             KZG_ERR_EC_*
+ *            The point at infinity is a valid commitment and a valid proof, as everywhere else in this ABI.  The length checks of
+ *            the specification stay in the caller: the ABI takes a single n.
+ * On a GROUP context the host-buffer call cuts the batch into contiguous shares, one per member, like kzg_verify_proof_batch; every
+ * member's partial second lincomb carries its own monomial terms, so the partials add.  The *_dev call acts on member 0.
+ * Not here: per-item verdicts (the *_each forms), a sharded phase-1 entry point for cells, a *_group_dev form, and deduplicating the
+ * commitments before they are decoded (the decoder runs on 2n points where 128 cells of one blob need n + 1).
+ */
+int32_t kzg_verify_cell_proof_batch(const kzg_ctx* ctx, const uint8_t* commitments48, const uint64_t* cell_indices, const uint8_t* cells /* n * 2048 */,
+                                    const uint8_t* proofs48, uint64_t n, int32_t* ok);
+int32_t kzg_verify_cell_proof_batch_dev(const kzg_ctx* ctx, const void* d_commitments48, const void* d_cell_indices, const void* d_cells,
+                                        const void* d_proofs48, uint64_t n, int32_t* ok, void* hip_stream);
 
 /*
  * PER-ITEM VERDICTS: which items of a batch are bad.  What a caller of the reference does when Setup::verify_blob_proof_batch is

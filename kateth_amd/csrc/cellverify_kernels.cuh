@@ -1,0 +1,197 @@
+// verify_cell_kzg_proof_batch (EIP-7594): the kernels of the cells kind of batch verification (compiled once: engine_verify.hip owns
+// this header).  k_cells_leaves is the front; k_cells_interp and k_cells_reduce run once the challenge r is known and leave the 64
+// scalars -S_j of lincomb B's monomial terms (arithmetic and layout: cellverify_math.cuh).
+#pragma once
+#include "cellverify_math.cuh"
+#include "verify_kernels.cuh"
+
+namespace kzg {
+#if defined(__HIPCC__)
+
+// The front: ONE LANE PER CELL.  A leaf is SHA-256(commitment48 || cell_index as 8 bytes big-endian || cell 2048 || proof48), a serial
+// chain of 34 compressions over 2,152 bytes; lanes of a group could only share it through a tree, which would be another leaf.  The
+// lane streams its cell once as 16-byte loads -- four per block, each 128-byte line used by two consecutive blocks of the same lane --
+// and range-checks the elements word by word while they sit in the message schedule: the cell's words lie two words off the block grid
+// (12 + 2 words come first), so the second half of the loaded quad that straddles a block boundary is carried to the next block.
+// It writes z_k = h_c^64 (from the 128-entry table; zero for a rejected index) and y_k = 0 where k_batch_scalars reads them, the status
+// words of the index (KZG_ERR_CELL_INDEX) and of the cell (KZG_ERR_BLOB_INVALID_FIELD_ELEMENT), and the leaf.
+// Like k_points_leaves it runs beside two decoder waves per SIMD: sha256_block_rolled, 64 VGPRs, no scratch.
+// hipcc -Rpass-analysis=kernel-resource-usage (gfx950): the figures are in DESIGN.md and asserted by tests/test_cellverify_host.py.
+static __global__ __launch_bounds__(256, 8) void k_cells_leaves(const uint8_t* __restrict__ commitments48, const unsigned long long* __restrict__ cell_indices,
+                                                                const uint8_t* __restrict__ cells, const uint8_t* __restrict__ proofs48, uint64_t n,
+                                                                const fr_t* __restrict__ h64_plain, fr_t* __restrict__ z_plain, fr_t* __restrict__ y_plain,
+                                                                int32_t* __restrict__ status_index, int32_t* __restrict__ status_cell,
+                                                                uint32_t* __restrict__ leaves /* n x 8 words */) {
+  issue_priority_latency();
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* c = reinterpret_cast<const uint32_t*>(commitments48 + i * 48);
+  const uint4* cell = reinterpret_cast<const uint4*>(cells + i * (uint64_t)KZG_BYTES_PER_CELL);
+  const unsigned long long index = cell_indices[i];
+  // The range check rides on the words as they pass, most significant first: `cmp` is the comparison of the current element's words so
+  // far with r's (0 undecided, 1 below, 2 above), so that nothing of an element is kept beyond the two words a block boundary cuts off.
+  uint32_t cmp = 0;
+  bool bad = false;
+  auto word = [&](uint32_t v, int q) {  // word q (0 = most significant) of an element; q = 7 ends it
+    const uint32_t m = modulus<FrParams>().v[7 - q];
+    cmp = cmp != 0u ? cmp : (v < m ? 1u : (v > m ? 2u : 0u));
+    if (q == 7) {
+      bad |= cmp != 1u;
+      cmp = 0;
+    }
+  };
+  sha256_state s;
+  sha256_init(s);
+  uint32_t w[16];
+#pragma unroll
+  for (int q = 0; q < 12; q++) w[q] = __builtin_bswap32(c[q]);
+  w[12] = (uint32_t)(index >> 32);
+  w[13] = (uint32_t)index;
+  uint32_t carry0, carry1;  // words 2 and 3 of quad 4 b, loaded for block b: its first two words end block b, these begin block b + 1
+  {
+    const uint4 q = cell[0];
+    w[14] = __builtin_bswap32(q.x);
+    w[15] = __builtin_bswap32(q.y);
+    carry0 = __builtin_bswap32(q.z);
+    carry1 = __builtin_bswap32(q.w);
+    word(w[14], 0);
+    word(w[15], 1);
+  }
+  sha256_block_rolled(s, w);
+  // block b: cell words 16 b - 14 .. 16 b + 1 = the carried two, quads 4 b - 3 .. 4 b - 1 and two words more: the first two of quad 4 b,
+  // or, in block 32, of the proof; elements 2 b - 2 and 2 b - 1 end in it
+  auto quads = [&](uint32_t b) {
+    w[0] = carry0;
+    w[1] = carry1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const uint4 q = cell[4 * b - 3 + k];
+      w[2 + 4 * k] = __builtin_bswap32(q.x);
+      w[3 + 4 * k] = __builtin_bswap32(q.y);
+      w[4 + 4 * k] = __builtin_bswap32(q.z);
+      w[5 + 4 * k] = __builtin_bswap32(q.w);
+    }
+#pragma unroll
+    for (int q = 0; q < 6; q++) word(w[q], 2 + q);
+#pragma unroll
+    for (int q = 0; q < 8; q++) word(w[6 + q], q);
+  };
+#pragma unroll 1
+  for (uint32_t b = 1; b < 32; b++) {
+    quads(b);
+    const uint4 q = cell[4 * b];
+    w[14] = __builtin_bswap32(q.x);
+    w[15] = __builtin_bswap32(q.y);
+    carry0 = __builtin_bswap32(q.z);
+    carry1 = __builtin_bswap32(q.w);
+    word(w[14], 0);
+    word(w[15], 1);
+    sha256_block_rolled(s, w);
+  }
+  quads(32);
+  // The item's index anew, opaque to the compiler: the proof's address and the three output addresses are computed HERE and not ahead of
+  // the loop, where they would be eight registers held through 33 blocks (and, at 64 registers, spilled)
+  uint32_t lane = threadIdx.x;
+  asm volatile("" : "+v"(lane));
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + lane;
+  const uint32_t* p = reinterpret_cast<const uint32_t*>(proofs48 + k * 48);
+  w[14] = __builtin_bswap32(p[0]);
+  w[15] = __builtin_bswap32(p[1]);
+  sha256_block_rolled(s, w);
+#pragma unroll
+  for (int q = 0; q < 10; q++) w[q] = __builtin_bswap32(p[2 + q]);
+  w[10] = 0x80000000u;
+#pragma unroll
+  for (int q = 11; q < 15; q++) w[q] = 0;
+  w[15] = (48 + 8 + KZG_BYTES_PER_CELL + 48) * 8;
+  sha256_block_rolled(s, w);
+  status_cell[k] = bad ? KZG_ERR_BLOB_INVALID_FIELD_ELEMENT : 0;
+#pragma unroll
+  for (int q = 0; q < 8; q++) leaves[k * 8 + q] = s.h[q];
+  {  // z, y and the index's status last, from the index read anew: nothing of them is held through the hash
+    const unsigned long long column = cell_indices[k];
+    const bool good = column < (unsigned long long)KZG_CELLS_PER_EXT_BLOB;
+    const uint4* h = reinterpret_cast<const uint4*>(h64_plain + (good ? (uint32_t)column : 0u));
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    const uint4 h0 = h[0], h1 = h[1];  // row 0 for a rejected index: loaded all the same, then masked
+    const uint32_t keep = good ? ~0u : 0u;
+    uint4* zd = reinterpret_cast<uint4*>(z_plain + k);
+    uint4* yd = reinterpret_cast<uint4*>(y_plain + k);
+    zd[0] = make_uint4(h0.x & keep, h0.y & keep, h0.z & keep, h0.w & keep);
+    zd[1] = make_uint4(h1.x & keep, h1.y & keep, h1.z & keep, h1.w & keep);
+    yd[0] = zero;
+    yd[1] = zero;
+    status_index[k] = good ? 0 : KZG_ERR_CELL_INDEX;
+  }
+}
+
+// S's partial vectors: one 128-thread workgroup per CELLV_CELLS cells, eight threads per cell.  A thread reads its eight elements (256
+// consecutive bytes, the cell's second and last trip from memory: 2 x 2 KiB per cell in all), runs the three steps of
+// cellverify_math.cuh with a barrier between them and the first 64 threads store the workgroup's 64 partial coefficients.  A cell
+// whose index or elements were rejected (the front's status words), and the cells past the batch's end in the last workgroup,
+// contribute zero.  r^k is lincomb A's scalar of item k as k_batch_scalars left it (plain).  No atomics: every sum has a fixed order.
+static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_interp(const uint8_t* __restrict__ cells, const unsigned long long* __restrict__ cell_indices,
+                                                                   const int32_t* __restrict__ status_index, const int32_t* __restrict__ status_cell,
+                                                                   const fr_t* __restrict__ rpow_plain, uint64_t n, const uint32_t* __restrict__ ctab,
+                                                                   const uint32_t* __restrict__ vtab, fr_t* __restrict__ partials /* gridDim.x x 64 */) {
+  __shared__ uint32_t img[CELLV_IMAGE_DWORDS];
+  const uint32_t cl = threadIdx.x >> 3, t = threadIdx.x & 7u;
+  const uint64_t k = (uint64_t)blockIdx.x * CELLV_CELLS + cl;
+  bool live = k < n;
+  if (live) live = status_index[k] == 0 && status_cell[k] == 0;
+  const uint32_t column = live ? (uint32_t)cell_indices[k] : 0u;
+  fr_t rk;
+  {
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    const uint4* src = reinterpret_cast<const uint4*>(rpow_plain + (live ? k : 0));
+    const uint4 lo = live ? src[0] : zero, hi = live ? src[1] : zero;
+    rk.v[0] = lo.x; rk.v[1] = lo.y; rk.v[2] = lo.z; rk.v[3] = lo.w;
+    rk.v[4] = hi.x; rk.v[5] = hi.y; rk.v[6] = hi.z; rk.v[7] = hi.w;
+  }
+  {
+    fr_t v[8];
+    const uint4* in = reinterpret_cast<const uint4*>(cells + (live ? k : 0) * (uint64_t)KZG_BYTES_PER_CELL) + 16u * t;
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      const uint4 zero = make_uint4(0, 0, 0, 0);
+      const uint4 w0 = live ? in[2 * e] : zero, w1 = live ? in[2 * e + 1] : zero;
+      v[e].v[7] = __builtin_bswap32(w0.x);
+      v[e].v[6] = __builtin_bswap32(w0.y);
+      v[e].v[5] = __builtin_bswap32(w0.z);
+      v[e].v[4] = __builtin_bswap32(w0.w);
+      v[e].v[3] = __builtin_bswap32(w1.x);
+      v[e].v[2] = __builtin_bswap32(w1.y);
+      v[e].v[1] = __builtin_bswap32(w1.z);
+      v[e].v[0] = __builtin_bswap32(w1.w);
+    }
+    cellv_step_a(img, ctab, cl, t, v);
+  }
+  __syncthreads();
+  cellv_step_b(img, ctab, vtab, cl, t, column, rk);
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    fr_t sum;
+    cellv_step_c(sum, img, threadIdx.x);
+    partials[(uint64_t)blockIdx.x * 64 + threadIdx.x] = sum;
+  }
+}
+
+// -S_j = -(sum of the partial vectors), j < 64, into the 64 scalar slots of lincomb B's monomial terms.  One workgroup: four threads
+// per coefficient take every fourth partial vector, thread j adds the four in their order.
+static __global__ __launch_bounds__(256) void k_cells_reduce(const fr_t* __restrict__ partials, uint32_t count, fr_t* __restrict__ out_neg_plain /* 64 */) {
+  __shared__ fr_t red[256];
+  const uint32_t j = threadIdx.x & 63u, g = threadIdx.x >> 6;
+  fr_t acc;
+  bn_zero(acc);
+  for (uint32_t k = g; k < count; k += 4) fr_add(acc, acc, partials[(uint64_t)k * 64 + j]);
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    fr_t out;
+    cellv_neg_sum(out, red + j, 4, 64);
+    out_neg_plain[j] = out;
+  }
+}
+
+#endif
+}  // namespace kzg

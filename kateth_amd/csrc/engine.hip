@@ -570,6 +570,9 @@ extern "C" void kzg_ctx_destroy(kzg_ctx* ctx) {
   if (ctx->d_eval_tab) (void)hipFree(ctx->d_eval_tab);
   if (ctx->d_cells_tab) (void)hipFree(ctx->d_cells_tab);
   if (ctx->d_recover_tab) (void)hipFree(ctx->d_recover_tab);
+  if (ctx->d_cellv_tab) (void)hipFree(ctx->d_cellv_tab);
+  if (ctx->d_cellv_h64) (void)hipFree(ctx->d_cellv_h64);
+  if (ctx->d_g1_monomial) (void)hipFree(ctx->d_g1_monomial);
   if (ctx->d_gen_affine) (void)hipFree(ctx->d_gen_affine);
   if (ctx->d_comb_k) (void)hipFree(ctx->d_comb_k);
   if (ctx->d_comb_k_lat) (void)hipFree(ctx->d_comb_k_lat);
@@ -782,12 +785,13 @@ static int32_t ctx_build(kzg_ctx* ctx, const uint8_t* g1_lagrange, const uint8_t
   hipStream_t st = nullptr;
   // ---- G2 monomial points (host): P2::decompress of all 65 (src/kzg/setup.rs:67-72) ----
   {
-    host::g2_affine tau{};
+    host::g2_affine tau{}, tau64{};
     for (int i = 0; i < KZG_SETUP_G2_POINTS; i++) {
       host::g2_affine q;
       int32_t stq = host::g2_decompress(q, g2_monomial + 96 * i);
       if (stq != 0) return fail_detail(KZG_FAIL_SETUP_G2, stq, "g2_monomial[" + std::to_string(i) + "] rejected, code " + std::to_string(stq));
       if (i == 1) tau = q;
+      if (i == KZG_G1_MONOMIAL_POINTS) tau64 = q;
     }
     ctx->pairing = new host::pairing_ctx();
     ctx->pairing->fc = host::make_frob_consts();
@@ -804,6 +808,7 @@ static int32_t ctx_build(kzg_ctx* ctx, const uint8_t* g1_lagrange, const uint8_t
     }
     ctx->pairing->lines_g2 = host::precompute_lines(gen);
     ctx->pairing->lines_tau = host::precompute_lines(tau);
+    ctx->pairing->lines_tau64 = host::precompute_lines(tau64);
   }
   tt.mark("G2 decode + Miller lines (host)");
   // ---- G1 generator (BLS12_381_G1, src/bls.rs:391) ----
@@ -849,6 +854,9 @@ static int32_t ctx_build(kzg_ctx* ctx, const uint8_t* g1_lagrange, const uint8_t
   hipLaunchKernelGGL(k_setup_cells_tab, dim3(CELLS_TAB_ENTRIES / 64), dim3(64), 0, st, ctx->d_cells_tab);
   HIP_TRY(hipMalloc(&ctx->d_recover_tab, (size_t)RECOVER_TAB_ENTRIES * CELLS_TAB_ENTRY * sizeof(uint32_t)));
   hipLaunchKernelGGL(k_setup_recover_tab, dim3(RECOVER_TAB_ENTRIES / 64), dim3(64), 0, st, ctx->d_recover_tab);
+  HIP_TRY(hipMalloc(&ctx->d_cellv_tab, (size_t)CELLV_TAB_ENTRIES * CELLS_TAB_ENTRY * sizeof(uint32_t)));
+  HIP_TRY(hipMalloc(&ctx->d_cellv_h64, 128 * sizeof(fr_t)));
+  hipLaunchKernelGGL(k_setup_cellv_tab, dim3(CELLV_TAB_ENTRIES / 64), dim3(64), 0, st, ctx->d_cellv_tab, ctx->d_cellv_h64);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   tt.mark("roots + evaluation table");
@@ -1208,6 +1216,70 @@ extern "C" int32_t kzg_blob_to_commitment_batch_dev(const kzg_ctx* ctx, const vo
   if (rc == 0) rc = commit_dev_locked(ctx, d_blobs, n, d_out48, nullptr, reinterpret_cast<int32_t*>(d_status), st);
   if (rc == 0) rc = ws.end();
   return rc;
+} catch (...) {
+  return abi_exception();
+}
+
+// The first 64 monomial setup points, which the setup file of a Setup<4096, 65> does not carry: [tau^j]_1 is the commitment of X^j, i.e.
+// of the blob whose element i is roots_brp[i]^j.  64 such blobs are built on the device and committed through the context's own
+// commitment path on whichever table stands then (commitments do not depend on the table, so a KZG_CFG_BUILD_ASYNC context needs nothing
+// more); the 48-byte results are kept for kzg_ctx_g1_monomial and decoded -- by the verification path's decoder -- into the affine form
+// lincomb B reads, with their [z^2]-images behind them.  Every member of a group context derives its own copy.  About 8 MiB of scratch,
+// freed here.  It runs ONCE per context, on the first call that needs the points (ensure_g1_monomial), not inside kzg_ctx_create: a
+// context that only commits, proves and verifies blobs launches exactly the kernels it launched before.
+static int32_t derive_g1_monomial(const kzg_ctx* ctx) {
+  TraceTimer tt(ctx->knobs.trace, "monomial G1 points");
+  constexpr uint32_t M = KZG_G1_MONOMIAL_POINTS;
+  ScratchAllocs scratch;
+  uint8_t *d_blobs = nullptr, *d_out48 = nullptr, *d_inf = nullptr;
+  int32_t* d_status = nullptr;
+  HIP_TRY(scratch.alloc(&d_blobs, (size_t)M * KZG_BYTES_PER_BLOB));
+  HIP_TRY(scratch.alloc(&d_out48, (size_t)M * 48));
+  HIP_TRY(scratch.alloc(&d_status, 2 * (size_t)M * sizeof(int32_t)));
+  HIP_TRY(scratch.alloc(&d_inf, 2 * (size_t)M));
+  uint4* d_points = nullptr;
+  HIP_TRY(scratch.alloc(&d_points, 2 * (size_t)M * 96));
+  hipStream_t st = nullptr;
+  hipLaunchKernelGGL(k_setup_monomial_blobs, dim3(M * 4096 / 256), dim3(256), 0, st, ctx->d_roots_brp, M, d_blobs);
+  HIP_TRY(hipGetLastError());
+  int32_t rc = kzg_blob_to_commitment_batch_dev(ctx, d_blobs, M, d_out48, d_status, st);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(d_inf, 0, 2 * (size_t)M, st));
+  launch_g1_decompress(st, d_out48, M, d_status + M, nullptr, 0, nullptr, d_points, d_inf);
+  launch_glv_points(st, d_points, M, M);
+  HIP_TRY(hipGetLastError());
+  int32_t h_status[2 * M];
+  uint8_t h_inf[M];
+  HIP_TRY(hipMemcpyAsync(h_status, d_status, sizeof(h_status), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_inf, d_inf, sizeof(h_inf), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(ctx->g1_monomial48, d_out48, (size_t)M * 48, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (uint32_t j = 0; j < 2 * M; j++)
+    if (h_status[j]) return fail(KZG_FAIL_HIP, "monomial G1 points: commitment " + std::to_string(j % M) + " failed, code " + std::to_string(h_status[j]));
+  // a setup whose Lagrange points are not the basis of one tau can commit X^j to the identity; lincomb B's terms are affine points
+  for (uint32_t j = 0; j < M; j++)
+    if (h_inf[j]) return fail(KZG_FAIL_SETUP_UNSUPPORTED, "degenerate setup: the commitment of X^" + std::to_string(j) + " is the point at infinity");
+  scratch.ptrs.erase(std::find(scratch.ptrs.begin(), scratch.ptrs.end(), (void*)d_points));  // kept: the context's from here on
+  ctx->d_g1_monomial = d_points;
+  tt.mark("64 blobs, commitments, decoding");
+  return 0;
+}
+int32_t ensure_g1_monomial(const kzg_ctx* ctx) {
+  if (ctx->g1_monomial_ready.load(std::memory_order_acquire)) return 0;
+  std::lock_guard<std::mutex> guard(ctx->g1_monomial_mu);
+  if (ctx->g1_monomial_ready.load(std::memory_order_relaxed)) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int32_t rc = derive_g1_monomial(ctx);
+  if (rc == 0) ctx->g1_monomial_ready.store(true, std::memory_order_release);
+  return rc;
+}
+
+extern "C" int32_t kzg_ctx_g1_monomial(const kzg_ctx* ctx, uint32_t first, uint32_t count, uint8_t* out48) try {
+  if (!ctx || (count && !out48) || first > KZG_G1_MONOMIAL_POINTS || count > KZG_G1_MONOMIAL_POINTS - first) return fail(KZG_FAIL_ARGUMENT, "bad argument");
+  const int32_t rc = ensure_g1_monomial(ctx);
+  if (rc) return rc;
+  memcpy(out48, ctx->g1_monomial48 + (size_t)first * 48, (size_t)count * 48);
+  return 0;
 } catch (...) {
   return abi_exception();
 }

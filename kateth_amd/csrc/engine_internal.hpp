@@ -27,7 +27,7 @@
 //   engine.hip        setup_kernels.cuh, msm_comb.cuh, msm_fixed.cuh   -> msm_launch / msm_finish / msm_pipeline
 //   engine_blob.hip   blob_kernels.cuh (hash, point decoding, scalars) -> launch_challenge*, launch_g1_decompress*, launch_fr_*
 //   engine_proof.hip  poly_kernels.cuh, cells_kernels.cuh              (its only user)
-//   engine_verify.hip verify_kernels.cuh                               (its only user)
+//   engine_verify.hip verify_kernels.cuh, cellverify_kernels.cuh      (its only user)      -> launch_glv_points
 #include "comb_geom.hpp"
 #include "g1.cuh"
 #include "sha256.cuh"
@@ -238,6 +238,16 @@ struct kzg_ctx {
   uint32_t* d_eval_tab = nullptr;  // 256 hexes x twenty 9-limb slots in radix-2^29 limbs (layout: fr29.cuh; k_eval_frac, verify_kernels.cuh)
   uint32_t* d_cells_tab = nullptr;  // compute_cells' twiddles: 12,288 entries of twelve dwords (layout: cells_math.cuh; k_compute_cells, cells_kernels.cuh)
   uint32_t* d_recover_tab = nullptr;  // recover_cells' twists, omega_128 powers and coset points: 12,480 such entries (layout: recover_math.cuh; k_recover_cells)
+  uint32_t* d_cellv_tab = nullptr;  // cell verification's h_c^-j / 64: 8,192 such entries (layout: cellverify_math.cuh; k_cells_interp, cellverify_kernels.cuh)
+  fr_t* d_cellv_h64 = nullptr;  // h_c^64 of the 128 columns, plain: z of a cell in the batched check (k_cells_leaves)
+  // The first 64 monomial setup points [tau^j]_1, derived as the commitments of the blobs of X^j (ensure_g1_monomial, engine.hip) by the
+  // context's FIRST cell verification or kzg_ctx_g1_monomial call -- not at kzg_ctx_create: a context that never verifies cells launches and
+  // holds nothing for them.  64 affine points as lincomb B reads them (2^392-Montgomery, the decoder's output), their 64 [z^2]-images behind
+  // them (GLV route), and the 48-byte encodings for kzg_ctx_g1_monomial; written once under g1_monomial_mu, then read-only.
+  mutable std::mutex g1_monomial_mu;
+  mutable std::atomic<bool> g1_monomial_ready{false};
+  mutable uint4* d_g1_monomial = nullptr;
+  mutable uint8_t g1_monomial48[KZG_G1_MONOMIAL_POINTS * 48] = {};
   uint4* d_gen_affine = nullptr; // G1 generator and its [z^2]-image (GLV cross-check path), affine, 2^392-Montgomery (2 x 96 B): a term of batch verification's second lincomb
   host::pairing_ctx* pairing = nullptr;  // host: Frobenius constants + Miller lines of G2 and [tau]_2
   uint64_t table_bytes = 0;
@@ -317,15 +327,23 @@ static inline int32_t on_members(const kzg_ctx* ctx, uint64_t n, Fn&& fn) {
 // reference's parse order:
 //   BLOBS  (verify_blob_proof_batch): blobs, commitments48, proofs48       -> {blob, commitment, proof}   = the ABI's err6
 //   POINTS (verify_proof_batch):      proofs48, commitments48, z32, y32    -> {proof, commitment, z, y}   = the ABI's err8
+//   CELLS  (verify_cell_proof_batch): commitments48, cell_indices, cells, proofs48 -> {cell index, commitment, cell, proof}
 struct VerifyInputs {
-  enum Kind { BLOBS, POINTS } kind;
+  enum Kind { BLOBS, POINTS, CELLS } kind;
   const uint8_t *blobs, *commitments48, *proofs48, *z32, *y32;
   bool on_host;
+  const uint64_t* cell_indices = nullptr;
+  const uint8_t* cells = nullptr;
   int kinds() const { return kind == BLOBS ? 3 : 4; }
-  bool any_null() const { return !commitments48 || !proofs48 || (kind == BLOBS ? !blobs : (!z32 || !y32)); }
+  bool any_null() const {
+    return !commitments48 || !proofs48 || (kind == BLOBS ? !blobs : kind == POINTS ? (!z32 || !y32) : (!cell_indices || !cells));
+  }
   VerifyInputs advanced(uint64_t first) const {  // the same inputs from item `first` on
-    return VerifyInputs{kind, blobs ? blobs + first * (size_t)KZG_BYTES_PER_BLOB : nullptr, commitments48 + first * 48, proofs48 + first * 48,
-                        z32 ? z32 + first * 32 : nullptr, y32 ? y32 + first * 32 : nullptr, on_host};
+    VerifyInputs a{kind, blobs ? blobs + first * (size_t)KZG_BYTES_PER_BLOB : nullptr, commitments48 + first * 48, proofs48 + first * 48,
+                   z32 ? z32 + first * 32 : nullptr, y32 ? y32 + first * 32 : nullptr, on_host};
+    a.cell_indices = cell_indices ? cell_indices + first : nullptr;
+    a.cells = cells ? cells + first * (size_t)KZG_BYTES_PER_CELL : nullptr;
+    return a;
   }
 };
 static inline VerifyInputs blob_inputs(const void* blobs, const void* commitments48, const void* proofs48, bool on_host) {
@@ -334,6 +352,14 @@ static inline VerifyInputs blob_inputs(const void* blobs, const void* commitment
 static inline VerifyInputs point_inputs(const void* proofs48, const void* commitments48, const void* z32, const void* y32, bool on_host) {
   return VerifyInputs{VerifyInputs::POINTS, nullptr, (const uint8_t*)commitments48, (const uint8_t*)proofs48, (const uint8_t*)z32, (const uint8_t*)y32, on_host};
 }
+static inline VerifyInputs cell_inputs(const void* commitments48, const void* cell_indices, const void* cells, const void* proofs48, bool on_host) {
+  VerifyInputs in{VerifyInputs::CELLS, nullptr, (const uint8_t*)commitments48, (const uint8_t*)proofs48, nullptr, nullptr, on_host};
+  in.cell_indices = (const uint64_t*)cell_indices;
+  in.cells = (const uint8_t*)cells;
+  return in;
+}
+// the terms behind the 2n points of lincomb B: the generator, or the 64 monomial points of the cells kind
+static inline uint64_t verify_tail_terms(VerifyInputs::Kind kind) { return kind == VerifyInputs::CELLS ? KZG_G1_MONOMIAL_POINTS : 1; }
 // the wanted ending of a batch call: one boolean (no VerifyEach), or the per-item verdicts of kzg_verify_*_batch_each beside it
 struct VerifyEach {
   uint8_t* ok_each;
@@ -346,6 +372,10 @@ int32_t verify_phase1(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hi
 // the same over a group's members, from host buffers (engine_multi.hip)
 int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, int32_t* ok);
 int32_t multi_verify_each(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, const VerifyEach& each, int32_t* ok);
+// kzg_verify_batch_finish for either pairing: `cells` checks the summed partials against [tau^64]_2 (engine_verify.hip)
+// the context's monomial G1 points stand (derived by the first caller, engine.hip); every cells call of a member passes through here
+int32_t ensure_g1_monomial(const kzg_ctx* ctx);
+int32_t verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint64_t world, bool cells, int32_t* ok);
 // one member's device-resident share of a group verification (kzg_verify_*_batch_group_dev): global range [first, first + count),
 // inputs resident on member->device
 struct GroupDevShare {
@@ -535,6 +565,8 @@ void launch_fr_parse(hipStream_t st, const uint8_t* in32, uint64_t n, fr_t* out_
 void launch_fr_store_be(hipStream_t st, const fr_t* plain, uint64_t n, const int32_t* status, uint8_t* out32);
 // kzg_to_versioned_hash (EIP-4844) of n commitments: 0x01 || SHA-256(commitment48)[1:32]; 32 zero bytes where status[i] != 0
 void launch_versioned_hash(hipStream_t st, const uint8_t* commitments48, uint64_t n, const int32_t* status, uint8_t* out32);
+// [z^2]-images of points [0, npts) of `aff` at [phi_off, phi_off + npts) (engine_verify.hip: k_glv_points)
+void launch_glv_points(hipStream_t st, uint4* aff, uint64_t npts, uint64_t phi_off);
 void launch_synth_blobs(hipStream_t st, uint64_t seed, uint64_t first_index, uint64_t n, uint8_t* d_blobs);
 constexpr uint64_t KZG_FUSED_PREP_MAX = 16384;  // the two-wave kernel's limit: 512 hash waves + 512 decode waves (verify), one wave per SIMD on 256 CUs
 

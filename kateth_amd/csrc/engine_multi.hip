@@ -73,7 +73,7 @@ int32_t multi_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, const uin
   return verify_proof_single(member_of(ctx, ctx->rr.fetch_add(1u, std::memory_order_relaxed) % S), proof48, commitment48, z32, y32, ok);
 }
 
-// Setup::verify_blob_proof_batch (src/kzg/setup.rs:247-275) or Setup::verify_proof_batch (:115-161) from host buffers over the members'
+// Setup::verify_blob_proof_batch (src/kzg/setup.rs:247-275), Setup::verify_proof_batch (:115-161) or verify_cell_proof_batch from host buffers over the members'
 // shares; one share is exactly the single-device call on that member.  Otherwise every share runs the single-device phase 1
 // (verify_phase1) on its member; the challenge is seeded by all the shares' roots, so r differs from the single-device call's while the
 // boolean and the first-error code are the same.
@@ -103,7 +103,7 @@ int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t 
     error_publish(keep);
   }
   if (rc || code) return rc ? rc : code;
-  return kzg_verify_batch_finish(ctx, partials.data(), W, ok);
+  return verify_batch_finish(ctx, partials.data(), W, in.kind == VerifyInputs::CELLS, ok);
 }
 
 // Per-item verdicts (kzg_verify_*_batch_each) over the members: the same contiguous shares, each member's share its own batch with its

@@ -10,6 +10,7 @@
 
 #include <thread>
 #include "verify_kernels.cuh"
+#include "cellverify_kernels.cuh"
 #include "host_lincomb.hpp"
 #include "each_descent.hpp"
 // A verification session: device scratch for n items, a second stream (point decoding beside the evaluation kernel,
@@ -26,13 +27,14 @@ struct kzg_verify_session {
   hipEvent_t ev_nodes = nullptr, ev_stat = nullptr, ev_aux = nullptr;  // owned: transcript digests read back; statuses read back; aux fork
   uint8_t* buf = nullptr;      // owned: one device allocation of `cap` bytes, carved below
   size_t cap = 0;
-  uint4* aff = nullptr;    // [2n+1] affine points: proofs, commitments, generator
-  uint8_t* inf = nullptr;  // [2n+1]
+  uint64_t tail = 1;       // lincomb B's terms behind the 2n points: the generator, or the cells kind's 64 monomial points (verify_tail_terms)
+  uint4* aff = nullptr;    // [2n+tail] affine points: proofs, commitments, generator | monomial points
+  uint8_t* inf = nullptr;  // [2n+tail]
   fr_t* z = nullptr;       // [n] plain
   fr_t* y = nullptr;       // [n] plain
-  fr_t* scal = nullptr;    // [2n+1] plain: r_i*z_i (n), r_i (n), -sum r_i*y_i
+  fr_t* scal = nullptr;    // [2n+tail] plain: r_i*z_i (n), r_i (n), -sum r_i*y_i | cells: -S_j (64)
   bool glv = false;        // n >= 32,768: both lincombs on GLV-split scalars (use_glv)
-  fr_t* glv_b = nullptr;   // [2 (2n+1)]: k1 | k2 of scal
+  fr_t* glv_b = nullptr;   // [2 (2n+tail)]: k1 | k2 of scal
   fr_t* glv_a = nullptr;   // [2n]: k1 | k2 of the r_i
   int32_t* stat = nullptr;   // [4n] blob / commitment / proof status; verify_proof_batch: z / commitment / proof / y status
   unsigned long long* first4 = nullptr;  // verify_proof_batch: (index << 32) | code of the first rejected proof, commitment, z, y (k_first_errors)
@@ -52,6 +54,12 @@ struct kzg_verify_session {
   unsigned long long* h_first4 = nullptr;  // [4] read-back of first4
   size_t h_cap = 0;
   bool points = false;       // the front was verify_proof_batch's: the status arrays are z / commitment / proof / y
+  // the cells kind (front_enqueue sets them): the status arrays are cell / commitment / proof / cell index; phase 2 reads the cells again
+  bool cells = false;
+  const uint8_t* d_cells = nullptr;
+  const uint64_t* d_cell_indices = nullptr;
+  fr_t* cell_part = nullptr;   // [ceil(n / CELLV_CELLS) x 64] k_cells_interp's partial coefficient vectors
+  uint8_t* cells_in = nullptr; // [n * 2048 | n * 8] device copy of cells || cell indices (host-buffer entry point)
   // per-item verdicts (kzg_verify_*_batch_each, kzg_verify_session_tree): a device allocation of its own (owned), made on first use
   // and kept with the pooled session; carved by each_carve for the current n
   uint8_t* tree = nullptr;
@@ -435,19 +443,22 @@ static void scan_first_error(const int32_t* st, uint64_t n, int32_t* idx, int32_
 
 // ---- session set-up -----------------------------------------------------------------------------------------------
 struct SessionLayout {
-  size_t o_aff, o_inf, o_z, o_y, o_scal, o_glv_b, o_glv_a, o_stat, o_first4, o_leaves, o_mids, o_nodes, o_pts, o_zy, o_msm_a, o_msm_b, o_rpow, o_ysum, total;
+  size_t o_aff, o_inf, o_z, o_y, o_scal, o_glv_b, o_glv_a, o_stat, o_first4, o_leaves, o_mids, o_nodes, o_pts, o_zy, o_msm_a, o_msm_b, o_rpow, o_ysum, o_cell_part,
+      o_cells_in, total;
 };
-static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n) {
+// `tail`: verify_tail_terms of the call's kind; `stage_cells`: room for a host-buffer cells call's device copies.  With tail = 1 the
+// layout of the blob and points kinds is what it always was.
+static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n, uint64_t tail, bool stage_cells) {
   SessionLayout L{};
   const uint64_t groups = (n + 255) / 256;
   Carve pool;
   const bool glv = use_glv(ctx, n);
-  L.o_aff = pool.take((glv ? 2 : 1) * (2 * n + 1) * 96);  // GLV: the [z^2]-images behind the points
-  L.o_inf = pool.take(2 * n + 1);
+  L.o_aff = pool.take((glv ? 2 : 1) * (2 * n + tail) * 96);  // GLV: the [z^2]-images behind the points
+  L.o_inf = pool.take(2 * n + tail);
   L.o_z = pool.take(n * 32 + 32);
   L.o_y = pool.take(n * 32 + 32);
-  L.o_scal = pool.take((2 * n + 1) * 32);
-  L.o_glv_b = pool.take(glv ? 2 * (2 * n + 1) * 32 : 0);
+  L.o_scal = pool.take((2 * n + tail) * 32);
+  L.o_glv_b = pool.take(glv ? 2 * (2 * n + tail) * 32 : 0);
   L.o_glv_a = pool.take(glv ? 2 * n * 32 : 0);
   L.o_stat = pool.take(4 * n * 4 + 4);
   L.o_first4 = pool.take(4 * sizeof(unsigned long long));
@@ -456,18 +467,20 @@ static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n) {
   L.o_nodes = pool.take(groups * 32 + 32);
   L.o_pts = pool.take(2 * n * 48 + 48);
   L.o_zy = pool.take(2 * n * 32 + 32);
-  L.o_msm_a = pool.take((glv ? msm_var_layout(ctx, 2 * n, true) : msm_var_layout(ctx, n, false, 3 * n + 1)).total + 256);
-  L.o_msm_b = pool.take((glv ? msm_var_layout(ctx, 2 * (2 * n + 1), true) : msm_var_layout(ctx, 2 * n + 1, false, 3 * n + 1)).total + 256);
+  L.o_msm_a = pool.take((glv ? msm_var_layout(ctx, 2 * n, true) : msm_var_layout(ctx, n, false, 3 * n + tail)).total + 256);
+  L.o_msm_b = pool.take((glv ? msm_var_layout(ctx, 2 * (2 * n + tail), true) : msm_var_layout(ctx, 2 * n + tail, false, 3 * n + tail)).total + 256);
   L.o_rpow = pool.take(64 * 32);
   L.o_ysum = pool.take(((n + 255) / 256 + 1) * 32);
+  L.o_cell_part = pool.take(tail > 1 ? blocks_for(n, CELLV_CELLS) * (size_t)64 * sizeof(fr_t) : 0);
+  L.o_cells_in = pool.take(stage_cells ? n * ((size_t)KZG_BYTES_PER_CELL + 8) : 0);
   L.total = pool.off;
   return L;
 }
 
 // Takes a session from the context's pool (or creates one), sized for n items, and enqueues its initialisation on `st`.
-static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, kzg_verify_session** out) {
+static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, kzg_verify_session** out, uint64_t tail = 1, bool stage_cells = false) {
   *out = nullptr;
-  const SessionLayout L = session_layout(ctx, n);
+  const SessionLayout L = session_layout(ctx, n, tail, stage_cells);
   kzg_verify_session* s = nullptr;
   {
     std::lock_guard<std::mutex> guard(ctx->pool_lock);
@@ -539,6 +552,10 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
   s->n = n;
   s->st = st;
   s->points = false;
+  s->cells = false;
+  s->d_cells = nullptr;
+  s->d_cell_indices = nullptr;
+  s->tail = tail;
   s->tree_n = 0;
   s->aff = (uint4*)(s->buf + L.o_aff);
   s->inf = s->buf + L.o_inf;
@@ -559,10 +576,13 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
   s->msm_b = s->buf + L.o_msm_b;
   s->rpow2 = (fr_t*)(s->buf + L.o_rpow);
   s->ysum = (fr_t*)(s->buf + L.o_ysum);
-  // generator term, cleared flags and statuses
-  if (hipMemcpyAsync(s->aff + (2 * n) * 6, ctx->d_gen_affine, 96, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-      (s->glv && hipMemcpyAsync(s->aff + ((2 * n + 1) + 2 * n) * 6, ctx->d_gen_affine + 6, 96, hipMemcpyDeviceToDevice, st) != hipSuccess) ||  // [z^2]G
-      hipMemsetAsync(s->inf, 0, 2 * n + 1, st) != hipSuccess || hipMemsetAsync(s->stat, 0, 4 * n * 4 + 4, st) != hipSuccess) {
+  s->cell_part = (fr_t*)(s->buf + L.o_cell_part);
+  s->cells_in = s->buf + L.o_cells_in;
+  // generator term (cells: the monomial terms), cleared flags and statuses
+  const uint4* fixed = tail > 1 ? ctx->d_g1_monomial : ctx->d_gen_affine;  // `tail` points, their [z^2]-images behind them
+  if (hipMemcpyAsync(s->aff + (2 * n) * 6, fixed, tail * 96, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+      (s->glv && hipMemcpyAsync(s->aff + ((2 * n + tail) + 2 * n) * 6, fixed + tail * 6, tail * 96, hipMemcpyDeviceToDevice, st) != hipSuccess) ||  // [z^2]G
+      hipMemsetAsync(s->inf, 0, 2 * n + tail, st) != hipSuccess || hipMemsetAsync(s->stat, 0, 4 * n * 4 + 4, st) != hipSuccess) {
     kzg_verify_session_destroy(s);
     return fail(KZG_FAIL_HIP, "verify session init failed");
   }
@@ -593,7 +613,7 @@ static void decode_on_side(kzg_verify_session* s, hipStream_t side, uint64_t fir
       launch_g1_decompress_range(side, first, count, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
   }
   if (!(how & DECODE_FINISH)) return;
-  if (s->glv) hipLaunchKernelGGL(k_glv_points, dim3(blocks_for(2 * n, 64)), dim3(64), 0, side, s->aff, 2 * n, 2 * n + 1);
+  if (s->glv) hipLaunchKernelGGL(k_glv_points, dim3(blocks_for(2 * n, 64)), dim3(64), 0, side, s->aff, 2 * n, 2 * n + s->tail);
   (void)hipEventRecord(s->ev_join, side);
 }
 
@@ -683,6 +703,7 @@ static int32_t p1_root(kzg_verify_session* s, uint8_t* out_root32) {
 // the device copies of a host-buffer call in its session: proofs || commitments, z || y (the blobs pass through the staging arena)
 static VerifyInputs staged_inputs(const kzg_verify_session* s, VerifyInputs::Kind kind) {
   const uint64_t n = s->n;
+  if (kind == VerifyInputs::CELLS) return cell_inputs(s->pts48 + n * 48, s->cells_in + n * (size_t)KZG_BYTES_PER_CELL, s->cells_in, s->pts48, false);
   return kind == VerifyInputs::BLOBS ? blob_inputs(nullptr, s->pts48 + n * 48, s->pts48, false)
                                      : point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32, false);
 }
@@ -698,6 +719,7 @@ static int32_t first_error_code(const int32_t* err, int kinds) {
 // Everything of phase 1 that can be enqueued at once.  When this returns z, y and the statuses are being produced, the decoder's
 // end is ev_join and the transcript's node digests are on their way back behind ev_nodes (p1_root).
 //   BLOBS:  hash, [decoder] || evaluation, transcript (phase1_items, p1_transcript)
+//   CELLS:  as POINTS, with k_cells_leaves (cellverify_kernels.cuh) in k_points_leaves' place
 //   POINTS: neither hash nor evaluation: [decoder for all 2n points on the side stream] || k_points_leaves (parses z and y, their
 //           statuses in the blob slot and the fourth) -> k_transcript_nodes x 2.  The statuses never cross to the host (front_status).
 static int32_t front_enqueue(kzg_verify_session* s, const VerifyInputs& in) {
@@ -710,14 +732,24 @@ static int32_t front_enqueue(kzg_verify_session* s, const VerifyInputs& in) {
       const int32_t rc = phase1_items(s, in.blobs, com, prf, 0, n, st, true);
       return rc ? rc : p1_transcript(s, com, prf);
     }
-    case VerifyInputs::POINTS: {
-      s->points = true;
+    case VerifyInputs::POINTS:
+    case VerifyInputs::CELLS: {
+      // CELLS: the points call's launch order with k_cells_leaves as the front kernel: it parses the index and the cell (their statuses in
+      // the fourth slot and the blob slot), writes z = h^64 and y = 0, and hashes the 34-block leaf; the cells are read again in phase 2
+      s->points = in.kind == VerifyInputs::POINTS;
+      s->cells = in.kind == VerifyInputs::CELLS;
+      s->d_cells = in.cells;
+      s->d_cell_indices = in.cell_indices;
       // the decoder is ONE launch over proofs and commitments: no event after the proof half for lincomb A to wait on instead of ev_join
       decode_on_side(s, s->side, 0, 2 * n, prf, com, DECODE_FINISH | (fused_prep_fits(ctx, n, 2 * n) ? DECODE_WHOLE : 0u));
       if (hipMemsetAsync(s->first4, 0xff, 4 * sizeof(unsigned long long), s->side) != hipSuccess)  // for k_first_errors, later on this stream
         return fail(KZG_FAIL_HIP, "verify_proof_batch: fork failed");
       const uint64_t groups = (n + 255) / 256, nmid = (n + 15) / 16;
-      hipLaunchKernelGGL(k_points_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, prf, in.z32, in.y32, n, s->z, s->y, s->stat, s->stat + 3 * n, s->leaves);
+      if (s->cells)
+        hipLaunchKernelGGL(k_cells_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, reinterpret_cast<const unsigned long long*>(in.cell_indices), in.cells, prf, n,
+                           ctx->d_cellv_h64, s->z, s->y, s->stat + 3 * n, s->stat, s->leaves);
+      else
+        hipLaunchKernelGGL(k_points_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, prf, in.z32, in.y32, n, s->z, s->y, s->stat, s->stat + 3 * n, s->leaves);
       hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(nmid, 64)), dim3(64), 0, st, s->leaves, n, 16u, s->mids);
       hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(groups, 64)), dim3(64), 0, st, s->mids, nmid, 16u, s->nodes);
       if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: phase 1 launch failed");
@@ -732,7 +764,7 @@ static int32_t front_enqueue(kzg_verify_session* s, const VerifyInputs& in) {
 // decoder, not on the caller's: there they would queue up behind the bucket kernels of phase 2.
 //   BLOBS:  3n status words come back and the host scans them beside the bucket kernels (the blob statuses were written by the
 //           evaluation kernel, which ended before the root was read)
-//   POINTS: k_first_errors (it also waits for k_points_leaves' two status arrays: ev_nodes was recorded after it) and 32 bytes come back
+//   POINTS, CELLS: k_first_errors (it also waits for k_points_leaves' two status arrays: ev_nodes was recorded after it) and 32 bytes come back
 static int32_t front_status(kzg_verify_session* s, const VerifyInputs& in, int32_t* err) {
   const uint64_t n = s->n;
   hipStream_t side = s->side;
@@ -744,8 +776,12 @@ static int32_t front_status(kzg_verify_session* s, const VerifyInputs& in, int32
       for (int k = 0; k < 3; k++) scan_first_error(s->h_stat + k * n, n, &err[2 * k], &err[2 * k + 1]);
       return 0;
     case VerifyInputs::POINTS:
+    case VerifyInputs::CELLS:
       if (hipStreamWaitEvent(side, s->ev_nodes, 0) != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: status wait failed");
-      hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(n, 256)), dim3(256), 0, side, s->stat + 2 * n, s->stat + n, s->stat, s->stat + 3 * n, n, s->first4);
+      if (in.kind == VerifyInputs::CELLS)  // cell index, commitment, cell, proof
+        hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(n, 256)), dim3(256), 0, side, s->stat + 3 * n, s->stat + n, s->stat, s->stat + 2 * n, n, s->first4);
+      else
+        hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(n, 256)), dim3(256), 0, side, s->stat + 2 * n, s->stat + n, s->stat, s->stat + 3 * n, n, s->first4);
       if (hipGetLastError() != hipSuccess || hipMemcpyAsync(s->h_first4, s->first4, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, side) != hipSuccess ||
           hipEventRecord(s->ev_stat, side) != hipSuccess || hipEventSynchronize(s->ev_stat) != hipSuccess)
         return fail(KZG_FAIL_HIP, "verify_proof_batch: status readback failed");
@@ -856,6 +892,7 @@ static int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, cons
   return 0;
 }
 
+// Host cells (CELLS): 2,152 bytes per tuple the same way, the cells and indices into the session's cells_in.
 // Host points: 160 bytes per tuple cross PCIe whole into the session's own staging (proofs || commitments, z || y) on the
 // context's verification stream; nothing of the blob calls' staging arena is used, so stage_lock is held for stage_init only.
 static int32_t points_stage_host(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, kzg_verify_session** out) {
@@ -866,13 +903,17 @@ static int32_t points_stage_host(const kzg_ctx* ctx, const VerifyInputs& in, uin
     if (rc) return rc;
   }
   SessionUse use;
-  const int32_t rc = session_acquire(ctx, n, ctx->verify_stream, &use.s);
+  const bool cells = in.kind == VerifyInputs::CELLS;
+  const int32_t rc = session_acquire(ctx, n, ctx->verify_stream, &use.s, verify_tail_terms(in.kind), cells);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   if (hipMemcpyAsync(s->pts48, in.proofs48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-      hipMemcpyAsync(s->pts48 + n * 48, in.commitments48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-      hipMemcpyAsync(s->zy32, in.z32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-      hipMemcpyAsync(s->zy32 + n * 32, in.y32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess)
+      hipMemcpyAsync(s->pts48 + n * 48, in.commitments48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess)
+    return fail(KZG_FAIL_HIP, "host-to-device copy failed");
+  if (cells ? (hipMemcpyAsync(s->cells_in, in.cells, n * (size_t)KZG_BYTES_PER_CELL, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+               hipMemcpyAsync(s->cells_in + n * (size_t)KZG_BYTES_PER_CELL, in.cell_indices, n * 8, hipMemcpyHostToDevice, s->st) != hipSuccess)
+            : (hipMemcpyAsync(s->zy32, in.z32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+               hipMemcpyAsync(s->zy32 + n * 32, in.y32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess))
     return fail(KZG_FAIL_HIP, "host-to-device copy failed");
   *out = use.release();
   return 0;
@@ -883,12 +924,16 @@ static int32_t points_stage_host(const kzg_ctx* ctx, const VerifyInputs& in, uin
 int32_t verify_phase1(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, uint8_t* out_root32, int32_t* err, kzg_verify_session** session) {
   *session = nullptr;
   HIP_TRY(hipSetDevice(ctx->device));
+  if (in.kind == VerifyInputs::CELLS) {
+    const int32_t rc = ensure_g1_monomial(ctx);
+    if (rc) return rc;
+  }
   if (in.on_host && in.kind == VerifyInputs::BLOBS)  // through the staging arena: front and root while stage_lock is held
     return verify_phase1_host(ctx, in.blobs, in.commitments48, in.proofs48, n, out_root32, err, session);
   TraceTimer tt(ctx->knobs.trace, "phase1");
   err_clear(err, in.kinds());
   SessionUse use;
-  int32_t rc = in.on_host ? points_stage_host(ctx, in, n, &use.s) : session_acquire(ctx, n, st, &use.s);
+  int32_t rc = in.on_host ? points_stage_host(ctx, in, n, &use.s) : session_acquire(ctx, n, st, &use.s, verify_tail_terms(in.kind));
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   tt.mark("session");
@@ -1068,7 +1113,7 @@ struct Phase2 {
 static int32_t p2_seed(kzg_verify_session* s, const uint8_t* roots32, uint64_t world, uint64_t n_total) {
   hipStream_t st = s->st;
   std::vector<uint8_t> msg(48 + 32 * world);
-  memcpy(msg.data(), "RCKZGBATCH___V1_", 16);
+  memcpy(msg.data(), s->cells ? "RCKZGCBATCH__V1_" : "RCKZGBATCH___V1_", 16);  // the spec's domains of the blob batch and the cell batch
   memset(msg.data() + 16, 0, 32);
   msg[30] = 0x10;  // 4096 as u128 big-endian
   for (int k = 0; k < 8; k++) msg[47 - k] = (uint8_t)(n_total >> (8 * k));
@@ -1092,8 +1137,17 @@ static int32_t p2_scalars(kzg_verify_session* s, const uint8_t* roots32, uint64_
   if (rc) return rc;
   const unsigned nblk = blocks_for(n, 256);
   hipLaunchKernelGGL(k_batch_scalars, dim3(nblk), dim3(256), 0, st, s->rpow2, s->z, s->y, n, first_index, s->scal + n, s->scal, s->ysum);
-  hipLaunchKernelGGL(k_batch_ysum_finish, dim3(1), dim3(256), 0, st, s->ysum, nblk, s->scal + 2 * n);
-  if (s->glv) hipLaunchKernelGGL(k_glv_split, dim3(blocks_for(2 * n + 1, 256)), dim3(256), 0, st, s->scal, n, s->glv_b, s->glv_a);
+  if (s->cells) {
+    // y = 0: the generator's slot is S_0's.  The 64 scalars -S_j of the monomial terms: r^k (s->scal + n, just written) times the
+    // interpolation polynomial of cell k, summed per workgroup, then over the workgroups
+    const unsigned ngrp = blocks_for(n, CELLV_CELLS);
+    hipLaunchKernelGGL(k_cells_interp, dim3(ngrp), dim3(CELLV_THREADS), 0, st, s->d_cells, reinterpret_cast<const unsigned long long*>(s->d_cell_indices),
+                       s->stat + 3 * n, s->stat, s->scal + n, n, s->ctx->d_cells_tab, s->ctx->d_cellv_tab, s->cell_part);
+    hipLaunchKernelGGL(k_cells_reduce, dim3(1), dim3(256), 0, st, s->cell_part, ngrp, s->scal + 2 * n);
+  } else {
+    hipLaunchKernelGGL(k_batch_ysum_finish, dim3(1), dim3(256), 0, st, s->ysum, nblk, s->scal + 2 * n);
+  }
+  if (s->glv) hipLaunchKernelGGL(k_glv_split, dim3(blocks_for(2 * n + s->tail, 256)), dim3(256), 0, st, s->scal, n, s->tail, s->glv_b, s->glv_a);
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "verify phase 2 launch failed");
   return 0;
 }
@@ -1103,7 +1157,7 @@ static int32_t p2_scalars(kzg_verify_session* s, const uint8_t* roots32, uint64_
 //     infinity flags (which the decoder may not have written yet).
 static int32_t p2_sort(kzg_verify_session* s, Phase2& p2, bool beside_decoder) {
   const kzg_ctx* ctx = s->ctx;
-  const uint64_t n = s->n;
+  const uint64_t n = s->n, nb = 2 * n + s->tail;  // lincomb B's terms
   (void)hipEventRecord(s->ev_aux, s->st);
   (void)hipStreamWaitEvent(s->aux, s->ev_aux, 0);
   const uint8_t* inf = beside_decoder ? nullptr : s->inf;
@@ -1111,21 +1165,21 @@ static int32_t p2_sort(kzg_verify_session* s, Phase2& p2, bool beside_decoder) {
   if (s->glv) {  // (points at infinity are all-zero entries, theirs and their images': the bucket chains skip them, no flags needed)
     {
       ProfScope psb(ctx, PROF_VAR_MSM, s->st);
-      rc = msm_var_sort(ctx, p2.jb, nullptr, s->glv_b, 2 * (2 * n + 1), s->st, s->msm_b, beside_decoder, true, 2 * n + 1, 2 * n + 1);
+      rc = msm_var_sort(ctx, p2.jb, nullptr, s->glv_b, 2 * nb, s->st, s->msm_b, beside_decoder, true, nb, nb);
     }
     if (rc == 0) {
       ProfScope psa(ctx, PROF_VAR_MSM, s->aux);
-      rc = msm_var_sort(ctx, p2.ja, nullptr, s->glv_a, 2 * n, s->aux, s->msm_a, beside_decoder, true, n, 2 * n + 1);
+      rc = msm_var_sort(ctx, p2.ja, nullptr, s->glv_a, 2 * n, s->aux, s->msm_a, beside_decoder, true, n, nb);
     }
     return rc;
   }
   {
     ProfScope psb(ctx, PROF_VAR_MSM, s->st);
-    rc = msm_var_sort(ctx, p2.jb, inf, s->scal, 2 * n + 1, s->st, s->msm_b, beside_decoder, false, 0, 0, 3 * n + 1);
+    rc = msm_var_sort(ctx, p2.jb, inf, s->scal, nb, s->st, s->msm_b, beside_decoder, false, 0, 0, n + nb);
   }
   if (rc == 0) {
     ProfScope psa(ctx, PROF_VAR_MSM, s->aux);
-    rc = msm_var_sort(ctx, p2.ja, inf, s->scal + n, n, s->aux, s->msm_a, beside_decoder, false, 0, 0, 3 * n + 1);
+    rc = msm_var_sort(ctx, p2.ja, inf, s->scal + n, n, s->aux, s->msm_a, beside_decoder, false, 0, 0, n + nb);
   }
   return rc;
 }
@@ -1187,7 +1241,7 @@ static int32_t p2_finish_and_pair(kzg_verify_session* s, Phase2& p2, int32_t* ok
   if (!(p2.ja.active && p2.jb.active && (p2.ja.nout + p2.jb.nout) >= 64)) {  // a handful of terms: the plain path
     uint8_t partial[192];
     int32_t rc = p2_finish(s, p2, partial);
-    return rc ? rc : kzg_verify_batch_finish(ctx, partial, 1, ok);
+    return rc ? rc : verify_batch_finish(ctx, partial, 1, s->cells, ok);
   }
   TraceTimer tt(ctx->knobs.trace, "phase2 finish + pairing");
   host::fp12 fa = host::f12_one(), fb = host::f12_one();
@@ -1207,7 +1261,7 @@ static int32_t p2_finish_and_pair(kzg_verify_session* s, Phase2& p2, int32_t* ok
   (void)run_on_helpers(2, [&](uint32_t k) -> int32_t {
     if (k == 0) return rcb = one(p2.jb, ctx->pairing->lines_g2, false, fb);
     (void)hipSetDevice(device);
-    return rca = one(p2.ja, ctx->pairing->lines_tau, true, fa);
+    return rca = one(p2.ja, s->cells ? ctx->pairing->lines_tau64 : ctx->pairing->lines_tau, true, fa);  // cells: e(A, [tau^64]_2)
   });
   (void)hipStreamSynchronize(s->st);
   tt.mark("read-backs, horner, miller loops (two threads)");
@@ -1317,6 +1371,11 @@ extern "C" int32_t kzg_verify_session_zy(kzg_verify_session* s, uint64_t first, 
 
 extern "C" int32_t kzg_verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint64_t world, int32_t* ok) try {
   if (!ctx || !ok || (world && !partials192)) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return verify_batch_finish(ctx, partials192, world, false, ok);
+} catch (...) {
+  return abi_exception();
+}
+int32_t verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint64_t world, bool cells, int32_t* ok) {
   *ok = 0;
   g1_xyzz A, B;
   xyzz_set_inf(A);
@@ -1332,11 +1391,9 @@ extern "C" int32_t kzg_verify_batch_finish(const kzg_ctx* ctx, const uint8_t* pa
   TraceTimer tt(ctx->knobs.trace, "finish");
   host_affine_from_xyzz(a, A);
   host_affine_from_xyzz(b, B);
-  *ok = host::verify_pairings_fixed(*ctx->pairing, a, b) ? 1 : 0;
+  *ok = host::verify_pairings_fixed(*ctx->pairing, a, b, cells) ? 1 : 0;
   tt.mark("pairing");
   return 0;
-} catch (...) {
-  return abi_exception();
 }
 
 // The answer every batch entry point gives before anything else is looked at: the empty batch verifies (reference quirk Q4).
@@ -1748,6 +1805,11 @@ static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, const Ver
 int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, const VerifyEach* each, int32_t* ok) {
   *ok = 0;
   const bool blobs = in.kind == VerifyInputs::BLOBS;
+  if (each && in.kind == VerifyInputs::CELLS) return fail(KZG_FAIL_ARGUMENT, "per-item verdicts are not available for cells");
+  if (in.kind == VerifyInputs::CELLS) {  // lincomb B's fixed terms: derived by this member's first cells call
+    const int32_t rc = ensure_g1_monomial(ctx);
+    if (rc) return rc;
+  }
   if (each && n == 1) {  // per-item verdicts of one item: the boolean call's answer in the per-item outputs
     int32_t one = 0;
     const int32_t rc = verify_batch_single(ctx, in, 1, st, nullptr, &one);
@@ -1757,7 +1819,7 @@ int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t
     return 0;
   }
   // one tuple from host buffers: z and y parsed on the host, the lincombs there too (verify_one_on_host)
-  if (n == 1 && in.on_host && !blobs) return verify_proof_single(ctx, in.proofs48, in.commitments48, in.z32, in.y32, ok);
+  if (n == 1 && in.on_host && in.kind == VerifyInputs::POINTS) return verify_proof_single(ctx, in.proofs48, in.commitments48, in.z32, in.y32, ok);
   HIP_TRY(hipSetDevice(ctx->device));
   SessionUse use;
   uint8_t root[32];
@@ -1767,7 +1829,7 @@ int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t
   const bool front_done = in.on_host && blobs;
   int32_t rc = front_done   ? verify_phase1_host(ctx, in.blobs, in.commitments48, in.proofs48, n, root, each ? err6 : nullptr, &use.s)
                : in.on_host ? points_stage_host(ctx, in, n, &use.s)
-                            : session_acquire(ctx, n, st, &use.s);
+                            : session_acquire(ctx, n, st, &use.s, verify_tail_terms(in.kind));
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   const VerifyInputs dev = in.on_host ? staged_inputs(s, in.kind) : in;
@@ -1775,7 +1837,9 @@ int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t
     if (!front_done) rc = phase1_items(s, dev.blobs, dev.commitments48, dev.proofs48, 0, 1, s->st, true);
     return rc ? rc : verify_one_tail(s, ok);
   }
-  if (!each) return verify_fused(s, dev, ok, blobs ? "verify (fused phases)" : "verify_proof_batch (fused phases)", front_done ? root : nullptr);
+  if (!each)
+    return verify_fused(s, dev, ok, blobs ? "verify (fused phases)" : in.kind == VerifyInputs::CELLS ? "verify_cell_proof_batch (fused phases)" : "verify_proof_batch (fused phases)",
+                        front_done ? root : nullptr);
   if (!front_done) {
     rc = front_enqueue(s, dev);
     if (rc == 0) rc = p1_root(s, root);
@@ -1822,6 +1886,32 @@ extern "C" int32_t kzg_verify_proof_batch_each(const kzg_ctx* ctx, const uint8_t
   return is_group(ctx) ? multi_verify_each(ctx, in, n, each, ok) : verify_batch_single(ctx, in, n, nullptr, &each, ok);
 } catch (...) {
   return abi_exception();
+}
+
+// ---- verify_cell_kzg_proof_batch (EIP-7594) as the third kind of batch call: n (commitment, cell index, cell, proof) tuples -------------
+// The points batch's drivers over cell_inputs: the front (k_cells_leaves), the 64 scalars of the monomial terms in p2_scalars
+// (k_cells_interp, k_cells_reduce), lincomb B's 2n + 64 terms and the pairing against [tau^64]_2 differ -- each behind the session's kind.
+extern "C" int32_t kzg_verify_cell_proof_batch_dev(const kzg_ctx* ctx, const void* d_commitments48, const void* d_cell_indices, const void* d_cells,
+                                                   const void* d_proofs48, uint64_t n, int32_t* ok, void* hip_stream) try {
+  const VerifyInputs in = cell_inputs(d_commitments48, d_cell_indices, d_cells, d_proofs48, false);
+  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, nullptr, ok) : empty_batch(ok);
+} catch (...) {
+  return abi_exception();
+}
+
+extern "C" int32_t kzg_verify_cell_proof_batch(const kzg_ctx* ctx, const uint8_t* commitments48, const uint64_t* cell_indices, const uint8_t* cells,
+                                               const uint8_t* proofs48, uint64_t n, int32_t* ok) try {
+  const VerifyInputs in = cell_inputs(commitments48, cell_indices, cells, proofs48, true);
+  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return empty_batch(ok);
+  return is_group(ctx) ? multi_verify_batch(ctx, in, n, ok) : verify_batch_single(ctx, in, n, nullptr, nullptr, ok);
+} catch (...) {
+  return abi_exception();
+}
+
+void launch_glv_points(hipStream_t st, uint4* aff, uint64_t npts, uint64_t phi_off) {
+  if (npts) hipLaunchKernelGGL(k_glv_points, dim3(blocks_for(npts, 64)), dim3(64), 0, st, aff, npts, phi_off);
 }
 
 void warm_code_object_verify() {

@@ -519,15 +519,17 @@ inline fp12 f12_pow_big(const fp12& a, const std::vector<uint32_t>& e) {
 struct pairing_ctx {
   frob_consts fc;
   miller_lines lines_g2, lines_tau;  // Q = G2 generator, Q = [tau]_2
+  miller_lines lines_tau64;          // Q = [tau^64]_2 = g2_monomial[64]: the cells kind of batch verification (EIP-7594)
 };
 
 // e(-A, [tau]_2) * e(B, G2) == 1   (bls::verify_pairings, src/bls.rs:572-598, with
 // (a1,a2) = (A,[tau]_2) and (b1,b2) = (B, G2) as called at src/kzg/setup.rs:157-160)
-inline bool verify_pairings_fixed(const pairing_ctx& pc, const g1_host_affine& a, const g1_host_affine& b) {
+// `cells`: e(-A, [tau^64]_2) * e(B, G2) == 1, the batched cell check
+inline bool verify_pairings_fixed(const pairing_ctx& pc, const g1_host_affine& a, const g1_host_affine& b, bool cells = false) {
   g1_host_affine na = a;
   if (!na.inf) fp_neg(na.y, na.y);
   g1_host_affine ps[2] = {na, b};
-  const miller_lines* ls[2] = {&pc.lines_tau, &pc.lines_g2};
+  const miller_lines* ls[2] = {cells ? &pc.lines_tau64 : &pc.lines_tau, &pc.lines_g2};
   fp12 f = multi_miller(ps, ls, 2);
   return final_exp_is_one(f, pc.fc);
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include "cells_math.cuh"
 #include "recover_math.cuh"
+#include "cellverify_math.cuh"
 #include "fp30.cuh"
 #include "fr29.cuh"
 #include "msm_fixed.cuh"
@@ -217,6 +218,39 @@ static __global__ __launch_bounds__(64) void k_setup_recover_tab(uint32_t* __res
   recover_tab_entry(i, e);
 #pragma unroll
   for (int q = 0; q < CELLS_TAB_ENTRY; q++) recover_tab[(uint64_t)i * CELLS_TAB_ENTRY + q] = e[q];
+}
+
+// the same for cell verification's table (cellverify_math.cuh) and, by its first 128 threads, z of every column: h_c^64, plain
+static __global__ __launch_bounds__(64) void k_setup_cellv_tab(uint32_t* __restrict__ cellv_tab, fr_t* __restrict__ h64_plain) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= CELLV_TAB_ENTRIES) return;
+  uint32_t e[CELLS_TAB_ENTRY];
+  cellv_tab_entry(i, e);
+#pragma unroll
+  for (int q = 0; q < CELLS_TAB_ENTRY; q++) cellv_tab[(uint64_t)i * CELLS_TAB_ENTRY + q] = e[q];
+  if (i < 128u) {
+    fr_t h;
+    cellv_h64_plain(h, i);
+    h64_plain[i] = h;
+  }
+}
+
+// The blobs whose commitments are the first `count` monomial setup points: [tau^j]_1 commits to X^j, i.e. to the blob whose element i is
+// roots_brp[i]^j.  One thread per element, 32 big-endian bytes each.
+static __global__ __launch_bounds__(256) void k_setup_monomial_blobs(const fr_t* __restrict__ roots_brp, uint32_t count, uint8_t* __restrict__ blobs) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t j = t >> 12, i = t & 4095u;
+  if (j >= count) return;
+  const fr_t w = roots_brp[i];
+  fr_t acc = fr_one();
+  for (int bit = 7; bit >= 0; bit--) {
+    fr_sqr(acc, acc);
+    if ((j >> bit) & 1u) fr_mul(acc, acc, w);
+  }
+  from_mont<FrParams>(acc, acc);
+  uint4* out = reinterpret_cast<uint4*>(blobs + (uint64_t)j * 131072u + 32u * i);
+  out[0] = make_uint4(__builtin_bswap32(acc.v[7]), __builtin_bswap32(acc.v[6]), __builtin_bswap32(acc.v[5]), __builtin_bswap32(acc.v[4]));
+  out[1] = make_uint4(__builtin_bswap32(acc.v[3]), __builtin_bswap32(acc.v[2]), __builtin_bswap32(acc.v[1]), __builtin_bswap32(acc.v[0]));
 }
 
 #endif

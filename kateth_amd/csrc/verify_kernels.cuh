@@ -793,11 +793,13 @@ static __global__ __launch_bounds__(256) void k_var_scatter(const fr_t* __restri
 }
 
 // ---- GLV (glv.cuh): scalars split at z^2, points mapped by [z^2](x, y) = (beta x, -y) ------------------------------------------
-// scal = the batch scalars as k_batch_scalars / k_batch_ysum_finish leave them: [r_i z_i (n) | r_i (n) | -sum r_i y_i (1)], plain.
-// out_b (2 (2n + 1)): lincomb B's terms  [k1 of all 2n + 1 | k2 of all 2n + 1];  out_a (2n): lincomb A's  [k1 of r_i | k2 of r_i].
-static __global__ __launch_bounds__(256) void k_glv_split(const fr_t* __restrict__ scal, uint64_t n, fr_t* __restrict__ out_b, fr_t* __restrict__ out_a) {
+// scal = the batch scalars as k_batch_scalars / k_batch_ysum_finish leave them: [r_i z_i (n) | r_i (n) | -sum r_i y_i (1)], plain; the
+// cells kind has its 64 monomial scalars in the last slot's place: tail = 1 or 64.
+// out_b (2 (2n + tail)): lincomb B's terms  [k1 of all 2n + tail | k2 of all 2n + tail];  out_a (2n): lincomb A's  [k1 of r_i | k2 of r_i].
+static __global__ __launch_bounds__(256) void k_glv_split(const fr_t* __restrict__ scal, uint64_t n, uint64_t tail, fr_t* __restrict__ out_b,
+                                                   fr_t* __restrict__ out_a) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t nt = 2 * n + 1;
+  const uint64_t nt = 2 * n + tail;
   if (t >= nt) return;
   fr_t k1, k2;
   glv_split(k1, k2, scal[t]);

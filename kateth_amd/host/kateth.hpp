@@ -10,6 +10,7 @@
 //   proof(blob, z)                       <- src/kzg/setup.rs:185-194
 //   verify_proof(proof, commitment, z, y)<- src/kzg/setup.rs:96-113
 //   verify_proof_batch(ps, cs, zs, ys)   <- src/kzg/setup.rs:115-161 behind :96-113 per tuple
+//   verify_cell_proof_batch(cs, idx, cells, ps) <- EIP-7594 verify_cell_kzg_proof_batch (specs/fulu/polynomial-commitments-sampling.md)
 //   decompress(bytes48) -> P1            <- P1::decompress, src/bls.rs:505-531
 //   verify_blob_proof(blob, c, p)        <- src/kzg/setup.rs:208-221
 //   verify_blob_proof_batch(blobs,cs,ps) <- src/kzg/setup.rs:247-275
@@ -51,6 +52,7 @@ enum class ErrorKind : int32_t {
   FiniteFieldNotInFiniteField = KZG_ERR_FF_NOT_IN_FIELD,         // src/bls.rs:24
   CellsNotEnough = KZG_ERR_CELLS_NOT_ENOUGH,                     // recover_cells: fewer than 64 cells
   CellsInconsistent = KZG_ERR_CELLS_INCONSISTENT,                // recover_cells: the cells do not lie on one polynomial of degree < 4096
+  CellIndex = KZG_ERR_CELL_INDEX,                                // verify_cell_proof_batch: a cell index >= 128
 };
 
 class Error : public std::runtime_error {
@@ -442,6 +444,33 @@ class Setup {
     int32_t ok = 0;
     int32_t rc = kzg_verify_proof_batch(ctx_.get(), ps.data(), cs.data(), zs.data(), ys.data(), n, &ok);
     return finish(rc, ok, "kzg_verify_proof_batch");
+  }
+
+  // verify_cell_kzg_proof_batch (EIP-7594) with c-kzg-4844's argument shape: one commitment per cell; cells = the cells concatenated,
+  // 2,048 bytes each.  Throws Error with the kind of the first rejected input in the spec's order of assertions lifted to lists:
+  // every index (CellIndex), then every commitment, then every cell (BlobInvalidFieldElement), then every proof.
+  bool verify_cell_proof_batch(const std::vector<Bytes48>& commitments, const std::vector<uint64_t>& cell_indices, const uint8_t* cells, size_t cells_len,
+                               const std::vector<Bytes48>& proofs) const {
+    const size_t n = commitments.size();
+    if (cell_indices.size() != n || proofs.size() != n || cells_len != n * BYTES_PER_CELL)
+      throw std::invalid_argument("verify_cell_proof_batch: one index, one 2048-byte cell and one proof per commitment");
+    std::vector<uint8_t> cs(n * 48), ps(n * 48);
+    for (size_t i = 0; i < n; i++) {
+      std::copy(commitments[i].begin(), commitments[i].end(), cs.begin() + i * 48);
+      std::copy(proofs[i].begin(), proofs[i].end(), ps.begin() + i * 48);
+    }
+    int32_t ok = 0;
+    int32_t rc = kzg_verify_cell_proof_batch(ctx_.get(), cs.data(), cell_indices.data(), cells, ps.data(), n, &ok);
+    return finish(rc, ok, "kzg_verify_cell_proof_batch");
+  }
+
+  // the first 64 monomial G1 setup points [tau^j]_1 the context derives on first use, 48 bytes each
+  std::vector<Bytes48> g1_monomial(uint32_t first = 0, uint32_t count = KZG_G1_MONOMIAL_POINTS) const {
+    std::vector<Bytes48> out(count);
+    std::vector<uint8_t> raw(static_cast<size_t>(count) * 48);
+    check(kzg_ctx_g1_monomial(ctx_.get(), first, count, raw.data()), "kzg_ctx_g1_monomial");
+    for (uint32_t i = 0; i < count; i++) std::copy(raw.begin() + i * 48, raw.begin() + (i + 1) * 48, out[i].begin());
+    return out;
   }
 
   // Per-item verdicts: entry i is what verify_blob_proof / verify_proof returns for item i alone -- `ok`, or with status != 0 the

@@ -13,6 +13,7 @@ Method names, argument meaning and error behaviour follow the reference:
     Setup.verify_blob_proof(blob, c, p)          src/kzg/setup.rs:208-221
     Setup.verify_blob_proof_batch(blobs, cs, ps) src/kzg/setup.rs:247-275
     Setup.verify_proof_batch(ps, cs, zs, ys)     src/kzg/setup.rs:115-161 behind :96-113 per tuple
+    Setup.verify_cell_proof_batch(cs, idx, cells, ps)  EIP-7594 verify_cell_kzg_proof_batch (same document as compute_cells)
 
 Points cross this boundary in their 48-byte compressed form (what every caller
 of the reference does next: benches/kzg.rs:25-32, src/kzg/setup.rs:341-343).
@@ -75,7 +76,7 @@ class LoadSetupError(Exception):
 
 
 class CellsError(Exception):
-    """rejections of `recover_cells` (EIP-7594); the reference has no counterpart."""
+    """rejections of `recover_cells` and of a cell index in `verify_cell_proof_batch` (EIP-7594); the reference has no counterpart."""
 
     def __init__(self, kind: str):
         super().__init__("cells::Error::" + kind)
@@ -96,6 +97,7 @@ _STATUS = {
     7: lambda: FiniteFieldError("NotInFiniteField"),
     8: lambda: CellsError("NotEnoughCells"),
     9: lambda: CellsError("Inconsistent"),
+    10: lambda: CellsError("CellIndex"),
 }
 
 
@@ -106,6 +108,12 @@ def error_from_status(code: int) -> Exception:
 def _kzg_error(code: int) -> KzgError:
     inner = error_from_status(code)
     return KzgError(inner if isinstance(inner, BlobError) else BlsError(inner))
+
+
+def _cell_verify_error(code: int) -> Exception:
+    """verify_cell_proof_batch's rejections: CellsError for a cell index, KzgError for a commitment, a cell or a proof"""
+    inner = error_from_status(code)
+    return inner if isinstance(inner, CellsError) else _kzg_error(code)
 
 
 # ---------------------------------------------------------------------------
@@ -181,6 +189,9 @@ _SIGNATURES = {
     "kzg_verify_proof": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, _u8p, _i32p]),
     "kzg_verify_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
     "kzg_verify_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
+    "kzg_verify_cell_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u64p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
+    "kzg_verify_cell_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
+    "kzg_ctx_g1_monomial": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, _u8p]),
     "kzg_verify_proof_batch_group_dev": (ctypes.c_int32, [ctypes.c_void_p, _vpp, _vpp, _vpp, _vpp, _u64p, _i32p, _vpp]),
     "kzg_verify_proof_phase1_dev": (
         ctypes.c_int32,
@@ -851,6 +862,50 @@ class Setup:
             raise _kzg_error(rc)
         return bool(ok.value)
 
+    def verify_cell_proof_batch(self, commitments: Sequence[bytes], cell_indices: Sequence[int], cells: Sequence[bytes], proofs: Sequence[bytes]) -> bool:
+        """`verify_cell_kzg_proof_batch` (EIP-7594) with c-kzg-4844's argument shape: one commitment per cell.  Unequal lengths, an item
+        of the wrong size and an index that is no uint64 are a ValueError in the caller.  Raises CellsError CellIndex for an index >= 128
+        and KzgError for a rejected commitment, cell (BlobError InvalidFieldElement) or proof -- the first rejected input in the spec's
+        order of assertions lifted to lists: every index, then every commitment, then every cell, then every proof."""
+        n = len(commitments)
+        if not (len(cell_indices) == n and len(cells) == n and len(proofs) == n):
+            raise ValueError("verify_cell_proof_batch: %d commitments, %d indices, %d cells, %d proofs" % (n, len(cell_indices), len(cells), len(proofs)))
+        commitments, cells, proofs = [_buf(v) for v in commitments], [_buf(v) for v in cells], [_buf(v) for v in proofs]
+        cell_indices = [int(c) for c in cell_indices]
+        if any(len(v) != 48 for v in commitments) or any(len(v) != 48 for v in proofs):
+            raise ValueError("verify_cell_proof_batch: a commitment or proof is 48 bytes")
+        if any(len(v) != BYTES_PER_CELL for v in cells):
+            raise ValueError("verify_cell_proof_batch: a cell is %d bytes" % BYTES_PER_CELL)
+        if any(not 0 <= c < 1 << 64 for c in cell_indices):
+            raise ValueError("verify_cell_proof_batch: a cell index is a uint64")
+        return self.verify_cell_proof_batch_host(b"".join(commitments), cell_indices, b"".join(cells), b"".join(proofs), n)
+
+    def verify_cell_proof_batch_host(self, commitments, cell_indices, cells, proofs, n: int) -> bool:
+        """kzg_verify_cell_proof_batch on n CONTIGUOUS tuples in host memory: bytes-like objects or raw host addresses (ints); the
+        indices as a sequence of ints, a bytes-like object of n native uint64 or a raw host address"""
+        ok = ctypes.c_int32(0)
+        if isinstance(cell_indices, int):
+            cell_indices = ctypes.cast(cell_indices, _u64p)
+        elif isinstance(cell_indices, (bytes, bytearray, memoryview)):
+            cell_indices = (ctypes.c_uint64 * n).from_buffer_copy(cell_indices)
+        else:
+            cell_indices = (ctypes.c_uint64 * n)(*cell_indices)
+        args = [a if isinstance(a, int) else _buf(a) for a in (commitments, cells, proofs)]
+        rc = self._lib.kzg_verify_cell_proof_batch(self._h, args[0], cell_indices, args[1], args[2], n, ctypes.byref(ok))
+        self._check(rc, "kzg_verify_cell_proof_batch")
+        if rc > 0:
+            raise _cell_verify_error(rc)
+        return bool(ok.value)
+
+    def g1_monomial(self, first: int = 0, count: int = 64) -> List[bytes]:
+        """the 48-byte encodings of the monomial G1 setup points [tau^j]_1, first <= j < first + count <= 64, which the context derives
+        on first use (kzg_ctx_g1_monomial)"""
+        out = (ctypes.c_uint8 * (48 * count))()
+        rc = self._lib.kzg_ctx_g1_monomial(self._h, first, count, ctypes.cast(out, _u8p))
+        self._check(rc, "kzg_ctx_g1_monomial")
+        raw = bytes(out)
+        return [raw[48 * k:48 * k + 48] for k in range(count)]
+
     def verify_blob_proof(self, blob: bytes, commitment: bytes, proof: bytes) -> bool:
         blob, commitment, proof = _buf(blob), _buf(commitment), _buf(proof)
         if len(blob) != BYTES_PER_BLOB:
@@ -1016,6 +1071,15 @@ class Setup:
         rc = self._lib.kzg_verify_blob_proof_batch_each_dev(self._h, d_blobs, d_commitments, d_proofs, n, ctypes.cast(ok_each, ctypes.c_void_p), status,
                                                             ctypes.byref(ok), stream)
         return self._each_result(rc, "kzg_verify_blob_proof_batch_each_dev", n, ok_each, status, ok)
+
+    def verify_cell_proof_batch_dev(self, d_commitments: int, d_cell_indices: int, d_cells: int, d_proofs: int, n: int, stream: int = 0) -> bool:
+        """kzg_verify_cell_proof_batch_dev: device pointers (16-byte aligned) to n commitments, n uint64 indices, n cells, n proofs"""
+        ok = ctypes.c_int32(0)
+        rc = self._lib.kzg_verify_cell_proof_batch_dev(self._h, d_commitments, d_cell_indices, d_cells, d_proofs, n, ctypes.byref(ok), stream)
+        self._check(rc, "kzg_verify_cell_proof_batch_dev")
+        if rc > 0:
+            raise _cell_verify_error(rc)
+        return bool(ok.value)
 
     def verify_proof_batch_each_dev(self, d_proofs: int, d_commitments: int, d_points: int, d_evals: int, n: int, stream: int = 0):
         """-> (ok_each: List[bool], status: List[int], ok: bool); synchronous, results in host memory"""
