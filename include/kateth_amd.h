@@ -388,7 +388,7 @@ int32_t kzg_verify_proof_batch_group_dev(const kzg_ctx* ctx, const void* const* 
  * Introspection: the 48-byte encodings of the monomial G1 setup points [tau^j]_1, first <= j < first + count, first + count <= 64.
  * A Setup<4096, 65> file carries the Lagrange form only; the context derives these 64 on the device as the commitments of the
  * blobs of X^j (element i = roots_brp[i]^j) through its own commitment path, on whichever table stands then -- ONCE, in its first
- * kzg_verify_cell_proof_batch[_dev] or kzg_ctx_g1_monomial call (64 commitments, about a millisecond), not in kzg_ctx_create: a
+ * kzg_verify_cell_proof_batch[_each][_dev], kzg_g1_monomial_lincomb or kzg_ctx_g1_monomial call (64 commitments, about a millisecond), not in kzg_ctx_create: a
  * context that never verifies cells launches nothing for them.  Point 0 is the G1 generator.  They are the fixed terms of cell
  * verification's second lincomb; a group context's members each derive and hold a copy (this call reads member 0's).
  */
@@ -423,8 +423,9 @@ int32_t kzg_ctx_g1_monomial(const kzg_ctx* ctx, uint32_t first, uint32_t count, 
  *            the specification stay in the caller: the ABI takes a single n.
  * On a GROUP context the host-buffer call cuts the batch into contiguous shares, one per member, like kzg_verify_proof_batch; every
  * member's partial second lincomb carries its own monomial terms, so the partials add.  The *_dev call acts on member 0.
- * Not here: per-item verdicts (the *_each forms), a sharded phase-1 entry point for cells, a *_group_dev form, and deduplicating the
- * commitments before they are decoded (the decoder runs on 2n points where 128 cells of one blob need n + 1).
+ * Per-item verdicts: kzg_verify_cell_proof_batch_each[_dev], below with the other *_each calls.
+ * Not here: a sharded phase-1 entry point for cells, a *_group_dev form, and deduplicating the commitments before they are decoded
+ * (the decoder runs on 2n points where 128 cells of one blob need n + 1).
  */
 int32_t kzg_verify_cell_proof_batch(const kzg_ctx* ctx, const uint8_t* commitments48, const uint64_t* cell_indices, const uint8_t* cells /* n * 2048 */,
                                     const uint8_t* proofs48, uint64_t n, int32_t* ok);
@@ -470,6 +471,40 @@ int32_t kzg_verify_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_proofs
                                         uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream);
 uint64_t kzg_verify_each_checks(const kzg_ctx* ctx);
 uint64_t kzg_ctx_sessions_created(const kzg_ctx* ctx);
+
+/*
+ * PER-ITEM VERDICTS FOR CELLS: which (commitment, cell index, cell, proof) tuples of a kzg_verify_cell_proof_batch are bad -- what a
+ * PeerDAS node needs to drop the cells, down-score their senders and reconstruct from the rest.  Inputs as
+ * kzg_verify_cell_proof_batch(_dev); the outputs and the contract are those of the *_each calls above:
+ *   status[i]  what kzg_verify_cell_proof_batch returns for item i ALONE: 0, or the positive code of its first rejected input in the
+ *              order cell index, commitment, cell, proof.
+ *   ok_each[i] that call's *ok; 0 whenever status[i] != 0.
+ *   *ok        the AND of all verdicts.  n == 0: *ok = 1.  n == 1: the boolean call.  A null required pointer with n > 0 returns
+ *              KZG_FAIL_ARGUMENT; a rejected item never makes the call return a positive code.
+ *   ok_each (n bytes), status (n x int32) and ok are HOST memory; the *_dev call is synchronous.
+ * How: nothing rejected -> the batch check runs first and true means every item is true.  Otherwise per item
+ *   A_i = [r_i] proof_i      B_i = [r_i] commitment_i + [r_i h_i^64] proof_i - sum_{j<64} [v_ij] [tau^j]_1,   v_i = r_i I_i,
+ * and e(-A_i, [tau^64]_2) e(B_i, G2) == 1 is the spec's single-cell check scaled by r_i != 0.  The two point terms are the leaves of
+ * the two point trees above (z_i = h_i^64, y_i = 0).  The 64-term sum is NOT computed per item: the coefficient vectors v_i are the
+ * leaves of a third sum tree (a node = 64 field elements, about 4 KiB of session storage per item), and the point sum_j [S_j] [tau^j]_1
+ * is computed only for the nodes the host's descent asks for, O(k log n) of them for k false items, one wave per node.  The bound on
+ * the two-pairing checks is the same 1 + 2 k ceil(log2 n).
+ * GROUP context: the host-buffer call cuts the batch into the members' shares like the other *_each calls; the *_dev call acts on
+ * member 0.  Not here: a kzg_verify_session_tree form for cells and a *_group_dev form.
+ */
+int32_t kzg_verify_cell_proof_batch_each(const kzg_ctx* ctx, const uint8_t* commitments48, const uint64_t* cell_indices, const uint8_t* cells /* n * 2048 */,
+                                         const uint8_t* proofs48, uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok);
+int32_t kzg_verify_cell_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_commitments48, const void* d_cell_indices, const void* d_cells,
+                                             const void* d_proofs48, uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream);
+
+/*
+ * Introspection: out96[k] = sum_{j<64} s_kj [tau^j]_1 for m vectors of 64 scalars (scalars32: m x 64 x 32 bytes big-endian, canonical;
+ * a scalar >= r is rejected with KZG_ERR_FF_NOT_IN_FIELD), in kzg_verify_phase2_dev's point format: x || y big-endian, all-zero = the
+ * point at infinity.  It runs through the kernel that computes the monomial term of a fetched node in the cells *_each calls, which
+ * pins that kernel exactly; the monomial points are derived on first use like kzg_ctx_g1_monomial's.  Host memory in and out;
+ * synchronous; a group context answers from member 0.
+ */
+int32_t kzg_g1_monomial_lincomb(const kzg_ctx* ctx, const uint8_t* scalars32, uint64_t m, uint8_t* out96);
 
 /*
  * DEVICE-RESIDENT sharded calls on a GROUP context (kzg_config.devices / ndev): member k's share of the batch is resident on

@@ -1,6 +1,7 @@
 // verify_cell_kzg_proof_batch (EIP-7594): the kernels of the cells kind of batch verification (compiled once: engine_verify.hip owns
 // this header).  k_cells_leaves is the front; k_cells_interp and k_cells_reduce run once the challenge r is known and leave the 64
-// scalars -S_j of lincomb B's monomial terms (arithmetic and layout: cellverify_math.cuh).
+// scalars -S_j of lincomb B's monomial terms (arithmetic and layout: cellverify_math.cuh).  The per-item verdicts add k_cells_each_leaves,
+// k_each_vec_level and k_each_gather_cells (at the end of this file).
 #pragma once
 #include "cellverify_math.cuh"
 #include "verify_kernels.cuh"
@@ -125,6 +126,25 @@ static __global__ __launch_bounds__(256, 8) void k_cells_leaves(const uint8_t* _
   }
 }
 
+// elements 8 t .. 8 t + 7 of cell k as they lie in memory (256 consecutive bytes, big-endian) -> plain limbs; zero for a cell that
+// contributes nothing
+__device__ __forceinline__ void cellv_load_elements(fr_t (&v)[8], const uint8_t* __restrict__ cells, uint64_t k, uint32_t t, bool live) {
+  const uint4* in = reinterpret_cast<const uint4*>(cells + (live ? k : 0) * (uint64_t)KZG_BYTES_PER_CELL) + 16u * t;
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    const uint4 w0 = live ? in[2 * e] : zero, w1 = live ? in[2 * e + 1] : zero;
+    v[e].v[7] = __builtin_bswap32(w0.x);
+    v[e].v[6] = __builtin_bswap32(w0.y);
+    v[e].v[5] = __builtin_bswap32(w0.z);
+    v[e].v[4] = __builtin_bswap32(w0.w);
+    v[e].v[3] = __builtin_bswap32(w1.x);
+    v[e].v[2] = __builtin_bswap32(w1.y);
+    v[e].v[1] = __builtin_bswap32(w1.z);
+    v[e].v[0] = __builtin_bswap32(w1.w);
+  }
+}
+
 // S's partial vectors: one 128-thread workgroup per CELLV_CELLS cells, eight threads per cell.  A thread reads its eight elements (256
 // consecutive bytes, the cell's second and last trip from memory: 2 x 2 KiB per cell in all), runs the three steps of
 // cellverify_math.cuh with a barrier between them and the first 64 threads store the workgroup's 64 partial coefficients.  A cell
@@ -150,20 +170,7 @@ static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_interp(const uin
   }
   {
     fr_t v[8];
-    const uint4* in = reinterpret_cast<const uint4*>(cells + (live ? k : 0) * (uint64_t)KZG_BYTES_PER_CELL) + 16u * t;
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      const uint4 zero = make_uint4(0, 0, 0, 0);
-      const uint4 w0 = live ? in[2 * e] : zero, w1 = live ? in[2 * e + 1] : zero;
-      v[e].v[7] = __builtin_bswap32(w0.x);
-      v[e].v[6] = __builtin_bswap32(w0.y);
-      v[e].v[5] = __builtin_bswap32(w0.z);
-      v[e].v[4] = __builtin_bswap32(w0.w);
-      v[e].v[3] = __builtin_bswap32(w1.x);
-      v[e].v[2] = __builtin_bswap32(w1.y);
-      v[e].v[1] = __builtin_bswap32(w1.z);
-      v[e].v[0] = __builtin_bswap32(w1.w);
-    }
+    cellv_load_elements(v, cells, k, t, live);
     cellv_step_a(img, ctab, cl, t, v);
   }
   __syncthreads();
@@ -191,6 +198,136 @@ static __global__ __launch_bounds__(256) void k_cells_reduce(const fr_t* __restr
     cellv_neg_sum(out, red + j, 4, 64);
     out_neg_plain[j] = out;
   }
+}
+
+
+// ---- per-item verdicts for cells (kzg_verify_cell_proof_batch_each): the monomial term of the batch check item by item ----------------
+//   B_i = [r_i] C_i + [r_i h_i^64] proof_i - sum_j [v_ij] [tau^j]_1,   v_i = r_i I_i (64 coefficients)
+// The two point terms are k_each_terms' (the front wrote z = h^64, y = 0).  The 64-term sum is NOT taken per item: the v_i are the
+// leaves of a third sum tree whose nodes are 64 Fr values, and the points  T = sum_j [S_j] [tau^j]_1  are computed only for the nodes
+// the host asks for (k_each_gather_cells).
+
+// Leaf vectors: k_cells_interp's workgroup (16 cells, eight threads each, the same three steps and tables) with the scaled coefficients
+// stored per cell instead of summed.  r_i = r^(first_index + i) comes from the seed's powers r^(2^k) (Montgomery) as in k_each_terms:
+// on the rejected-items route k_batch_scalars has not run.  An item whose single-item code is non-zero (status: k_each_status' output,
+// which covers the index and the elements) contributes the zero vector.
+static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_each_leaves(const uint8_t* __restrict__ cells, const unsigned long long* __restrict__ cell_indices,
+                                                                        const int32_t* __restrict__ status, const fr_t* __restrict__ rpow2, uint64_t n,
+                                                                        uint64_t first_index, const uint32_t* __restrict__ ctab, const uint32_t* __restrict__ vtab,
+                                                                        fr_t* __restrict__ leaves /* n x 64, plain, canonical */) {
+  __shared__ uint32_t img[CELLV_IMAGE_DWORDS];
+  const uint32_t cl = threadIdx.x >> 3, t = threadIdx.x & 7u;
+  const uint64_t k = (uint64_t)blockIdx.x * CELLV_CELLS + cl;
+  bool live = k < n;
+  if (live) live = status[k] == 0;
+  const uint32_t column = live ? (uint32_t)cell_indices[k] : 0u;
+  fr_t rk;
+  bn_zero(rk);
+  if (live) {
+    const uint64_t e = first_index + k;
+    fr_t r = fr_one();
+    for (int b = 0; b < 64 && (e >> b); b++)
+      if ((e >> b) & 1) fr_mul(r, r, rpow2[b]);
+    from_mont<FrParams>(rk, r);
+  }
+  {
+    fr_t v[8];
+    cellv_load_elements(v, cells, k, t, live);
+    cellv_step_a(img, ctab, cl, t, v);
+  }
+  __syncthreads();
+  cellv_step_b(img, ctab, vtab, cl, t, column, rk);
+  __syncthreads();
+  // 16 x 64 coefficients, eight per thread: consecutive threads store consecutive coefficients of one cell
+#pragma unroll 1
+  for (uint32_t q = 0; q < 8; q++) {
+    const uint32_t flat = threadIdx.x + (uint32_t)CELLV_THREADS * q, c2 = flat >> 6, j = flat & 63u;
+    const uint64_t item = (uint64_t)blockIdx.x * CELLV_CELLS + c2;
+    if (item >= n) continue;
+    fr_t o;
+    cellv_cell_coeff(o, img, c2, j);
+    leaves[item * 64 + j] = o;
+  }
+}
+
+// one level of the vector tree: out[j] = in[2 j] + in[2 j + 1] coefficient by coefficient, a missing sibling being zero; one thread per
+// coefficient, k_each_level's geometry
+static __global__ __launch_bounds__(256) void k_each_vec_level(const fr_t* __restrict__ in, uint64_t cnt_in, fr_t* __restrict__ out, uint64_t cnt_out) {
+  const uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= cnt_out * 64) return;
+  const uint64_t j = id >> 6, c = id & 63u;
+  fr_t acc = in[2 * j * 64 + c];
+  if (2 * j + 1 < cnt_in) cellv_vec_add(acc, in[(2 * j + 1) * 64 + c]);
+  out[id] = acc;
+}
+
+// The fetch of the cells kind: ONE WAVE PER REQUESTED NODE.  Lane j multiplies the monomial point M_j (affine, lincomb B's format) by
+// the node's coefficient S_j -- a 255-step double-and-add as in k_each_terms, the doubling uniform over the wave, the addition masked
+// by the lane's scalar bit -- and a six-step tree of complete additions through LDS sums the 64 products: T.  Lane 0 then adds B'
+// (the node of k_each_terms' tree B) and lanes 0 and 1 write B' -+ T and A in the 12 x 32-limb host format, as k_each_gather does.
+// `subtract` loads the bases negated (B' - T, the verdicts); without it the sum is B' + T (kzg_g1_monomial_lincomb).  tree_a / tree_b
+// null: the identity in their place; idx null: node k is vector k.  S_j = 0 leaves the lane's accumulator at the identity, the zero
+// vector gives T = identity, T = B' cancels in the complete adder.  Grid: exactly m workgroups.
+static __global__ __launch_bounds__(64, 2) void k_each_gather_cells(const g1_xyzz28* __restrict__ tree_a, const g1_xyzz28* __restrict__ tree_b,
+                                                                   const fr_t* __restrict__ vecs, const uint4* __restrict__ monomial,
+                                                                   const uint32_t* __restrict__ idx, uint32_t m, bool subtract, g1_xyzz* __restrict__ out) {
+  __shared__ g1_xyzz28 lds[32];
+  const uint32_t node = blockIdx.x, lane = threadIdx.x;
+  if (node >= m) return;  // uniform over the workgroup
+  const uint64_t pos = idx ? idx[node] : node;
+  fr_t s = vecs[pos * 64 + lane];
+  fp28 cx, cy;
+  {
+    fp_t px, py;
+    load_affine96(px, py, monomial, lane);
+    if (bn_is_zero(px) && bn_is_zero(py)) bn_zero(s);  // a point at infinity (a context never holds one: ensure_g1_monomial rejects the setup)
+    f28_load_entry(cx, cy, px, py, subtract);
+  }
+  g1_xyzz28 acc;
+  xyzz28_set_inf(acc);
+  // the scalar is below r < 2^255: bit 255 is dropped, 255 steps, bit 254 first
+  auto shl1 = [](fr_t& v) {
+#pragma unroll
+    for (int q = 7; q > 0; q--) v.v[q] = (v.v[q] << 1) | (v.v[q - 1] >> 31);
+    v.v[0] <<= 1;
+  };
+  shl1(s);
+#pragma unroll 1
+  for (int step = 0; step < 255; step++) {
+    xyzz28_dbl_inl(acc);
+    if (s.v[7] >> 31) {
+      bool done = false;
+      if (!acc.inf) done = xyzz28_madd_fast(acc, cx, cy);
+      if (!done) {
+        g1_xyzz28 tmp = acc;  // copy: the call takes addresses
+        xyzz28_madd_complete(tmp, cx, cy);
+        acc = tmp;
+      }
+    }
+    shl1(s);
+  }
+#pragma unroll 1
+  for (uint32_t step = 32; step >= 1; step >>= 1) {
+    if (lane >= step && lane < 2 * step) lds[lane - step] = acc;
+    __syncthreads();
+    if (lane < step) {
+      const g1_xyzz28 other = lds[lane];
+      xyzz28_add_complete_inl<true>(acc, other);
+    }
+    __syncthreads();
+  }
+  if (lane >= 2) return;
+  g1_xyzz28 p;
+  xyzz28_set_inf(p);
+  if (lane == 0) {
+    if (tree_b) p = tree_b[pos];
+    xyzz28_add_complete_inl<true>(p, acc);
+  } else if (tree_a) {
+    p = tree_a[pos];
+  }
+  g1_xyzz o;
+  xyzz28_to_xyzz(o, p);
+  out[2 * node + (lane ^ 1u)] = o;
 }
 
 #endif

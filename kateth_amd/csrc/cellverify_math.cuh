@@ -159,6 +159,17 @@ KZG_HD void cellv_step_c(fr_t& out, const uint32_t* img, uint32_t j) {
   f29_to_canonical_bn(out, acc);
 }
 
+// per-item verdicts: coefficient j of the workgroup's cell cl as step B left it (r_i [X^j] I_i), canonical -- a leaf of the vector tree
+KZG_HD void cellv_cell_coeff(fr_t& out, const uint32_t* img, uint32_t cl, uint32_t j) {
+  fr_t v;
+  fr29 x;
+  cellv_get(v, img, cl, j);
+  f29_from_bn(x, v);
+  f29_to_canonical_bn(out, x);
+}
+// the vector tree's inner nodes: canonical plain values summed coefficient by coefficient, canonical again
+KZG_HD void cellv_vec_add(fr_t& acc, const fr_t& other) { fr_add(acc, acc, other); }
+
 // the reduce launch's arithmetic: partial vectors (canonical, plain) summed in their order, negated: lincomb B's scalar -S_j
 KZG_HD void cellv_neg_sum(fr_t& out, const fr_t* partials, uint32_t count, uint32_t stride) {
   fr_t acc;

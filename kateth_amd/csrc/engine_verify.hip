@@ -71,6 +71,7 @@ struct kzg_verify_session {
   g1_xyzz28* t_b = nullptr;
   uint32_t* t_idx = nullptr;       // [EACH_GATHER] node positions of one fetch
   g1_xyzz* t_out = nullptr;        // [2 EACH_GATHER] the fetched nodes, A and B side by side
+  fr_t* t_vec = nullptr;           // cells: the third tree, a node = 64 coefficients (k_cells_each_leaves, k_each_vec_level), same geometry
 };
 
 static void session_free(kzg_verify_session* s) {
@@ -1600,13 +1601,16 @@ static EachGeom each_geom(uint64_t n) {
   for (uint32_t l = 0; l <= g.height; l++) g.off[l + 1] = g.off[l] + kzg::each::level_count(n, l);
   return g;
 }
-// the session's tree storage for its current n (about 50 MB at 65,536 items; grown on demand, freed with the session)
+// the session's tree storage for its current n (about 50 MB at 65,536 items; grown on demand, freed with the session).  The cells kind
+// carves its vector tree BEHIND everything else (2 KiB per node, about 4 KiB per item: 268 MB at 65,536 items); the other kinds' carve
+// is what it was.
 static int32_t each_reserve(kzg_verify_session* s, const EachGeom& g) {
   const uint64_t n = s->n, total = g.off[g.height + 1];
   if (total >> 32) return fail(KZG_FAIL_ARGUMENT, "per-item verdicts: batch too large");
   Carve c;
   const size_t o_status = c.take(n * sizeof(int32_t)), o_rej = c.take(sizeof(uint32_t)), o_a = c.take(total * sizeof(g1_xyzz28)),
                o_b = c.take(total * sizeof(g1_xyzz28)), o_idx = c.take(EACH_GATHER * sizeof(uint32_t)), o_out = c.take(2 * EACH_GATHER * sizeof(g1_xyzz));
+  const size_t o_vec = s->cells ? c.take(total * 64 * sizeof(fr_t)) : 0;
   if (s->tree_cap < c.off) {
     if (s->tree) (void)hipFree(s->tree);
     s->tree = nullptr;
@@ -1621,10 +1625,12 @@ static int32_t each_reserve(kzg_verify_session* s, const EachGeom& g) {
   s->t_b = reinterpret_cast<g1_xyzz28*>(s->tree + o_b);
   s->t_idx = reinterpret_cast<uint32_t*>(s->tree + o_idx);
   s->t_out = reinterpret_cast<g1_xyzz*>(s->tree + o_out);
+  s->t_vec = s->cells ? reinterpret_cast<fr_t*>(s->tree + o_vec) : nullptr;
   return 0;
 }
-// per-item codes in the single-item call's parse order -- blob, commitment, proof (src/kzg/setup.rs:214-217) or proof, commitment, z, y
-// (:103-109) -- on the caller's stream, behind the front's kernels there and the decoder (ev_join)
+// per-item codes in the single-item call's parse order -- blob, commitment, proof (src/kzg/setup.rs:214-217), proof, commitment, z, y
+// (:103-109) or, for cells, index, commitment, cell, proof (front_enqueue: the cell's status lies in the blob slot, the index's in the
+// fourth) -- on the caller's stream, behind the front's kernels there and the decoder (ev_join)
 static int32_t each_status_enqueue(kzg_verify_session* s) {
   const uint64_t n = s->n;
   hipStream_t st = s->st;
@@ -1632,13 +1638,15 @@ static int32_t each_status_enqueue(kzg_verify_session* s) {
     return fail(KZG_FAIL_HIP, "per-item verdicts: status enqueue failed");
   if (s->points)
     hipLaunchKernelGGL(k_each_status, dim3(blocks_for(n, 256)), dim3(256), 0, st, s->stat + 2 * n, s->stat + n, s->stat, s->stat + 3 * n, n, s->t_status, s->t_rejected);
+  else if (s->cells)
+    hipLaunchKernelGGL(k_each_status, dim3(blocks_for(n, 256)), dim3(256), 0, st, s->stat + 3 * n, s->stat + n, s->stat, s->stat + 2 * n, n, s->t_status, s->t_rejected);
   else
     hipLaunchKernelGGL(k_each_status, dim3(blocks_for(n, 256)), dim3(256), 0, st, s->stat, s->stat + n, s->stat + 2 * n, (const int32_t*)nullptr, n, s->t_status,
                        s->t_rejected);
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "per-item verdicts: status launch failed");
   return 0;
 }
-// terms and both trees, on the caller's stream behind each_status_enqueue and the seed (p2_seed)
+// terms and both trees -- cells: the vector tree as well -- on the caller's stream behind each_status_enqueue and the seed (p2_seed)
 static int32_t each_build(kzg_verify_session* s, const EachGeom& g, uint64_t first_index) {
   const uint64_t n = s->n;
   hipStream_t st = s->st;
@@ -1648,11 +1656,21 @@ static int32_t each_build(kzg_verify_session* s, const EachGeom& g, uint64_t fir
     hipLaunchKernelGGL(k_each_level, dim3(blocks_for(2 * cout, 64)), dim3(64), 0, st, s->t_a + g.off[l], s->t_b + g.off[l], cin, s->t_a + g.off[l + 1],
                        s->t_b + g.off[l + 1], cout);
   }
+  if (s->cells) {  // the monomial term's coefficient vectors r_i I_i and their sums; the points are taken per fetched node (each_fetch)
+    hipLaunchKernelGGL(k_cells_each_leaves, dim3(blocks_for(n, CELLV_CELLS)), dim3(CELLV_THREADS), 0, st, s->d_cells,
+                       reinterpret_cast<const unsigned long long*>(s->d_cell_indices), s->t_status, s->rpow2, n, first_index, s->ctx->d_cells_tab, s->ctx->d_cellv_tab,
+                       s->t_vec);
+    for (uint32_t l = 0; l < g.height; l++) {
+      const uint64_t cin = g.off[l + 1] - g.off[l], cout = g.off[l + 2] - g.off[l + 1];
+      hipLaunchKernelGGL(k_each_vec_level, dim3(blocks_for(cout * 64, 256)), dim3(256), 0, st, s->t_vec + g.off[l] * 64, cin, s->t_vec + g.off[l + 1] * 64, cout);
+    }
+  }
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "per-item verdicts: tree launch failed");
   s->tree_n = n;
   return 0;
 }
-// nodes at `pos` (positions in the node arrays) of both trees -> out[2 k] = A's, out[2 k + 1] = B's; synchronous
+// nodes at `pos` (positions in the node arrays) of both trees -> out[2 k] = A's, out[2 k + 1] = B's; synchronous.  Cells: B's node
+// minus the monomial term of the node's coefficient vector, one wave per node (k_each_gather_cells)
 static int32_t each_fetch(kzg_verify_session* s, const std::vector<uint32_t>& pos, std::vector<g1_xyzz>& out) {
   hipStream_t st = s->st;
   out.resize(2 * pos.size());
@@ -1660,7 +1678,10 @@ static int32_t each_fetch(kzg_verify_session* s, const std::vector<uint32_t>& po
     const uint32_t m = (uint32_t)std::min<size_t>(EACH_GATHER, pos.size() - done);
     if (hipMemcpyAsync(s->t_idx, pos.data() + done, m * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess)
       return fail(KZG_FAIL_HIP, "per-item verdicts: node fetch failed");
-    hipLaunchKernelGGL(k_each_gather, dim3(blocks_for(2 * (uint64_t)m, 64)), dim3(64), 0, st, s->t_a, s->t_b, s->t_idx, m, s->t_out);
+    if (s->cells)
+      hipLaunchKernelGGL(k_each_gather_cells, dim3(m), dim3(64), 0, st, s->t_a, s->t_b, s->t_vec, s->ctx->d_g1_monomial, s->t_idx, m, true, s->t_out);
+    else
+      hipLaunchKernelGGL(k_each_gather, dim3(blocks_for(2 * (uint64_t)m, 64)), dim3(64), 0, st, s->t_a, s->t_b, s->t_idx, m, s->t_out);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out.data() + 2 * done, s->t_out, 2 * (size_t)m * sizeof(g1_xyzz), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
       return fail(KZG_FAIL_HIP, "per-item verdicts: node fetch failed");
@@ -1689,7 +1710,7 @@ static int32_t each_descend(kzg_verify_session* s, const EachGeom& g, uint8_t* o
         host::g1_host_affine a, b;
         host_affine_from_xyzz(a, nodes[2 * k]);
         host_affine_from_xyzz(b, nodes[2 * k + 1]);
-        pass[k] = host::verify_pairings_fixed(*ctx->pairing, a, b) ? 1 : 0;
+        pass[k] = host::verify_pairings_fixed(*ctx->pairing, a, b, s->cells) ? 1 : 0;  // cells: e(A, [tau^64]_2)
       }
       return 0;
     });
@@ -1805,7 +1826,6 @@ static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, const Ver
 int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, const VerifyEach* each, int32_t* ok) {
   *ok = 0;
   const bool blobs = in.kind == VerifyInputs::BLOBS;
-  if (each && in.kind == VerifyInputs::CELLS) return fail(KZG_FAIL_ARGUMENT, "per-item verdicts are not available for cells");
   if (in.kind == VerifyInputs::CELLS) {  // lincomb B's fixed terms: derived by this member's first cells call
     const int32_t rc = ensure_g1_monomial(ctx);
     if (rc) return rc;
@@ -1906,6 +1926,74 @@ extern "C" int32_t kzg_verify_cell_proof_batch(const kzg_ctx* ctx, const uint8_t
   if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
   if (n == 0) return empty_batch(ok);
   return is_group(ctx) ? multi_verify_batch(ctx, in, n, ok) : verify_batch_single(ctx, in, n, nullptr, nullptr, ok);
+} catch (...) {
+  return abi_exception();
+}
+
+// Per-item verdicts for cells: the third kind through the same driver (each_finish); what differs lies behind the session's kind --
+// the order of the status arrays, the vector tree beside the two point trees, the fetch kernel and the pairing against [tau^64]_2.
+extern "C" int32_t kzg_verify_cell_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_commitments48, const void* d_cell_indices, const void* d_cells,
+                                                        const void* d_proofs48, uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream) try {
+  const VerifyInputs in = cell_inputs(d_commitments48, d_cell_indices, d_cells, d_proofs48, false);
+  const VerifyEach each{ok_each, status};
+  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, &each, ok) : empty_batch(ok);
+} catch (...) {
+  return abi_exception();
+}
+
+extern "C" int32_t kzg_verify_cell_proof_batch_each(const kzg_ctx* ctx, const uint8_t* commitments48, const uint64_t* cell_indices, const uint8_t* cells,
+                                                    const uint8_t* proofs48, uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok) try {
+  const VerifyInputs in = cell_inputs(commitments48, cell_indices, cells, proofs48, true);
+  const VerifyEach each{ok_each, status};
+  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return empty_batch(ok);
+  return is_group(ctx) ? multi_verify_each(ctx, in, n, each, ok) : verify_batch_single(ctx, in, n, nullptr, &each, ok);
+} catch (...) {
+  return abi_exception();
+}
+
+// Introspection: sum_j s_j [tau^j]_1 per 64-scalar vector THROUGH k_each_gather_cells -- the vectors stand where the vector tree's nodes
+// do, no point trees (B' = identity), the bases not negated.  On a group context member 0 answers.  Scratch of its own, freed here.
+extern "C" int32_t kzg_g1_monomial_lincomb(const kzg_ctx* ctx, const uint8_t* scalars32, uint64_t m, uint8_t* out96) try {
+  if (!ctx || (m && (!scalars32 || !out96))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (m == 0) return 0;
+  std::vector<fr_t> vecs((size_t)m * 64);
+  for (size_t k = 0; k < vecs.size(); k++) {
+    fr_from_be_bytes_plain(vecs[k], scalars32 + 32 * k);
+    if (!fr_is_canonical(vecs[k])) return KZG_ERR_FF_NOT_IN_FIELD;
+  }
+  const int32_t rc = ensure_g1_monomial(ctx);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  struct Scratch {
+    fr_t* vec = nullptr;
+    g1_xyzz* out = nullptr;
+    ~Scratch() {
+      if (vec) (void)hipFree(vec);
+      if (out) (void)hipFree(out);
+    }
+  } d;
+  const uint64_t chunk = std::min<uint64_t>(m, EACH_GATHER);
+  HIP_TRY(hipMalloc(&d.vec, chunk * 64 * sizeof(fr_t)));
+  HIP_TRY(hipMalloc(&d.out, 2 * chunk * sizeof(g1_xyzz)));
+  hipStream_t st = nullptr;  // as the derivation of the points itself: an introspection call, waited for here
+  std::vector<g1_xyzz> nodes(2 * chunk);
+  for (uint64_t done = 0; done < m; done += chunk) {
+    const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, m - done);
+    HIP_TRY(hipMemcpyAsync(d.vec, vecs.data() + done * 64, (size_t)cnt * 64 * sizeof(fr_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_each_gather_cells, dim3(cnt), dim3(64), 0, st, (const g1_xyzz28*)nullptr, (const g1_xyzz28*)nullptr, d.vec, ctx->d_g1_monomial,
+                       (const uint32_t*)nullptr, cnt, false, d.out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(nodes.data(), d.out, 2 * (size_t)cnt * sizeof(g1_xyzz), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t k = 0; k < cnt; k++) {
+      host::g1_host_affine t;
+      host_affine_from_xyzz(t, nodes[2 * k + 1]);
+      host_affine_to_be96(out96 + 96 * (done + k), t);
+    }
+  }
+  return 0;
 } catch (...) {
   return abi_exception();
 }

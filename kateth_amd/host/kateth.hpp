@@ -11,6 +11,7 @@
 //   verify_proof(proof, commitment, z, y)<- src/kzg/setup.rs:96-113
 //   verify_proof_batch(ps, cs, zs, ys)   <- src/kzg/setup.rs:115-161 behind :96-113 per tuple
 //   verify_cell_proof_batch(cs, idx, cells, ps) <- EIP-7594 verify_cell_kzg_proof_batch (specs/fulu/polynomial-commitments-sampling.md)
+//   verify_cell_proof_batch_each(...)    <- the same, one Verdict per tuple
 //   decompress(bytes48) -> P1            <- P1::decompress, src/bls.rs:505-531
 //   verify_blob_proof(blob, c, p)        <- src/kzg/setup.rs:208-221
 //   verify_blob_proof_batch(blobs,cs,ps) <- src/kzg/setup.rs:247-275
@@ -521,6 +522,26 @@ class Setup {
     int32_t ok = 0;
     check(kzg_verify_proof_batch_each(ctx_.get(), ps.data(), cs.data(), zs.data(), ys.data(), n, ok_each.data(), status.data(), &ok),
           "kzg_verify_proof_batch_each");
+    std::vector<Verdict> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = Verdict{ok_each[i] != 0, status[i]};
+    return out;
+  }
+  // entry i: what verify_cell_proof_batch returns for tuple i alone (status: CellIndex, or the kind of its rejected commitment, cell or
+  // proof); arguments and length checks as verify_cell_proof_batch
+  std::vector<Verdict> verify_cell_proof_batch_each(const std::vector<Bytes48>& commitments, const std::vector<uint64_t>& cell_indices, const uint8_t* cells,
+                                                    size_t cells_len, const std::vector<Bytes48>& proofs) const {
+    const size_t n = commitments.size();
+    if (cell_indices.size() != n || proofs.size() != n || cells_len != n * BYTES_PER_CELL)
+      throw std::invalid_argument("verify_cell_proof_batch_each: one index, one 2048-byte cell and one proof per commitment");
+    std::vector<uint8_t> cs(n * 48), ps(n * 48), ok_each(n);
+    std::vector<int32_t> status(n);
+    for (size_t i = 0; i < n; i++) {
+      std::copy(commitments[i].begin(), commitments[i].end(), cs.begin() + i * 48);
+      std::copy(proofs[i].begin(), proofs[i].end(), ps.begin() + i * 48);
+    }
+    int32_t ok = 0;
+    check(kzg_verify_cell_proof_batch_each(ctx_.get(), cs.data(), cell_indices.data(), cells, ps.data(), n, ok_each.data(), status.data(), &ok),
+          "kzg_verify_cell_proof_batch_each");
     std::vector<Verdict> out(n);
     for (size_t i = 0; i < n; i++) out[i] = Verdict{ok_each[i] != 0, status[i]};
     return out;

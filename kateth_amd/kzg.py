@@ -14,6 +14,7 @@ Method names, argument meaning and error behaviour follow the reference:
     Setup.verify_blob_proof_batch(blobs, cs, ps) src/kzg/setup.rs:247-275
     Setup.verify_proof_batch(ps, cs, zs, ys)     src/kzg/setup.rs:115-161 behind :96-113 per tuple
     Setup.verify_cell_proof_batch(cs, idx, cells, ps)  EIP-7594 verify_cell_kzg_proof_batch (same document as compute_cells)
+    Setup.verify_cell_proof_batch_each(cs, idx, cells, ps)  the same, one verdict (or error) per tuple
 
 Points cross this boundary in their 48-byte compressed form (what every caller
 of the reference does next: benches/kzg.rs:25-32, src/kzg/setup.rs:341-343).
@@ -207,6 +208,12 @@ _SIGNATURES = {
         ctypes.c_int32,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p, _i32p, ctypes.c_void_p],
     ),
+    "kzg_verify_cell_proof_batch_each": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u64p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p, _i32p]),
+    "kzg_verify_cell_proof_batch_each_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p, _i32p, ctypes.c_void_p],
+    ),
+    "kzg_g1_monomial_lincomb": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p]),
     "kzg_verify_each_checks": (ctypes.c_uint64, [ctypes.c_void_p]),
     "kzg_ctx_sessions_created": (ctypes.c_uint64, [ctypes.c_void_p]),
     "kzg_verify_session_tree": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]),
@@ -867,17 +874,7 @@ class Setup:
         of the wrong size and an index that is no uint64 are a ValueError in the caller.  Raises CellsError CellIndex for an index >= 128
         and KzgError for a rejected commitment, cell (BlobError InvalidFieldElement) or proof -- the first rejected input in the spec's
         order of assertions lifted to lists: every index, then every commitment, then every cell, then every proof."""
-        n = len(commitments)
-        if not (len(cell_indices) == n and len(cells) == n and len(proofs) == n):
-            raise ValueError("verify_cell_proof_batch: %d commitments, %d indices, %d cells, %d proofs" % (n, len(cell_indices), len(cells), len(proofs)))
-        commitments, cells, proofs = [_buf(v) for v in commitments], [_buf(v) for v in cells], [_buf(v) for v in proofs]
-        cell_indices = [int(c) for c in cell_indices]
-        if any(len(v) != 48 for v in commitments) or any(len(v) != 48 for v in proofs):
-            raise ValueError("verify_cell_proof_batch: a commitment or proof is 48 bytes")
-        if any(len(v) != BYTES_PER_CELL for v in cells):
-            raise ValueError("verify_cell_proof_batch: a cell is %d bytes" % BYTES_PER_CELL)
-        if any(not 0 <= c < 1 << 64 for c in cell_indices):
-            raise ValueError("verify_cell_proof_batch: a cell index is a uint64")
+        n, commitments, cell_indices, cells, proofs = self._cell_lists("verify_cell_proof_batch", commitments, cell_indices, cells, proofs)
         return self.verify_cell_proof_batch_host(b"".join(commitments), cell_indices, b"".join(cells), b"".join(proofs), n)
 
     def verify_cell_proof_batch_host(self, commitments, cell_indices, cells, proofs, n: int) -> bool:
@@ -1012,6 +1009,67 @@ class Setup:
         sent = [placeholder if i in early else it for i, it in enumerate(items)]
         ok_each, status, _ = self.verify_proof_batch_each_host(*[b"".join(s[k] for s in sent) for k in range(4)], n)
         return self._each_list(n, early, ok_each, status)
+
+    @staticmethod
+    def _cell_lists(what, commitments, cell_indices, cells, proofs):
+        """the length checks of the cells calls' list forms -> (n, commitments, indices, cells, proofs) as buffers and ints"""
+        n = len(commitments)
+        if not (len(cell_indices) == n and len(cells) == n and len(proofs) == n):
+            raise ValueError("%s: %d commitments, %d indices, %d cells, %d proofs" % (what, n, len(cell_indices), len(cells), len(proofs)))
+        commitments, cells, proofs = [_buf(v) for v in commitments], [_buf(v) for v in cells], [_buf(v) for v in proofs]
+        cell_indices = [int(c) for c in cell_indices]
+        if any(len(v) != 48 for v in commitments) or any(len(v) != 48 for v in proofs):
+            raise ValueError("%s: a commitment or proof is 48 bytes" % what)
+        if any(len(v) != BYTES_PER_CELL for v in cells):
+            raise ValueError("%s: a cell is %d bytes" % (what, BYTES_PER_CELL))
+        if any(not 0 <= c < 1 << 64 for c in cell_indices):
+            raise ValueError("%s: a cell index is a uint64" % what)
+        return n, commitments, cell_indices, cells, proofs
+
+    def verify_cell_proof_batch_each(self, commitments: Sequence[bytes], cell_indices: Sequence[int], cells: Sequence[bytes],
+                                     proofs: Sequence[bytes]) -> List[Union[bool, KzgError]]:
+        """Entry i is what `verify_cell_proof_batch` of tuple i alone returns -- or the error it raises (CellsError CellIndex, or KzgError
+        for a commitment, cell or proof), RETURNED in the list.  The length checks are verify_cell_proof_batch's: a ValueError."""
+        n, commitments, cell_indices, cells, proofs = self._cell_lists("verify_cell_proof_batch_each", commitments, cell_indices, cells, proofs)
+        ok_each, status, _ = self.verify_cell_proof_batch_each_host(b"".join(commitments), cell_indices, b"".join(cells), b"".join(proofs), n)
+        return [_cell_verify_error(status[i]) if status[i] else ok_each[i] for i in range(n)]
+
+    def verify_cell_proof_batch_each_host(self, commitments, cell_indices, cells, proofs, n: int):
+        """kzg_verify_cell_proof_batch_each on n CONTIGUOUS tuples in host memory (arguments as verify_cell_proof_batch_host)
+        -> (ok_each, status, ok)"""
+        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
+        if isinstance(cell_indices, int):
+            cell_indices = ctypes.cast(cell_indices, _u64p)
+        elif isinstance(cell_indices, (bytes, bytearray, memoryview)):
+            cell_indices = (ctypes.c_uint64 * n).from_buffer_copy(cell_indices)
+        else:
+            cell_indices = (ctypes.c_uint64 * n)(*cell_indices)
+        args = [a if isinstance(a, int) else _buf(a) for a in (commitments, cells, proofs)]
+        rc = self._lib.kzg_verify_cell_proof_batch_each(self._h, args[0], cell_indices, args[1], args[2], n, ctypes.cast(ok_each, _u8p), status, ctypes.byref(ok))
+        return self._each_result(rc, "kzg_verify_cell_proof_batch_each", n, ok_each, status, ok)
+
+    def verify_cell_proof_batch_each_dev(self, d_commitments: int, d_cell_indices: int, d_cells: int, d_proofs: int, n: int, stream: int = 0):
+        """-> (ok_each: List[bool], status: List[int], ok: bool); synchronous, results in host memory"""
+        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
+        rc = self._lib.kzg_verify_cell_proof_batch_each_dev(self._h, d_commitments, d_cell_indices, d_cells, d_proofs, n, ctypes.cast(ok_each, _u8p), status,
+                                                            ctypes.byref(ok), stream)
+        return self._each_result(rc, "kzg_verify_cell_proof_batch_each_dev", n, ok_each, status, ok)
+
+    def g1_monomial_lincomb(self, vectors: Sequence[Sequence[int]]) -> List[bytes]:
+        """sum_j s_j [tau^j]_1 for each vector of 64 scalars (ints below r) as 96 bytes x || y big-endian, all-zero = the point at
+        infinity: the kernel behind the cells *_each calls' monomial term, on its own (kzg_g1_monomial_lincomb).  A scalar >= r raises
+        KzgError."""
+        m = len(vectors)
+        if any(len(v) != 64 for v in vectors):
+            raise ValueError("g1_monomial_lincomb: a vector is 64 scalars")
+        raw = b"".join(int(x).to_bytes(32, "big") for v in vectors for x in v)
+        out = (ctypes.c_uint8 * (96 * max(m, 1)))()
+        rc = self._lib.kzg_g1_monomial_lincomb(self._h, raw, m, ctypes.cast(out, _u8p))
+        self._check(rc, "kzg_g1_monomial_lincomb")
+        if rc > 0:
+            raise _kzg_error(rc)
+        res = bytes(out)
+        return [res[96 * k:96 * k + 96] for k in range(m)]
 
     def verify_blob_proof_batch_host(self, blobs, commitments, proofs, n: int) -> bool:
         """kzg_verify_blob_proof_batch on n CONTIGUOUS items in host memory: bytes-like objects or raw host addresses
