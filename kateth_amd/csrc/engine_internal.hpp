@@ -32,6 +32,7 @@
 #include "g1.cuh"
 #include "sha256.cuh"
 #include "pairing.hpp"
+#include "verify_kind.hpp"
 
 using namespace kzg;
 
@@ -322,21 +323,22 @@ template <class Fn>
 static inline int32_t on_members(const kzg_ctx* ctx, uint64_t n, Fn&& fn) {
   return is_group(ctx) ? on_group_members(ctx, n, std::ref(fn)) : fn(ctx, (uint64_t)0, n);
 }
-// The inputs of one batch verification call (engine_verify.hip: front_enqueue / front_status switch on `kind`), in the caller's host
-// buffers (`on_host`) or device-resident.  Its error record is `kinds()` x {local index of the first rejected item or -1, code}, in the
-// reference's parse order:
-//   BLOBS  (verify_blob_proof_batch): blobs, commitments48, proofs48       -> {blob, commitment, proof}   = the ABI's err6
-//   POINTS (verify_proof_batch):      proofs48, commitments48, z32, y32    -> {proof, commitment, z, y}   = the ABI's err8
-//   CELLS  (verify_cell_proof_batch): commitments48, cell_indices, cells, proofs48 -> {cell index, commitment, cell, proof}
+// The inputs of one batch verification call, in the caller's host buffers (`on_host`) or device-resident.  What the kinds differ in --
+// the error record among it -- is verify_kind.hpp's table:
+//   BLOBS  (verify_blob_proof_batch): blobs, commitments48, proofs48
+//   POINTS (verify_proof_batch):      proofs48, commitments48, z32, y32
+//   CELLS  (verify_cell_proof_batch): commitments48, cell_indices, cells, proofs48
+using VerifyKind = kzg::verify::Kind;
+using kzg::verify::facts;
+static_assert(facts(VerifyKind::CELLS).tail_terms == KZG_G1_MONOMIAL_POINTS, "lincomb B's fixed terms of the cells kind are the context's monomial points");
 struct VerifyInputs {
-  enum Kind { BLOBS, POINTS, CELLS } kind;
+  VerifyKind kind;
   const uint8_t *blobs, *commitments48, *proofs48, *z32, *y32;
   bool on_host;
   const uint64_t* cell_indices = nullptr;
   const uint8_t* cells = nullptr;
-  int kinds() const { return kind == BLOBS ? 3 : 4; }
   bool any_null() const {
-    return !commitments48 || !proofs48 || (kind == BLOBS ? !blobs : kind == POINTS ? (!z32 || !y32) : (!cell_indices || !cells));
+    return !commitments48 || !proofs48 || (kind == VerifyKind::BLOBS ? !blobs : kind == VerifyKind::POINTS ? (!z32 || !y32) : (!cell_indices || !cells));
   }
   VerifyInputs advanced(uint64_t first) const {  // the same inputs from item `first` on
     VerifyInputs a{kind, blobs ? blobs + first * (size_t)KZG_BYTES_PER_BLOB : nullptr, commitments48 + first * 48, proofs48 + first * 48,
@@ -347,19 +349,17 @@ struct VerifyInputs {
   }
 };
 static inline VerifyInputs blob_inputs(const void* blobs, const void* commitments48, const void* proofs48, bool on_host) {
-  return VerifyInputs{VerifyInputs::BLOBS, (const uint8_t*)blobs, (const uint8_t*)commitments48, (const uint8_t*)proofs48, nullptr, nullptr, on_host};
+  return VerifyInputs{VerifyKind::BLOBS, (const uint8_t*)blobs, (const uint8_t*)commitments48, (const uint8_t*)proofs48, nullptr, nullptr, on_host};
 }
 static inline VerifyInputs point_inputs(const void* proofs48, const void* commitments48, const void* z32, const void* y32, bool on_host) {
-  return VerifyInputs{VerifyInputs::POINTS, nullptr, (const uint8_t*)commitments48, (const uint8_t*)proofs48, (const uint8_t*)z32, (const uint8_t*)y32, on_host};
+  return VerifyInputs{VerifyKind::POINTS, nullptr, (const uint8_t*)commitments48, (const uint8_t*)proofs48, (const uint8_t*)z32, (const uint8_t*)y32, on_host};
 }
 static inline VerifyInputs cell_inputs(const void* commitments48, const void* cell_indices, const void* cells, const void* proofs48, bool on_host) {
-  VerifyInputs in{VerifyInputs::CELLS, nullptr, (const uint8_t*)commitments48, (const uint8_t*)proofs48, nullptr, nullptr, on_host};
+  VerifyInputs in{VerifyKind::CELLS, nullptr, (const uint8_t*)commitments48, (const uint8_t*)proofs48, nullptr, nullptr, on_host};
   in.cell_indices = (const uint64_t*)cell_indices;
   in.cells = (const uint8_t*)cells;
   return in;
 }
-// the terms behind the 2n points of lincomb B: the generator, or the 64 monomial points of the cells kind
-static inline uint64_t verify_tail_terms(VerifyInputs::Kind kind) { return kind == VerifyInputs::CELLS ? KZG_G1_MONOMIAL_POINTS : 1; }
 // the wanted ending of a batch call: one boolean (no VerifyEach), or the per-item verdicts of kzg_verify_*_batch_each beside it
 struct VerifyEach {
   uint8_t* ok_each;
@@ -372,10 +372,10 @@ int32_t verify_phase1(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hi
 // the same over a group's members, from host buffers (engine_multi.hip)
 int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, int32_t* ok);
 int32_t multi_verify_each(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, const VerifyEach& each, int32_t* ok);
-// kzg_verify_batch_finish for either pairing: `cells` checks the summed partials against [tau^64]_2 (engine_verify.hip)
-// the context's monomial G1 points stand (derived by the first caller, engine.hip); every cells call of a member passes through here
+// the context's monomial G1 points stand (derived by the first caller, engine.hip); every cells session of a member passes through here
 int32_t ensure_g1_monomial(const kzg_ctx* ctx);
-int32_t verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint64_t world, bool cells, int32_t* ok);
+// kzg_verify_batch_finish with the pairing of `kind`: the summed partials against [tau]_2 or [tau^64]_2 (engine_verify.hip)
+int32_t verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint64_t world, VerifyKind kind, int32_t* ok);
 // one member's device-resident share of a group verification (kzg_verify_*_batch_group_dev): global range [first, first + count),
 // inputs resident on member->device
 struct GroupDevShare {

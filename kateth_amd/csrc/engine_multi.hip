@@ -82,7 +82,7 @@ int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t 
   const std::vector<Share> shares = shares_of(ctx, n);
   if (shares.size() == 1) return verify_batch_single(member_of(ctx, shares[0].member), in, n, nullptr, nullptr, ok);
   const uint32_t W = (uint32_t)shares.size();
-  const int kinds = in.kinds();
+  const int kinds = facts(in.kind).entries;
   const size_t stride = 2 * (size_t)kinds;
   std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
   std::vector<int32_t> err(stride * W);
@@ -103,7 +103,7 @@ int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t 
     error_publish(keep);
   }
   if (rc || code) return rc ? rc : code;
-  return verify_batch_finish(ctx, partials.data(), W, in.kind == VerifyInputs::CELLS, ok);
+  return verify_batch_finish(ctx, partials.data(), W, in.kind, ok);
 }
 
 // Per-item verdicts (kzg_verify_*_batch_each) over the members: the same contiguous shares, each member's share its own batch with its
@@ -160,7 +160,7 @@ extern "C" int32_t kzg_compute_blob_proof_batch_group_dev(const kzg_ctx* ctx, co
 
 // the GroupDevShare list of the two *_group_dev calls: member k's pointers (an array the kind does not have is null) and its global range
 namespace {
-int32_t verify_group_shares(const kzg_ctx* ctx, VerifyInputs::Kind kind, const void* const* blobs, const void* const* commitments48, const void* const* proofs48,
+int32_t verify_group_shares(const kzg_ctx* ctx, VerifyKind kind, const void* const* blobs, const void* const* commitments48, const void* const* proofs48,
                             const void* const* z32, const void* const* y32, const uint64_t* n_local, void* const* hip_streams, int32_t* ok) {
   *ok = 0;
   const uint32_t S = 1u + (uint32_t)ctx->peers.size();
@@ -181,7 +181,7 @@ int32_t verify_group_shares(const kzg_ctx* ctx, VerifyInputs::Kind kind, const v
 extern "C" int32_t kzg_verify_blob_proof_batch_group_dev(const kzg_ctx* ctx, const void* const* d_blobs, const void* const* d_commitments48,
                                                          const void* const* d_proofs48, const uint64_t* n_local, int32_t* ok, void* const* hip_streams) try {
   if (!ctx || !ok || !d_blobs || !d_commitments48 || !d_proofs48 || !n_local) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return verify_group_shares(ctx, VerifyInputs::BLOBS, d_blobs, d_commitments48, d_proofs48, nullptr, nullptr, n_local, hip_streams, ok);
+  return verify_group_shares(ctx, VerifyKind::BLOBS, d_blobs, d_commitments48, d_proofs48, nullptr, nullptr, n_local, hip_streams, ok);
 } catch (...) {
   return abi_exception();
 }
@@ -190,7 +190,7 @@ extern "C" int32_t kzg_verify_proof_batch_group_dev(const kzg_ctx* ctx, const vo
                                                     const void* const* d_z32, const void* const* d_y32, const uint64_t* n_local, int32_t* ok,
                                                     void* const* hip_streams) try {
   if (!ctx || !ok || !d_proofs48 || !d_commitments48 || !d_z32 || !d_y32 || !n_local) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return verify_group_shares(ctx, VerifyInputs::POINTS, nullptr, d_commitments48, d_proofs48, d_z32, d_y32, n_local, hip_streams, ok);
+  return verify_group_shares(ctx, VerifyKind::POINTS, nullptr, d_commitments48, d_proofs48, d_z32, d_y32, n_local, hip_streams, ok);
 } catch (...) {
   return abi_exception();
 }

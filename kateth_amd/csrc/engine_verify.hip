@@ -27,7 +27,8 @@ struct kzg_verify_session {
   hipEvent_t ev_nodes = nullptr, ev_stat = nullptr, ev_aux = nullptr;  // owned: transcript digests read back; statuses read back; aux fork
   uint8_t* buf = nullptr;      // owned: one device allocation of `cap` bytes, carved below
   size_t cap = 0;
-  uint64_t tail = 1;       // lincomb B's terms behind the 2n points: the generator, or the cells kind's 64 monomial points (verify_tail_terms)
+  VerifyKind kind = VerifyKind::BLOBS;  // set when the session is acquired: every kind-dependent site below reads verify_kind.hpp's row of it
+  uint64_t tail = 1;       // facts(kind).tail_terms: lincomb B's terms behind the 2n points, the generator or the cells kind's 64 monomial points
   uint4* aff = nullptr;    // [2n+tail] affine points: proofs, commitments, generator | monomial points
   uint8_t* inf = nullptr;  // [2n+tail]
   fr_t* z = nullptr;       // [n] plain
@@ -36,7 +37,7 @@ struct kzg_verify_session {
   bool glv = false;        // n >= 32,768: both lincombs on GLV-split scalars (use_glv)
   fr_t* glv_b = nullptr;   // [2 (2n+tail)]: k1 | k2 of scal
   fr_t* glv_a = nullptr;   // [2n]: k1 | k2 of the r_i
-  int32_t* stat = nullptr;   // [4n] blob / commitment / proof status; verify_proof_batch: z / commitment / proof / y status
+  int32_t* stat = nullptr;   // [4n] one status array per entry of the kind's error record (stat_of)
   unsigned long long* first4 = nullptr;  // verify_proof_batch: (index << 32) | code of the first rejected proof, commitment, z, y (k_first_errors)
   uint32_t* leaves = nullptr;  // transcript: n leaves, ceil(n / 16) mid digests, ceil(n / 256) nodes
   uint32_t* mids = nullptr;
@@ -53,10 +54,7 @@ struct kzg_verify_session {
   uint32_t* h_nodes = nullptr;  // [ceil(n / 256) * 8]
   unsigned long long* h_first4 = nullptr;  // [4] read-back of first4
   size_t h_cap = 0;
-  bool points = false;       // the front was verify_proof_batch's: the status arrays are z / commitment / proof / y
-  // the cells kind (front_enqueue sets them): the status arrays are cell / commitment / proof / cell index; phase 2 reads the cells again
-  bool cells = false;
-  const uint8_t* d_cells = nullptr;
+  const uint8_t* d_cells = nullptr;  // the cells kind (front_enqueue records them): phase 2 reads the cells again
   const uint64_t* d_cell_indices = nullptr;
   fr_t* cell_part = nullptr;   // [ceil(n / CELLV_CELLS) x 64] k_cells_interp's partial coefficient vectors
   uint8_t* cells_in = nullptr; // [n * 2048 | n * 8] device copy of cells || cell indices (host-buffer entry point)
@@ -84,6 +82,14 @@ static void session_free(kzg_verify_session* s) {
   for (hipEvent_t e : {s->ev_fork, s->ev_join, s->ev_nodes, s->ev_stat, s->ev_aux})
     if (e) (void)hipEventDestroy(e);
   delete s;
+}
+// the status array of entry `entry` of the session's error record (verify_kind.hpp); null for an entry the record does not have
+static int32_t* stat_of(const kzg_verify_session* s, int entry) {
+  const int slot = facts(s->kind).slot[entry];
+  return slot < 0 ? nullptr : s->stat + (uint64_t)slot * s->n;
+}
+static const host::miller_lines& lines_against_a(const kzg_ctx* ctx, VerifyKind kind) {  // the G2 point of the pairing against A
+  return facts(kind).pair_tau64 ? ctx->pairing->lines_tau64 : ctx->pairing->lines_tau;
 }
 void session_pool_clear(const kzg_ctx* ctx) {
   std::lock_guard<std::mutex> guard(ctx->pool_lock);
@@ -447,10 +453,12 @@ struct SessionLayout {
   size_t o_aff, o_inf, o_z, o_y, o_scal, o_glv_b, o_glv_a, o_stat, o_first4, o_leaves, o_mids, o_nodes, o_pts, o_zy, o_msm_a, o_msm_b, o_rpow, o_ysum, o_cell_part,
       o_cells_in, total;
 };
-// `tail`: verify_tail_terms of the call's kind; `stage_cells`: room for a host-buffer cells call's device copies.  With tail = 1 the
-// layout of the blob and points kinds is what it always was.
-static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n, uint64_t tail, bool stage_cells) {
+// `staged`: room for the device copies of a host-buffer cells call's cells and indices (points_stage_host); the other kinds have nothing
+// that is carved on demand.  With one tail term the layout of the blob and points kinds is what it always was.
+static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n, VerifyKind kind, bool staged) {
   SessionLayout L{};
+  const bool is_cells = kind == VerifyKind::CELLS;
+  const uint64_t tail = facts(kind).tail_terms;
   const uint64_t groups = (n + 255) / 256;
   Carve pool;
   const bool glv = use_glv(ctx, n);
@@ -472,16 +480,23 @@ static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n, uint64_t tai
   L.o_msm_b = pool.take((glv ? msm_var_layout(ctx, 2 * (2 * n + tail), true) : msm_var_layout(ctx, 2 * n + tail, false, 3 * n + tail)).total + 256);
   L.o_rpow = pool.take(64 * 32);
   L.o_ysum = pool.take(((n + 255) / 256 + 1) * 32);
-  L.o_cell_part = pool.take(tail > 1 ? blocks_for(n, CELLV_CELLS) * (size_t)64 * sizeof(fr_t) : 0);
-  L.o_cells_in = pool.take(stage_cells ? n * ((size_t)KZG_BYTES_PER_CELL + 8) : 0);
+  L.o_cell_part = pool.take(is_cells ? blocks_for(n, CELLV_CELLS) * (size_t)64 * sizeof(fr_t) : 0);
+  L.o_cells_in = pool.take(is_cells && staged ? n * ((size_t)KZG_BYTES_PER_CELL + 8) : 0);
   L.total = pool.off;
   return L;
 }
 
-// Takes a session from the context's pool (or creates one), sized for n items, and enqueues its initialisation on `st`.
-static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, kzg_verify_session** out, uint64_t tail = 1, bool stage_cells = false) {
+// Takes a session from the context's pool (or creates one), sized for n items of `kind`, and enqueues its initialisation on `st`.
+// `staged`: session_layout's.  The caller has set the device.
+static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, VerifyKind kind, bool staged, kzg_verify_session** out) {
   *out = nullptr;
-  const SessionLayout L = session_layout(ctx, n, tail, stage_cells);
+  const bool is_cells = kind == VerifyKind::CELLS;
+  if (is_cells) {  // lincomb B's fixed terms, copied in below: derived by this member's first cells session
+    const int32_t rc = ensure_g1_monomial(ctx);
+    if (rc) return rc;
+  }
+  const uint64_t tail = facts(kind).tail_terms;
+  const SessionLayout L = session_layout(ctx, n, kind, staged);
   kzg_verify_session* s = nullptr;
   {
     std::lock_guard<std::mutex> guard(ctx->pool_lock);
@@ -552,11 +567,10 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
   if (st == KZG_SESSION_STREAM) st = s->side;
   s->n = n;
   s->st = st;
-  s->points = false;
-  s->cells = false;
+  s->kind = kind;
+  s->tail = tail;
   s->d_cells = nullptr;
   s->d_cell_indices = nullptr;
-  s->tail = tail;
   s->tree_n = 0;
   s->aff = (uint4*)(s->buf + L.o_aff);
   s->inf = s->buf + L.o_inf;
@@ -580,7 +594,7 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, k
   s->cell_part = (fr_t*)(s->buf + L.o_cell_part);
   s->cells_in = s->buf + L.o_cells_in;
   // generator term (cells: the monomial terms), cleared flags and statuses
-  const uint4* fixed = tail > 1 ? ctx->d_g1_monomial : ctx->d_gen_affine;  // `tail` points, their [z^2]-images behind them
+  const uint4* fixed = is_cells ? ctx->d_g1_monomial : ctx->d_gen_affine;  // `tail` points, their [z^2]-images behind them
   if (hipMemcpyAsync(s->aff + (2 * n) * 6, fixed, tail * 96, hipMemcpyDeviceToDevice, st) != hipSuccess ||
       (s->glv && hipMemcpyAsync(s->aff + ((2 * n + tail) + 2 * n) * 6, fixed + tail * 6, tail * 96, hipMemcpyDeviceToDevice, st) != hipSuccess) ||  // [z^2]G
       hipMemsetAsync(s->inf, 0, 2 * n + tail, st) != hipSuccess || hipMemsetAsync(s->stat, 0, 4 * n * 4 + 4, st) != hipSuccess) {
@@ -628,7 +642,7 @@ static int32_t phase1_items(kzg_verify_session* s, const uint8_t* blobs, const u
   if (m == 0) return 0;
   fr_t* z = s->z + base;
   fr_t* y = s->y + base;
-  int32_t* stat_blob = s->stat + base;
+  int32_t* stat_blob = stat_of(s, kzg::verify::BLOBS_BLOB) + base;
   // SHA-256 challenge first, alone: its long-lived waves (one per SIMD at n = 65,536) must be spread evenly -- launched
   // next to the decode kernel they were placed around its waves and the kernel took 3x longer (profiles/r01: 23 ms vs
   // 7.5 ms).  The point decoding then runs on the side stream concurrently with the evaluation kernel, whose short blocks
@@ -675,21 +689,24 @@ static int32_t phase1_items(kzg_verify_session* s, const uint8_t* blobs, const u
   return 0;
 }
 
-// ---- phase 1 in three pieces (the fused single-context call interleaves them with phase 2's, see verify_fused) -------------
-// (a) transcript over all n items -- it hashes the input BYTES and (z, y): it does not wait for the decoded points -- and the
-//     read-back of its node digests, enqueued on `st`
-static int32_t p1_transcript(kzg_verify_session* s, const uint8_t* com, const uint8_t* prf) {
-  const uint64_t n = s->n;
+// The transcript's upper levels behind a kind's leaf kernel on the caller's stream: 16 leaves per mid digest, 16 mid digests per node,
+// and the read-back of the node digests, done at ev_nodes.  Also the launch check of the leaf kernel before it.
+static int32_t p1_transcript_nodes(kzg_verify_session* s) {
+  const uint64_t n = s->n, nmid = (n + 15) / 16, groups = (n + 255) / 256;  // groups == ceil(nmid / 16)
   hipStream_t st = s->st;
-  const uint64_t groups = (n + 255) / 256;
-  hipLaunchKernelGGL(k_transcript_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, prf, s->z, s->y, n, s->leaves);
-  const uint64_t nmid = (n + 15) / 16;  // groups == ceil(nmid / 16)
   hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(nmid, 64)), dim3(64), 0, st, s->leaves, n, 16u, s->mids);
   hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(groups, 64)), dim3(64), 0, st, s->mids, nmid, 16u, s->nodes);
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "verify phase 1 launch failed");
   if (hipMemcpyAsync(s->h_nodes, s->nodes, groups * 32, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(s->ev_nodes, st) != hipSuccess)
     return fail(KZG_FAIL_HIP, "verify phase 1 readback failed");
   return 0;
+}
+// ---- phase 1 in three pieces (the fused single-context call interleaves them with phase 2's, see verify_fused) -------------
+// (a) transcript over all n items -- it hashes the input BYTES and (z, y): it does not wait for the decoded points -- and the
+//     read-back of its node digests, enqueued on `st`
+static int32_t p1_transcript(kzg_verify_session* s, const uint8_t* com, const uint8_t* prf) {
+  hipLaunchKernelGGL(k_transcript_leaves, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->st, com, prf, s->z, s->y, s->n, s->leaves);
+  return p1_transcript_nodes(s);
 }
 // (b) local transcript root = SHA-256 over the node digests (big-endian bytes); waits for (a) only -- the decoder may still run
 static int32_t p1_root(kzg_verify_session* s, uint8_t* out_root32) {
@@ -700,13 +717,17 @@ static int32_t p1_root(kzg_verify_session* s, uint8_t* out_root32) {
   sha256_bytes(out_root32, nb.data(), nb.size());
   return 0;
 }
-// ---- the two kinds of call (VerifyInputs, engine_internal.hpp): what differs between them is the front and how the error record is read ----
-// the device copies of a host-buffer call in its session: proofs || commitments, z || y (the blobs pass through the staging arena)
-static VerifyInputs staged_inputs(const kzg_verify_session* s, VerifyInputs::Kind kind) {
+// ---- the kinds of call (verify_kind.hpp): what differs between them is the front and how the error record is read ----
+// the device copies of a host-buffer call in its session: proofs || commitments, z || y, cells || indices (the blobs pass through the
+// staging arena)
+static VerifyInputs staged_inputs(const kzg_verify_session* s) {
   const uint64_t n = s->n;
-  if (kind == VerifyInputs::CELLS) return cell_inputs(s->pts48 + n * 48, s->cells_in + n * (size_t)KZG_BYTES_PER_CELL, s->cells_in, s->pts48, false);
-  return kind == VerifyInputs::BLOBS ? blob_inputs(nullptr, s->pts48 + n * 48, s->pts48, false)
-                                     : point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32, false);
+  switch (s->kind) {
+    case VerifyKind::BLOBS: return blob_inputs(nullptr, s->pts48 + n * 48, s->pts48, false);
+    case VerifyKind::POINTS: return point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32, false);
+    case VerifyKind::CELLS: break;
+  }
+  return cell_inputs(s->pts48 + n * 48, s->cells_in + n * (size_t)KZG_BYTES_PER_CELL, s->cells_in, s->pts48, false);
 }
 static void err_clear(int32_t* err, int kinds) {
   for (int k = 0; k < 2 * kinds; k++) err[k] = (k % 2 == 0) ? -1 : 0;
@@ -721,68 +742,59 @@ static int32_t first_error_code(const int32_t* err, int kinds) {
 // end is ev_join and the transcript's node digests are on their way back behind ev_nodes (p1_root).
 //   BLOBS:  hash, [decoder] || evaluation, transcript (phase1_items, p1_transcript)
 //   CELLS:  as POINTS, with k_cells_leaves (cellverify_kernels.cuh) in k_points_leaves' place
-//   POINTS: neither hash nor evaluation: [decoder for all 2n points on the side stream] || k_points_leaves (parses z and y, their
-//           statuses in the blob slot and the fourth) -> k_transcript_nodes x 2.  The statuses never cross to the host (front_status).
+//   POINTS: neither hash nor evaluation: [decoder for all 2n points on the side stream] || k_points_leaves (parses z and y and writes
+//           their statuses) -> k_transcript_nodes x 2.  The statuses never cross to the host (front_status).
+// `in`: device-resident inputs of the session's kind.
 static int32_t front_enqueue(kzg_verify_session* s, const VerifyInputs& in) {
   const kzg_ctx* ctx = s->ctx;
   const uint64_t n = s->n;
   hipStream_t st = s->st;
   const uint8_t *com = in.commitments48, *prf = in.proofs48;
-  switch (in.kind) {
-    case VerifyInputs::BLOBS: {
+  switch (s->kind) {
+    case VerifyKind::BLOBS: {
       const int32_t rc = phase1_items(s, in.blobs, com, prf, 0, n, st, true);
       return rc ? rc : p1_transcript(s, com, prf);
     }
-    case VerifyInputs::POINTS:
-    case VerifyInputs::CELLS: {
-      // CELLS: the points call's launch order with k_cells_leaves as the front kernel: it parses the index and the cell (their statuses in
-      // the fourth slot and the blob slot), writes z = h^64 and y = 0, and hashes the 34-block leaf; the cells are read again in phase 2
-      s->points = in.kind == VerifyInputs::POINTS;
-      s->cells = in.kind == VerifyInputs::CELLS;
+    case VerifyKind::POINTS:
+    case VerifyKind::CELLS: {
+      // CELLS: the points call's launch order with k_cells_leaves as the front kernel: it parses the index and the cell, writes
+      // z = h^64 and y = 0, and hashes the 34-block leaf; the cells are read again in phase 2
       s->d_cells = in.cells;
       s->d_cell_indices = in.cell_indices;
       // the decoder is ONE launch over proofs and commitments: no event after the proof half for lincomb A to wait on instead of ev_join
       decode_on_side(s, s->side, 0, 2 * n, prf, com, DECODE_FINISH | (fused_prep_fits(ctx, n, 2 * n) ? DECODE_WHOLE : 0u));
       if (hipMemsetAsync(s->first4, 0xff, 4 * sizeof(unsigned long long), s->side) != hipSuccess)  // for k_first_errors, later on this stream
         return fail(KZG_FAIL_HIP, "verify_proof_batch: fork failed");
-      const uint64_t groups = (n + 255) / 256, nmid = (n + 15) / 16;
-      if (s->cells)
+      if (s->kind == VerifyKind::CELLS)
         hipLaunchKernelGGL(k_cells_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, reinterpret_cast<const unsigned long long*>(in.cell_indices), in.cells, prf, n,
-                           ctx->d_cellv_h64, s->z, s->y, s->stat + 3 * n, s->stat, s->leaves);
+                           ctx->d_cellv_h64, s->z, s->y, stat_of(s, kzg::verify::CELLS_INDEX), stat_of(s, kzg::verify::CELLS_CELL), s->leaves);
       else
-        hipLaunchKernelGGL(k_points_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, prf, in.z32, in.y32, n, s->z, s->y, s->stat, s->stat + 3 * n, s->leaves);
-      hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(nmid, 64)), dim3(64), 0, st, s->leaves, n, 16u, s->mids);
-      hipLaunchKernelGGL(k_transcript_nodes, dim3(blocks_for(groups, 64)), dim3(64), 0, st, s->mids, nmid, 16u, s->nodes);
-      if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: phase 1 launch failed");
-      if (hipMemcpyAsync(s->h_nodes, s->nodes, groups * 32, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(s->ev_nodes, st) != hipSuccess)
-        return fail(KZG_FAIL_HIP, "verify_proof_batch: phase 1 readback failed");
-      return 0;
+        hipLaunchKernelGGL(k_points_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, prf, in.z32, in.y32, n, s->z, s->y, stat_of(s, kzg::verify::POINTS_Z),
+                           stat_of(s, kzg::verify::POINTS_Y), s->leaves);
+      return p1_transcript_nodes(s);
     }
   }
   return fail(KZG_FAIL_ARGUMENT, "unknown kind of verification call");
 }
-// The first rejected item of each kind -> err = in.kinds() x {local index, code}.  Both ride on the DECODER's stream, right behind the
+// The first rejected item of each entry of the error record -> err = entries x {local index, code}.  Both ride on the DECODER's stream, right behind the
 // decoder, not on the caller's: there they would queue up behind the bucket kernels of phase 2.
 //   BLOBS:  3n status words come back and the host scans them beside the bucket kernels (the blob statuses were written by the
 //           evaluation kernel, which ended before the root was read)
 //   POINTS, CELLS: k_first_errors (it also waits for k_points_leaves' two status arrays: ev_nodes was recorded after it) and 32 bytes come back
-static int32_t front_status(kzg_verify_session* s, const VerifyInputs& in, int32_t* err) {
+static int32_t front_status(kzg_verify_session* s, int32_t* err) {
   const uint64_t n = s->n;
   hipStream_t side = s->side;
-  switch (in.kind) {
-    case VerifyInputs::BLOBS:
+  switch (s->kind) {
+    case VerifyKind::BLOBS:
       if (hipStreamWaitEvent(side, s->ev_join, 0) != hipSuccess || hipMemcpyAsync(s->h_stat, s->stat, 3 * n * 4, hipMemcpyDeviceToHost, side) != hipSuccess ||
           hipEventRecord(s->ev_stat, side) != hipSuccess || hipEventSynchronize(s->ev_stat) != hipSuccess)
         return fail(KZG_FAIL_HIP, "verify phase 1 status readback failed");
-      for (int k = 0; k < 3; k++) scan_first_error(s->h_stat + k * n, n, &err[2 * k], &err[2 * k + 1]);
+      for (int k = 0; k < 3; k++) scan_first_error(s->h_stat + (uint64_t)facts(s->kind).slot[k] * n, n, &err[2 * k], &err[2 * k + 1]);
       return 0;
-    case VerifyInputs::POINTS:
-    case VerifyInputs::CELLS:
+    case VerifyKind::POINTS:
+    case VerifyKind::CELLS:
       if (hipStreamWaitEvent(side, s->ev_nodes, 0) != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: status wait failed");
-      if (in.kind == VerifyInputs::CELLS)  // cell index, commitment, cell, proof
-        hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(n, 256)), dim3(256), 0, side, s->stat + 3 * n, s->stat + n, s->stat, s->stat + 2 * n, n, s->first4);
-      else
-        hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(n, 256)), dim3(256), 0, side, s->stat + 2 * n, s->stat + n, s->stat, s->stat + 3 * n, n, s->first4);
+      hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(n, 256)), dim3(256), 0, side, stat_of(s, 0), stat_of(s, 1), stat_of(s, 2), stat_of(s, 3), n, s->first4);
       if (hipGetLastError() != hipSuccess || hipMemcpyAsync(s->h_first4, s->first4, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, side) != hipSuccess ||
           hipEventRecord(s->ev_stat, side) != hipSuccess || hipEventSynchronize(s->ev_stat) != hipSuccess)
         return fail(KZG_FAIL_HIP, "verify_proof_batch: status readback failed");
@@ -795,11 +807,14 @@ static int32_t front_status(kzg_verify_session* s, const VerifyInputs& in, int32
   }
   return fail(KZG_FAIL_ARGUMENT, "unknown kind of verification call");
 }
+// the body of the two kzg_verify_*phase1_dev entry points
+static int32_t phase1_entry(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, uint8_t* out_root32, int32_t* err, kzg_verify_session** session) {
+  if (!ctx || !out_root32 || !err || !session || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return verify_phase1(ctx, in, n, st, out_root32, err, session);
+}
 extern "C" int32_t kzg_verify_phase1_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_proofs48,
                                          uint64_t n, uint8_t* out_root32, int32_t* err6, kzg_verify_session** session, void* hip_stream) try {
-  const VerifyInputs in = blob_inputs(d_blobs, d_commitments48, d_proofs48, false);
-  if (!ctx || !out_root32 || !err6 || !session || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return verify_phase1(ctx, in, n, (hipStream_t)hip_stream, out_root32, err6, session);
+  return phase1_entry(ctx, blob_inputs(d_blobs, d_commitments48, d_proofs48, false), n, (hipStream_t)hip_stream, out_root32, err6, session);
 } catch (...) {
   return abi_exception();
 }
@@ -836,7 +851,7 @@ static int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, cons
   if (rc) return rc;
   hipStream_t st = ctx->verify_stream;
   SessionUse use;  // declared behind the lock: a failed call's session is drained and pooled before the arena is handed on
-  rc = session_acquire(ctx, n, st, &use.s);
+  rc = session_acquire(ctx, n, st, VerifyKind::BLOBS, false, &use.s);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   do {
@@ -882,7 +897,7 @@ static int32_t verify_phase1_host(const kzg_ctx* ctx, const uint8_t* blobs, cons
     }
     rc = p1_transcript(s, com, prf);
     if (rc == 0) rc = p1_root(s, out_root32);
-    if (rc == 0 && err6) rc = front_status(s, staged_inputs(s, VerifyInputs::BLOBS), err6);
+    if (rc == 0 && err6) rc = front_status(s, err6);
     tt.mark("gpu kernels + readback + root hash (+ status scan)");
   } while (0);
   if (rc) {
@@ -904,14 +919,14 @@ static int32_t points_stage_host(const kzg_ctx* ctx, const VerifyInputs& in, uin
     if (rc) return rc;
   }
   SessionUse use;
-  const bool cells = in.kind == VerifyInputs::CELLS;
-  const int32_t rc = session_acquire(ctx, n, ctx->verify_stream, &use.s, verify_tail_terms(in.kind), cells);
+  const bool is_cells = in.kind == VerifyKind::CELLS;
+  const int32_t rc = session_acquire(ctx, n, ctx->verify_stream, in.kind, true, &use.s);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   if (hipMemcpyAsync(s->pts48, in.proofs48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
       hipMemcpyAsync(s->pts48 + n * 48, in.commitments48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess)
     return fail(KZG_FAIL_HIP, "host-to-device copy failed");
-  if (cells ? (hipMemcpyAsync(s->cells_in, in.cells, n * (size_t)KZG_BYTES_PER_CELL, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+  if (is_cells ? (hipMemcpyAsync(s->cells_in, in.cells, n * (size_t)KZG_BYTES_PER_CELL, hipMemcpyHostToDevice, s->st) != hipSuccess ||
                hipMemcpyAsync(s->cells_in + n * (size_t)KZG_BYTES_PER_CELL, in.cell_indices, n * 8, hipMemcpyHostToDevice, s->st) != hipSuccess)
             : (hipMemcpyAsync(s->zy32, in.z32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess ||
                hipMemcpyAsync(s->zy32 + n * 32, in.y32, n * 32, hipMemcpyHostToDevice, s->st) != hipSuccess))
@@ -925,24 +940,19 @@ static int32_t points_stage_host(const kzg_ctx* ctx, const VerifyInputs& in, uin
 int32_t verify_phase1(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, uint8_t* out_root32, int32_t* err, kzg_verify_session** session) {
   *session = nullptr;
   HIP_TRY(hipSetDevice(ctx->device));
-  if (in.kind == VerifyInputs::CELLS) {
-    const int32_t rc = ensure_g1_monomial(ctx);
-    if (rc) return rc;
-  }
-  if (in.on_host && in.kind == VerifyInputs::BLOBS)  // through the staging arena: front and root while stage_lock is held
+  if (in.on_host && in.kind == VerifyKind::BLOBS)  // through the staging arena: front and root while stage_lock is held
     return verify_phase1_host(ctx, in.blobs, in.commitments48, in.proofs48, n, out_root32, err, session);
   TraceTimer tt(ctx->knobs.trace, "phase1");
-  err_clear(err, in.kinds());
+  err_clear(err, facts(in.kind).entries);
   SessionUse use;
-  int32_t rc = in.on_host ? points_stage_host(ctx, in, n, &use.s) : session_acquire(ctx, n, st, &use.s, verify_tail_terms(in.kind));
+  int32_t rc = in.on_host ? points_stage_host(ctx, in, n, &use.s) : session_acquire(ctx, n, st, in.kind, false, &use.s);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   tt.mark("session");
   if (n) {
-    const VerifyInputs dev = in.on_host ? staged_inputs(s, in.kind) : in;
-    rc = front_enqueue(s, dev);
+    rc = front_enqueue(s, in.on_host ? staged_inputs(s) : in);
     if (rc == 0) rc = p1_root(s, out_root32);
-    if (rc == 0) rc = front_status(s, dev, err);
+    if (rc == 0) rc = front_status(s, err);
     tt.mark("gpu kernels + readback + first errors + root hash");
   } else {
     sha256_bytes(out_root32, nullptr, 0);
@@ -1114,7 +1124,7 @@ struct Phase2 {
 static int32_t p2_seed(kzg_verify_session* s, const uint8_t* roots32, uint64_t world, uint64_t n_total) {
   hipStream_t st = s->st;
   std::vector<uint8_t> msg(48 + 32 * world);
-  memcpy(msg.data(), s->cells ? "RCKZGCBATCH__V1_" : "RCKZGBATCH___V1_", 16);  // the spec's domains of the blob batch and the cell batch
+  memcpy(msg.data(), facts(s->kind).domain, 16);  // the spec's domain of the blob batch or the cell batch
   memset(msg.data() + 16, 0, 32);
   msg[30] = 0x10;  // 4096 as u128 big-endian
   for (int k = 0; k < 8; k++) msg[47 - k] = (uint8_t)(n_total >> (8 * k));
@@ -1138,12 +1148,12 @@ static int32_t p2_scalars(kzg_verify_session* s, const uint8_t* roots32, uint64_
   if (rc) return rc;
   const unsigned nblk = blocks_for(n, 256);
   hipLaunchKernelGGL(k_batch_scalars, dim3(nblk), dim3(256), 0, st, s->rpow2, s->z, s->y, n, first_index, s->scal + n, s->scal, s->ysum);
-  if (s->cells) {
+  if (s->kind == VerifyKind::CELLS) {
     // y = 0: the generator's slot is S_0's.  The 64 scalars -S_j of the monomial terms: r^k (s->scal + n, just written) times the
     // interpolation polynomial of cell k, summed per workgroup, then over the workgroups
     const unsigned ngrp = blocks_for(n, CELLV_CELLS);
     hipLaunchKernelGGL(k_cells_interp, dim3(ngrp), dim3(CELLV_THREADS), 0, st, s->d_cells, reinterpret_cast<const unsigned long long*>(s->d_cell_indices),
-                       s->stat + 3 * n, s->stat, s->scal + n, n, s->ctx->d_cells_tab, s->ctx->d_cellv_tab, s->cell_part);
+                       stat_of(s, kzg::verify::CELLS_INDEX), stat_of(s, kzg::verify::CELLS_CELL), s->scal + n, n, s->ctx->d_cells_tab, s->ctx->d_cellv_tab, s->cell_part);
     hipLaunchKernelGGL(k_cells_reduce, dim3(1), dim3(256), 0, st, s->cell_part, ngrp, s->scal + 2 * n);
   } else {
     hipLaunchKernelGGL(k_batch_ysum_finish, dim3(1), dim3(256), 0, st, s->ysum, nblk, s->scal + 2 * n);
@@ -1242,7 +1252,7 @@ static int32_t p2_finish_and_pair(kzg_verify_session* s, Phase2& p2, int32_t* ok
   if (!(p2.ja.active && p2.jb.active && (p2.ja.nout + p2.jb.nout) >= 64)) {  // a handful of terms: the plain path
     uint8_t partial[192];
     int32_t rc = p2_finish(s, p2, partial);
-    return rc ? rc : verify_batch_finish(ctx, partial, 1, s->cells, ok);
+    return rc ? rc : verify_batch_finish(ctx, partial, 1, s->kind, ok);
   }
   TraceTimer tt(ctx->knobs.trace, "phase2 finish + pairing");
   host::fp12 fa = host::f12_one(), fb = host::f12_one();
@@ -1262,7 +1272,7 @@ static int32_t p2_finish_and_pair(kzg_verify_session* s, Phase2& p2, int32_t* ok
   (void)run_on_helpers(2, [&](uint32_t k) -> int32_t {
     if (k == 0) return rcb = one(p2.jb, ctx->pairing->lines_g2, false, fb);
     (void)hipSetDevice(device);
-    return rca = one(p2.ja, s->cells ? ctx->pairing->lines_tau64 : ctx->pairing->lines_tau, true, fa);  // cells: e(A, [tau^64]_2)
+    return rca = one(p2.ja, lines_against_a(ctx, s->kind), true, fa);
   });
   (void)hipStreamSynchronize(s->st);
   tt.mark("read-backs, horner, miller loops (two threads)");
@@ -1322,12 +1332,12 @@ static int32_t verify_one_tail(kzg_verify_session* s, int32_t* ok) {
 // so the bucket kernels start the moment the decoder ends.  Before, all of that queued up behind it: a host round trip and
 // ~0.7 ms of short kernels on a nearly idle chip (profiles/r03/verify65536_kernel_timeline.txt).  The statuses are read after
 // the bucket kernels are enqueued; a rejected input still wins (its code is returned, the sums are discarded).
-// `in`: either kind of call; `root_done`: the host-buffer blob path, whose front ran -- and whose root was taken -- while the staging
-// arena was still locked (verify_phase1_host).
-static int32_t verify_fused(kzg_verify_session* s, const VerifyInputs& in, int32_t* ok, const char* label, const uint8_t* root_done = nullptr) {
+// `in`: device-resident inputs of the session's kind; `root_done`: the host-buffer blob path, whose front ran -- and whose root was
+// taken -- while the staging arena was still locked (verify_phase1_host).
+static int32_t verify_fused(kzg_verify_session* s, const VerifyInputs& in, int32_t* ok, const uint8_t* root_done) {
   const kzg_ctx* ctx = s->ctx;
-  const int kinds = in.kinds();
-  TraceTimer tt(ctx->knobs.trace, label);
+  const int kinds = facts(s->kind).entries;
+  TraceTimer tt(ctx->knobs.trace, facts(s->kind).trace_fused);
   uint8_t root[32];
   int32_t err[8];
   err_clear(err, kinds);
@@ -1343,7 +1353,7 @@ static int32_t verify_fused(kzg_verify_session* s, const VerifyInputs& in, int32
   if (rc == 0) rc = p2_scalars(s, root, 1, 0, s->n);
   if (rc == 0) rc = p2_sort(s, p2, true);
   if (rc == 0) rc = p2_accumulate(s, p2);
-  if (rc == 0) rc = front_status(s, in, err);
+  if (rc == 0) rc = front_status(s, err);
   tt.mark("decoder done, first errors");
   const int32_t code = rc == 0 ? first_error_code(err, kinds) : 0;
   if (rc == 0 && code == 0) rc = p2_finish_and_pair(s, p2, ok);
@@ -1372,11 +1382,11 @@ extern "C" int32_t kzg_verify_session_zy(kzg_verify_session* s, uint64_t first, 
 
 extern "C" int32_t kzg_verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint64_t world, int32_t* ok) try {
   if (!ctx || !ok || (world && !partials192)) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return verify_batch_finish(ctx, partials192, world, false, ok);
+  return verify_batch_finish(ctx, partials192, world, VerifyKind::BLOBS, ok);  // the blob and points kinds' pairing: partials carry no kind
 } catch (...) {
   return abi_exception();
 }
-int32_t verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint64_t world, bool cells, int32_t* ok) {
+int32_t verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint64_t world, VerifyKind kind, int32_t* ok) {
   *ok = 0;
   g1_xyzz A, B;
   xyzz_set_inf(A);
@@ -1392,7 +1402,7 @@ int32_t verify_batch_finish(const kzg_ctx* ctx, const uint8_t* partials192, uint
   TraceTimer tt(ctx->knobs.trace, "finish");
   host_affine_from_xyzz(a, A);
   host_affine_from_xyzz(b, B);
-  *ok = host::verify_pairings_fixed(*ctx->pairing, a, b, cells) ? 1 : 0;
+  *ok = host::verify_pairings_fixed(*ctx->pairing, lines_against_a(ctx, kind), a, b) ? 1 : 0;
   tt.mark("pairing");
   return 0;
 }
@@ -1402,12 +1412,18 @@ static int32_t empty_batch(int32_t* ok) {
   *ok = 1;
   return 0;
 }
+// The body of the twelve kzg_verify_*_batch[_each][_dev] entry points: `each` = the per-item forms' outputs, `st` = the caller's stream
+// of the _dev forms.  Host buffers on a group context go over its members; device pointers stay on the context they were given to.
+static int32_t batch_entry(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, const VerifyEach* each, int32_t* ok, hipStream_t st) {
+  if (!ctx || !ok || (n && (in.any_null() || (each && (!each->ok_each || !each->status))))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return empty_batch(ok);
+  if (in.on_host && is_group(ctx)) return each ? multi_verify_each(ctx, in, n, *each, ok) : multi_verify_batch(ctx, in, n, ok);
+  return verify_batch_single(ctx, in, n, st, each, ok);
+}
 
 extern "C" int32_t kzg_verify_blob_proof_batch_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_proofs48,
                                                    uint64_t n, int32_t* ok, void* hip_stream) try {
-  const VerifyInputs in = blob_inputs(d_blobs, d_commitments48, d_proofs48, false);
-  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, nullptr, ok) : empty_batch(ok);
+  return batch_entry(ctx, blob_inputs(d_blobs, d_commitments48, d_proofs48, false), n, nullptr, ok, (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }
@@ -1422,11 +1438,11 @@ int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& s
   *ok = 0;
   const uint32_t W = (uint32_t)shares.size();
   if (W == 0) return empty_batch(ok);
-  const bool points = shares[0].in.kind == VerifyInputs::POINTS;
+  const VerifyKind kind = shares[0].in.kind;
   // one share: exactly the single-device call (one root seeds the challenge)
   if (W == 1) return verify_batch_single(shares[0].member, shares[0].in, shares[0].count, shares[0].st, nullptr, ok);
-  TraceTimer tt(ctx->knobs.trace, points ? "group verify_proof_batch (device-resident)" : "group verify (device-resident)");
-  const int kinds = shares[0].in.kinds();
+  TraceTimer tt(ctx->knobs.trace, facts(kind).trace_group_dev);
+  const int kinds = facts(kind).entries;
   const size_t stride = 2 * (size_t)kinds;
   std::vector<uint8_t> roots(32 * (size_t)W), partials(192 * (size_t)W);
   std::vector<int32_t> err(stride * W);
@@ -1440,7 +1456,7 @@ int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& s
   int32_t rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
     const GroupDevShare& sh = shares[j];
     if (hipSetDevice(sh.member->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
-    int32_t r = session_acquire(sh.member, sh.count, sh.st, &uses[j].s);
+    int32_t r = session_acquire(sh.member, sh.count, sh.st, kind, false, &uses[j].s);
     if (r == 0) r = front_enqueue(uses[j].s, sh.in);
     if (r == 0) r = p1_root(uses[j].s, roots.data() + 32 * (size_t)j);
     return r;
@@ -1460,7 +1476,7 @@ int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& s
     int32_t r = p2_scalars(s, roots.data(), W, sh.first, n_total);
     if (r == 0) r = p2_sort(s, p2, true);
     if (r == 0) r = p2_accumulate(s, p2);
-    if (r == 0) r = front_status(s, sh.in, e);
+    if (r == 0) r = front_status(s, e);
     if (r == 0) codes[j] = first_error_code(e, kinds);
     if (r == 0 && codes[j] == 0) r = p2_finish(s, p2, partials.data() + 192 * (size_t)j);  // a rejected input's sums are discarded
     return r;
@@ -1472,17 +1488,14 @@ int32_t verify_group_dev(const kzg_ctx* ctx, const std::vector<GroupDevShare>& s
   for (uint32_t j = 0; j < W; j++) ms[j] = kzg::multi::Share{j, shares[j].first, shares[j].count};
   const int32_t code = kzg::multi::merged_first_error(ms, err.data(), kinds);
   if (code) return code;
-  rc = kzg_verify_batch_finish(ctx, partials.data(), W, ok);
+  rc = verify_batch_finish(ctx, partials.data(), W, kind, ok);
   tt.mark("sum of partials + pairing");
   return rc;
 }
 
 extern "C" int32_t kzg_verify_blob_proof_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48,
                                                uint64_t n, int32_t* ok) try {
-  const VerifyInputs in = blob_inputs(blobs, commitments48, proofs48, true);
-  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return empty_batch(ok);
-  return is_group(ctx) ? multi_verify_batch(ctx, in, n, ok) : verify_batch_single(ctx, in, n, nullptr, nullptr, ok);
+  return batch_entry(ctx, blob_inputs(blobs, commitments48, proofs48, true), n, nullptr, ok, nullptr);
 } catch (...) {
   return abi_exception();
 }
@@ -1511,7 +1524,8 @@ int32_t verify_proof_single(const kzg_ctx* ctx, const uint8_t* proof48, const ui
   HIP_TRY(hipSetDevice(ctx->device));
   SessionUse use;
   // a private stream per call would cost a creation; the session's own stream carries the whole single-item call
-  int32_t rc = session_acquire(ctx, 1, KZG_SESSION_STREAM, &use.s);
+  // (POINTS: the one-item session is read by phase 2 only, where blobs and points do not differ)
+  int32_t rc = session_acquire(ctx, 1, KZG_SESSION_STREAM, VerifyKind::POINTS, false, &use.s);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   hipStream_t st = s->st;
@@ -1556,28 +1570,21 @@ int32_t verify_proof_single(const kzg_ctx* ctx, const uint8_t* proof48, const ui
 // reading of the four-kind error record differ -- front_enqueue / front_status, POINTS.
 extern "C" int32_t kzg_verify_proof_phase1_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
                                                uint64_t n, uint8_t* out_root32, int32_t* err8, kzg_verify_session** session, void* hip_stream) try {
-  const VerifyInputs in = point_inputs(d_proofs48, d_commitments48, d_z32, d_y32, false);
-  if (!ctx || !out_root32 || !err8 || !session || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return verify_phase1(ctx, in, n, (hipStream_t)hip_stream, out_root32, err8, session);
+  return phase1_entry(ctx, point_inputs(d_proofs48, d_commitments48, d_z32, d_y32, false), n, (hipStream_t)hip_stream, out_root32, err8, session);
 } catch (...) {
   return abi_exception();
 }
 
 extern "C" int32_t kzg_verify_proof_batch_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
                                               uint64_t n, int32_t* ok, void* hip_stream) try {
-  const VerifyInputs in = point_inputs(d_proofs48, d_commitments48, d_z32, d_y32, false);
-  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, nullptr, ok) : empty_batch(ok);
+  return batch_entry(ctx, point_inputs(d_proofs48, d_commitments48, d_z32, d_y32, false), n, nullptr, ok, (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }
 
 extern "C" int32_t kzg_verify_proof_batch(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32,
                                           uint64_t n, int32_t* ok) try {
-  const VerifyInputs in = point_inputs(proofs48, commitments48, z32, y32, true);
-  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return empty_batch(ok);
-  return is_group(ctx) ? multi_verify_batch(ctx, in, n, ok) : verify_batch_single(ctx, in, n, nullptr, nullptr, ok);
+  return batch_entry(ctx, point_inputs(proofs48, commitments48, z32, y32, true), n, nullptr, ok, nullptr);
 } catch (...) {
   return abi_exception();
 }
@@ -1610,7 +1617,8 @@ static int32_t each_reserve(kzg_verify_session* s, const EachGeom& g) {
   Carve c;
   const size_t o_status = c.take(n * sizeof(int32_t)), o_rej = c.take(sizeof(uint32_t)), o_a = c.take(total * sizeof(g1_xyzz28)),
                o_b = c.take(total * sizeof(g1_xyzz28)), o_idx = c.take(EACH_GATHER * sizeof(uint32_t)), o_out = c.take(2 * EACH_GATHER * sizeof(g1_xyzz));
-  const size_t o_vec = s->cells ? c.take(total * 64 * sizeof(fr_t)) : 0;
+  const bool is_cells = s->kind == VerifyKind::CELLS;
+  const size_t o_vec = is_cells ? c.take(total * 64 * sizeof(fr_t)) : 0;
   if (s->tree_cap < c.off) {
     if (s->tree) (void)hipFree(s->tree);
     s->tree = nullptr;
@@ -1625,24 +1633,18 @@ static int32_t each_reserve(kzg_verify_session* s, const EachGeom& g) {
   s->t_b = reinterpret_cast<g1_xyzz28*>(s->tree + o_b);
   s->t_idx = reinterpret_cast<uint32_t*>(s->tree + o_idx);
   s->t_out = reinterpret_cast<g1_xyzz*>(s->tree + o_out);
-  s->t_vec = s->cells ? reinterpret_cast<fr_t*>(s->tree + o_vec) : nullptr;
+  s->t_vec = is_cells ? reinterpret_cast<fr_t*>(s->tree + o_vec) : nullptr;
   return 0;
 }
-// per-item codes in the single-item call's parse order -- blob, commitment, proof (src/kzg/setup.rs:214-217), proof, commitment, z, y
-// (:103-109) or, for cells, index, commitment, cell, proof (front_enqueue: the cell's status lies in the blob slot, the index's in the
-// fourth) -- on the caller's stream, behind the front's kernels there and the decoder (ev_join)
+// per-item codes in the single-item call's parse order, which is the error record's (verify_kind.hpp; a three-entry record has no fourth
+// array) -- on the caller's stream, behind the front's kernels there and the decoder (ev_join)
 static int32_t each_status_enqueue(kzg_verify_session* s) {
   const uint64_t n = s->n;
   hipStream_t st = s->st;
   if (hipStreamWaitEvent(st, s->ev_join, 0) != hipSuccess || hipMemsetAsync(s->t_rejected, 0, sizeof(uint32_t), st) != hipSuccess)
     return fail(KZG_FAIL_HIP, "per-item verdicts: status enqueue failed");
-  if (s->points)
-    hipLaunchKernelGGL(k_each_status, dim3(blocks_for(n, 256)), dim3(256), 0, st, s->stat + 2 * n, s->stat + n, s->stat, s->stat + 3 * n, n, s->t_status, s->t_rejected);
-  else if (s->cells)
-    hipLaunchKernelGGL(k_each_status, dim3(blocks_for(n, 256)), dim3(256), 0, st, s->stat + 3 * n, s->stat + n, s->stat, s->stat + 2 * n, n, s->t_status, s->t_rejected);
-  else
-    hipLaunchKernelGGL(k_each_status, dim3(blocks_for(n, 256)), dim3(256), 0, st, s->stat, s->stat + n, s->stat + 2 * n, (const int32_t*)nullptr, n, s->t_status,
-                       s->t_rejected);
+  hipLaunchKernelGGL(k_each_status, dim3(blocks_for(n, 256)), dim3(256), 0, st, stat_of(s, 0), stat_of(s, 1), stat_of(s, 2), stat_of(s, 3), n, s->t_status,
+                     s->t_rejected);
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "per-item verdicts: status launch failed");
   return 0;
 }
@@ -1656,7 +1658,7 @@ static int32_t each_build(kzg_verify_session* s, const EachGeom& g, uint64_t fir
     hipLaunchKernelGGL(k_each_level, dim3(blocks_for(2 * cout, 64)), dim3(64), 0, st, s->t_a + g.off[l], s->t_b + g.off[l], cin, s->t_a + g.off[l + 1],
                        s->t_b + g.off[l + 1], cout);
   }
-  if (s->cells) {  // the monomial term's coefficient vectors r_i I_i and their sums; the points are taken per fetched node (each_fetch)
+  if (s->kind == VerifyKind::CELLS) {  // the monomial term's coefficient vectors r_i I_i and their sums; the points are taken per fetched node (each_fetch)
     hipLaunchKernelGGL(k_cells_each_leaves, dim3(blocks_for(n, CELLV_CELLS)), dim3(CELLV_THREADS), 0, st, s->d_cells,
                        reinterpret_cast<const unsigned long long*>(s->d_cell_indices), s->t_status, s->rpow2, n, first_index, s->ctx->d_cells_tab, s->ctx->d_cellv_tab,
                        s->t_vec);
@@ -1678,7 +1680,7 @@ static int32_t each_fetch(kzg_verify_session* s, const std::vector<uint32_t>& po
     const uint32_t m = (uint32_t)std::min<size_t>(EACH_GATHER, pos.size() - done);
     if (hipMemcpyAsync(s->t_idx, pos.data() + done, m * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess)
       return fail(KZG_FAIL_HIP, "per-item verdicts: node fetch failed");
-    if (s->cells)
+    if (s->kind == VerifyKind::CELLS)
       hipLaunchKernelGGL(k_each_gather_cells, dim3(m), dim3(64), 0, st, s->t_a, s->t_b, s->t_vec, s->ctx->d_g1_monomial, s->t_idx, m, true, s->t_out);
     else
       hipLaunchKernelGGL(k_each_gather, dim3(blocks_for(2 * (uint64_t)m, 64)), dim3(64), 0, st, s->t_a, s->t_b, s->t_idx, m, s->t_out);
@@ -1710,7 +1712,7 @@ static int32_t each_descend(kzg_verify_session* s, const EachGeom& g, uint8_t* o
         host::g1_host_affine a, b;
         host_affine_from_xyzz(a, nodes[2 * k]);
         host_affine_from_xyzz(b, nodes[2 * k + 1]);
-        pass[k] = host::verify_pairings_fixed(*ctx->pairing, a, b, s->cells) ? 1 : 0;  // cells: e(A, [tau^64]_2)
+        pass[k] = host::verify_pairings_fixed(*ctx->pairing, lines_against_a(ctx, s->kind), a, b) ? 1 : 0;
       }
       return 0;
     });
@@ -1825,11 +1827,7 @@ static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, const Ver
 // comes to be, the single-item shortcuts, and the ending.
 int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, const VerifyEach* each, int32_t* ok) {
   *ok = 0;
-  const bool blobs = in.kind == VerifyInputs::BLOBS;
-  if (in.kind == VerifyInputs::CELLS) {  // lincomb B's fixed terms: derived by this member's first cells call
-    const int32_t rc = ensure_g1_monomial(ctx);
-    if (rc) return rc;
-  }
+  const bool blobs = in.kind == VerifyKind::BLOBS;
   if (each && n == 1) {  // per-item verdicts of one item: the boolean call's answer in the per-item outputs
     int32_t one = 0;
     const int32_t rc = verify_batch_single(ctx, in, 1, st, nullptr, &one);
@@ -1839,7 +1837,7 @@ int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t
     return 0;
   }
   // one tuple from host buffers: z and y parsed on the host, the lincombs there too (verify_one_on_host)
-  if (n == 1 && in.on_host && in.kind == VerifyInputs::POINTS) return verify_proof_single(ctx, in.proofs48, in.commitments48, in.z32, in.y32, ok);
+  if (n == 1 && in.on_host && in.kind == VerifyKind::POINTS) return verify_proof_single(ctx, in.proofs48, in.commitments48, in.z32, in.y32, ok);
   HIP_TRY(hipSetDevice(ctx->device));
   SessionUse use;
   uint8_t root[32];
@@ -1849,17 +1847,15 @@ int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t
   const bool front_done = in.on_host && blobs;
   int32_t rc = front_done   ? verify_phase1_host(ctx, in.blobs, in.commitments48, in.proofs48, n, root, each ? err6 : nullptr, &use.s)
                : in.on_host ? points_stage_host(ctx, in, n, &use.s)
-                            : session_acquire(ctx, n, st, &use.s, verify_tail_terms(in.kind));
+                            : session_acquire(ctx, n, st, in.kind, false, &use.s);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
-  const VerifyInputs dev = in.on_host ? staged_inputs(s, in.kind) : in;
+  const VerifyInputs dev = in.on_host ? staged_inputs(s) : in;
   if (blobs && one_item_on_host(s)) {  // no transcript: the item's kernels, then the host (verify_one_tail)
     if (!front_done) rc = phase1_items(s, dev.blobs, dev.commitments48, dev.proofs48, 0, 1, s->st, true);
     return rc ? rc : verify_one_tail(s, ok);
   }
-  if (!each)
-    return verify_fused(s, dev, ok, blobs ? "verify (fused phases)" : in.kind == VerifyInputs::CELLS ? "verify_cell_proof_batch (fused phases)" : "verify_proof_batch (fused phases)",
-                        front_done ? root : nullptr);
+  if (!each) return verify_fused(s, dev, ok, front_done ? root : nullptr);
   if (!front_done) {
     rc = front_enqueue(s, dev);
     if (rc == 0) rc = p1_root(s, root);
@@ -1869,41 +1865,31 @@ int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t
 
 extern "C" int32_t kzg_verify_blob_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_proofs48, uint64_t n,
                                                         uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream) try {
-  const VerifyInputs in = blob_inputs(d_blobs, d_commitments48, d_proofs48, false);
   const VerifyEach each{ok_each, status};
-  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, &each, ok) : empty_batch(ok);
+  return batch_entry(ctx, blob_inputs(d_blobs, d_commitments48, d_proofs48, false), n, &each, ok, (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }
 
 extern "C" int32_t kzg_verify_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_proofs48, const void* d_commitments48, const void* d_z32, const void* d_y32,
                                                    uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream) try {
-  const VerifyInputs in = point_inputs(d_proofs48, d_commitments48, d_z32, d_y32, false);
   const VerifyEach each{ok_each, status};
-  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, &each, ok) : empty_batch(ok);
+  return batch_entry(ctx, point_inputs(d_proofs48, d_commitments48, d_z32, d_y32, false), n, &each, ok, (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }
 
 extern "C" int32_t kzg_verify_blob_proof_batch_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* proofs48, uint64_t n,
                                                     uint8_t* ok_each, int32_t* status, int32_t* ok) try {
-  const VerifyInputs in = blob_inputs(blobs, commitments48, proofs48, true);
   const VerifyEach each{ok_each, status};
-  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return empty_batch(ok);
-  return is_group(ctx) ? multi_verify_each(ctx, in, n, each, ok) : verify_batch_single(ctx, in, n, nullptr, &each, ok);
+  return batch_entry(ctx, blob_inputs(blobs, commitments48, proofs48, true), n, &each, ok, nullptr);
 } catch (...) {
   return abi_exception();
 }
 extern "C" int32_t kzg_verify_proof_batch_each(const kzg_ctx* ctx, const uint8_t* proofs48, const uint8_t* commitments48, const uint8_t* z32, const uint8_t* y32,
                                                uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok) try {
-  const VerifyInputs in = point_inputs(proofs48, commitments48, z32, y32, true);
   const VerifyEach each{ok_each, status};
-  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return empty_batch(ok);
-  return is_group(ctx) ? multi_verify_each(ctx, in, n, each, ok) : verify_batch_single(ctx, in, n, nullptr, &each, ok);
+  return batch_entry(ctx, point_inputs(proofs48, commitments48, z32, y32, true), n, &each, ok, nullptr);
 } catch (...) {
   return abi_exception();
 }
@@ -1913,19 +1899,14 @@ extern "C" int32_t kzg_verify_proof_batch_each(const kzg_ctx* ctx, const uint8_t
 // (k_cells_interp, k_cells_reduce), lincomb B's 2n + 64 terms and the pairing against [tau^64]_2 differ -- each behind the session's kind.
 extern "C" int32_t kzg_verify_cell_proof_batch_dev(const kzg_ctx* ctx, const void* d_commitments48, const void* d_cell_indices, const void* d_cells,
                                                    const void* d_proofs48, uint64_t n, int32_t* ok, void* hip_stream) try {
-  const VerifyInputs in = cell_inputs(d_commitments48, d_cell_indices, d_cells, d_proofs48, false);
-  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, nullptr, ok) : empty_batch(ok);
+  return batch_entry(ctx, cell_inputs(d_commitments48, d_cell_indices, d_cells, d_proofs48, false), n, nullptr, ok, (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }
 
 extern "C" int32_t kzg_verify_cell_proof_batch(const kzg_ctx* ctx, const uint8_t* commitments48, const uint64_t* cell_indices, const uint8_t* cells,
                                                const uint8_t* proofs48, uint64_t n, int32_t* ok) try {
-  const VerifyInputs in = cell_inputs(commitments48, cell_indices, cells, proofs48, true);
-  if (!ctx || !ok || (n && in.any_null())) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return empty_batch(ok);
-  return is_group(ctx) ? multi_verify_batch(ctx, in, n, ok) : verify_batch_single(ctx, in, n, nullptr, nullptr, ok);
+  return batch_entry(ctx, cell_inputs(commitments48, cell_indices, cells, proofs48, true), n, nullptr, ok, nullptr);
 } catch (...) {
   return abi_exception();
 }
@@ -1934,21 +1915,16 @@ extern "C" int32_t kzg_verify_cell_proof_batch(const kzg_ctx* ctx, const uint8_t
 // the order of the status arrays, the vector tree beside the two point trees, the fetch kernel and the pairing against [tau^64]_2.
 extern "C" int32_t kzg_verify_cell_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_commitments48, const void* d_cell_indices, const void* d_cells,
                                                         const void* d_proofs48, uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream) try {
-  const VerifyInputs in = cell_inputs(d_commitments48, d_cell_indices, d_cells, d_proofs48, false);
   const VerifyEach each{ok_each, status};
-  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return n ? verify_batch_single(ctx, in, n, (hipStream_t)hip_stream, &each, ok) : empty_batch(ok);
+  return batch_entry(ctx, cell_inputs(d_commitments48, d_cell_indices, d_cells, d_proofs48, false), n, &each, ok, (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }
 
 extern "C" int32_t kzg_verify_cell_proof_batch_each(const kzg_ctx* ctx, const uint8_t* commitments48, const uint64_t* cell_indices, const uint8_t* cells,
                                                     const uint8_t* proofs48, uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok) try {
-  const VerifyInputs in = cell_inputs(commitments48, cell_indices, cells, proofs48, true);
   const VerifyEach each{ok_each, status};
-  if (!ctx || !ok || (n && (in.any_null() || !ok_each || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return empty_batch(ok);
-  return is_group(ctx) ? multi_verify_each(ctx, in, n, each, ok) : verify_batch_single(ctx, in, n, nullptr, &each, ok);
+  return batch_entry(ctx, cell_inputs(commitments48, cell_indices, cells, proofs48, true), n, &each, ok, nullptr);
 } catch (...) {
   return abi_exception();
 }

@@ -524,12 +524,12 @@ struct pairing_ctx {
 
 // e(-A, [tau]_2) * e(B, G2) == 1   (bls::verify_pairings, src/bls.rs:572-598, with
 // (a1,a2) = (A,[tau]_2) and (b1,b2) = (B, G2) as called at src/kzg/setup.rs:157-160)
-// `cells`: e(-A, [tau^64]_2) * e(B, G2) == 1, the batched cell check
-inline bool verify_pairings_fixed(const pairing_ctx& pc, const g1_host_affine& a, const g1_host_affine& b, bool cells = false) {
+// `lines_a`: pc.lines_tau, or pc.lines_tau64 for e(-A, [tau^64]_2) * e(B, G2) == 1, the batched cell check
+inline bool verify_pairings_fixed(const pairing_ctx& pc, const miller_lines& lines_a, const g1_host_affine& a, const g1_host_affine& b) {
   g1_host_affine na = a;
   if (!na.inf) fp_neg(na.y, na.y);
   g1_host_affine ps[2] = {na, b};
-  const miller_lines* ls[2] = {cells ? &pc.lines_tau64 : &pc.lines_tau, &pc.lines_g2};
+  const miller_lines* ls[2] = {&lines_a, &pc.lines_g2};
   fp12 f = multi_miller(ps, ls, 2);
   return final_exp_is_one(f, pc.fc);
 }

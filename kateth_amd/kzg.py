@@ -550,6 +550,39 @@ class Setup:
         if rc < 0:
             raise EngineError("%s failed (%d): %s" % (what, rc, self._lib.kzg_last_error().decode()))
 
+    def _verdict(self, what: str, args, tail=(), to_error=_kzg_error) -> bool:
+        """a boolean verification call `what`(handle, *args, &ok, *tail): EngineError when the engine failed, to_error(code) for a rejected
+        input, else the verdict"""
+        ok = ctypes.c_int32(0)
+        rc = getattr(self._lib, what)(self._h, *args, ctypes.byref(ok), *tail)
+        self._check(rc, what)
+        if rc > 0:
+            raise to_error(rc)
+        return bool(ok.value)
+
+    def _verdicts(self, what: str, args, n: int, tail=()) -> Tuple[List[bool], List[int], bool]:
+        """a per-item verification call `what`(handle, *args, n, ok_each, status, &ok, *tail) -> (ok_each, status, ok)"""
+        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
+        rc = getattr(self._lib, what)(self._h, *args, n, ctypes.cast(ok_each, _u8p), status, ctypes.byref(ok), *tail)
+        self._check(rc, what)
+        if rc > 0:  # the ABI reports rejected items in status[], never as the call's code
+            raise EngineError("%s returned %d" % (what, rc))
+        return [bool(b) for b in ok_each.raw[:n]], list(status[:n]), bool(ok.value)
+
+    @staticmethod
+    def _host_args(*buffers):
+        """contiguous host inputs: bytes-like objects, or raw host addresses (ints) passed through"""
+        return [a if isinstance(a, int) else _buf(a) for a in buffers]
+
+    @staticmethod
+    def _cell_index_array(cell_indices, n: int):
+        """n cell indices for the C ABI: a sequence of ints, a bytes-like object of n native uint64, or a raw host address"""
+        if isinstance(cell_indices, int):
+            return ctypes.cast(cell_indices, _u64p)
+        if isinstance(cell_indices, (bytes, bytearray, memoryview)):
+            return (ctypes.c_uint64 * n).from_buffer_copy(cell_indices)
+        return (ctypes.c_uint64 * n)(*cell_indices)
+
     # -- batch entry points (host buffers) --------------------------------------
     def blob_to_commitment_batch(self, blobs: bytes, n: Optional[int] = None):
         """n concatenated blobs -> (n*48 bytes, [status])."""
@@ -819,12 +852,7 @@ class Setup:
             raise KzgError(BlsError(ECGroupError("InvalidEncoding")))
         if len(point) != 32 or len(evaluation) != 32:
             raise KzgError(BlsError(FiniteFieldError("InvalidEncoding")))
-        ok = ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_proof(self._h, proof, commitment, point, evaluation, ctypes.byref(ok))
-        self._check(rc, "kzg_verify_proof")
-        if rc > 0:
-            raise _kzg_error(rc)
-        return bool(ok.value)
+        return self._verdict("kzg_verify_proof", (proof, commitment, point, evaluation))
 
     def verify_proof_batch(self, proofs: Sequence[bytes], commitments: Sequence[bytes], points: Sequence[bytes], evals: Sequence[bytes]) -> bool:
         """`Setup::verify_proof` for n tuples in one call (the reference's private `verify_proof_batch`, src/kzg/setup.rs:115-161).
@@ -861,13 +889,7 @@ class Setup:
 
     def verify_proof_batch_host(self, proofs, commitments, points, evals, n: int) -> bool:
         """kzg_verify_proof_batch on n CONTIGUOUS tuples in host memory: bytes-like objects or raw host addresses (ints)"""
-        ok = ctypes.c_int32(0)
-        args = [a if isinstance(a, int) else _buf(a) for a in (proofs, commitments, points, evals)]
-        rc = self._lib.kzg_verify_proof_batch(self._h, args[0], args[1], args[2], args[3], n, ctypes.byref(ok))
-        self._check(rc, "kzg_verify_proof_batch")
-        if rc > 0:
-            raise _kzg_error(rc)
-        return bool(ok.value)
+        return self._verdict("kzg_verify_proof_batch", self._host_args(proofs, commitments, points, evals) + [n])
 
     def verify_cell_proof_batch(self, commitments: Sequence[bytes], cell_indices: Sequence[int], cells: Sequence[bytes], proofs: Sequence[bytes]) -> bool:
         """`verify_cell_kzg_proof_batch` (EIP-7594) with c-kzg-4844's argument shape: one commitment per cell.  Unequal lengths, an item
@@ -880,19 +902,9 @@ class Setup:
     def verify_cell_proof_batch_host(self, commitments, cell_indices, cells, proofs, n: int) -> bool:
         """kzg_verify_cell_proof_batch on n CONTIGUOUS tuples in host memory: bytes-like objects or raw host addresses (ints); the
         indices as a sequence of ints, a bytes-like object of n native uint64 or a raw host address"""
-        ok = ctypes.c_int32(0)
-        if isinstance(cell_indices, int):
-            cell_indices = ctypes.cast(cell_indices, _u64p)
-        elif isinstance(cell_indices, (bytes, bytearray, memoryview)):
-            cell_indices = (ctypes.c_uint64 * n).from_buffer_copy(cell_indices)
-        else:
-            cell_indices = (ctypes.c_uint64 * n)(*cell_indices)
-        args = [a if isinstance(a, int) else _buf(a) for a in (commitments, cells, proofs)]
-        rc = self._lib.kzg_verify_cell_proof_batch(self._h, args[0], cell_indices, args[1], args[2], n, ctypes.byref(ok))
-        self._check(rc, "kzg_verify_cell_proof_batch")
-        if rc > 0:
-            raise _cell_verify_error(rc)
-        return bool(ok.value)
+        idx = self._cell_index_array(cell_indices, n)
+        com, cells, prf = self._host_args(commitments, cells, proofs)
+        return self._verdict("kzg_verify_cell_proof_batch", (com, idx, cells, prf, n), to_error=_cell_verify_error)
 
     def g1_monomial(self, first: int = 0, count: int = 64) -> List[bytes]:
         """the 48-byte encodings of the monomial G1 setup points [tau^j]_1, first <= j < first + count <= 64, which the context derives
@@ -909,12 +921,7 @@ class Setup:
             raise KzgError(BlobError("InvalidLen"))
         if len(commitment) != 48 or len(proof) != 48:
             raise KzgError(BlsError(ECGroupError("InvalidEncoding")))
-        ok = ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_blob_proof(self._h, blob, commitment, proof, ctypes.byref(ok))
-        self._check(rc, "kzg_verify_blob_proof")
-        if rc > 0:
-            raise _kzg_error(rc)
-        return bool(ok.value)
+        return self._verdict("kzg_verify_blob_proof", (blob, commitment, proof))
 
     def verify_blob_proof_batch(self, blobs: Sequence[bytes], commitments: Sequence[bytes], proofs: Sequence[bytes]) -> bool:
         """`Setup::verify_blob_proof_batch`.  Length mismatch panics in the
@@ -934,35 +941,16 @@ class Setup:
         for c in list(commitments) + list(proofs):
             if len(c) != 48:
                 raise KzgError(BlsError(ECGroupError("InvalidEncoding")))
-        ok = ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_blob_proof_batch(
-            self._h, b"".join(_buf(b) for b in blobs), b"".join(_buf(c) for c in commitments), b"".join(_buf(p) for p in proofs), n, ctypes.byref(ok)
-        )
-        self._check(rc, "kzg_verify_blob_proof_batch")
-        if rc > 0:
-            raise _kzg_error(rc)
-        return bool(ok.value)
+        return self._verdict("kzg_verify_blob_proof_batch", [b"".join(_buf(v) for v in seq) for seq in (blobs, commitments, proofs)] + [n])
 
     # -- per-item verdicts: what a loop over verify_blob_proof / verify_proof would return or raise, from one batch call ---
-    def _each_result(self, rc: int, what: str, n: int, ok_each, status, ok) -> Tuple[List[bool], List[int], bool]:
-        self._check(rc, what)
-        if rc > 0:  # the ABI reports rejected items in status[], never as the call's code
-            raise EngineError("%s returned %d" % (what, rc))
-        return [bool(b) for b in ok_each.raw[:n]], list(status[:n]), bool(ok.value)
-
     def verify_blob_proof_batch_each_host(self, blobs, commitments, proofs, n: int):
         """kzg_verify_blob_proof_batch_each on n CONTIGUOUS items in host memory -> (ok_each, status, ok)"""
-        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
-        args = [a if isinstance(a, int) else _buf(a) for a in (blobs, commitments, proofs)]
-        rc = self._lib.kzg_verify_blob_proof_batch_each(self._h, args[0], args[1], args[2], n, ctypes.cast(ok_each, ctypes.c_void_p), status, ctypes.byref(ok))
-        return self._each_result(rc, "kzg_verify_blob_proof_batch_each", n, ok_each, status, ok)
+        return self._verdicts("kzg_verify_blob_proof_batch_each", self._host_args(blobs, commitments, proofs), n)
 
     def verify_proof_batch_each_host(self, proofs, commitments, points, evals, n: int):
         """kzg_verify_proof_batch_each on n CONTIGUOUS tuples in host memory -> (ok_each, status, ok)"""
-        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
-        args = [a if isinstance(a, int) else _buf(a) for a in (proofs, commitments, points, evals)]
-        rc = self._lib.kzg_verify_proof_batch_each(self._h, args[0], args[1], args[2], args[3], n, ctypes.cast(ok_each, ctypes.c_void_p), status, ctypes.byref(ok))
-        return self._each_result(rc, "kzg_verify_proof_batch_each", n, ok_each, status, ok)
+        return self._verdicts("kzg_verify_proof_batch_each", self._host_args(proofs, commitments, points, evals), n)
 
     @staticmethod
     def _each_list(n, early, ok_each, status):
@@ -1037,23 +1025,13 @@ class Setup:
     def verify_cell_proof_batch_each_host(self, commitments, cell_indices, cells, proofs, n: int):
         """kzg_verify_cell_proof_batch_each on n CONTIGUOUS tuples in host memory (arguments as verify_cell_proof_batch_host)
         -> (ok_each, status, ok)"""
-        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
-        if isinstance(cell_indices, int):
-            cell_indices = ctypes.cast(cell_indices, _u64p)
-        elif isinstance(cell_indices, (bytes, bytearray, memoryview)):
-            cell_indices = (ctypes.c_uint64 * n).from_buffer_copy(cell_indices)
-        else:
-            cell_indices = (ctypes.c_uint64 * n)(*cell_indices)
-        args = [a if isinstance(a, int) else _buf(a) for a in (commitments, cells, proofs)]
-        rc = self._lib.kzg_verify_cell_proof_batch_each(self._h, args[0], cell_indices, args[1], args[2], n, ctypes.cast(ok_each, _u8p), status, ctypes.byref(ok))
-        return self._each_result(rc, "kzg_verify_cell_proof_batch_each", n, ok_each, status, ok)
+        idx = self._cell_index_array(cell_indices, n)
+        com, cells, prf = self._host_args(commitments, cells, proofs)
+        return self._verdicts("kzg_verify_cell_proof_batch_each", (com, idx, cells, prf), n)
 
     def verify_cell_proof_batch_each_dev(self, d_commitments: int, d_cell_indices: int, d_cells: int, d_proofs: int, n: int, stream: int = 0):
         """-> (ok_each: List[bool], status: List[int], ok: bool); synchronous, results in host memory"""
-        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_cell_proof_batch_each_dev(self._h, d_commitments, d_cell_indices, d_cells, d_proofs, n, ctypes.cast(ok_each, _u8p), status,
-                                                            ctypes.byref(ok), stream)
-        return self._each_result(rc, "kzg_verify_cell_proof_batch_each_dev", n, ok_each, status, ok)
+        return self._verdicts("kzg_verify_cell_proof_batch_each_dev", (d_commitments, d_cell_indices, d_cells, d_proofs), n, (stream,))
 
     def g1_monomial_lincomb(self, vectors: Sequence[Sequence[int]]) -> List[bytes]:
         """sum_j s_j [tau^j]_1 for each vector of 64 scalars (ints below r) as 96 bytes x || y big-endian, all-zero = the point at
@@ -1074,13 +1052,7 @@ class Setup:
     def verify_blob_proof_batch_host(self, blobs, commitments, proofs, n: int) -> bool:
         """kzg_verify_blob_proof_batch on n CONTIGUOUS items in host memory: bytes-like objects or raw host addresses
         (ints, e.g. the data_ptr() of a pinned tensor -- pinned memory crosses PCIe at the full rate)."""
-        ok = ctypes.c_int32(0)
-        args = [a if isinstance(a, int) else _buf(a) for a in (blobs, commitments, proofs)]
-        rc = self._lib.kzg_verify_blob_proof_batch(self._h, args[0], args[1], args[2], n, ctypes.byref(ok))
-        self._check(rc, "kzg_verify_blob_proof_batch")
-        if rc > 0:
-            raise _kzg_error(rc)
-        return bool(ok.value)
+        return self._verdict("kzg_verify_blob_proof_batch", self._host_args(blobs, commitments, proofs) + [n])
 
     # -- device-resident entry points (raw HIP pointers, e.g. torch.Tensor.data_ptr()) ---
     def blob_to_commitment_batch_dev(self, d_blobs: int, n: int, d_out48: int, d_status: int, stream: int = 0):
@@ -1108,43 +1080,22 @@ class Setup:
         self._check(rc, "kzg_recover_cells_batch_dev")
 
     def verify_blob_proof_batch_dev(self, d_blobs: int, d_commitments: int, d_proofs: int, n: int, stream: int = 0) -> bool:
-        ok = ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_blob_proof_batch_dev(self._h, d_blobs, d_commitments, d_proofs, n, ctypes.byref(ok), stream)
-        self._check(rc, "kzg_verify_blob_proof_batch_dev")
-        if rc > 0:
-            raise _kzg_error(rc)
-        return bool(ok.value)
+        return self._verdict("kzg_verify_blob_proof_batch_dev", (d_blobs, d_commitments, d_proofs, n), (stream,))
 
     def verify_proof_batch_dev(self, d_proofs: int, d_commitments: int, d_points: int, d_evals: int, n: int, stream: int = 0) -> bool:
-        ok = ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_proof_batch_dev(self._h, d_proofs, d_commitments, d_points, d_evals, n, ctypes.byref(ok), stream)
-        self._check(rc, "kzg_verify_proof_batch_dev")
-        if rc > 0:
-            raise _kzg_error(rc)
-        return bool(ok.value)
+        return self._verdict("kzg_verify_proof_batch_dev", (d_proofs, d_commitments, d_points, d_evals, n), (stream,))
 
     def verify_blob_proof_batch_each_dev(self, d_blobs: int, d_commitments: int, d_proofs: int, n: int, stream: int = 0):
         """-> (ok_each: List[bool], status: List[int], ok: bool); synchronous, results in host memory"""
-        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_blob_proof_batch_each_dev(self._h, d_blobs, d_commitments, d_proofs, n, ctypes.cast(ok_each, ctypes.c_void_p), status,
-                                                            ctypes.byref(ok), stream)
-        return self._each_result(rc, "kzg_verify_blob_proof_batch_each_dev", n, ok_each, status, ok)
+        return self._verdicts("kzg_verify_blob_proof_batch_each_dev", (d_blobs, d_commitments, d_proofs), n, (stream,))
 
     def verify_cell_proof_batch_dev(self, d_commitments: int, d_cell_indices: int, d_cells: int, d_proofs: int, n: int, stream: int = 0) -> bool:
         """kzg_verify_cell_proof_batch_dev: device pointers (16-byte aligned) to n commitments, n uint64 indices, n cells, n proofs"""
-        ok = ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_cell_proof_batch_dev(self._h, d_commitments, d_cell_indices, d_cells, d_proofs, n, ctypes.byref(ok), stream)
-        self._check(rc, "kzg_verify_cell_proof_batch_dev")
-        if rc > 0:
-            raise _cell_verify_error(rc)
-        return bool(ok.value)
+        return self._verdict("kzg_verify_cell_proof_batch_dev", (d_commitments, d_cell_indices, d_cells, d_proofs, n), (stream,), to_error=_cell_verify_error)
 
     def verify_proof_batch_each_dev(self, d_proofs: int, d_commitments: int, d_points: int, d_evals: int, n: int, stream: int = 0):
         """-> (ok_each: List[bool], status: List[int], ok: bool); synchronous, results in host memory"""
-        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_proof_batch_each_dev(self._h, d_proofs, d_commitments, d_points, d_evals, n, ctypes.cast(ok_each, ctypes.c_void_p), status,
-                                                       ctypes.byref(ok), stream)
-        return self._each_result(rc, "kzg_verify_proof_batch_each_dev", n, ok_each, status, ok)
+        return self._verdicts("kzg_verify_proof_batch_each_dev", (d_proofs, d_commitments, d_points, d_evals), n, (stream,))
 
     def verify_each_checks(self) -> int:
         """two-pairing checks the per-item verdict calls have spent on this context so far"""
@@ -1184,24 +1135,14 @@ class Setup:
     def verify_blob_proof_batch_group_dev(self, d_blobs, d_commitments, d_proofs, n_local, streams=None) -> bool:
         """Setup::verify_blob_proof_batch over the members' resident shares (global order = member order): the boolean, or the
         reference's first error"""
-        ok = ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_blob_proof_batch_group_dev(self._h, self._per_member(d_blobs, "d_blobs"), self._per_member(d_commitments, "d_commitments"),
-                                                             self._per_member(d_proofs, "d_proofs"), self._counts(n_local), ctypes.byref(ok), self._streams(streams))
-        self._check(rc, "kzg_verify_blob_proof_batch_group_dev")
-        if rc > 0:
-            raise _kzg_error(rc)
-        return bool(ok.value)
+        args = (self._per_member(d_blobs, "d_blobs"), self._per_member(d_commitments, "d_commitments"), self._per_member(d_proofs, "d_proofs"), self._counts(n_local))
+        return self._verdict("kzg_verify_blob_proof_batch_group_dev", args, (self._streams(streams),))
 
     def verify_proof_batch_group_dev(self, d_proofs, d_commitments, d_points, d_evals, n_local, streams=None) -> bool:
         """Setup::verify_proof for the tuples of the members' resident shares (global order = member order)"""
-        ok = ctypes.c_int32(0)
-        rc = self._lib.kzg_verify_proof_batch_group_dev(self._h, self._per_member(d_proofs, "d_proofs"), self._per_member(d_commitments, "d_commitments"),
-                                                        self._per_member(d_points, "d_points"), self._per_member(d_evals, "d_evals"), self._counts(n_local),
-                                                        ctypes.byref(ok), self._streams(streams))
-        self._check(rc, "kzg_verify_proof_batch_group_dev")
-        if rc > 0:
-            raise _kzg_error(rc)
-        return bool(ok.value)
+        args = (self._per_member(d_proofs, "d_proofs"), self._per_member(d_commitments, "d_commitments"), self._per_member(d_points, "d_points"),
+                self._per_member(d_evals, "d_evals"), self._counts(n_local))
+        return self._verdict("kzg_verify_proof_batch_group_dev", args, (self._streams(streams),))
 
     def verify_proof_phase1_dev(self, d_proofs: int, d_commitments: int, d_points: int, d_evals: int, n_local: int, stream: int = 0):
         """-> (session handle, 32-byte transcript root, err8): phase 1 of verify_proof_batch; the session takes verify_phase2_dev,

@@ -7,6 +7,7 @@ one defect at every position, rejections and their order, the grid loop at 4,096
 batch call on the same context before and after."""
 import ctypes
 import random
+import sys
 
 import pytest
 
@@ -14,9 +15,9 @@ pytestmark = pytest.mark.gpu
 
 from conftest import TRUSTED_SETUP  # noqa: E402
 
-import cells_model as cm  # noqa: E402
 import cellverify_model as cv  # noqa: E402
-from oracle.pyref import bls, synth  # noqa: E402
+import verify_routes as vr  # noqa: E402
+from oracle.pyref import bls  # noqa: E402
 
 R = cv.R
 SEED = 0x7594
@@ -50,25 +51,10 @@ def group2():
     s.close()
 
 
-def _cell(cells, c):
-    return cells[cv.CELL * c: cv.CELL * (c + 1)]
-
-
 @pytest.fixture(scope="module")
 def data(engine):
-    """three synthetic blobs; valid (commitment, index, cell, proof) tuples for all 128 cells of blob 0 and cells 0, 63, 64, 127 of
-    blobs 1 and 2: 136 quotient commitments in one commit call"""
-    blobs = [synth.blob_bytes(SEED, b) for b in range(3)]
-    coms, status = engine.blob_to_commitment_batch(b"".join(blobs))
-    assert not any(status)
-    coms = [coms[48 * b: 48 * b + 48] for b in range(3)]
-    cells = [cm.cells_bytes(b) for b in blobs]
-    which = [(0, c) for c in range(128)] + [(b, c) for b in (1, 2) for c in (0, 63, 64, 127)]
-    quotients = b"".join(cv.quotient_blob(blobs[b], c, cv.elements(_cell(cells[b], c))) for b, c in which)
-    proofs, status = engine.blob_to_commitment_batch(quotients)
-    assert not any(status)
-    tuples = [(coms[b], c, _cell(cells[b], c), proofs[48 * k: 48 * k + 48]) for k, (b, c) in enumerate(which)]
-    return {"blobs": blobs, "coms": coms, "tuples": tuples}
+    """verify_routes.cell_tuples: 136 valid (commitment, index, cell, proof) tuples over three synthetic blobs"""
+    return vr.cell_tuples(engine, SEED)
 
 
 def _arrays(tuples):
@@ -325,6 +311,34 @@ def test_group_context_host_buffers(engine, group2, data):
     assert raw_host(group2, _patched(base, [(5, IDX, 200), (1, PRF, bad[3])])) == (10, 0)
     assert raw_host(group2, _patched(base, [(5, COM, bad[5]), (4, COM, bad[4])])) == (4, 0)
     assert raw_host(group2, base[:1]) == (0, 1)
+
+
+# ---- every route ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [1, 2, 17, 257])
+def test_every_route(engine, group2, data, torch_cuda, n):
+    """Cells through every route of tests/verify_routes.py -- host, device and group host, one boolean and per-item verdicts, the
+    latter also on member 0 of the group.  n = 1: the single-item shortcuts; 2: the first true batch; 17: two k_cells_interp workgroups,
+    the second nearly empty; 257: two leaf blocks and transcript groups, uneven group shares."""
+    com, idx, cells, prf = vr.cell_arrays(data["tuples"], n)
+    last, mid = n - 1, n // 2
+    cases = [
+        ((com, idx, cells, prf), (0, 1), [1] * n, [0] * n),
+        # tuple n - 1 carries another tuple's proof (a neighbouring column of the same blob)
+        ((com, idx, cells, vr.put(prf, last, 48, data["tuples"][(last + 7) % 136][PRF])), (0, 0), [1] * last + [0], [0] * n),
+        # one index >= 128: KZG_ERR_CELL_INDEX, the call's code or that item's status
+        ((com, vr.put(idx, mid, 8, (200).to_bytes(8, sys.byteorder)), cells, prf), (10, 0), [1] * mid + [0] + [1] * (n - mid - 1),
+         [0] * mid + [10] + [0] * (n - mid - 1)),
+    ]
+    for arrays, boolean, ok_each, status in cases:
+        x = vr.Inputs(torch_cuda, "cells", arrays, n)
+        routes = vr.boolean_routes(engine, group2, x)
+        assert sorted(routes) == ["dev", "group host", "host"]
+        for name, call in routes.items():
+            assert call() == boolean, (name, n, boolean)
+        routes = vr.each_routes(engine, group2, x)
+        assert len(routes) == 4
+        for name, call in routes.items():
+            assert call() == (0, ok_each, status, int(all(ok_each))), (name, n, ok_each, status)
 
 
 # ---- nothing else moved --------------------------------------------------------------------------------------------------------------

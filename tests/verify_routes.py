@@ -1,16 +1,20 @@
-"""Every route to a batch verification as a raw C-ABI call, for both kinds of input:
-  "points"  (proofs, commitments, z, y)      kzg_verify_proof_batch*      / kzg_verify_proof_phase1_dev
-  "blobs"   (blobs, commitments, proofs)     kzg_verify_blob_proof_batch* / kzg_verify_phase1_dev
-The arrays are in the C argument order, so one caller serves both.  BOOLEAN routes answer (rc, ok), PER-ITEM routes
-(rc, ok_each, status, ok).  Shared by the route tests (tests/test_gpu_verify_proof_batch.py, tests/test_gpu_verify_each.py) and by
-tools/gpu_verify_routes.py, which runs the same calls under a profiler."""
+"""Every route to a batch verification as a raw C-ABI call, for every kind of input:
+  "points"  (proofs, commitments, z, y)              kzg_verify_proof_batch*      / kzg_verify_proof_phase1_dev
+  "blobs"   (blobs, commitments, proofs)             kzg_verify_blob_proof_batch* / kzg_verify_phase1_dev
+  "cells"   (commitments, indices, cells, proofs)    kzg_verify_cell_proof_batch* (no phase-1 and no group-device form; the indices are
+            native uint64)
+The arrays are in the C argument order, so one caller serves all.  BOOLEAN routes answer (rc, ok), PER-ITEM routes
+(rc, ok_each, status, ok).  Shared by the route tests (tests/test_gpu_verify_proof_batch.py, tests/test_gpu_verify_each.py,
+tests/test_gpu_cellverify.py) and by tools/gpu_verify_routes.py, which runs the same calls under a profiler."""
 import ctypes
+import struct
 
-from verify_points import put  # noqa: F401  (re-exported: the callers patch items of both kinds with it)
+from verify_points import put  # noqa: F401  (re-exported: the callers patch items of every kind with it)
 
 BLOB_BYTES = 131072
-WIDTHS = {"points": (48, 48, 32, 32), "blobs": (BLOB_BYTES, 48, 48)}
-BATCH = {"points": "kzg_verify_proof_batch", "blobs": "kzg_verify_blob_proof_batch"}
+CELL_BYTES = 2048
+WIDTHS = {"points": (48, 48, 32, 32), "blobs": (BLOB_BYTES, 48, 48), "cells": (48, 8, CELL_BYTES, 48)}
+BATCH = {"points": "kzg_verify_proof_batch", "blobs": "kzg_verify_blob_proof_batch", "cells": "kzg_verify_cell_proof_batch"}
 PHASE1 = {"points": "kzg_verify_proof_phase1_dev", "blobs": "kzg_verify_phase1_dev"}
 
 
@@ -22,6 +26,8 @@ class Inputs:
         self.host = tuple(bytes(a[:w * n]) for a, w in zip(arrays, self.width))
         self.dev = [torch.frombuffer(bytearray(a), dtype=torch.uint8).cuda() for a in self.host]
         torch.cuda.synchronize()
+        if kind == "cells":  # the host call takes the indices as a uint64 pointer
+            self.host = (self.host[0], (ctypes.c_uint64 * n).from_buffer_copy(self.host[1]), self.host[2], self.host[3])
 
     def ptrs(self, lo=0):
         return [t.data_ptr() + w * lo for t, w in zip(self.dev, self.width)]
@@ -97,10 +103,14 @@ def boolean_routes(engine, group, x):
         "host": lambda: host(engine, x),
         "dev": lambda: dev(engine, x),
         "group host": lambda: host(group, x),
+    }
+    if x.kind == "cells":
+        return routes
+    routes.update({
         "group dev": lambda: group_dev(group, x, group_counts(n)),
         "group dev, one busy member": lambda: group_dev(group, x, [0, n, 0]),
         "phase 1 -> phase 2 -> finish": lambda: phases(engine, x, [(0, n)]),
-    }
+    })
     if n >= 2:
         routes["phases, two shares"] = lambda: phases(engine, x, [(0, n // 2), (n // 2, n)])
     return routes
@@ -142,3 +152,31 @@ def blob_arrays(engine, torch, n, seed=0x0E17):
     assert not any(st) and not any(st2)
     return blobs, coms, proofs
 
+
+# ---- cell batches -------------------------------------------------------------------------------------------------------------
+def cell_tuples(engine, seed=0x7594):
+    """three synthetic blobs; valid (commitment, index, cell, proof) tuples for all 128 cells of blob 0 and cells 0, 63, 64, 127 of
+    blobs 1 and 2: 136 quotient commitments in one commit call.  Nothing goes through the path under test: the cells come from the
+    big-int model of compute_cells, a cell's proof is the engine's COMMITMENT of the quotient blob (tests/cellverify_model.py)"""
+    import cells_model as cm
+    import cellverify_model as cv
+    from oracle.pyref import synth
+
+    blobs = [synth.blob_bytes(seed, b) for b in range(3)]
+    coms, status = engine.blob_to_commitment_batch(b"".join(blobs))
+    assert not any(status)
+    coms = [coms[48 * b: 48 * b + 48] for b in range(3)]
+    cells = [cm.cells_bytes(b) for b in blobs]
+    cell = lambda b, c: cells[b][CELL_BYTES * c: CELL_BYTES * (c + 1)]  # noqa: E731
+    which = [(0, c) for c in range(128)] + [(b, c) for b in (1, 2) for c in (0, 63, 64, 127)]
+    quotients = b"".join(cv.quotient_blob(blobs[b], c, cv.elements(cell(b, c))) for b, c in which)
+    proofs, status = engine.blob_to_commitment_batch(quotients)
+    assert not any(status)
+    tuples = [(coms[b], c, cell(b, c), proofs[48 * k: 48 * k + 48]) for k, (b, c) in enumerate(which)]
+    return {"blobs": blobs, "coms": coms, "tuples": tuples}
+
+
+def cell_arrays(tuples, n):
+    """(commitments, indices, cells, proofs) of n tuples, the given ones cycled"""
+    t = [tuples[k % len(tuples)] for k in range(n)]
+    return b"".join(x[0] for x in t), struct.pack("=%dQ" % n, *[x[1] for x in t]), b"".join(x[2] for x in t), b"".join(x[3] for x in t)

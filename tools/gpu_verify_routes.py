@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Calls every route to a batch verification once -- {blobs, points} x {host, device, group host, group device, phase 1 -> phase 2 ->
-finish, phase 1 alone} x {one boolean, per-item verdicts} (tests/verify_routes.py) -- at n = 1, 2 and 257, on a single context and on
-a group that lists ordinal 0 three times.  Valid inputs, then one false item (the per-item descent).  To be run under
+finish, phase 1 alone} x {one boolean, per-item verdicts}, and for cells the routes that exist (tests/verify_routes.py) -- at n = 1, 2
+and 257, on a single context and on a group that lists ordinal 0 three times.  Valid inputs, then one false item (the per-item
+descent).  To be run under
   rocprofv3 --kernel-trace --memory-copy-trace --stats -- python3 tools/gpu_verify_routes.py
 once per build (KATETH_AMD_LIB selects the library): kernel names, calls per kernel and copies per direction are the call table."""
 import os
@@ -24,15 +25,18 @@ engine = kateth_amd.Setup.load_json(SETUP, window_bits=8)
 group = kateth_amd.Setup.load_json(SETUP, window_bits=8, devices=[0, 0, 0])
 points = vp.LinearBatch(N, vp.tau_g1(oracle), oracle.roots_of_unity_brp).arrays()
 blobs, coms, proofs = vr.blob_arrays(engine, torch, N)
-false = {"points": vp.spoil(points, "y+1", 100), "blobs": (blobs, coms, vr.put(proofs, 100, 48, proofs[48 * 101:48 * 102]))}
+cells = vr.cell_arrays(vr.cell_tuples(engine)["tuples"], N)  # the 136 tuples cycled
+false = {"points": vp.spoil(points, "y+1", 100), "blobs": (blobs, coms, vr.put(proofs, 100, 48, proofs[48 * 101:48 * 102])),
+         "cells": cells[:3] + (vr.put(cells[3], 100, 48, cells[3][48 * 101:48 * 102]),)}
 calls = 0
-for kind, valid in (("points", points), ("blobs", (blobs, coms, proofs))):
+for kind, valid in (("points", points), ("blobs", (blobs, coms, proofs)), ("cells", cells)):
     for arrays, n, ok in ((valid, 1, 1), (valid, 2, 1), (valid, N, 1), (false[kind], N, 0)):
         x = vr.Inputs(torch, kind, arrays, n)
         for name, call in vr.boolean_routes(engine, group, x).items():
             assert call() == (0, ok), (kind, n, name)
             calls += 1
-        assert vr.phases(engine, x, [(0, n)], finish=False) == (0, None)
+        if kind in vr.PHASE1:
+            assert vr.phases(engine, x, [(0, n)], finish=False) == (0, None)
         for name, call in vr.each_routes(engine, group, x).items():
             got = call()
             assert (got[0], got[3], sum(got[1])) == (0, ok, n if ok else n - 1), (kind, n, name)
