@@ -283,8 +283,8 @@ int32_t kzg_blob_sidecar_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint
  *   blobs     : n * 131072 bytes
  *   out_cells : n * 128 * 2048 bytes; cells 0..63 of an accepted blob are the blob, byte for byte
  *   status    : n * int32 ; 0 or KZG_ERR_BLOB_INVALID_FIELD_ELEMENT per blob.  A rejected blob gets 262144 zero bytes.
- * Not here: cell proofs (they need FK20; the first 64 monomial G1 points exist, kzg_ctx_g1_monomial).  Cell recovery is
- *   kzg_recover_cells_batch, cell verification kzg_verify_cell_proof_batch.
+ * With the cell proofs: kzg_compute_cells_and_proofs_batch.  Cell recovery is kzg_recover_cells_batch, cell verification
+ *   kzg_verify_cell_proof_batch.
  * Bounds: nothing beyond n items is written; n == 0 returns 0.  A null pointer with n > 0 returns KZG_FAIL_ARGUMENT.
  * The *_dev form takes HIP device pointers resident on ctx's device (16-byte aligned), enqueues one kernel on `hip_stream` and returns
  *   without synchronising; it needs no workspace and takes no lock, so calls on different streams run side by side.
@@ -316,8 +316,7 @@ int32_t kzg_compute_cells_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uin
  *   input is consistent; the check can fire from 65 cells on.
  * out_cells must not overlap cells.  The kernel uses an item's own output region as scratch before the final stores: while a call
  *   is in flight the region holds intermediate values.
- * Not here: the proofs half of recovery (it needs FK20 over the full monomial G1 setup, like cell proofs; a context derives the first 64
- *   of those points, kzg_ctx_g1_monomial).
+ * With the proofs half of recovery: kzg_recover_cells_and_proofs_batch.
  * Bounds: nothing beyond n items is written; n == 0 returns 0.  A null pointer with n > 0 returns KZG_FAIL_ARGUMENT.
  * The *_dev form takes HIP device pointers resident on ctx's device (16-byte aligned), enqueues one kernel on `hip_stream` and returns
  *   without synchronising; it needs no workspace and takes no lock, so calls on different streams run side by side.
@@ -330,6 +329,42 @@ int32_t kzg_recover_cells_batch(const kzg_ctx* ctx, const uint8_t* cells /* n * 
                                 uint8_t* out_cells /* n * 128 * 2048 */, int32_t* status);
 int32_t kzg_recover_cells_batch_dev(const kzg_ctx* ctx, const void* d_cells, const void* d_present, uint64_t n, void* d_out_cells, void* d_status,
                                     void* hip_stream);
+
+/*
+ * The cells of n blobs AND their 128 cell proofs (EIP-7594, PeerDAS): compute_cells_and_kzg_proofs of
+ * specs/fulu/polynomial-commitments-sampling.md; and recover_cells_and_kzg_proofs, both halves, for n cell sets.
+ * Cells: out_cells and status are byte for byte what kzg_compute_cells_batch / kzg_recover_cells_batch write (their kernels run first);
+ *   inputs, masks, statuses and their precedence are those calls'.
+ * Proofs: proof k of an item is at byte 48 * (128 * item + k) of out_proofs48: the 48-byte encoding of the commitment of
+ *   q_k = (p - I_k) / (X^64 - z_k), z_k = omega_128^brp7(k), with I_k the interpolant of cell k -- what verify_cell_kzg_proof_batch
+ *   checks.  The point at infinity (c0 00 ...) is an ordinary proof (every proof of a blob of degree < 64).
+ *   Method: q_k is the plain quotient of p by X^64 - z_k; its evaluations on the blob's domain are a scalar vector that the fixed-base
+ *   MSM commits like a blob -- 128 scalar transforms and 128 MSMs per blob.  This is not FK20: no monomial setup and no G1 transform.
+ *   out_cells    : n * 128 * 2048 bytes; of the compute call may be NULL (proofs only)
+ *   out_proofs48 : n * 128 * 48 bytes
+ *   status       : n * int32
+ * Rejected items: the item's status code, 128 * 48 zero bytes of proofs and the zero cells it gets today; its neighbours are untouched.
+ * Recovery: a recovered item's blob is cells 0..63 of its own output; items kzg_recover_cells_batch rejects are not looked at again.
+ *   out_cells must not overlap cells.
+ * Bounds: nothing beyond n items is written; n == 0 returns 0.  A null required pointer with n > 0 returns KZG_FAIL_ARGUMENT; only
+ *   out_cells of the compute call may be null.
+ * The *_dev forms take HIP device pointers resident on ctx's device (16-byte aligned), enqueue on `hip_stream` and return without
+ *   synchronising (a context's first cell-proof call builds a 6 KiB table and waits for it); they take a workspace slot like the proof
+ *   *_dev calls.  The batch is walked in passes of KATETH_AMD_CELLPROOF_PASS items (default 32: 4,096 vectors, 512 MiB of them).
+ * The host-buffer forms stream the items through the staging ring in the same passes: blobs up, the extension half and 6 KiB of
+ *   proofs down, cells 0..63 copied from the caller's blob (compute); whole cell sets up and down (recovery).
+ * Group contexts: the host-buffer calls cut the batch into the same contiguous shares as kzg_blob_to_commitment_batch; the *_dev
+ *   calls act on member 0.
+ * Not here: FK20; a *_group_dev form; cell proofs without the transforms, for callers who hold coefficients.
+ */
+int32_t kzg_compute_cells_and_proofs_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells /* n * 128 * 2048, may be NULL */,
+                                           uint8_t* out_proofs48 /* n * 128 * 48 */, int32_t* status);
+int32_t kzg_compute_cells_and_proofs_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_cells /* may be NULL */, void* d_out_proofs48,
+                                               void* d_status, void* hip_stream);
+int32_t kzg_recover_cells_and_proofs_batch(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells,
+                                           uint8_t* out_proofs48, int32_t* status);
+int32_t kzg_recover_cells_and_proofs_batch_dev(const kzg_ctx* ctx, const void* d_cells, const void* d_present, uint64_t n, void* d_out_cells,
+                                               void* d_out_proofs48, void* d_status, void* hip_stream);
 
 /*
  * Replaces Setup::proof for n (blob, z) pairs (src/kzg/setup.rs:185-194):

@@ -503,6 +503,7 @@ EnvKnobs read_env_knobs() {
     if (const char* e = getenv("KATETH_AMD_PROOF_CHUNK")) k.proof_chunk = (uint64_t)atoll(e) > 0 ? (uint64_t)atoll(e) : 0;
     if (const char* e = getenv("KATETH_AMD_SIDECAR_PASS")) k.sidecar_pass = (uint64_t)atoll(e) > 0 ? (uint64_t)atoll(e) : 0;
     if (const char* e = getenv("KATETH_AMD_CELLS_PASS")) k.cells_pass = (uint64_t)atoll(e) > 0 ? (uint64_t)atoll(e) : 0;
+    if (const char* e = getenv("KATETH_AMD_CELLPROOF_PASS")) k.cellproof_pass = (uint64_t)atoll(e) > 0 ? (uint64_t)atoll(e) : 0;
     if (const char* e = getenv("KATETH_AMD_PROOF_OVERLAP")) k.proof_overlap = atoi(e) != 0;
     if (const char* e = getenv("KATETH_AMD_EVAL_GROUP")) k.eval_group = atoi(e);
     k.verify_serial = getenv("KATETH_AMD_VERIFY_SERIAL") != nullptr;
@@ -573,6 +574,7 @@ extern "C" void kzg_ctx_destroy(kzg_ctx* ctx) {
   if (ctx->d_cellv_tab) (void)hipFree(ctx->d_cellv_tab);
   if (ctx->d_cellv_h64) (void)hipFree(ctx->d_cellv_h64);
   if (ctx->d_g1_monomial) (void)hipFree(ctx->d_g1_monomial);
+  if (ctx->d_cellproof_tab) (void)hipFree(ctx->d_cellproof_tab);
   if (ctx->d_gen_affine) (void)hipFree(ctx->d_gen_affine);
   if (ctx->d_comb_k) (void)hipFree(ctx->d_comb_k);
   if (ctx->d_comb_k_lat) (void)hipFree(ctx->d_comb_k_lat);

@@ -26,7 +26,7 @@
 // the library used to carry each kernel once per engine*.hip that included its header):
 //   engine.hip        setup_kernels.cuh, msm_comb.cuh, msm_fixed.cuh   -> msm_launch / msm_finish / msm_pipeline
 //   engine_blob.hip   blob_kernels.cuh (hash, point decoding, scalars) -> launch_challenge*, launch_g1_decompress*, launch_fr_*
-//   engine_proof.hip  poly_kernels.cuh, cells_kernels.cuh              (its only user)
+//   engine_proof.hip  poly_kernels.cuh, cells_kernels.cuh, cellproof_kernels.cuh   (its only user)
 //   engine_verify.hip verify_kernels.cuh, cellverify_kernels.cuh      (its only user)      -> launch_glv_points
 #include "comb_geom.hpp"
 #include "g1.cuh"
@@ -139,6 +139,7 @@ struct EnvKnobs {
   uint64_t challenge_split_max = 0;  // KATETH_AMD_CHALLENGE_SPLIT_MAX: largest batch hashed by the two-wave SHA-256 kernel (0 = default)
   uint64_t sidecar_pass = 0;     // KATETH_AMD_SIDECAR_PASS: blobs per staging pass of kzg_blob_sidecar_batch (0 = the plan of the host-buffer proof call)
   uint64_t cells_pass = 0;       // KATETH_AMD_CELLS_PASS: items per staging pass of kzg_compute_cells_batch and kzg_recover_cells_batch (0 = default)
+  uint64_t cellproof_pass = 0;   // KATETH_AMD_CELLPROOF_PASS: items per pass of the cell-proof calls, on the device and through the staging ring (0 = default: 32)
 };
 EnvKnobs read_env_knobs();
 
@@ -249,6 +250,11 @@ struct kzg_ctx {
   mutable std::atomic<bool> g1_monomial_ready{false};
   mutable uint4* d_g1_monomial = nullptr;
   mutable uint8_t g1_monomial48[KZG_G1_MONOMIAL_POINTS * 48] = {};
+  // cell proofs' omega_128 powers: 128 such entries (layout: cellproof_math.cuh; k_cell_quotients), built by the context's first cell-proof call
+  // (ensure_cellproof_tab, engine_proof.hip); written once under cellproof_mu, then read-only
+  mutable std::mutex cellproof_mu;
+  mutable std::atomic<bool> cellproof_ready{false};
+  mutable uint32_t* d_cellproof_tab = nullptr;
   uint4* d_gen_affine = nullptr; // G1 generator and its [z^2]-image (GLV cross-check path), affine, 2^392-Montgomery (2 x 96 B): a term of batch verification's second lincomb
   host::pairing_ctx* pairing = nullptr;  // host: Frobenius constants + Miller lines of G2 and [tau]_2
   uint64_t table_bytes = 0;

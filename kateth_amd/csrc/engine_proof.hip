@@ -4,6 +4,7 @@
 #include "engine_internal.hpp"
 #include "poly_kernels.cuh"  // this translation unit owns the quotient / evaluation kernels of the proof path
 #include "cells_kernels.cuh"  // ... and the blob extension kernel of compute_cells
+#include "cellproof_kernels.cuh"  // ... and the quotient vectors of the cell proofs
 
 __global__ __launch_bounds__(256) void k_merge_status(int32_t* __restrict__ primary, const int32_t* __restrict__ secondary, uint64_t n) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -376,6 +377,23 @@ extern "C" int32_t kzg_compute_cells_batch_dev(const kzg_ctx* ctx, const void* d
 // 0..63 of an accepted blob ARE the caller's blob and are copied on the host.  Passes of KATETH_AMD_CELLS_PASS blobs (default 512)
 // through the staging ring; a slot holds a pass's blobs and, behind them, its 256 KiB of cells per blob, and is free again when the
 // pass's download has been enqueued behind its kernel.
+// a pass of the host-buffer forms: the kernel, and the extension halves of its m cell sets down to the caller's buffer
+static int32_t cells_pass_enqueue(const kzg_ctx* ctx, const uint8_t* d_blobs, uint64_t m, uint8_t* d_cells, int32_t* d_status, uint8_t* out_cells, hipStream_t st) {
+  const int32_t e = cells_enqueue(ctx, d_blobs, m, d_cells, d_status, st);
+  if (e == 0 && hipMemcpy2DAsync(out_cells + KZG_BYTES_PER_BLOB, KZG_BYTES_PER_CELL_SET, d_cells + KZG_BYTES_PER_BLOB, KZG_BYTES_PER_CELL_SET, KZG_BYTES_PER_BLOB, m,
+                                  hipMemcpyDeviceToHost, st) != hipSuccess)
+    return fail(KZG_FAIL_HIP, "device-to-host copy failed");
+  return e;
+}
+// ... and, once the statuses are on the host, cells 0..63 of every item: the caller's blob, or zero bytes
+static void cells_first_halves(const uint8_t* blobs, uint64_t n, const int32_t* status, uint8_t* out_cells) {
+  for (uint64_t i = 0; i < n; i++) {
+    if (status[i] == 0)
+      memcpy(out_cells + i * KZG_BYTES_PER_CELL_SET, blobs + i * (size_t)KZG_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB);
+    else
+      memset(out_cells + i * KZG_BYTES_PER_CELL_SET, 0, KZG_BYTES_PER_BLOB);
+  }
+}
 int32_t cells_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status) {
   if (n == 0) return 0;
   HostCall hc(ctx);
@@ -385,20 +403,11 @@ int32_t cells_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t
   int32_t* d_status = hc.dev<int32_t>(a_st);
   rc = hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
     uint8_t* d_cells = d_blobs + hc.max_pass * (size_t)KZG_BYTES_PER_BLOB;
-    const int32_t e = cells_enqueue(ctx, d_blobs, m, d_cells, d_status + base, hc.st);
-    if (e == 0 && hipMemcpy2DAsync(out_cells + base * KZG_BYTES_PER_CELL_SET + KZG_BYTES_PER_BLOB, KZG_BYTES_PER_CELL_SET, d_cells + KZG_BYTES_PER_BLOB,
-                                    KZG_BYTES_PER_CELL_SET, KZG_BYTES_PER_BLOB, m, hipMemcpyDeviceToHost, hc.st) != hipSuccess)
-      return fail(KZG_FAIL_HIP, "device-to-host copy failed");
-    return e;
+    return cells_pass_enqueue(ctx, d_blobs, m, d_cells, d_status + base, out_cells + base * KZG_BYTES_PER_CELL_SET, hc.st);
   });
   rc = hc.close(rc);
   if (rc) return rc;
-  for (uint64_t i = 0; i < n; i++) {
-    if (status[i] == 0)
-      memcpy(out_cells + i * KZG_BYTES_PER_CELL_SET, blobs + i * (size_t)KZG_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB);
-    else
-      memset(out_cells + i * KZG_BYTES_PER_CELL_SET, 0, KZG_BYTES_PER_BLOB);
-  }
+  cells_first_halves(blobs, n, status, out_cells);
   return 0;
 }
 
@@ -459,6 +468,216 @@ extern "C" int32_t kzg_recover_cells_batch(const kzg_ctx* ctx, const uint8_t* ce
   if (!ctx || (n && (!cells || !present || !out_cells || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
   return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
     return recover_host(m, cells + first * KZG_BYTES_PER_CELL_SET, present + first * 16, count, out_cells + first * KZG_BYTES_PER_CELL_SET, status + first);
+  });
+} catch (...) {
+  return abi_exception();
+}
+
+// ---------------------------------------------------------------------------
+// cell proofs (EIP-7594): compute_cells_and_kzg_proofs, recover_cells_and_kzg_proofs -- by quotient MSMs, not FK20
+// ---------------------------------------------------------------------------
+// The proof of cell k is the commitment of q_k = p / (X^64 - z_k) (cellproof_math.cuh): 128 scalar vectors per blob, which the
+// fixed-base MSM commits as it commits blobs.  The omega_128 table the division reads is built by the context's FIRST cell-proof call, as
+// the monomial points are (ensure_g1_monomial): a context that never asks for cell proofs launches and holds nothing for them.
+static int32_t ensure_cellproof_tab(const kzg_ctx* ctx) {
+  if (ctx->cellproof_ready.load(std::memory_order_acquire)) return 0;
+  std::lock_guard<std::mutex> guard(ctx->cellproof_mu);
+  if (ctx->cellproof_ready.load(std::memory_order_relaxed)) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  uint32_t* tab = nullptr;
+  HIP_TRY(hipMalloc(&tab, (size_t)CELLPROOF_TAB_ENTRIES * CELLS_TAB_ENTRY * sizeof(uint32_t)));
+  hipStream_t st = nullptr;
+  hipLaunchKernelGGL(k_setup_cellproof_tab, dim3(CELLPROOF_TAB_ENTRIES / 64), dim3(64), 0, st, tab);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // once per context: every later call, on whichever stream, finds the table written
+  if (e != hipSuccess) {
+    (void)hipFree(tab);
+    return fail(KZG_FAIL_HIP, std::string("cell-proof table: ") + hipGetErrorString(e));
+  }
+  ctx->d_cellproof_tab = tab;
+  ctx->cellproof_ready.store(true, std::memory_order_release);
+  return 0;
+}
+
+// Blobs per pass: 32 by default -- 4,096 vectors, the MSM's best shape, in 512 MiB, the size of the blob-proof path's own quotient slot;
+// at most 128 (16,384 vectors: the chunk bound of the commitment path's lane sums).  KATETH_AMD_CELLPROOF_PASS overrides.
+static uint64_t cellproof_pass(const kzg_ctx* ctx) { return std::min<uint64_t>(ctx->knobs.cellproof_pass ? ctx->knobs.cellproof_pass : 32, 128); }
+// workspace of a pass of m blobs: their coefficients, the 128 m vector statuses and quotient vectors, and one set of MSM buffers
+struct CellProofLayout {
+  uint32_t splits = 1;
+  size_t o_coeff = 0, o_vst = 0, o_q = 0, o_part = 0, o_sum = 0, o_msm = 0, total = 0;
+};
+static CellProofLayout cellproof_layout(const kzg_ctx* ctx, uint64_t m) {
+  CellProofLayout L;
+  const uint64_t vectors = m * KZG_CELLS_PER_EXT_BLOB;
+  L.splits = choose_splits(ctx, vectors);
+  Carve ws;
+  L.o_coeff = ws.take(m * (size_t)CELLPROOF_COEFF_BYTES);
+  L.o_vst = ws.take(vectors * sizeof(int32_t));
+  L.o_q = ws.take(vectors * 4096 * sizeof(fr_t));
+  L.o_part = ws.take(vectors * L.splits * 65 * sizeof(g1_xyzz));  // 64 lane sums + 1 unit sum per (vector, split)
+  L.o_sum = ws.take(vectors * sizeof(g1_xyzz));
+  L.o_msm = ws.take(msm_scratch_bytes(ctx, vectors));
+  L.total = ws.off;
+  return L;
+}
+// what a call over n items reserves before anything is in flight: a ragged last pass may take more splits than a full one
+static size_t cellproof_ws_bytes(const kzg_ctx* ctx, uint64_t n) {
+  const uint64_t P = cellproof_pass(ctx), full = std::min(n, P), rest = n > P ? n % P : 0;
+  return std::max(cellproof_layout(ctx, full).total, rest ? cellproof_layout(ctx, rest).total : (size_t)0);
+}
+
+// The 128 proofs of each of n items resident on the device, 48 bytes each at d_out_proofs48 + 6,144 item.  Item i is the 131,072 bytes
+// at d_items + i * stride: a blob (stride 131,072; skip_rejected = false: the item is range-checked and d_status[i] written) or cells
+// 0..63 of a recovered cell set (stride 262,144; skip_rejected = true: d_status[i] is k_recover_cells' verdict).  A rejected item gets
+// 6,144 zero bytes.  One stream, pass after pass; the two new kernels are timed with the blob-proof path's quotient kernel (PROF_POLY).
+static int32_t cellproof_dev_locked(const kzg_ctx* ctx, const uint8_t* d_items, uint64_t stride, bool skip_rejected, uint64_t n, uint8_t* d_out_proofs48,
+                                    int32_t* d_status, hipStream_t st) {
+  if (n == 0) return 0;
+  int32_t rc = ws_reserve(ctx, cellproof_ws_bytes(ctx, n), st);
+  if (rc) return rc;
+  uint8_t* ws = ws_ptr(ctx);
+  const uint64_t P = cellproof_pass(ctx);
+  for (uint64_t base = 0; base < n; base += P) {
+    const uint64_t m = std::min(n - base, P), vectors = m * KZG_CELLS_PER_EXT_BLOB;
+    const CellProofLayout L = cellproof_layout(ctx, m);
+    uint32_t* coeffs = reinterpret_cast<uint32_t*>(ws + L.o_coeff);
+    int32_t* vstatus = reinterpret_cast<int32_t*>(ws + L.o_vst);
+    uint32_t* q = reinterpret_cast<uint32_t*>(ws + L.o_q);
+    {
+      ProfScope ps(ctx, PROF_POLY, st);
+      hipLaunchKernelGGL(k_cell_coeffs, dim3((unsigned)std::min<uint64_t>(m, ctx->num_cus)), dim3(CELLS_THREADS), 0, st, d_items + base * stride, stride, m,
+                         skip_rejected, ctx->d_cells_tab, coeffs, d_status + base, vstatus);
+      hipLaunchKernelGGL(k_cell_quotients, dim3((unsigned)vectors), dim3(CELLS_THREADS), 0, st, coeffs, ctx->d_cells_tab, ctx->d_cellproof_tab, vstatus, q);
+    }
+    rc = msm_pipeline(ctx, false, reinterpret_cast<const uint8_t*>(q), vectors, d_out_proofs48 + base * (KZG_CELLS_PER_EXT_BLOB * 48), nullptr, vstatus,
+                      reinterpret_cast<g1_xyzz*>(ws + L.o_part), reinterpret_cast<g1_xyzz*>(ws + L.o_sum), L.splits, ws + L.o_msm, st);
+    if (rc) return rc;
+  }
+  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "cell-proof pipeline launch failed");
+  return 0;
+}
+
+// the device calls: the cells by the existing kernel, launched first, then the proofs under a workspace slot
+static int32_t cellproof_dev_call(const kzg_ctx* ctx, const uint8_t* d_items, uint64_t stride, bool skip_rejected, uint64_t n, uint8_t* d_out_proofs48,
+                                  int32_t* d_status, hipStream_t st) {
+  std::lock_guard<std::mutex> guard(ctx->lock);
+  WsCall ws(ctx, st);
+  int32_t rc = ws.begin();
+  if (rc == 0) rc = cellproof_dev_locked(ctx, d_items, stride, skip_rejected, n, d_out_proofs48, d_status, st);
+  if (rc == 0) rc = ws.end();
+  return rc;
+}
+extern "C" int32_t kzg_compute_cells_and_proofs_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_cells, void* d_out_proofs48, void* d_status,
+                                                          void* hip_stream) try {
+  if (!ctx || (n && (!d_blobs || !d_out_proofs48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  int32_t rc = ensure_cellproof_tab(ctx);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (rc == 0 && d_out_cells) rc = cells_enqueue(ctx, (const uint8_t*)d_blobs, n, (uint8_t*)d_out_cells, (int32_t*)d_status, st);
+  if (rc == 0) rc = cellproof_dev_call(ctx, (const uint8_t*)d_blobs, KZG_BYTES_PER_BLOB, false, n, (uint8_t*)d_out_proofs48, (int32_t*)d_status, st);
+  return rc;
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_recover_cells_and_proofs_batch_dev(const kzg_ctx* ctx, const void* d_cells, const void* d_present, uint64_t n, void* d_out_cells,
+                                                          void* d_out_proofs48, void* d_status, void* hip_stream) try {
+  if (!ctx || (n && (!d_cells || !d_present || !d_out_cells || !d_out_proofs48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  int32_t rc = ensure_cellproof_tab(ctx);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (rc == 0) rc = recover_enqueue(ctx, (const uint8_t*)d_cells, (const uint8_t*)d_present, n, (uint8_t*)d_out_cells, (int32_t*)d_status, st);
+  // a recovered item's blob is cells 0..63 of its own output
+  if (rc == 0) rc = cellproof_dev_call(ctx, (const uint8_t*)d_out_cells, KZG_BYTES_PER_CELL_SET, true, n, (uint8_t*)d_out_proofs48, (int32_t*)d_status, st);
+  return rc;
+} catch (...) {
+  return abi_exception();
+}
+
+// Host-buffer forms, after cells_host and recover_host: a staging pass is a pass of the device path (KATETH_AMD_CELLPROOF_PASS items,
+// default 32 -- about 28 ms of MSM each, so the pass's copy hides behind its predecessor).  Up: the blobs, or the cell sets and masks.
+// Down: the extension half (compute; cells 0..63 are the caller's blob) or the whole cell set (recovery), and 6 KiB of proofs per item.
+// One workspace slot for all passes, sized before anything is in flight.
+int32_t cellproofs_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, uint8_t* out_proofs48, int32_t* status) {
+  if (n == 0) return 0;
+  int32_t rc = ensure_cellproof_tab(ctx);
+  if (rc) return rc;
+  HostCall hc(ctx);
+  const int a_prf = hc.download(out_proofs48, n * (KZG_CELLS_PER_EXT_BLOB * 48)), a_st = hc.download(status, n * sizeof(int32_t));
+  rc = hc.open(even_plan(n, cellproof_pass(ctx)), KZG_BYTES_PER_BLOB + (out_cells ? KZG_BYTES_PER_CELL_SET : 0));
+  if (rc) return rc;
+  uint8_t* d_prf = hc.dev(a_prf);
+  int32_t* d_status = hc.dev<int32_t>(a_st);
+  {
+    std::lock_guard<std::mutex> guard(ctx->lock);
+    WsCall ws(ctx, hc.st);
+    rc = ws.begin();
+    if (rc == 0) rc = ws_reserve(ctx, cellproof_ws_bytes(ctx, n), hc.st);
+    if (rc == 0)
+      rc = hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
+        int32_t e = 0;
+        if (out_cells)
+          e = cells_pass_enqueue(ctx, d_blobs, m, d_blobs + hc.max_pass * (size_t)KZG_BYTES_PER_BLOB, d_status + base, out_cells + base * KZG_BYTES_PER_CELL_SET, hc.st);
+        if (e == 0) e = cellproof_dev_locked(ctx, d_blobs, KZG_BYTES_PER_BLOB, false, m, d_prf + base * (KZG_CELLS_PER_EXT_BLOB * 48), d_status + base, hc.st);
+        return e;
+      });
+    if (rc == 0) rc = ws.end();
+  }
+  rc = hc.close(rc);
+  if (rc) return rc;
+  if (out_cells) cells_first_halves(blobs, n, status, out_cells);
+  return 0;
+}
+int32_t recover_proofs_host(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, uint8_t* out_proofs48,
+                            int32_t* status) {
+  if (n == 0) return 0;
+  int32_t rc = ensure_cellproof_tab(ctx);
+  if (rc) return rc;
+  HostCall hc(ctx);
+  const int a_mask = hc.upload(present, n * 16), a_prf = hc.download(out_proofs48, n * (KZG_CELLS_PER_EXT_BLOB * 48)),
+            a_st = hc.download(status, n * sizeof(int32_t));
+  rc = hc.open(even_plan(n, cellproof_pass(ctx)), 2 * KZG_BYTES_PER_CELL_SET);
+  if (rc) return rc;
+  const uint8_t* d_present = hc.dev(a_mask);
+  uint8_t* d_prf = hc.dev(a_prf);
+  int32_t* d_status = hc.dev<int32_t>(a_st);
+  {
+    std::lock_guard<std::mutex> guard(ctx->lock);
+    WsCall ws(ctx, hc.st);
+    rc = ws.begin();
+    if (rc == 0) rc = ws_reserve(ctx, cellproof_ws_bytes(ctx, n), hc.st);
+    if (rc == 0)
+      rc = hc.passes(cells, KZG_BYTES_PER_CELL_SET, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_cells) {
+        uint8_t* d_out = d_cells + hc.max_pass * KZG_BYTES_PER_CELL_SET;
+        int32_t e = recover_enqueue(ctx, d_cells, d_present + base * 16, m, d_out, d_status + base, hc.st);
+        if (e == 0 && hipMemcpyAsync(out_cells + base * KZG_BYTES_PER_CELL_SET, d_out, m * KZG_BYTES_PER_CELL_SET, hipMemcpyDeviceToHost, hc.st) != hipSuccess)
+          return fail(KZG_FAIL_HIP, "device-to-host copy failed");
+        if (e == 0) e = cellproof_dev_locked(ctx, d_out, KZG_BYTES_PER_CELL_SET, true, m, d_prf + base * (KZG_CELLS_PER_EXT_BLOB * 48), d_status + base, hc.st);
+        return e;
+      });
+    if (rc == 0) rc = ws.end();
+  }
+  return hc.close(rc);
+}
+
+extern "C" int32_t kzg_compute_cells_and_proofs_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, uint8_t* out_proofs48,
+                                                      int32_t* status) try {
+  if (!ctx || (n && (!blobs || !out_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
+    return cellproofs_host(m, blobs + first * (size_t)KZG_BYTES_PER_BLOB, count, out_cells ? out_cells + first * KZG_BYTES_PER_CELL_SET : nullptr,
+                           out_proofs48 + first * (KZG_CELLS_PER_EXT_BLOB * 48), status + first);
+  });
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_recover_cells_and_proofs_batch(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells,
+                                                      uint8_t* out_proofs48, int32_t* status) try {
+  if (!ctx || (n && (!cells || !present || !out_cells || !out_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
+    return recover_proofs_host(m, cells + first * KZG_BYTES_PER_CELL_SET, present + first * 16, count, out_cells + first * KZG_BYTES_PER_CELL_SET,
+                               out_proofs48 + first * (KZG_CELLS_PER_EXT_BLOB * 48), status + first);
   });
 } catch (...) {
   return abi_exception();

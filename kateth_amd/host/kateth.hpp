@@ -298,8 +298,7 @@ class Setup {
   }
 
   // compute_cells (EIP-7594, specs/fulu/polynomial-commitments-sampling.md): the blob extended to 8192 evaluations, as 128 cells of
-  // 2,048 bytes in one buffer; cells 0..63 are the blob itself.  Cell proofs, cell verification and the proofs half of recovery are not
-  // part of the engine.
+  // 2,048 bytes in one buffer; cells 0..63 are the blob itself.  With their proofs: compute_cells_and_proofs below.
   static constexpr size_t CELLS_PER_EXT_BLOB = KZG_CELLS_PER_EXT_BLOB, FIELD_ELEMENTS_PER_CELL = KZG_FIELD_ELEMENTS_PER_CELL, BYTES_PER_CELL = KZG_BYTES_PER_CELL;
   std::vector<uint8_t> compute_cells(const uint8_t* blob, size_t len) const {
     if (len != BLOB_BYTES) throw Error(ErrorKind::BlobInvalidLen);
@@ -314,19 +313,52 @@ class Setup {
   // cells: the cells of those indices, concatenated (2,048 bytes each).  Returns all 128 cells in one buffer.  Beyond the spec, cells that
   // do not lie on one polynomial of degree < 4096 are rejected (ErrorKind::CellsInconsistent) instead of giving an arbitrary result.
   std::vector<uint8_t> recover_cells(const std::vector<uint64_t>& cell_indices, const uint8_t* cells, size_t len) const {
+    std::vector<uint8_t> in, out(CELLS_PER_EXT_BLOB * BYTES_PER_CELL);
+    std::array<uint8_t, 16> present{};
+    cell_set(cell_indices, cells, len, in, present);
+    int32_t status = 0;
+    check(kzg_recover_cells_batch(ctx_.get(), in.data(), present.data(), 1, out.data(), &status), "kzg_recover_cells_batch");
+    if (status) throw Error(static_cast<ErrorKind>(status));
+    return out;
+  }
+
+  // the spec's (cell_indices, cells) as one flat cell set and its 16-byte mask, after the spec's assertions
+  static void cell_set(const std::vector<uint64_t>& cell_indices, const uint8_t* cells, size_t len, std::vector<uint8_t>& flat, std::array<uint8_t, 16>& present) {
     const size_t m = cell_indices.size();
     if (len != m * BYTES_PER_CELL || m > CELLS_PER_EXT_BLOB) throw std::invalid_argument("recover_cells: one 2048-byte cell per index, at most 128");
     if (m < CELLS_PER_EXT_BLOB / 2) throw Error(ErrorKind::CellsNotEnough);
-    std::vector<uint8_t> in(CELLS_PER_EXT_BLOB * BYTES_PER_CELL), out(CELLS_PER_EXT_BLOB * BYTES_PER_CELL);
-    std::array<uint8_t, 16> present{};
+    flat.assign(CELLS_PER_EXT_BLOB * BYTES_PER_CELL, 0);
+    present.fill(0);
     for (size_t i = 0; i < m; i++) {
       const uint64_t c = cell_indices[i];
       if (c >= CELLS_PER_EXT_BLOB || (i && c <= cell_indices[i - 1])) throw std::invalid_argument("recover_cells: indices must be < 128 and strictly ascending");
-      std::memcpy(in.data() + c * BYTES_PER_CELL, cells + i * BYTES_PER_CELL, BYTES_PER_CELL);
+      std::memcpy(flat.data() + c * BYTES_PER_CELL, cells + i * BYTES_PER_CELL, BYTES_PER_CELL);
       present[c >> 3] |= static_cast<uint8_t>(1u << (c & 7));
     }
+  }
+
+  // compute_cells_and_kzg_proofs (EIP-7594): the 128 cells in one buffer and their 128 proofs, 48 bytes each, in another.  Proof k is the
+  // commitment of the quotient of the blob's polynomial by X^64 - z_k: 128 fixed-base MSMs per blob on the device, not FK20.
+  struct CellsAndProofs {
+    std::vector<uint8_t> cells, proofs;
+  };
+  CellsAndProofs compute_cells_and_proofs(const uint8_t* blob, size_t len) const {
+    if (len != BLOB_BYTES) throw Error(ErrorKind::BlobInvalidLen);
+    CellsAndProofs out{std::vector<uint8_t>(CELLS_PER_EXT_BLOB * BYTES_PER_CELL), std::vector<uint8_t>(CELLS_PER_EXT_BLOB * 48)};
     int32_t status = 0;
-    check(kzg_recover_cells_batch(ctx_.get(), in.data(), present.data(), 1, out.data(), &status), "kzg_recover_cells_batch");
+    check(kzg_compute_cells_and_proofs_batch(ctx_.get(), blob, 1, out.cells.data(), out.proofs.data(), &status), "kzg_compute_cells_and_proofs_batch");
+    if (status) throw Error(static_cast<ErrorKind>(status));
+    return out;
+  }
+  // recover_cells_and_kzg_proofs: arguments and errors as recover_cells
+  CellsAndProofs recover_cells_and_proofs(const std::vector<uint64_t>& cell_indices, const uint8_t* cells, size_t len) const {
+    std::vector<uint8_t> in;
+    std::array<uint8_t, 16> present{};
+    cell_set(cell_indices, cells, len, in, present);
+    CellsAndProofs out{std::vector<uint8_t>(CELLS_PER_EXT_BLOB * BYTES_PER_CELL), std::vector<uint8_t>(CELLS_PER_EXT_BLOB * 48)};
+    int32_t status = 0;
+    check(kzg_recover_cells_and_proofs_batch(ctx_.get(), in.data(), present.data(), 1, out.cells.data(), out.proofs.data(), &status),
+          "kzg_recover_cells_and_proofs_batch");
     if (status) throw Error(static_cast<ErrorKind>(status));
     return out;
   }
@@ -568,6 +600,23 @@ class Setup {
   // cells, out_cells: n * 128 * 2048 bytes (they must not overlap); present: n * 16 bytes, bit c & 7 of byte c >> 3 = cell c
   void recover_cells_batch(const uint8_t* cells, const uint8_t* present, size_t n, uint8_t* out_cells, int32_t* status) const {
     check(kzg_recover_cells_batch(ctx_.get(), cells, present, n, out_cells, status), "kzg_recover_cells_batch");
+  }
+
+  // out_cells: n * 128 * 2048 bytes, or null (not wanted); out_proofs48: n * 128 * 48 bytes, proof k of item i at byte 48 (128 i + k)
+  void compute_cells_and_proofs_batch(const uint8_t* blobs, size_t n, uint8_t* out_cells, uint8_t* out_proofs48, int32_t* status) const {
+    check(kzg_compute_cells_and_proofs_batch(ctx_.get(), blobs, n, out_cells, out_proofs48, status), "kzg_compute_cells_and_proofs_batch");
+  }
+  void recover_cells_and_proofs_batch(const uint8_t* cells, const uint8_t* present, size_t n, uint8_t* out_cells, uint8_t* out_proofs48, int32_t* status) const {
+    check(kzg_recover_cells_and_proofs_batch(ctx_.get(), cells, present, n, out_cells, out_proofs48, status), "kzg_recover_cells_and_proofs_batch");
+  }
+  // the same on HIP device pointers (16-byte aligned): enqueued on `hip_stream`, not synchronised
+  void compute_cells_and_proofs_batch_dev(const void* d_blobs, size_t n, void* d_out_cells, void* d_out_proofs48, void* d_status, void* hip_stream) const {
+    check(kzg_compute_cells_and_proofs_batch_dev(ctx_.get(), d_blobs, n, d_out_cells, d_out_proofs48, d_status, hip_stream), "kzg_compute_cells_and_proofs_batch_dev");
+  }
+  void recover_cells_and_proofs_batch_dev(const void* d_cells, const void* d_present, size_t n, void* d_out_cells, void* d_out_proofs48, void* d_status,
+                                          void* hip_stream) const {
+    check(kzg_recover_cells_and_proofs_batch_dev(ctx_.get(), d_cells, d_present, n, d_out_cells, d_out_proofs48, d_status, hip_stream),
+          "kzg_recover_cells_and_proofs_batch_dev");
   }
 
   const kzg_ctx* raw() const { return ctx_.get(); }

@@ -183,6 +183,16 @@ _SIGNATURES = {
         ctypes.c_int32,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "kzg_compute_cells_and_proofs_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
+    "kzg_compute_cells_and_proofs_batch_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "kzg_recover_cells_and_proofs_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
+    "kzg_recover_cells_and_proofs_batch_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "kzg_compute_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
     "kzg_verify_blob_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
     "kzg_verify_blob_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
@@ -649,6 +659,37 @@ class Setup:
         self._check(rc, "kzg_recover_cells_batch")
         return out.raw, list(status)
 
+    def compute_cells_and_proofs_batch(self, blobs: bytes, n: Optional[int] = None, want_cells: bool = True):
+        """n concatenated blobs -> (n * 128 * 2048 bytes of cells, or None without `want_cells`; n * 128 * 48 bytes of cell proofs;
+        [status]): EIP-7594's `compute_cells_and_kzg_proofs` per blob.  Proof k of blob i is at byte 48 * (128 i + k).  A rejected blob
+        gets zero bytes for both."""
+        blobs = _buf(blobs)
+        n = len(blobs) // BYTES_PER_BLOB if n is None else n
+        if len(blobs) != n * BYTES_PER_BLOB:
+            raise BlobError("InvalidLen")
+        cells = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * n) if want_cells else None
+        proofs = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * 48 * n)
+        status = (ctypes.c_int32 * n)()
+        rc = self._lib.kzg_compute_cells_and_proofs_batch(self._h, blobs, n, ctypes.cast(cells, ctypes.c_void_p) if want_cells else None,
+                                                          ctypes.cast(proofs, ctypes.c_void_p), status)
+        self._check(rc, "kzg_compute_cells_and_proofs_batch")
+        return (cells.raw if want_cells else None), proofs.raw, list(status)
+
+    def recover_cells_and_proofs_batch(self, cells: bytes, present: bytes, n: Optional[int] = None):
+        """`recover_cells_batch` with the 128 cell proofs of every item: -> (n * 128 * 2048 bytes of cells, n * 128 * 48 bytes of proofs,
+        [status]).  Statuses as `recover_cells_batch`; a rejected item gets zero bytes for both."""
+        cells, present = _buf(cells), _buf(present)
+        n = len(present) // 16 if n is None else n
+        if len(cells) != n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL or len(present) != n * 16:
+            raise ValueError("recover_cells_and_proofs_batch: n * 262144 bytes of cells and n * 16 bytes of mask")
+        out = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * n)
+        proofs = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * 48 * n)
+        status = (ctypes.c_int32 * n)()
+        rc = self._lib.kzg_recover_cells_and_proofs_batch(self._h, cells, present, n, ctypes.cast(out, ctypes.c_void_p),
+                                                          ctypes.cast(proofs, ctypes.c_void_p), status)
+        self._check(rc, "kzg_recover_cells_and_proofs_batch")
+        return out.raw, proofs.raw, list(status)
+
     def compute_proof_batch(self, blobs: bytes, zs: bytes):
         blobs, zs = _buf(blobs), _buf(zs)
         n = len(zs) // 32
@@ -759,11 +800,9 @@ class Setup:
             raise error_from_status(status[0])
         return [out[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
 
-    def recover_cells(self, cell_indices: Sequence[int], cells: Sequence[bytes]) -> List[bytes]:
-        """The cells half of `recover_cells_and_kzg_proofs` (EIP-7594): all 128 cells from at least 64 of them.  As the spec asserts:
-        one cell per index, 64..128 of them, every index < 128, indices strictly ascending, every cell 2,048 bytes (ValueError).
-        Raises BlobError InvalidFieldElement for an element >= r and, beyond the spec, CellsError Inconsistent when the cells do not lie
-        on one polynomial of degree < 4096."""
+    @staticmethod
+    def _cell_set(cell_indices: Sequence[int], cells: Sequence[bytes]):
+        """(flat cell set, mask) of one item from the spec's (indices, cells), after the spec's assertions (ValueError)"""
         cell_indices = [int(c) for c in cell_indices]
         cells = [_buf(c) for c in cells]
         if len(cell_indices) != len(cells):
@@ -780,10 +819,40 @@ class Setup:
         for c, cell in zip(cell_indices, cells):
             flat[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] = cell
             mask[c >> 3] |= 1 << (c & 7)
-        out, status = self.recover_cells_batch(bytes(flat), bytes(mask), 1)
+        return bytes(flat), bytes(mask)
+
+    def recover_cells(self, cell_indices: Sequence[int], cells: Sequence[bytes]) -> List[bytes]:
+        """The cells half of `recover_cells_and_kzg_proofs` (EIP-7594): all 128 cells from at least 64 of them.  As the spec asserts:
+        one cell per index, 64..128 of them, every index < 128, indices strictly ascending, every cell 2,048 bytes (ValueError).
+        Raises BlobError InvalidFieldElement for an element >= r and, beyond the spec, CellsError Inconsistent when the cells do not lie
+        on one polynomial of degree < 4096."""
+        flat, mask = self._cell_set(cell_indices, cells)
+        out, status = self.recover_cells_batch(flat, mask, 1)
         if status[0]:
             raise error_from_status(status[0])
         return [out[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
+
+    def compute_cells_and_proofs(self, blob: bytes):
+        """`compute_cells_and_kzg_proofs` (EIP-7594): (the 128 cells of one blob, their 128 proofs of 48 bytes); raises what
+        `compute_cells` raises."""
+        blob = _buf(blob)
+        if len(blob) != BYTES_PER_BLOB:
+            raise BlobError("InvalidLen")
+        cells, proofs, status = self.compute_cells_and_proofs_batch(blob, 1)
+        if status[0]:
+            raise error_from_status(status[0])
+        return ([cells[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)],
+                [proofs[48 * c:48 * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)])
+
+    def recover_cells_and_proofs(self, cell_indices: Sequence[int], cells: Sequence[bytes]):
+        """`recover_cells_and_kzg_proofs` (EIP-7594): (all 128 cells, their 128 proofs) from at least 64 cells; arguments and errors as
+        `recover_cells`."""
+        flat, mask = self._cell_set(cell_indices, cells)
+        out, proofs, status = self.recover_cells_and_proofs_batch(flat, mask, 1)
+        if status[0]:
+            raise error_from_status(status[0])
+        return ([out[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)],
+                [proofs[48 * c:48 * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)])
 
     def blob_proof(self, blob: bytes, commitment: bytes) -> bytes:
         """`Setup::blob_proof` + `compress` (kzg::Error on bad input)."""
@@ -1078,6 +1147,17 @@ class Setup:
         `stream` and returns.  `d_out_cells` must not overlap `d_cells`."""
         rc = self._lib.kzg_recover_cells_batch_dev(self._h, d_cells, d_present, n, d_out_cells, d_status, stream)
         self._check(rc, "kzg_recover_cells_batch_dev")
+
+    def compute_cells_and_proofs_batch_dev(self, d_blobs: int, n: int, d_out_cells: int, d_out_proofs: int, d_status: int, stream: int = 0):
+        """n blobs resident on the device -> n * 128 * 2048 bytes of cells (d_out_cells = 0: no cells wanted), n * 128 * 48 bytes of cell
+        proofs and n int32 statuses; enqueues on `stream` and returns"""
+        rc = self._lib.kzg_compute_cells_and_proofs_batch_dev(self._h, d_blobs, n, d_out_cells or None, d_out_proofs, d_status, stream)
+        self._check(rc, "kzg_compute_cells_and_proofs_batch_dev")
+
+    def recover_cells_and_proofs_batch_dev(self, d_cells: int, d_present: int, n: int, d_out_cells: int, d_out_proofs: int, d_status: int, stream: int = 0):
+        """`recover_cells_batch_dev` with n * 128 * 48 bytes of cell proofs; enqueues on `stream` and returns"""
+        rc = self._lib.kzg_recover_cells_and_proofs_batch_dev(self._h, d_cells, d_present, n, d_out_cells, d_out_proofs, d_status, stream)
+        self._check(rc, "kzg_recover_cells_and_proofs_batch_dev")
 
     def verify_blob_proof_batch_dev(self, d_blobs: int, d_commitments: int, d_proofs: int, n: int, stream: int = 0) -> bool:
         return self._verdict("kzg_verify_blob_proof_batch_dev", (d_blobs, d_commitments, d_proofs, n), (stream,))
