@@ -1171,11 +1171,12 @@ int32_t msm_finish(const kzg_ctx* ctx, uint64_t n, uint8_t* d_out48, uint8_t* d_
 }
 // MSM + reduce + compress
 int32_t msm_pipeline(const kzg_ctx* ctx, bool be_bytes, const uint8_t* d_scalars, uint64_t n, uint8_t* d_out48, uint8_t* d_out_affine96, int32_t* d_status,
-                            g1_xyzz* partials, g1_xyzz* sums, uint32_t splits, void* scratch, hipStream_t st) {
-  const uint32_t lpb = msm_lanes_per_blob(ctx, n, splits);
-  int32_t rc = msm_launch(ctx, be_bytes, d_scalars, n, d_status, partials, splits, lpb, scratch, st);
+                     const MsmBufs& bufs, uint8_t* ws, hipStream_t st) {
+  g1_xyzz* partials = reinterpret_cast<g1_xyzz*>(ws + bufs.o_part);
+  const uint32_t lpb = msm_lanes_per_blob(ctx, n, bufs.splits);
+  int32_t rc = msm_launch(ctx, be_bytes, d_scalars, n, d_status, partials, bufs.splits, lpb, ws + bufs.o_scratch, st);
   if (rc) return rc;
-  return msm_finish(ctx, n, d_out48, d_out_affine96, d_status, partials, sums, splits, lpb, st);
+  return msm_finish(ctx, n, d_out48, d_out_affine96, d_status, partials, reinterpret_cast<g1_xyzz*>(ws + bufs.o_sum), bufs.splits, lpb, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1186,22 +1187,16 @@ static int32_t commit_dev_locked(const kzg_ctx* ctx, const void* d_blobs, uint64
   if (n == 0) return 0;
   const uint64_t chunk_max = 16384;  // bounds the lane-partial scratch (12 KiB per blob)
   const uint64_t cn = n < chunk_max ? n : chunk_max;
-  const uint32_t splits = choose_splits(ctx, cn);
-  const size_t partial_bytes = align_up((size_t)cn * splits * 65 * sizeof(g1_xyzz), 256);  // 64 lane sums + 1 unit sum per (blob, split)
-  const size_t sums_bytes = align_up((size_t)cn * sizeof(g1_xyzz), 256);
-  const size_t need = partial_bytes + sums_bytes + msm_scratch_bytes(ctx, cn);
-  int32_t rc = ws_reserve(ctx, need, st);
+  Carve carve;
+  const MsmBufs bufs = msm_carve(ctx, carve, cn);
+  int32_t rc = ws_reserve(ctx, carve.off, st);
   if (rc) return rc;
-  g1_xyzz* partials = reinterpret_cast<g1_xyzz*>(ws_ptr(ctx));
-  g1_xyzz* sums = reinterpret_cast<g1_xyzz*>(ws_ptr(ctx) + partial_bytes);
-  void* msm_scratch = ws_ptr(ctx) + partial_bytes + sums_bytes;
   HIP_TRY(hipMemsetAsync(d_status, 0, n * sizeof(int32_t), st));
   for (uint64_t base = 0; base < n; base += cn) {
     const uint64_t m = (n - base < cn) ? (n - base) : cn;
     rc = msm_pipeline(ctx, true, reinterpret_cast<const uint8_t*>(d_blobs) + base * (uint64_t)KZG_BYTES_PER_BLOB, m,
                             d_out48 ? reinterpret_cast<uint8_t*>(d_out48) + base * 48 : nullptr,
-                            d_out_affine96 ? reinterpret_cast<uint8_t*>(d_out_affine96) + base * 96 : nullptr, d_status + base, partials, sums,
-                            splits, msm_scratch, st);
+                            d_out_affine96 ? reinterpret_cast<uint8_t*>(d_out_affine96) + base * 96 : nullptr, d_status + base, bufs, ws_ptr(ctx), st);
     if (rc) return rc;
   }
   return 0;
@@ -1211,13 +1206,8 @@ extern "C" int32_t kzg_blob_to_commitment_batch_dev(const kzg_ctx* ctx, const vo
                                                     void* hip_stream) try {
   if (!ctx || (n && (!d_blobs || !d_out48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> guard(ctx->lock);
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  WsCall ws(ctx, st);
-  int32_t rc = ws.begin();
-  if (rc == 0) rc = commit_dev_locked(ctx, d_blobs, n, d_out48, nullptr, reinterpret_cast<int32_t*>(d_status), st);
-  if (rc == 0) rc = ws.end();
-  return rc;
+  return with_workspace(ctx, st, [&] { return commit_dev_locked(ctx, d_blobs, n, d_out48, nullptr, reinterpret_cast<int32_t*>(d_status), st); });
 } catch (...) {
   return abi_exception();
 }
@@ -1339,7 +1329,9 @@ int32_t commit_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_
   uint8_t* d_res = hc.dev(a_res);
   int32_t* d_status = hc.dev<int32_t>(a_st);
   hipStream_t comp[2] = {ctx->stage_streams[0], ctx->stage_streams[1]};
-  std::lock_guard<std::mutex> guard(ctx->lock);  // the workspace: per slot the lane sums, the sums and the bit-plane masks of a chunk
+  // The workspace: per slot the lane sums, the sums and the bit-plane masks of a chunk.  Not msm_carve's: the lane sums are sized by the
+  // msm_units of the ramp's largest shape, twice, and the bracket spans two streams.
+  std::lock_guard<std::mutex> guard(ctx->lock);
   WsCall ws(ctx, comp[0]);
   uint64_t max_units = 1;  // launch shapes follow the table in use, which only changes under this lock
   for (uint64_t m : plan) {

@@ -311,8 +311,23 @@ int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side
                    uint8_t* out_affine96, uint8_t* out_y32, int32_t* status);  // engine_proof.hip
 int32_t sidecar_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_proofs48, uint8_t* out_versioned_hashes32,
                      int32_t* status);  // engine_proof.hip
-int32_t cells_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status);  // engine_proof.hip
-int32_t recover_host(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status);  // engine_proof.hip
+// One cell call (EIP-7594) over n items, all of it in the caller's host buffers (das_host) or all of it device-resident (das_dev):
+//   in            the blobs (131,072 bytes per item), or with `present` the cell sets (262,144)
+//   present       16-byte masks: recover the absent cells; null: compute the cells of blobs
+//   out_cells     the 128 cells of every item; null (compute with proofs only): no cells wanted
+//   out_proofs48  the 128 proofs of every item, 6,144 bytes; null: cells only -- the call takes neither ctx->lock nor a workspace slot
+struct CellCall {
+  const uint8_t *in, *present;
+  uint8_t *out_cells, *out_proofs48;
+  int32_t* status;
+  CellCall advanced(uint64_t first) const {  // the same call from item `first` on
+    return CellCall{in + first * (present ? KZG_BYTES_PER_CELL_SET : (size_t)KZG_BYTES_PER_BLOB), present ? present + first * 16 : nullptr,
+                    out_cells ? out_cells + first * KZG_BYTES_PER_CELL_SET : nullptr,
+                    out_proofs48 ? out_proofs48 + first * (KZG_CELLS_PER_EXT_BLOB * 48) : nullptr, status + first};
+  }
+};
+int32_t das_host(const kzg_ctx* ctx, const CellCall& call, uint64_t n);                // engine_proof.hip
+int32_t das_dev(const kzg_ctx* ctx, const CellCall& call, uint64_t n, hipStream_t st);  // engine_proof.hip
 int32_t verify_proof_single(const kzg_ctx* ctx, const uint8_t* proof48, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32, int32_t* ok);
 int32_t g1_decompress_single(const kzg_ctx* ctx, const uint8_t* in48, uint64_t n, uint8_t* out_affine96, int32_t* status);
 int32_t evaluate_blobs_single(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* z32, uint64_t n, uint8_t* out_y32, int32_t* status);
@@ -403,7 +418,7 @@ void stage_drain(const kzg_ctx* ctx);  // verify_phase1_host's failure path: the
 void stage_destroy(const kzg_ctx* ctx);
 // record `ev` on `signaller`, then `waiter` waits for it
 int32_t stream_after(hipStream_t waiter, hipStream_t signaller, hipEvent_t ev);
-// The slot protocol of the host-buffer pipelines, stated once.  Its users are HostCall (below: the seven producer calls) and
+// The slot protocol of the host-buffer pipelines, stated once.  Its users are HostCall (below: the producer calls) and
 // verify_phase1_host (engine_verify.hip).
 // The caller's blobs cross PCIe in chunks through `slots` equal slots of the context's staging arena; chunk k lives in slot k % slots:
 //   feed(k)      the copy stream waits for the slot's previous consumer (done_event(k - slots), when k >= slots), copies the chunk in and
@@ -425,8 +440,8 @@ struct StageRing {
   int32_t consumed(uint64_t k, hipStream_t comp);
 };
 
-// The driver of a host-buffer producer call on one device (commit_host; proof_host, sidecar_host, cells_host, recover_host; evaluate_blobs_single,
-// g1_decompress_single), which owns the call's StageRing:
+// The driver of a host-buffer producer call on one device (commit_host; proof_host, sidecar_host, das_host; evaluate_blobs_single,
+// g1_decompress_single: six implementations under thirteen entry points), which owns the call's StageRing:
 //   upload / download / scratch   register the call's small per-item arrays in the host-i/o pool by host pointer and byte count, BEFORE the
 //                                 pools are sized; the statuses are one more downloaded array.  A null host pointer (an output the caller does
 //                                 not want) registers nothing: its handle resolves to a null device pointer and nothing is copied.
@@ -439,7 +454,7 @@ struct StageRing {
 //   close(rc)                     the one exit of the call, `rc` = the code of the steps since open(): the downloads and the synchronisation of `st`,
 //                                 or, after any failure (its own included), a wait for the whole device -- copies into and out of the caller's buffers
 //                                 may be in flight -- and the first code, its text untouched.  A failing open() has taken this exit already.
-// Workspaces and ctx->lock are the caller's business, between open() and close().  commit_host runs its two-stream loop on `ring` itself.
+// Workspaces and ctx->lock are the caller's business, between open() and close() (with_workspace).  commit_host runs its two-stream loop on `ring` itself.
 struct HostCall {
   const kzg_ctx* ctx;
   StageRing ring;
@@ -531,6 +546,18 @@ struct WsCall {
   }
 };
 static inline uint8_t* ws_ptr(const kzg_ctx* ctx) { return reinterpret_cast<uint8_t*>(ctx->wss[ctx->ws_cur].p); }
+// The workspace bracket of a call on one stream: ctx->lock and a slot are held while body() ENQUEUES on `st` -- ws_reserve, then the
+// launches -- and given back before the host waits for anything: the slot's event orders its next user behind this call.  Returns the
+// first non-zero code.
+template <class Body>
+static inline int32_t with_workspace(const kzg_ctx* ctx, hipStream_t st, Body&& body) {
+  std::lock_guard<std::mutex> guard(ctx->lock);
+  WsCall ws(ctx, st);
+  int32_t rc = ws.begin();
+  if (rc == 0) rc = body();
+  if (rc == 0) rc = ws.end();
+  return rc;
+}
 int32_t prof_next(const kzg_ctx* ctx, int kind, hipEvent_t* e0, hipEvent_t* e1);
 // brackets the launches enqueued on `st` during its lifetime with an event pair (no-op unless profiling)
 struct ProfScope {
@@ -603,6 +630,20 @@ int32_t msm_launch(const kzg_ctx* ctx, bool be_bytes, const uint8_t* d_scalars, 
 // of a blob.  `partials` must have room for n * splits unit sums after the n * splits * 64 lane sums.
 int32_t msm_finish(const kzg_ctx* ctx, uint64_t n, uint8_t* d_out48, uint8_t* d_out_affine96, const int32_t* d_status, g1_xyzz* partials, g1_xyzz* sums,
                    uint32_t splits, uint32_t lpb, hipStream_t st);
-// MSM + reduce + compress
+// The buffers of one MSM + reduce + compress over up to n scalar vectors, as offsets into a workspace: the lane sums (64 lane sums + 1 unit
+// sum per (vector, split)), the n sums and msm_scratch_bytes; `splits` is choose_splits(ctx, n).
+struct MsmBufs {
+  uint32_t splits = 1;
+  size_t o_part = 0, o_sum = 0, o_scratch = 0;
+};
+static inline MsmBufs msm_carve(const kzg_ctx* ctx, Carve& ws, uint64_t n) {
+  MsmBufs b;
+  b.splits = choose_splits(ctx, n);
+  b.o_part = ws.take((size_t)n * b.splits * 65 * sizeof(g1_xyzz));
+  b.o_sum = ws.take((size_t)n * sizeof(g1_xyzz));
+  b.o_scratch = ws.take(msm_scratch_bytes(ctx, n));
+  return b;
+}
+// MSM + reduce + compress of n vectors in the buffers `bufs` of the workspace at `ws`
 int32_t msm_pipeline(const kzg_ctx* ctx, bool be_bytes, const uint8_t* d_scalars, uint64_t n, uint8_t* d_out48, uint8_t* d_out_affine96, int32_t* d_status,
-                     g1_xyzz* partials, g1_xyzz* sums, uint32_t splits, void* scratch, hipStream_t st);
+                     const MsmBufs& bufs, uint8_t* ws, hipStream_t st);

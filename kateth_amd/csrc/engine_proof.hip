@@ -1,4 +1,5 @@
-// compute_blob_kzg_proof / compute_kzg_proof entry points
+// The producers behind the commitment: blob proofs and proofs at a point, the blob sidecar, and the cell calls of EIP-7594 (compute_cells,
+// recover_cells and their cell proofs) -- entry points, host-buffer drivers and the kernels they alone launch
 #include <algorithm>
 
 #include "engine_internal.hpp"
@@ -15,14 +16,13 @@ __global__ __launch_bounds__(256) void k_merge_status(int32_t* __restrict__ prim
 // commitment statuses, quotient scalars) and one set of MSM buffers
 struct ProofLayout {
   uint64_t cn = 0;
-  uint32_t splits = 1;
-  size_t o_z[2], o_y[2], o_cs[2], o_q[2], o_ir[2], o_part = 0, o_sum = 0, o_msm = 0, total = 0;
+  size_t o_z[2], o_y[2], o_cs[2], o_q[2], o_ir[2], total = 0;
+  MsmBufs msm;
 };
 static ProofLayout proof_layout(const kzg_ctx* ctx, uint64_t n) {
   ProofLayout L;
   const uint64_t chunk_max = ctx->knobs.proof_chunk ? ctx->knobs.proof_chunk : 16384;
   L.cn = n < chunk_max ? n : chunk_max;
-  L.splits = choose_splits(ctx, L.cn);
   Carve ws;
   for (int sl = 0; sl < 2; sl++) {
     L.o_z[sl] = ws.take(L.cn * sizeof(fr_t));
@@ -31,9 +31,7 @@ static ProofLayout proof_layout(const kzg_ctx* ctx, uint64_t n) {
     L.o_cs[sl] = ws.take(L.cn * sizeof(int32_t));
     L.o_q[sl] = ws.take(L.cn * 4096 * sizeof(fr_t));
   }
-  L.o_part = ws.take(L.cn * L.splits * 65 * sizeof(g1_xyzz));  // 64 lane sums + 1 unit sum per (blob, split)
-  L.o_sum = ws.take(L.cn * sizeof(g1_xyzz));
-  L.o_msm = ws.take(msm_scratch_bytes(ctx, L.cn));
+  L.msm = msm_carve(ctx, ws, L.cn);
   L.total = ws.off;
   return L;
 }
@@ -54,14 +52,10 @@ static int32_t proof_dev_locked(const kzg_ctx* ctx, const uint8_t* d_blobs, cons
   bool overlap = ctx->knobs.proof_overlap > 0;
   const ProofLayout L = proof_layout(ctx, n);
   const uint64_t cn = L.cn, nchunks = (n + cn - 1) / cn;
-  const uint32_t splits = L.splits;
   int32_t rc = ws_reserve(ctx, L.total, st);
   if (rc) return rc;
   uint8_t* ws = ws_ptr(ctx);
   const size_t *o_z = L.o_z, *o_y = L.o_y, *o_cs = L.o_cs, *o_q = L.o_q, *o_ir = L.o_ir;
-  const size_t o_msm = L.o_msm;
-  g1_xyzz* partials = reinterpret_cast<g1_xyzz*>(ws + L.o_part);
-  g1_xyzz* sums = reinterpret_cast<g1_xyzz*>(ws + L.o_sum);
   hipStream_t side = overlap ? ctx->side_stream : st;
   // events come from the context's pool (guarded by ctx->lock, which the caller holds): 4 per chunk + 1, created once
   std::vector<hipEvent_t>& pool = ctx->proof_events;
@@ -131,7 +125,7 @@ static int32_t proof_dev_locked(const kzg_ctx* ctx, const uint8_t* d_blobs, cons
       fr_t* q = reinterpret_cast<fr_t*>(ws + o_q[sl]);
       (void)hipStreamWaitEvent(st, ev_prep[k], 0);
       rc = msm_pipeline(ctx, false, reinterpret_cast<const uint8_t*>(q), m, d_out48 ? d_out48 + base * 48 : nullptr,
-                               d_out_affine96 ? d_out_affine96 + base * 96 : nullptr, d_status + base, partials, sums, splits, ws + o_msm, st);
+                               d_out_affine96 ? d_out_affine96 + base * 96 : nullptr, d_status + base, L.msm, ws, st);
       if (rc) break;
       if (d_y32) launch_fr_store_be(st, y, m, d_status + base, d_y32 + base * 32);
       (void)hipEventRecord(ev_done[k], st);
@@ -146,15 +140,10 @@ extern "C" int32_t kzg_compute_blob_proof_batch_dev(const kzg_ctx* ctx, const vo
                                                     void* d_out48, void* d_status, void* hip_stream) try {
   if (!ctx || (n && (!d_blobs || !d_commitments48 || !d_out48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> guard(ctx->lock);
   hipStream_t st = (hipStream_t)hip_stream;
-  WsCall ws(ctx, st);
-  int32_t rc = ws.begin();
-  if (rc == 0)
-    rc = proof_dev_locked(ctx, (const uint8_t*)d_blobs, (const uint8_t*)d_commitments48, nullptr, n, (uint8_t*)d_out48, nullptr, nullptr,
-                          (int32_t*)d_status, st);
-  if (rc == 0) rc = ws.end();
-  return rc;
+  return with_workspace(ctx, st, [&] {
+    return proof_dev_locked(ctx, (const uint8_t*)d_blobs, (const uint8_t*)d_commitments48, nullptr, n, (uint8_t*)d_out48, nullptr, nullptr, (int32_t*)d_status, st);
+  });
 } catch (...) {
   return abi_exception();
 }
@@ -195,18 +184,16 @@ int32_t proof_host(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* side
   if (rc) return rc;
   uint8_t *d_side = hc.dev(a_side), *d_out = hc.dev(a_out), *d_aff = hc.dev(a_aff), *d_y = hc.dev(a_y);
   int32_t* d_status = hc.dev<int32_t>(a_st);
-  std::lock_guard<std::mutex> guard(ctx->lock);
-  WsCall ws(ctx, hc.st);
   // one workspace slot for all passes (they follow each other on the call's stream), sized for the largest pass BEFORE anything is in
   // flight: growing it between passes would free memory under the pipeline
-  rc = ws.begin();
-  if (rc == 0) rc = ws_reserve(ctx, proof_layout(ctx, hc.max_pass).total, hc.st);
-  if (rc == 0)
-    rc = hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
+  rc = with_workspace(ctx, hc.st, [&] {
+    const int32_t e = ws_reserve(ctx, proof_layout(ctx, hc.max_pass).total, hc.st);
+    if (e) return e;
+    return hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
       return proof_dev_locked(ctx, d_blobs, side_is_commitment ? d_side + base * side_bytes : nullptr, side_is_commitment ? nullptr : d_side + base * side_bytes, m,
                               d_out ? d_out + base * 48 : nullptr, d_aff ? d_aff + base * 96 : nullptr, d_y ? d_y + base * 32 : nullptr, d_status + base, hc.st);
     });
-  if (rc == 0) rc = ws.end();
+  });
   return hc.close(rc);
 }
 
@@ -269,14 +256,12 @@ static int32_t sidecar_dev_locked(const kzg_ctx* ctx, const uint8_t* d_blobs, ui
   fr_t* y = reinterpret_cast<fr_t*>(ws + L.o_y[0]);
   fr_t* invr = reinterpret_cast<fr_t*>(ws + L.o_ir[0]);
   fr_t* q = reinterpret_cast<fr_t*>(ws + L.o_q[0]);
-  g1_xyzz* partials = reinterpret_cast<g1_xyzz*>(ws + L.o_part);
-  g1_xyzz* sums = reinterpret_cast<g1_xyzz*>(ws + L.o_sum);
   HIP_TRY(hipMemsetAsync(d_status, 0, n * sizeof(int32_t), st));
   for (uint64_t base = 0; base < n; base += cn) {
     const uint64_t m = (n - base < cn) ? (n - base) : cn;
     const uint8_t* blobs = d_blobs + base * (uint64_t)KZG_BYTES_PER_BLOB;
     uint8_t* com = d_out_commitments48 + base * 48;
-    rc = msm_pipeline(ctx, true, blobs, m, com, nullptr, d_status + base, partials, sums, L.splits, ws + L.o_msm, st);
+    rc = msm_pipeline(ctx, true, blobs, m, com, nullptr, d_status + base, L.msm, ws, st);
     if (rc) return rc;
     launch_challenge(ctx, st, blobs, com, m, z);
     {
@@ -284,8 +269,7 @@ static int32_t sidecar_dev_locked(const kzg_ctx* ctx, const uint8_t* d_blobs, ui
       hipLaunchKernelGGL(k_poly_root_inverse, dim3(blocks_for(m, 64)), dim3(64), 0, st, z, m, invr);
       hipLaunchKernelGGL(k_poly<true>, dim3((unsigned)m), dim3(512), 0, st, blobs, z, ctx->d_roots_brp, invr, y, q, d_status + base);
     }
-    rc = msm_pipeline(ctx, false, reinterpret_cast<const uint8_t*>(q), m, d_out_proofs48 + base * 48, nullptr, d_status + base, partials, sums, L.splits,
-                      ws + L.o_msm, st);
+    rc = msm_pipeline(ctx, false, reinterpret_cast<const uint8_t*>(q), m, d_out_proofs48 + base * 48, nullptr, d_status + base, L.msm, ws, st);
     if (rc) return rc;
     if (d_out_vh32) launch_versioned_hash(st, com, m, d_status + base, d_out_vh32 + base * 32);
   }
@@ -298,15 +282,11 @@ extern "C" int32_t kzg_blob_sidecar_batch_dev(const kzg_ctx* ctx, const void* d_
   if (!ctx || (n && (!d_blobs || !d_out_commitments48 || !d_out_proofs48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(ctx->device));
-  std::lock_guard<std::mutex> guard(ctx->lock);
   hipStream_t st = (hipStream_t)hip_stream;
-  WsCall ws(ctx, st);
-  int32_t rc = ws.begin();
-  if (rc == 0)
-    rc = sidecar_dev_locked(ctx, (const uint8_t*)d_blobs, n, (uint8_t*)d_out_commitments48, (uint8_t*)d_out_proofs48, (uint8_t*)d_out_versioned_hashes32,
-                            (int32_t*)d_status, st);
-  if (rc == 0) rc = ws.end();
-  return rc;
+  return with_workspace(ctx, st, [&] {
+    return sidecar_dev_locked(ctx, (const uint8_t*)d_blobs, n, (uint8_t*)d_out_commitments48, (uint8_t*)d_out_proofs48, (uint8_t*)d_out_versioned_hashes32,
+                              (int32_t*)d_status, st);
+  });
 } catch (...) {
   return abi_exception();
 }
@@ -325,19 +305,17 @@ int32_t sidecar_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8
   if (rc) return rc;
   uint8_t *d_com = hc.dev(a_com), *d_prf = hc.dev(a_prf), *d_vh = hc.dev(a_vh);
   int32_t* d_status = hc.dev<int32_t>(a_st);
-  std::lock_guard<std::mutex> guard(ctx->lock);
-  WsCall ws(ctx, hc.st);
   // one workspace slot for all passes, sized BEFORE anything is in flight for the pass that asks most (a short last pass may take
   // more splits, and so more lane sums, than a full one): growing it between passes would free memory under the pipeline
-  rc = ws.begin();
-  size_t need = 0;
-  for (uint64_t m : hc.plan) need = std::max(need, proof_layout(ctx, m).total);
-  if (rc == 0) rc = ws_reserve(ctx, need, hc.st);
-  if (rc == 0)
-    rc = hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
+  rc = with_workspace(ctx, hc.st, [&] {
+    size_t need = 0;
+    for (uint64_t m : hc.plan) need = std::max(need, proof_layout(ctx, m).total);
+    const int32_t e = ws_reserve(ctx, need, hc.st);
+    if (e) return e;
+    return hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
       return sidecar_dev_locked(ctx, d_blobs, m, d_com + base * 48, d_prf + base * 48, d_vh ? d_vh + base * 32 : nullptr, d_status + base, hc.st);
     });
-  if (rc == 0) rc = ws.end();
+  });
   return hc.close(rc);
 }
 
@@ -353,77 +331,17 @@ extern "C" int32_t kzg_blob_sidecar_batch(const kzg_ctx* ctx, const uint8_t* blo
 }
 
 // ---------------------------------------------------------------------------
-// compute_cells (EIP-7594): the 128 cells of every blob
+// the cell calls (EIP-7594): compute_cells, recover_cells, and either with the 128 cell proofs of every item
 // ---------------------------------------------------------------------------
-// One launch, one workgroup per CU looping over the blobs (a workgroup holds its blob in all of the CU's LDS it may claim, so a
-// larger grid would only queue).  The kernel writes every output byte and every status: nothing is cleared first.
+// The cells of n device-resident items: compute_cells' kernel over blobs, or recover_cells' over cell sets and masks.  One launch, one workgroup
+// per CU looping over the items (a workgroup holds its item in all of the CU's LDS it may claim, so a larger grid would only queue).  Either
+// kernel writes every output byte and every status: nothing is cleared first.
 static int32_t cells_enqueue(const kzg_ctx* ctx, const uint8_t* d_blobs, uint64_t n, uint8_t* d_out_cells, int32_t* d_status, hipStream_t st) {
   const unsigned grid = (unsigned)std::min<uint64_t>(n, ctx->num_cus);
   hipLaunchKernelGGL(k_compute_cells, dim3(grid), dim3(CELLS_THREADS), 0, st, d_blobs, n, ctx->d_cells_tab, d_out_cells, d_status);
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "compute_cells launch failed");
   return 0;
 }
-
-extern "C" int32_t kzg_compute_cells_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_cells, void* d_status, void* hip_stream) try {
-  if (!ctx || (n && (!d_blobs || !d_out_cells || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(ctx->device));
-  return cells_enqueue(ctx, (const uint8_t*)d_blobs, n, (uint8_t*)d_out_cells, (int32_t*)d_status, (hipStream_t)hip_stream);
-} catch (...) {
-  return abi_exception();
-}
-
-// Host-buffer form.  PCIe is this call's limit (128 KiB up and 256 KiB down per blob), so only the extension half comes back: cells
-// 0..63 of an accepted blob ARE the caller's blob and are copied on the host.  Passes of KATETH_AMD_CELLS_PASS blobs (default 512)
-// through the staging ring; a slot holds a pass's blobs and, behind them, its 256 KiB of cells per blob, and is free again when the
-// pass's download has been enqueued behind its kernel.
-// a pass of the host-buffer forms: the kernel, and the extension halves of its m cell sets down to the caller's buffer
-static int32_t cells_pass_enqueue(const kzg_ctx* ctx, const uint8_t* d_blobs, uint64_t m, uint8_t* d_cells, int32_t* d_status, uint8_t* out_cells, hipStream_t st) {
-  const int32_t e = cells_enqueue(ctx, d_blobs, m, d_cells, d_status, st);
-  if (e == 0 && hipMemcpy2DAsync(out_cells + KZG_BYTES_PER_BLOB, KZG_BYTES_PER_CELL_SET, d_cells + KZG_BYTES_PER_BLOB, KZG_BYTES_PER_CELL_SET, KZG_BYTES_PER_BLOB, m,
-                                  hipMemcpyDeviceToHost, st) != hipSuccess)
-    return fail(KZG_FAIL_HIP, "device-to-host copy failed");
-  return e;
-}
-// ... and, once the statuses are on the host, cells 0..63 of every item: the caller's blob, or zero bytes
-static void cells_first_halves(const uint8_t* blobs, uint64_t n, const int32_t* status, uint8_t* out_cells) {
-  for (uint64_t i = 0; i < n; i++) {
-    if (status[i] == 0)
-      memcpy(out_cells + i * KZG_BYTES_PER_CELL_SET, blobs + i * (size_t)KZG_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB);
-    else
-      memset(out_cells + i * KZG_BYTES_PER_CELL_SET, 0, KZG_BYTES_PER_BLOB);
-  }
-}
-int32_t cells_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status) {
-  if (n == 0) return 0;
-  HostCall hc(ctx);
-  const int a_st = hc.download(status, n * sizeof(int32_t));
-  int32_t rc = hc.open(even_plan(n, ctx->knobs.cells_pass ? ctx->knobs.cells_pass : 512), KZG_BYTES_PER_BLOB + KZG_BYTES_PER_CELL_SET);
-  if (rc) return rc;
-  int32_t* d_status = hc.dev<int32_t>(a_st);
-  rc = hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
-    uint8_t* d_cells = d_blobs + hc.max_pass * (size_t)KZG_BYTES_PER_BLOB;
-    return cells_pass_enqueue(ctx, d_blobs, m, d_cells, d_status + base, out_cells + base * KZG_BYTES_PER_CELL_SET, hc.st);
-  });
-  rc = hc.close(rc);
-  if (rc) return rc;
-  cells_first_halves(blobs, n, status, out_cells);
-  return 0;
-}
-
-extern "C" int32_t kzg_compute_cells_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status) try {
-  if (!ctx || (n && (!blobs || !out_cells || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
-    return cells_host(m, blobs + first * (size_t)KZG_BYTES_PER_BLOB, count, out_cells + first * KZG_BYTES_PER_CELL_SET, status + first);
-  });
-} catch (...) {
-  return abi_exception();
-}
-
-// ---------------------------------------------------------------------------
-// recover_cells (EIP-7594): the absent cells of every cell set
-// ---------------------------------------------------------------------------
-// One launch shaped like compute_cells'.  The kernel writes every output byte and every status.
 static int32_t recover_enqueue(const kzg_ctx* ctx, const uint8_t* d_cells, const uint8_t* d_present, uint64_t n, uint8_t* d_out_cells, int32_t* d_status,
                                hipStream_t st) {
   const unsigned grid = (unsigned)std::min<uint64_t>(n, ctx->num_cus);
@@ -432,53 +350,14 @@ static int32_t recover_enqueue(const kzg_ctx* ctx, const uint8_t* d_cells, const
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "recover_cells launch failed");
   return 0;
 }
-
-extern "C" int32_t kzg_recover_cells_batch_dev(const kzg_ctx* ctx, const void* d_cells, const void* d_present, uint64_t n, void* d_out_cells, void* d_status,
-                                               void* hip_stream) try {
-  if (!ctx || (n && (!d_cells || !d_present || !d_out_cells || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(ctx->device));
-  return recover_enqueue(ctx, (const uint8_t*)d_cells, (const uint8_t*)d_present, n, (uint8_t*)d_out_cells, (int32_t*)d_status, (hipStream_t)hip_stream);
-} catch (...) {
-  return abi_exception();
+static int32_t cells_of(const kzg_ctx* ctx, const CellCall& d, uint64_t n, hipStream_t st) {
+  return d.present ? recover_enqueue(ctx, d.in, d.present, n, d.out_cells, d.status, st) : cells_enqueue(ctx, d.in, n, d.out_cells, d.status, st);
 }
 
-// Host-buffer form: whole cell sets up and whole cell sets down (256 KiB each way per item), in passes of KATETH_AMD_CELLS_PASS items
-// (default 256) through the staging ring; a slot holds a pass's input and, behind it, its output.  The masks of the whole call go up
-// once, next to the statuses.
-int32_t recover_host(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status) {
-  if (n == 0) return 0;
-  HostCall hc(ctx);
-  const int a_mask = hc.upload(present, n * 16), a_st = hc.download(status, n * sizeof(int32_t));
-  int32_t rc = hc.open(even_plan(n, ctx->knobs.cells_pass ? ctx->knobs.cells_pass : 256), 2 * KZG_BYTES_PER_CELL_SET);
-  if (rc) return rc;
-  const uint8_t* d_present = hc.dev(a_mask);
-  int32_t* d_status = hc.dev<int32_t>(a_st);
-  rc = hc.passes(cells, KZG_BYTES_PER_CELL_SET, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_cells) {
-    uint8_t* d_out = d_cells + hc.max_pass * KZG_BYTES_PER_CELL_SET;
-    const int32_t e = recover_enqueue(ctx, d_cells, d_present + base * 16, m, d_out, d_status + base, hc.st);
-    if (e == 0 && hipMemcpyAsync(out_cells + base * KZG_BYTES_PER_CELL_SET, d_out, m * KZG_BYTES_PER_CELL_SET, hipMemcpyDeviceToHost, hc.st) != hipSuccess)
-      return fail(KZG_FAIL_HIP, "device-to-host copy failed");
-    return e;
-  });
-  return hc.close(rc);
-}
-
-extern "C" int32_t kzg_recover_cells_batch(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status) try {
-  if (!ctx || (n && (!cells || !present || !out_cells || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
-    return recover_host(m, cells + first * KZG_BYTES_PER_CELL_SET, present + first * 16, count, out_cells + first * KZG_BYTES_PER_CELL_SET, status + first);
-  });
-} catch (...) {
-  return abi_exception();
-}
-
-// ---------------------------------------------------------------------------
-// cell proofs (EIP-7594): compute_cells_and_kzg_proofs, recover_cells_and_kzg_proofs -- by quotient MSMs, not FK20
-// ---------------------------------------------------------------------------
-// The proof of cell k is the commitment of q_k = p / (X^64 - z_k) (cellproof_math.cuh): 128 scalar vectors per blob, which the
-// fixed-base MSM commits as it commits blobs.  The omega_128 table the division reads is built by the context's FIRST cell-proof call, as
-// the monomial points are (ensure_g1_monomial): a context that never asks for cell proofs launches and holds nothing for them.
+// Cell proofs -- by quotient MSMs, not FK20.  The proof of cell k is the commitment of q_k = p / (X^64 - z_k) (cellproof_math.cuh): 128 scalar
+// vectors per blob, which the fixed-base MSM commits as it commits blobs.  The omega_128 table the division reads is built by the context's
+// FIRST cell-proof call, as the monomial points are (ensure_g1_monomial): a context that never asks for cell proofs launches and holds nothing
+// for them.
 static int32_t ensure_cellproof_tab(const kzg_ctx* ctx) {
   if (ctx->cellproof_ready.load(std::memory_order_acquire)) return 0;
   std::lock_guard<std::mutex> guard(ctx->cellproof_mu);
@@ -504,20 +383,17 @@ static int32_t ensure_cellproof_tab(const kzg_ctx* ctx) {
 static uint64_t cellproof_pass(const kzg_ctx* ctx) { return std::min<uint64_t>(ctx->knobs.cellproof_pass ? ctx->knobs.cellproof_pass : 32, 128); }
 // workspace of a pass of m blobs: their coefficients, the 128 m vector statuses and quotient vectors, and one set of MSM buffers
 struct CellProofLayout {
-  uint32_t splits = 1;
-  size_t o_coeff = 0, o_vst = 0, o_q = 0, o_part = 0, o_sum = 0, o_msm = 0, total = 0;
+  size_t o_coeff = 0, o_vst = 0, o_q = 0, total = 0;
+  MsmBufs msm;
 };
 static CellProofLayout cellproof_layout(const kzg_ctx* ctx, uint64_t m) {
   CellProofLayout L;
   const uint64_t vectors = m * KZG_CELLS_PER_EXT_BLOB;
-  L.splits = choose_splits(ctx, vectors);
   Carve ws;
   L.o_coeff = ws.take(m * (size_t)CELLPROOF_COEFF_BYTES);
   L.o_vst = ws.take(vectors * sizeof(int32_t));
   L.o_q = ws.take(vectors * 4096 * sizeof(fr_t));
-  L.o_part = ws.take(vectors * L.splits * 65 * sizeof(g1_xyzz));  // 64 lane sums + 1 unit sum per (vector, split)
-  L.o_sum = ws.take(vectors * sizeof(g1_xyzz));
-  L.o_msm = ws.take(msm_scratch_bytes(ctx, vectors));
+  L.msm = msm_carve(ctx, ws, vectors);
   L.total = ws.off;
   return L;
 }
@@ -550,135 +426,164 @@ static int32_t cellproof_dev_locked(const kzg_ctx* ctx, const uint8_t* d_items, 
                          skip_rejected, ctx->d_cells_tab, coeffs, d_status + base, vstatus);
       hipLaunchKernelGGL(k_cell_quotients, dim3((unsigned)vectors), dim3(CELLS_THREADS), 0, st, coeffs, ctx->d_cells_tab, ctx->d_cellproof_tab, vstatus, q);
     }
-    rc = msm_pipeline(ctx, false, reinterpret_cast<const uint8_t*>(q), vectors, d_out_proofs48 + base * (KZG_CELLS_PER_EXT_BLOB * 48), nullptr, vstatus,
-                      reinterpret_cast<g1_xyzz*>(ws + L.o_part), reinterpret_cast<g1_xyzz*>(ws + L.o_sum), L.splits, ws + L.o_msm, st);
+    rc = msm_pipeline(ctx, false, reinterpret_cast<const uint8_t*>(q), vectors, d_out_proofs48 + base * (KZG_CELLS_PER_EXT_BLOB * 48), nullptr, vstatus, L.msm, ws,
+                      st);
     if (rc) return rc;
   }
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "cell-proof pipeline launch failed");
   return 0;
 }
 
-// the device calls: the cells by the existing kernel, launched first, then the proofs under a workspace slot
-static int32_t cellproof_dev_call(const kzg_ctx* ctx, const uint8_t* d_items, uint64_t stride, bool skip_rejected, uint64_t n, uint8_t* d_out_proofs48,
-                                  int32_t* d_status, hipStream_t st) {
-  std::lock_guard<std::mutex> guard(ctx->lock);
-  WsCall ws(ctx, st);
-  int32_t rc = ws.begin();
-  if (rc == 0) rc = cellproof_dev_locked(ctx, d_items, stride, skip_rejected, n, d_out_proofs48, d_status, st);
-  if (rc == 0) rc = ws.end();
+// What the two sources of a cell call differ in.  With proofs, either takes passes of cellproof_pass items instead of `cells_pass`, and
+// a staging slot holds a pass's input and, where cells are wanted, its cell sets behind it.
+struct CellSource {
+  // bytes per item up to the device
+  size_t up_bytes;
+  // items per pass of a call without proofs (KATETH_AMD_CELLS_PASS overrides)
+  uint64_t cells_pass;
+  // true: only cells 64..127 come down and, once the statuses are on the host, cells_first_halves fills cells 0..63;
+  // false: the whole cell set comes down
+  bool ext_half_down;
+  // what the proof kernels read.  false: the input, a blob they range-check themselves (stride up_bytes, skip_rejected = false);
+  // true: cells 0..63 of the item's own output, under the cells kernel's verdict (stride 262,144, skip_rejected = true)
+  bool proofs_of_own_cells;
+};
+// compute: PCIe is the limit (128 KiB up and 256 KiB down per blob), so only the extension half comes back: cells 0..63 of an
+// accepted blob ARE the caller's blob and are copied on the host.  recover: whole cell sets both ways, 256 KiB each per item.
+constexpr CellSource CELLS_OF_BLOBS{KZG_BYTES_PER_BLOB, 512, true, false};
+constexpr CellSource CELLS_OF_CELL_SETS{KZG_BYTES_PER_CELL_SET, 256, false, true};
+static const CellSource& cell_source(const CellCall& c) { return c.present ? CELLS_OF_CELL_SETS : CELLS_OF_BLOBS; }
+// the proofs of n device-resident items whose cells kernel has been enqueued; the caller holds a workspace (with_workspace)
+static int32_t cellproofs_locked(const kzg_ctx* ctx, const CellCall& d, uint64_t n, hipStream_t st) {
+  const CellSource& src = cell_source(d);
+  return cellproof_dev_locked(ctx, src.proofs_of_own_cells ? d.out_cells : d.in, src.proofs_of_own_cells ? KZG_BYTES_PER_CELL_SET : src.up_bytes,
+                              src.proofs_of_own_cells, n, d.out_proofs48, d.status, st);
+}
+
+// The device-resident cell call: the cells by their kernel, launched first and outside the lock, then the proofs under a workspace slot.
+int32_t das_dev(const kzg_ctx* ctx, const CellCall& d, uint64_t n, hipStream_t st) {
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  int32_t rc = d.out_proofs48 ? ensure_cellproof_tab(ctx) : 0;
+  if (rc == 0 && d.out_cells) rc = cells_of(ctx, d, n, st);
+  if (rc == 0 && d.out_proofs48) rc = with_workspace(ctx, st, [&] { return cellproofs_locked(ctx, d, n, st); });
   return rc;
+}
+
+// cells 0..63 of every item of a compute call: the caller's blob, or zero bytes
+static void cells_first_halves(const uint8_t* blobs, uint64_t n, const int32_t* status, uint8_t* out_cells) {
+  for (uint64_t i = 0; i < n; i++) {
+    if (status[i] == 0)
+      memcpy(out_cells + i * KZG_BYTES_PER_CELL_SET, blobs + i * (size_t)KZG_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB);
+    else
+      memset(out_cells + i * KZG_BYTES_PER_CELL_SET, 0, KZG_BYTES_PER_BLOB);
+  }
+}
+// The host-buffer cell call.  The input crosses PCIe in passes through the staging ring.  The masks of the whole call go up once, and
+// the proofs (6 KiB per item) and the statuses come down once, through the host-i/o pool.  A pass's cells come down behind its kernel,
+// and its slot is free again behind all the pass enqueued.  With proofs a staging pass is a pass of the device path (about 28 ms of
+// MSM each at the default of 32, so a pass's copy hides behind its predecessor), and one workspace slot serves all passes, sized
+// before anything is in flight.
+int32_t das_host(const kzg_ctx* ctx, const CellCall& c, uint64_t n) {
+  if (n == 0) return 0;
+  const CellSource& src = cell_source(c);
+  const bool proofs = c.out_proofs48 != nullptr;
+  int32_t rc = proofs ? ensure_cellproof_tab(ctx) : 0;
+  if (rc) return rc;
+  HostCall hc(ctx);
+  const int a_mask = hc.upload(c.present, n * 16), a_prf = hc.download(c.out_proofs48, n * (KZG_CELLS_PER_EXT_BLOB * 48)),
+            a_st = hc.download(c.status, n * sizeof(int32_t));
+  const uint64_t pass = proofs ? cellproof_pass(ctx) : ctx->knobs.cells_pass ? ctx->knobs.cells_pass : src.cells_pass;
+  rc = hc.open(even_plan(n, pass), src.up_bytes + (c.out_cells ? KZG_BYTES_PER_CELL_SET : 0));
+  if (rc) return rc;
+  const uint8_t* d_present = hc.dev(a_mask);  // resolved after open(): opening may move the pools
+  uint8_t* d_prf = hc.dev(a_prf);
+  int32_t* d_status = hc.dev<int32_t>(a_st);
+  auto enqueue = [&] {
+    return hc.passes(c.in, src.up_bytes, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_in) {
+      const CellCall d{d_in, d_present ? d_present + base * 16 : nullptr, c.out_cells ? d_in + hc.max_pass * src.up_bytes : nullptr,
+                       d_prf ? d_prf + base * (KZG_CELLS_PER_EXT_BLOB * 48) : nullptr, d_status + base};
+      if (d.out_cells) {
+        const int32_t e = cells_of(ctx, d, m, hc.st);
+        if (e) return e;
+        uint8_t* out = c.out_cells + base * KZG_BYTES_PER_CELL_SET;
+        const hipError_t down = src.ext_half_down ? hipMemcpy2DAsync(out + KZG_BYTES_PER_BLOB, KZG_BYTES_PER_CELL_SET, d.out_cells + KZG_BYTES_PER_BLOB,
+                                                                     KZG_BYTES_PER_CELL_SET, KZG_BYTES_PER_BLOB, m, hipMemcpyDeviceToHost, hc.st)
+                                                  : hipMemcpyAsync(out, d.out_cells, m * KZG_BYTES_PER_CELL_SET, hipMemcpyDeviceToHost, hc.st);
+        if (down != hipSuccess) return fail(KZG_FAIL_HIP, "device-to-host copy failed");
+      }
+      return proofs ? cellproofs_locked(ctx, d, m, hc.st) : 0;
+    });
+  };
+  if (proofs)
+    rc = with_workspace(ctx, hc.st, [&] {
+      const int32_t e = ws_reserve(ctx, cellproof_ws_bytes(ctx, n), hc.st);
+      return e ? e : enqueue();
+    });
+  else
+    rc = enqueue();
+  rc = hc.close(rc);
+  if (rc == 0 && src.ext_half_down && c.out_cells) cells_first_halves(c.in, n, c.status, c.out_cells);
+  return rc;
+}
+
+// The eight entry points: each states which of its arguments may be null (out_cells, and only where proofs are computed from blobs)
+static int32_t das_on_members(const kzg_ctx* ctx, const CellCall& call, uint64_t n) {
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) { return das_host(m, call.advanced(first), count); });
+}
+static CellCall cell_call(const void* in, const void* present, void* out_cells, void* out_proofs48, void* status) {
+  return CellCall{(const uint8_t*)in, (const uint8_t*)present, (uint8_t*)out_cells, (uint8_t*)out_proofs48, (int32_t*)status};
+}
+extern "C" int32_t kzg_compute_cells_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_cells, void* d_status, void* hip_stream) try {
+  if (!ctx || (n && (!d_blobs || !d_out_cells || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return das_dev(ctx, cell_call(d_blobs, nullptr, d_out_cells, nullptr, d_status), n, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_compute_cells_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, int32_t* status) try {
+  if (!ctx || (n && (!blobs || !out_cells || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return das_on_members(ctx, cell_call(blobs, nullptr, out_cells, nullptr, status), n);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_recover_cells_batch_dev(const kzg_ctx* ctx, const void* d_cells, const void* d_present, uint64_t n, void* d_out_cells, void* d_status,
+                                               void* hip_stream) try {
+  if (!ctx || (n && (!d_cells || !d_present || !d_out_cells || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return das_dev(ctx, cell_call(d_cells, d_present, d_out_cells, nullptr, d_status), n, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_recover_cells_batch(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, int32_t* status) try {
+  if (!ctx || (n && (!cells || !present || !out_cells || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return das_on_members(ctx, cell_call(cells, present, out_cells, nullptr, status), n);
+} catch (...) {
+  return abi_exception();
 }
 extern "C" int32_t kzg_compute_cells_and_proofs_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_cells, void* d_out_proofs48, void* d_status,
                                                           void* hip_stream) try {
   if (!ctx || (n && (!d_blobs || !d_out_proofs48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(ctx->device));
-  int32_t rc = ensure_cellproof_tab(ctx);
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (rc == 0 && d_out_cells) rc = cells_enqueue(ctx, (const uint8_t*)d_blobs, n, (uint8_t*)d_out_cells, (int32_t*)d_status, st);
-  if (rc == 0) rc = cellproof_dev_call(ctx, (const uint8_t*)d_blobs, KZG_BYTES_PER_BLOB, false, n, (uint8_t*)d_out_proofs48, (int32_t*)d_status, st);
-  return rc;
+  return das_dev(ctx, cell_call(d_blobs, nullptr, d_out_cells, d_out_proofs48, d_status), n, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_compute_cells_and_proofs_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, uint8_t* out_proofs48,
+                                                      int32_t* status) try {
+  if (!ctx || (n && (!blobs || !out_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return das_on_members(ctx, cell_call(blobs, nullptr, out_cells, out_proofs48, status), n);
 } catch (...) {
   return abi_exception();
 }
 extern "C" int32_t kzg_recover_cells_and_proofs_batch_dev(const kzg_ctx* ctx, const void* d_cells, const void* d_present, uint64_t n, void* d_out_cells,
                                                           void* d_out_proofs48, void* d_status, void* hip_stream) try {
   if (!ctx || (n && (!d_cells || !d_present || !d_out_cells || !d_out_proofs48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(ctx->device));
-  int32_t rc = ensure_cellproof_tab(ctx);
-  hipStream_t st = (hipStream_t)hip_stream;
-  if (rc == 0) rc = recover_enqueue(ctx, (const uint8_t*)d_cells, (const uint8_t*)d_present, n, (uint8_t*)d_out_cells, (int32_t*)d_status, st);
-  // a recovered item's blob is cells 0..63 of its own output
-  if (rc == 0) rc = cellproof_dev_call(ctx, (const uint8_t*)d_out_cells, KZG_BYTES_PER_CELL_SET, true, n, (uint8_t*)d_out_proofs48, (int32_t*)d_status, st);
-  return rc;
-} catch (...) {
-  return abi_exception();
-}
-
-// Host-buffer forms, after cells_host and recover_host: a staging pass is a pass of the device path (KATETH_AMD_CELLPROOF_PASS items,
-// default 32 -- about 28 ms of MSM each, so the pass's copy hides behind its predecessor).  Up: the blobs, or the cell sets and masks.
-// Down: the extension half (compute; cells 0..63 are the caller's blob) or the whole cell set (recovery), and 6 KiB of proofs per item.
-// One workspace slot for all passes, sized before anything is in flight.
-int32_t cellproofs_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, uint8_t* out_proofs48, int32_t* status) {
-  if (n == 0) return 0;
-  int32_t rc = ensure_cellproof_tab(ctx);
-  if (rc) return rc;
-  HostCall hc(ctx);
-  const int a_prf = hc.download(out_proofs48, n * (KZG_CELLS_PER_EXT_BLOB * 48)), a_st = hc.download(status, n * sizeof(int32_t));
-  rc = hc.open(even_plan(n, cellproof_pass(ctx)), KZG_BYTES_PER_BLOB + (out_cells ? KZG_BYTES_PER_CELL_SET : 0));
-  if (rc) return rc;
-  uint8_t* d_prf = hc.dev(a_prf);
-  int32_t* d_status = hc.dev<int32_t>(a_st);
-  {
-    std::lock_guard<std::mutex> guard(ctx->lock);
-    WsCall ws(ctx, hc.st);
-    rc = ws.begin();
-    if (rc == 0) rc = ws_reserve(ctx, cellproof_ws_bytes(ctx, n), hc.st);
-    if (rc == 0)
-      rc = hc.passes(blobs, KZG_BYTES_PER_BLOB, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_blobs) {
-        int32_t e = 0;
-        if (out_cells)
-          e = cells_pass_enqueue(ctx, d_blobs, m, d_blobs + hc.max_pass * (size_t)KZG_BYTES_PER_BLOB, d_status + base, out_cells + base * KZG_BYTES_PER_CELL_SET, hc.st);
-        if (e == 0) e = cellproof_dev_locked(ctx, d_blobs, KZG_BYTES_PER_BLOB, false, m, d_prf + base * (KZG_CELLS_PER_EXT_BLOB * 48), d_status + base, hc.st);
-        return e;
-      });
-    if (rc == 0) rc = ws.end();
-  }
-  rc = hc.close(rc);
-  if (rc) return rc;
-  if (out_cells) cells_first_halves(blobs, n, status, out_cells);
-  return 0;
-}
-int32_t recover_proofs_host(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells, uint8_t* out_proofs48,
-                            int32_t* status) {
-  if (n == 0) return 0;
-  int32_t rc = ensure_cellproof_tab(ctx);
-  if (rc) return rc;
-  HostCall hc(ctx);
-  const int a_mask = hc.upload(present, n * 16), a_prf = hc.download(out_proofs48, n * (KZG_CELLS_PER_EXT_BLOB * 48)),
-            a_st = hc.download(status, n * sizeof(int32_t));
-  rc = hc.open(even_plan(n, cellproof_pass(ctx)), 2 * KZG_BYTES_PER_CELL_SET);
-  if (rc) return rc;
-  const uint8_t* d_present = hc.dev(a_mask);
-  uint8_t* d_prf = hc.dev(a_prf);
-  int32_t* d_status = hc.dev<int32_t>(a_st);
-  {
-    std::lock_guard<std::mutex> guard(ctx->lock);
-    WsCall ws(ctx, hc.st);
-    rc = ws.begin();
-    if (rc == 0) rc = ws_reserve(ctx, cellproof_ws_bytes(ctx, n), hc.st);
-    if (rc == 0)
-      rc = hc.passes(cells, KZG_BYTES_PER_CELL_SET, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_cells) {
-        uint8_t* d_out = d_cells + hc.max_pass * KZG_BYTES_PER_CELL_SET;
-        int32_t e = recover_enqueue(ctx, d_cells, d_present + base * 16, m, d_out, d_status + base, hc.st);
-        if (e == 0 && hipMemcpyAsync(out_cells + base * KZG_BYTES_PER_CELL_SET, d_out, m * KZG_BYTES_PER_CELL_SET, hipMemcpyDeviceToHost, hc.st) != hipSuccess)
-          return fail(KZG_FAIL_HIP, "device-to-host copy failed");
-        if (e == 0) e = cellproof_dev_locked(ctx, d_out, KZG_BYTES_PER_CELL_SET, true, m, d_prf + base * (KZG_CELLS_PER_EXT_BLOB * 48), d_status + base, hc.st);
-        return e;
-      });
-    if (rc == 0) rc = ws.end();
-  }
-  return hc.close(rc);
-}
-
-extern "C" int32_t kzg_compute_cells_and_proofs_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_cells, uint8_t* out_proofs48,
-                                                      int32_t* status) try {
-  if (!ctx || (n && (!blobs || !out_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
-    return cellproofs_host(m, blobs + first * (size_t)KZG_BYTES_PER_BLOB, count, out_cells ? out_cells + first * KZG_BYTES_PER_CELL_SET : nullptr,
-                           out_proofs48 + first * (KZG_CELLS_PER_EXT_BLOB * 48), status + first);
-  });
+  return das_dev(ctx, cell_call(d_cells, d_present, d_out_cells, d_out_proofs48, d_status), n, (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }
 extern "C" int32_t kzg_recover_cells_and_proofs_batch(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, uint64_t n, uint8_t* out_cells,
                                                       uint8_t* out_proofs48, int32_t* status) try {
   if (!ctx || (n && (!cells || !present || !out_cells || !out_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) {
-    return recover_proofs_host(m, cells + first * KZG_BYTES_PER_CELL_SET, present + first * 16, count, out_cells + first * KZG_BYTES_PER_CELL_SET,
-                               out_proofs48 + first * (KZG_CELLS_PER_EXT_BLOB * 48), status + first);
-  });
+  return das_on_members(ctx, cell_call(cells, present, out_cells, out_proofs48, status), n);
 } catch (...) {
   return abi_exception();
 }

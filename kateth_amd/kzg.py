@@ -579,6 +579,15 @@ class Setup:
             raise EngineError("%s returned %d" % (what, rc))
         return [bool(b) for b in ok_each.raw[:n]], list(status[:n]), bool(ok.value)
 
+    def _produce(self, what: str, inputs, n: int, out_bytes):
+        """a host-buffer producer call `what`(handle, *inputs, n, *outputs, status) -> (output, ..., [status]).  `out_bytes`: bytes per item of
+        every output, None for one the caller does not want (a null pointer goes down, None comes back)"""
+        outs = [None if b is None else ctypes.create_string_buffer(b * n) for b in out_bytes]
+        status = (ctypes.c_int32 * n)()
+        rc = getattr(self._lib, what)(self._h, *inputs, n, *[None if o is None else ctypes.cast(o, ctypes.c_void_p) for o in outs], status)
+        self._check(rc, what)
+        return tuple(None if o is None else o.raw for o in outs) + (list(status),)
+
     @staticmethod
     def _host_args(*buffers):
         """contiguous host inputs: bytes-like objects, or raw host addresses (ints) passed through"""
@@ -600,22 +609,14 @@ class Setup:
         n = len(blobs) // BYTES_PER_BLOB if n is None else n
         if len(blobs) != n * BYTES_PER_BLOB:
             raise BlobError("InvalidLen")
-        out = ctypes.create_string_buffer(48 * n)
-        status = (ctypes.c_int32 * n)()
-        rc = self._lib.kzg_blob_to_commitment_batch(self._h, blobs, n, ctypes.cast(out, ctypes.c_void_p), status)
-        self._check(rc, "kzg_blob_to_commitment_batch")
-        return out.raw, list(status)
+        return self._produce("kzg_blob_to_commitment_batch", [blobs], n, [48])
 
     def compute_blob_proof_batch(self, blobs: bytes, commitments: bytes):
         blobs, commitments = _buf(blobs), _buf(commitments)
         n = len(commitments) // 48
         if len(blobs) != n * BYTES_PER_BLOB or len(commitments) != 48 * n:
             raise BlobError("InvalidLen")
-        out = ctypes.create_string_buffer(48 * n)
-        status = (ctypes.c_int32 * n)()
-        rc = self._lib.kzg_compute_blob_proof_batch(self._h, blobs, commitments, n, ctypes.cast(out, ctypes.c_void_p), status)
-        self._check(rc, "kzg_compute_blob_proof_batch")
-        return out.raw, list(status)
+        return self._produce("kzg_compute_blob_proof_batch", [blobs, commitments], n, [48])
 
     def blob_sidecar_batch(self, blobs: bytes, n: Optional[int] = None):
         """n concatenated blobs -> (n*48 bytes of commitments, n*48 bytes of blob proofs, n*32 bytes of versioned hashes, [status]):
@@ -624,12 +625,7 @@ class Setup:
         n = len(blobs) // BYTES_PER_BLOB if n is None else n
         if len(blobs) != n * BYTES_PER_BLOB:
             raise BlobError("InvalidLen")
-        coms, proofs, hashes = ctypes.create_string_buffer(48 * n), ctypes.create_string_buffer(48 * n), ctypes.create_string_buffer(32 * n)
-        status = (ctypes.c_int32 * n)()
-        rc = self._lib.kzg_blob_sidecar_batch(self._h, blobs, n, ctypes.cast(coms, ctypes.c_void_p), ctypes.cast(proofs, ctypes.c_void_p),
-                                              ctypes.cast(hashes, ctypes.c_void_p), status)
-        self._check(rc, "kzg_blob_sidecar_batch")
-        return coms.raw, proofs.raw, hashes.raw, list(status)
+        return self._produce("kzg_blob_sidecar_batch", [blobs], n, [48, 48, 32])
 
     def compute_cells_batch(self, blobs: bytes, n: Optional[int] = None):
         """n concatenated blobs -> (n * 128 * 2048 bytes of cells, [status]): EIP-7594's `compute_cells` per blob.  Cells 0..63 of an
@@ -638,11 +634,7 @@ class Setup:
         n = len(blobs) // BYTES_PER_BLOB if n is None else n
         if len(blobs) != n * BYTES_PER_BLOB:
             raise BlobError("InvalidLen")
-        out = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * n)
-        status = (ctypes.c_int32 * n)()
-        rc = self._lib.kzg_compute_cells_batch(self._h, blobs, n, ctypes.cast(out, ctypes.c_void_p), status)
-        self._check(rc, "kzg_compute_cells_batch")
-        return out.raw, list(status)
+        return self._produce("kzg_compute_cells_batch", [blobs], n, [CELLS_PER_EXT_BLOB * BYTES_PER_CELL])
 
     def recover_cells_batch(self, cells: bytes, present: bytes, n: Optional[int] = None):
         """n cell sets (128 * 2048 bytes each, laid out like `compute_cells_batch`'s output) and n 16-byte masks (cell c present iff bit
@@ -653,11 +645,7 @@ class Setup:
         n = len(present) // 16 if n is None else n
         if len(cells) != n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL or len(present) != n * 16:
             raise ValueError("recover_cells_batch: n * 262144 bytes of cells and n * 16 bytes of mask")
-        out = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * n)
-        status = (ctypes.c_int32 * n)()
-        rc = self._lib.kzg_recover_cells_batch(self._h, cells, present, n, ctypes.cast(out, ctypes.c_void_p), status)
-        self._check(rc, "kzg_recover_cells_batch")
-        return out.raw, list(status)
+        return self._produce("kzg_recover_cells_batch", [cells, present], n, [CELLS_PER_EXT_BLOB * BYTES_PER_CELL])
 
     def compute_cells_and_proofs_batch(self, blobs: bytes, n: Optional[int] = None, want_cells: bool = True):
         """n concatenated blobs -> (n * 128 * 2048 bytes of cells, or None without `want_cells`; n * 128 * 48 bytes of cell proofs;
@@ -667,13 +655,8 @@ class Setup:
         n = len(blobs) // BYTES_PER_BLOB if n is None else n
         if len(blobs) != n * BYTES_PER_BLOB:
             raise BlobError("InvalidLen")
-        cells = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * n) if want_cells else None
-        proofs = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * 48 * n)
-        status = (ctypes.c_int32 * n)()
-        rc = self._lib.kzg_compute_cells_and_proofs_batch(self._h, blobs, n, ctypes.cast(cells, ctypes.c_void_p) if want_cells else None,
-                                                          ctypes.cast(proofs, ctypes.c_void_p), status)
-        self._check(rc, "kzg_compute_cells_and_proofs_batch")
-        return (cells.raw if want_cells else None), proofs.raw, list(status)
+        return self._produce("kzg_compute_cells_and_proofs_batch", [blobs], n,
+                             [CELLS_PER_EXT_BLOB * BYTES_PER_CELL if want_cells else None, CELLS_PER_EXT_BLOB * 48])
 
     def recover_cells_and_proofs_batch(self, cells: bytes, present: bytes, n: Optional[int] = None):
         """`recover_cells_batch` with the 128 cell proofs of every item: -> (n * 128 * 2048 bytes of cells, n * 128 * 48 bytes of proofs,
@@ -682,25 +665,14 @@ class Setup:
         n = len(present) // 16 if n is None else n
         if len(cells) != n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL or len(present) != n * 16:
             raise ValueError("recover_cells_and_proofs_batch: n * 262144 bytes of cells and n * 16 bytes of mask")
-        out = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * n)
-        proofs = ctypes.create_string_buffer(CELLS_PER_EXT_BLOB * 48 * n)
-        status = (ctypes.c_int32 * n)()
-        rc = self._lib.kzg_recover_cells_and_proofs_batch(self._h, cells, present, n, ctypes.cast(out, ctypes.c_void_p),
-                                                          ctypes.cast(proofs, ctypes.c_void_p), status)
-        self._check(rc, "kzg_recover_cells_and_proofs_batch")
-        return out.raw, proofs.raw, list(status)
+        return self._produce("kzg_recover_cells_and_proofs_batch", [cells, present], n, [CELLS_PER_EXT_BLOB * BYTES_PER_CELL, CELLS_PER_EXT_BLOB * 48])
 
     def compute_proof_batch(self, blobs: bytes, zs: bytes):
         blobs, zs = _buf(blobs), _buf(zs)
         n = len(zs) // 32
         if len(blobs) != n * BYTES_PER_BLOB:
             raise BlobError("InvalidLen")
-        proofs = ctypes.create_string_buffer(48 * n)
-        ys = ctypes.create_string_buffer(32 * n)
-        status = (ctypes.c_int32 * n)()
-        rc = self._lib.kzg_compute_proof_batch(self._h, blobs, zs, n, ctypes.cast(proofs, ctypes.c_void_p), ctypes.cast(ys, ctypes.c_void_p), status)
-        self._check(rc, "kzg_compute_proof_batch")
-        return proofs.raw, ys.raw, list(status)
+        return self._produce("kzg_compute_proof_batch", [blobs, zs], n, [48, 32])
 
     # -- the same producers returning POINTS (`Commitment = Proof = P1`, src/kzg/mod.rs:9-10) as 96-byte blst_p1_affine images
     def blob_to_commitment_batch_affine(self, blobs: bytes, n: Optional[int] = None):
@@ -708,32 +680,21 @@ class Setup:
         n = len(blobs) // BYTES_PER_BLOB if n is None else n
         if len(blobs) != n * BYTES_PER_BLOB:
             raise BlobError("InvalidLen")
-        out = ctypes.create_string_buffer(96 * n)
-        status = (ctypes.c_int32 * n)()
-        self._check(self._lib.kzg_blob_to_commitment_batch_affine(self._h, blobs, n, ctypes.cast(out, ctypes.c_void_p), status), "kzg_blob_to_commitment_batch_affine")
-        return out.raw, list(status)
+        return self._produce("kzg_blob_to_commitment_batch_affine", [blobs], n, [96])
 
     def compute_blob_proof_batch_affine(self, blobs: bytes, commitments: bytes):
         blobs, commitments = _buf(blobs), _buf(commitments)
         n = len(commitments) // 48
         if len(blobs) != n * BYTES_PER_BLOB or len(commitments) != 48 * n:
             raise BlobError("InvalidLen")
-        out = ctypes.create_string_buffer(96 * n)
-        status = (ctypes.c_int32 * n)()
-        self._check(self._lib.kzg_compute_blob_proof_batch_affine(self._h, blobs, commitments, n, ctypes.cast(out, ctypes.c_void_p), status), "kzg_compute_blob_proof_batch_affine")
-        return out.raw, list(status)
+        return self._produce("kzg_compute_blob_proof_batch_affine", [blobs, commitments], n, [96])
 
     def compute_proof_batch_affine(self, blobs: bytes, zs: bytes):
         blobs, zs = _buf(blobs), _buf(zs)
         n = len(zs) // 32
         if len(blobs) != n * BYTES_PER_BLOB:
             raise BlobError("InvalidLen")
-        proofs = ctypes.create_string_buffer(96 * n)
-        ys = ctypes.create_string_buffer(32 * n)
-        status = (ctypes.c_int32 * n)()
-        rc = self._lib.kzg_compute_proof_batch_affine(self._h, blobs, zs, n, ctypes.cast(proofs, ctypes.c_void_p), ctypes.cast(ys, ctypes.c_void_p), status)
-        self._check(rc, "kzg_compute_proof_batch_affine")
-        return proofs.raw, ys.raw, list(status)
+        return self._produce("kzg_compute_proof_batch_affine", [blobs, zs], n, [96, 32])
 
     # -- reference-shaped API ----------------------------------------------------
     # `Setup::blob_to_commitment / blob_proof / proof` with the reference's return type (a point), for call sites shaped

@@ -213,15 +213,42 @@ def test_passes_of_two(engine, torch_cuda, three, monkeypatch):
     assert engine.compute_cells_and_proofs_batch(batch) == want  # one pass
 
 
+def _recovery_batch(three):
+    """three items -- 64 cells missing, 65 missing (63 present: status 8), none missing -- their masks and the expected result"""
+    full = three["cells"]
+    masks = [rm.mask_of(rm.random_missing(64, 64)), rm.mask_of(rm.random_missing(65, 65)), rm.mask_of([])]
+    batch = b"".join(rm.knock_out(full[i], masks[i]) for i in range(3))
+    want = (full[0] + bytes(SET) + full[2], three["proofs"][0] + bytes(PROOFS) + three["proofs"][2], [0, 8, 0])
+    return batch, b"".join(masks), want
+
+
+def test_recovery_passes_of_two(engine, torch_cuda, three, monkeypatch):
+    """KATETH_AMD_CELLPROOF_PASS=2 at n = 3: a full pass and a ragged one, a rejected item in the first"""
+    import kateth_amd
+
+    batch, masks, want = _recovery_batch(three)
+    monkeypatch.setenv("KATETH_AMD_CELLPROOF_PASS", "2")  # read once, at kzg_ctx_create
+    e2 = kateth_amd.Setup.load_json(TRUSTED_SETUP, window_bits=8)
+    try:
+        assert e2.recover_cells_and_proofs_batch(batch, masks) == want
+        assert recover_dev(torch_cuda, e2, batch, masks) == want
+    finally:
+        e2.close()
+    assert engine.recover_cells_and_proofs_batch(batch, masks) == want  # one pass
+    assert recover_dev(torch_cuda, engine, batch, masks) == want
+
+
 def test_group_context_shares(engine, torch_cuda, three):
     import kateth_amd
 
     blobs = b"".join(three["blobs"])
     want = (three["out_cells"], b"".join(three["proofs"]), [0, 0, 0])
+    batch, masks, want_recovered = _recovery_batch(three)
     group = kateth_amd.Setup.load_json(TRUSTED_SETUP, window_bits=8, devices=[0, 0])
     try:
         assert group.compute_cells_and_proofs_batch(blobs) == want
         assert compute_dev(torch_cuda, group, blobs) == want  # the _dev call acts on member 0
+        assert group.recover_cells_and_proofs_batch(batch, masks) == engine.recover_cells_and_proofs_batch(batch, masks) == want_recovered
     finally:
         group.close()
 

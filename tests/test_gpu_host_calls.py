@@ -1,4 +1,4 @@
-"""The seven host-buffer producer calls run through one driver and share one context's pools (the staging arena and the host-i/o pool,
+"""The host-buffer producer calls (ten kinds here: two of them cell calls with proofs) run through one driver and share one context's pools (the staging arena and the host-i/o pool,
 which only grow): call kinds that need different amounts of both, back to back on one context, in one order and then in the reverse
 order.  Every result is compared with the device-resident form of the same call, or with the golden vectors where there is none."""
 import json
@@ -12,6 +12,7 @@ from conftest import GOLDEN, TRUSTED_SETUP  # noqa: E402
 
 BLOB = 131072
 SET = 2 * BLOB  # the 128 cells of one blob
+PROOFS = 128 * 48  # the cell proofs of one blob
 R = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 GEN48 = bytes.fromhex("97f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb")
 BAD = 1  # the blob with an element >= r
@@ -45,7 +46,7 @@ def _bytes(t):
 
 @pytest.fixture(scope="module")
 def expected(torch_cuda, golden):
-    """the inputs of the eight calls and what each must return, from the device-resident calls of a context of its own and the golden
+    """the inputs of the ten calls and what each must return, from the device-resident calls of a context of its own and the golden
     vectors (computed once, never written to).  Five golden blobs, blob 1 with its element 7 replaced by r."""
     import kateth_amd
     from oracle.pyref import bls
@@ -101,6 +102,15 @@ def expected(torch_cuda, golden):
         (recovered,) = dev_call(lambda c: eng.recover_cells_batch_dev(d_holes.data_ptr(), d_masks.data_ptr(), 3, c, st3.data_ptr()), 3 * SET)
         assert st3.cpu().tolist() == [0, 2, 0]
         assert recovered == cells[:SET] + bytes(SET) + cells[2 * SET:]
+        # the same two calls with cell proofs: the cells above, 6,144 zero bytes of proofs for a rejected item
+        cells_p, cell_proofs = dev_call(lambda c, p: eng.compute_cells_and_proofs_batch_dev(d_blobs.data_ptr(), 3, c, p, st3.data_ptr()), 3 * SET, 3 * PROOFS)
+        assert st3.cpu().tolist() == [0, 2, 0] and cells_p == cells
+        recovered_p, recover_proofs = dev_call(
+            lambda c, p: eng.recover_cells_and_proofs_batch_dev(d_holes.data_ptr(), d_masks.data_ptr(), 3, c, p, st3.data_ptr()), 3 * SET, 3 * PROOFS)
+        assert st3.cpu().tolist() == [0, 2, 0] and recovered_p == recovered
+        for prf in (cell_proofs, recover_proofs):
+            assert prf[PROOFS: 2 * PROOFS] == bytes(PROOFS) and any(prf[:PROOFS]) and any(prf[2 * PROOFS:])
+        assert recover_proofs[:PROOFS] == cell_proofs[:PROOFS] and recover_proofs[2 * PROOFS:] == cell_proofs[2 * PROOFS:]
         # proofs at points and evaluations: the golden records (there is no device-resident form of either call)
         zs = b"".join(bytes.fromhex(r["kzg_proof_at"]["z"]) for r in recs)
         ys = b"".join(bytes(32) if i == BAD else bytes.fromhex(r["kzg_proof_at"]["y"]) for i, r in enumerate(recs))
@@ -123,6 +133,8 @@ def expected(torch_cuda, golden):
         "evaluate": (ys, status),
         "recover_in": (holes, EVEN_PRESENT * 3),
         "recover": (recovered, [0, 2, 0]),
+        "cell_proofs": (cells, cell_proofs, [0, 2, 0]),
+        "recover_proofs": (recovered, recover_proofs, [0, 2, 0]),
         "sidecar": (coms, proofs, side[2], status),
         "blob_proof": (proofs, proof_status),
         "proof_at": (proofs_at, ys, status),
@@ -130,7 +142,7 @@ def expected(torch_cuda, golden):
 
 
 def _calls(eng, want, n):
-    """the eight calls on the first n items each (n = None: 5 blobs, 11 points, 3 cell sets), as (name, result, expected result)"""
+    """the ten calls on the first n items each (n = None: 5 blobs, 11 points, 3 cell sets), as (name, result, expected result)"""
     blobs = want["blobs"]
     k5, k11, k3 = (5, 11, 3) if n is None else (n, n, n)
 
@@ -145,6 +157,10 @@ def _calls(eng, want, n):
         ("evaluate", lambda: eng.evaluate_blobs(blobs[: k5 * BLOB], want["evaluate_in"][: 32 * k5]), (want["evaluate"][0][: 32 * k5], want["evaluate"][1][:k5])),
         ("recover", lambda: eng.recover_cells_batch(want["recover_in"][0][: k3 * SET], want["recover_in"][1][: 16 * k3]),
          (want["recover"][0][: k3 * SET], want["recover"][1][:k3])),
+        ("cell_proofs", lambda: eng.compute_cells_and_proofs_batch(blobs[: k3 * BLOB]),
+         (want["cell_proofs"][0][: k3 * SET], want["cell_proofs"][1][: k3 * PROOFS], want["cell_proofs"][2][:k3])),
+        ("recover_proofs", lambda: eng.recover_cells_and_proofs_batch(want["recover_in"][0][: k3 * SET], want["recover_in"][1][: 16 * k3]),
+         (want["recover_proofs"][0][: k3 * SET], want["recover_proofs"][1][: k3 * PROOFS], want["recover_proofs"][2][:k3])),
         ("sidecar", lambda: eng.blob_sidecar_batch(blobs[: k5 * BLOB]),
          (want["sidecar"][0][: 48 * k5], want["sidecar"][1][: 48 * k5], want["sidecar"][2][: 32 * k5], want["sidecar"][3][:k5])),
         ("blob_proof", lambda: eng.compute_blob_proof_batch(blobs[: k5 * BLOB], want["commit"][0][: 48 * k5]),
@@ -168,7 +184,8 @@ def _both_rounds(eng, want, n):
 @pytest.mark.parametrize("members", [1, 2])
 def test_pools_shared_across_call_kinds(expected, members):
     """commit (5 blobs), decompress (11 points), cells (3: a larger arena, so the pool is reallocated), evaluate (5), recover (3: larger
-    again), sidecar (5), blob proof (5), proof at a point (5) on a fresh context, then the same eight in reverse order: a call that
+    again), the same two with cell proofs (3 each: a smaller slot, a workspace), sidecar (5), blob proof (5), proof at a point (5) on a fresh
+    context, then the same ten in reverse order: a call that
     resolved a device pointer before the pools had moved, or that left work behind on a pool the next call frees, shows here.
     members = 2: the same sequence with 3 items per call on two members over one device (shares of 2 and 1), and against a single context"""
     import kateth_amd

@@ -252,6 +252,7 @@ def test_host_passes_walk_the_ring(engine, three, monkeypatch):
     e2 = kateth_amd.Setup.load_json(TRUSTED_SETUP, window_bits=8)
     try:
         cells, st = e2.recover_cells_batch(batch, masks)
+        assert e2.workspace_bytes() == [0, 0, 0]  # a call without proofs takes no workspace slot
     finally:
         e2.close()
     assert st == st4 + [0]

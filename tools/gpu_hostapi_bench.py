@@ -2,7 +2,8 @@
 """Host-buffer (PCIe-inclusive) throughput of the batch entry points: the caller's blobs live in host memory, as in
 kateth's byte-slice API.  Pageable memory (a Python bytes object) and pinned memory (torch pin_memory) are both timed;
 the device-resident rate of the same batch is printed beside them; kzg_evaluate_blobs, the sidecar call, compute_cells, recover_cells
-(the last two on min(n, 1024) items: 256 KiB down, or up and down, per item) and the point decoder are timed over pageable memory.
+(the last two on min(n, 1024) items: 256 KiB down, or up and down, per item), the same two with cell proofs (on min(n, 64) items: two
+passes at the default of 32) and the point decoder are timed over pageable memory.
 usage: gpu_hostapi_bench.py [n] [window_bits]"""
 import ctypes
 import json
@@ -89,7 +90,24 @@ torch.cuda.synchronize()
 assert d_rec.cpu().numpy().tobytes() == cells and not d_st[:m].any().item()
 assert s.recover_cells_batch(cells, masks, m) == (cells, [0] * m)
 rec("recover_host_pageable", timed(lambda: s.recover_cells_batch(cells, masks, m)), m)
-del d_cells, d_rec, cells
+# the same two calls with the 128 cell proofs of every item, on k items; each against its device-resident form first
+k = min(n, 64)
+PROOFS = 128 * 48
+d_prf = torch.empty(k * PROOFS, dtype=torch.uint8, device="cuda")
+s.compute_cells_and_proofs_batch_dev(d_blobs.data_ptr(), k, d_rec.data_ptr(), d_prf.data_ptr(), d_st.data_ptr())
+torch.cuda.synchronize()
+want = (d_rec[: k * SET].cpu().numpy().tobytes(), d_prf.cpu().numpy().tobytes(), d_st[:k].cpu().tolist())
+assert want[0] == cells[: k * SET] and want[2] == [0] * k
+assert s.compute_cells_and_proofs_batch(blobs[: k * 131072], k) == want
+rec("cellproofs_host_pageable", timed(lambda: s.compute_cells_and_proofs_batch(blobs[: k * 131072], k)), k)
+d_rec.zero_()
+d_prf.zero_()
+s.recover_cells_and_proofs_batch_dev(d_cells.data_ptr(), d_masks.data_ptr(), k, d_rec.data_ptr(), d_prf.data_ptr(), d_st.data_ptr())
+torch.cuda.synchronize()
+assert (d_rec[: k * SET].cpu().numpy().tobytes(), d_prf.cpu().numpy().tobytes(), d_st[:k].cpu().tolist()) == want
+assert s.recover_cells_and_proofs_batch(cells[: k * SET], masks[: 16 * k], k) == want
+rec("recover_proofs_host_pageable", timed(lambda: s.recover_cells_and_proofs_batch(cells[: k * SET], masks[: 16 * k], k)), k)
+del d_cells, d_rec, d_prf, cells
 # the point decoder on the n commitments, through the C ABI with the caller's buffers allocated once (there is no device-resident form: the
 # decoded points are compressed again on the host)
 pts, pst = s.decompress_g1_batch(cs)
