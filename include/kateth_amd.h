@@ -367,6 +367,46 @@ int32_t kzg_recover_cells_and_proofs_batch_dev(const kzg_ctx* ctx, const void* d
                                                void* d_out_proofs48, void* d_status, void* hip_stream);
 
 /*
+ * The select forms of the two calls above: the proofs of CHOSEN cells.  A node that rebuilds a blob from 64 or more columns holds the
+ * proofs of the cells it received and needs those of the absent ones only; a node that serves its custody columns needs 8 of 128.  Only
+ * the wanted (item, cell) pairs are divided, transformed and committed -- one MSM per wanted proof instead of 128 per item -- and the
+ * results go where the full calls put them.  A caller writes the proofs it holds into the buffer, calls once, and holds the complete set.
+ *   want           : n * 16 bytes, a 128-bit mask per item in the bit order of `present`: cell c is wanted iff bit (c & 7), least
+ *                    significant first, of byte (c >> 3) is set.  HOST memory in every form, the *_dev ones included: it shapes the
+ *                    launches (the host must know how many vectors a pass commits, as it knows n).  It is read before the call
+ *                    returns; the caller may free or overwrite it then.  Independent of `present`: proofs of present cells may be wanted.
+ *   inout_proofs48 : n * 128 * 48 bytes.  For an accepted item every wanted position 48 * (128 * item + k) holds exactly the bytes the
+ *                    full call writes there; for a rejected item the wanted positions hold 48 zero bytes.  Unwanted positions are not
+ *                    written: the caller's bytes stay.
+ *   out_cells, status : byte for byte the full calls', whatever the masks say: an item with an empty mask is still range-checked or
+ *                    recovered and gets its status.  out_cells of the compute forms may be NULL; out_cells must not overlap cells.
+ * Bounds: nothing beyond n items is written; n == 0 returns 0.  A null required pointer with n > 0 returns KZG_FAIL_ARGUMENT, `want`
+ *   included; only out_cells of the compute forms may be null.
+ * Passes: consecutive items share a pass while its wanted proofs stay <= 128 * KATETH_AMD_CELLPROOF_PASS (default 32: 4,096 vectors)
+ *   and its items <= 128; an item is never split.  With all-ones masks the passes are the full call's.
+ * The *_dev forms take HIP device pointers resident on ctx's device (16-byte aligned) for everything but `want`, enqueue on `hip_stream`
+ *   and return without synchronising on the device: the list of wanted pairs goes up through a pinned buffer the context keeps.  They
+ *   take a workspace slot like the full *_dev calls.
+ * The host-buffer forms bring only the selected proofs down (48 bytes each) and put them in place on the host.
+ * Group contexts: the host-buffer calls cut the batch into the same contiguous shares as the full calls, `want` advanced with the items;
+ *   the *_dev calls act on member 0.
+ * kzg_ctx_cellproof_vectors: the quotient vectors `ctx` and its members have committed in cell-proof calls so far, the full calls
+ *   included at 128 per item (measurement aid, like kzg_verify_each_checks).  The count is by launch size: the wanted vectors of a
+ *   rejected item count.
+ * Not here: a device-resident `want` (it would need a device-built pair list and worst-case launches); FK20; *_group_dev forms.
+ */
+int32_t kzg_compute_cells_and_proofs_select_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* want /* n * 16, HOST */, uint64_t n,
+                                                  uint8_t* out_cells /* n * 128 * 2048, may be NULL */, uint8_t* inout_proofs48 /* n * 128 * 48 */,
+                                                  int32_t* status);
+int32_t kzg_compute_cells_and_proofs_select_batch_dev(const kzg_ctx* ctx, const void* d_blobs, const uint8_t* want /* n * 16, HOST */, uint64_t n,
+                                                      void* d_out_cells /* may be NULL */, void* d_inout_proofs48, void* d_status, void* hip_stream);
+int32_t kzg_recover_cells_and_proofs_select_batch(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, const uint8_t* want /* n * 16, HOST */,
+                                                  uint64_t n, uint8_t* out_cells, uint8_t* inout_proofs48, int32_t* status);
+int32_t kzg_recover_cells_and_proofs_select_batch_dev(const kzg_ctx* ctx, const void* d_cells, const void* d_present, const uint8_t* want /* n * 16, HOST */,
+                                                      uint64_t n, void* d_out_cells, void* d_inout_proofs48, void* d_status, void* hip_stream);
+uint64_t kzg_ctx_cellproof_vectors(const kzg_ctx* ctx);
+
+/*
  * Replaces Setup::proof for n (blob, z) pairs (src/kzg/setup.rs:185-194):
  *   z32 : n * 32 bytes big-endian ; out_proof48 : n * 48 ; out_y32 : n * 32
  *   status : per item 0, KZG_ERR_BLOB_*, KZG_ERR_FF_NOT_IN_FIELD for z

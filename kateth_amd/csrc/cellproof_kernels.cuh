@@ -58,22 +58,17 @@ static __global__ __launch_bounds__(CELLS_THREADS) void k_cell_coeffs(const uint
   }
 }
 
-// The quotient vector of one (blob, cell) per 512-thread workgroup: block = 128 blob + cell.  The blob's coefficients come from global
-// memory (the 128 workgroups of a blob read the same 128 KiB: L2), the division and the four forward passes are cellproof_math.cuh's, and
-// the 4096 evaluations leave as 8 x u32 little-endian words at q[(128 blob + cell) * 4096 + e] -- the MSM's scalar vector, in the blob's
-// own order.  A vector whose status is non-zero is neither read nor written: the MSM's encoder zeroes its 48 bytes.
-// LDS: the image and 16 KiB of segment totals, 147,456 B.
-static __global__ __launch_bounds__(CELLS_THREADS) void k_cell_quotients(const uint32_t* __restrict__ coeffs, const uint32_t* __restrict__ tab,
-                                                                      const uint32_t* __restrict__ ztab, const int32_t* __restrict__ vstatus,
-                                                                      uint32_t* __restrict__ q) {
-  __shared__ uint32_t img[CELLS_IMAGE_DWORDS];
-  __shared__ uint32_t carry[CELLPROOF_CARRY_DWORDS];
-  const uint32_t vec = blockIdx.x, cell = vec & 127u;
-  if (vstatus[vec] != 0) return;  // block-uniform
+// The quotient vector of one (blob, cell) by a 512-thread workgroup, the body k_cell_quotients and k_cell_quotients_sel share: the blob's
+// coefficients come from global memory (the workgroups of a blob read the same 128 KiB: L2), the division and the four forward passes are
+// cellproof_math.cuh's, and the 4096 evaluations leave as 8 x u32 little-endian words at out[e * 8 ..] -- the MSM's scalar vector, in the
+// blob's own order.  `img`: the image, `carry`: the segment totals, both in LDS.
+static __device__ __forceinline__ void cell_quotient_vector(uint32_t* img, uint32_t* carry, const uint32_t* __restrict__ item_coeffs,
+                                                            const uint32_t* __restrict__ tab, const uint32_t* __restrict__ ztab, uint32_t cell,
+                                                            uint32_t* __restrict__ out) {
   const uint32_t t = threadIdx.x;
   {
     fr29 c[8], z, z8;
-    cellproof_load_segment(c, coeffs + (uint64_t)(vec >> 7) * (CELLPROOF_COEFF_BYTES / 4), t);
+    cellproof_load_segment(c, item_coeffs, t);
     cells_tw(z, ztab, cellproof_zpow(cell, 1));
     cellproof_segment_total(carry, c, z, t);
     __syncthreads();
@@ -88,7 +83,53 @@ static __global__ __launch_bounds__(CELLS_THREADS) void k_cell_quotients(const u
   }
   uint32_t ts = t;
   asm volatile("" : "+v"(ts));
-  cellproof_store_words(q + (uint64_t)vec * 32768u, img, ts);
+  cellproof_store_words(out, img, ts);
+}
+
+// All 128 vectors of every blob: block = 128 blob + cell, the vector at q[(128 blob + cell) * 4096 + e].  A vector whose status is non-zero
+// is neither read nor written: the MSM's encoder zeroes its 48 bytes.
+// LDS: the image and 16 KiB of segment totals, 147,456 B.
+static __global__ __launch_bounds__(CELLS_THREADS) void k_cell_quotients(const uint32_t* __restrict__ coeffs, const uint32_t* __restrict__ tab,
+                                                                      const uint32_t* __restrict__ ztab, const int32_t* __restrict__ vstatus,
+                                                                      uint32_t* __restrict__ q) {
+  __shared__ uint32_t img[CELLS_IMAGE_DWORDS];
+  __shared__ uint32_t carry[CELLPROOF_CARRY_DWORDS];
+  const uint32_t vec = blockIdx.x, cell = vec & 127u;
+  if (vstatus[vec] != 0) return;  // block-uniform
+  cell_quotient_vector(img, carry, coeffs + (uint64_t)(vec >> 7) * (CELLPROOF_COEFF_BYTES / 4), tab, ztab, cell, q + (uint64_t)vec * 32768u);
+}
+
+// The vectors of chosen (blob, cell) pairs only (the select calls): block s takes pair = pairs[s] = 128 blob + cell (the host's list,
+// cellproof_plan.hpp; the blob counted within the pass), writes its vector at the COMPACT slot q[s * 4096 + e] and hands the blob's verdict
+// on as cstat[s] = vstatus[pair], whatever the code: the MSM's encoder zeroes the slots of a rejected blob.  The grid is the number of
+// pairs: every block has one.  Both reads are block-uniform, like k_cell_quotients' one.  LDS as k_cell_quotients.
+static __global__ __launch_bounds__(CELLS_THREADS) void k_cell_quotients_sel(const uint32_t* __restrict__ coeffs, const uint32_t* __restrict__ tab,
+                                                                          const uint32_t* __restrict__ ztab, const int32_t* __restrict__ vstatus,
+                                                                          const uint32_t* __restrict__ pairs, int32_t* __restrict__ cstat,
+                                                                          uint32_t* __restrict__ q) {
+  __shared__ uint32_t img[CELLS_IMAGE_DWORDS];
+  __shared__ uint32_t carry[CELLPROOF_CARRY_DWORDS];
+  const uint32_t slot = blockIdx.x, pair = pairs[slot];
+  const int32_t code = vstatus[pair];
+  if (threadIdx.x == 0) cstat[slot] = code;
+  if (code != 0) return;  // block-uniform
+  cell_quotient_vector(img, carry, coeffs + (uint64_t)cellproof_pair_item(pair) * (CELLPROOF_COEFF_BYTES / 4), tab, ztab, cellproof_pair_cell(pair),
+                       q + (uint64_t)slot * 32768u);
+}
+
+// The compact proofs of a pass to their places: slot s (48 bytes at compact + 48 s, three uint4) goes to proofs + 48 pairs[s], where `proofs`
+// is the caller's buffer at the pass's first item.  One thread per slot; both buffers are 16-byte aligned.  Positions no pair names are
+// not touched.
+static __global__ __launch_bounds__(256) void k_cellproof_scatter(const uint4* __restrict__ compact, const uint32_t* __restrict__ pairs, uint32_t nslots,
+                                                                  uint4* __restrict__ proofs) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nslots) return;
+  const uint4* src = compact + (uint64_t)s * 3u;
+  uint4* dst = proofs + (uint64_t)pairs[s] * 3u;
+  const uint4 a = src[0], b = src[1], c = src[2];
+  dst[0] = a;
+  dst[1] = b;
+  dst[2] = c;
 }
 
 #endif

@@ -37,6 +37,9 @@ KZG_HD uint32_t cellproof_brp7(uint32_t k) {
 }
 // index of z_k^e in the table
 KZG_HD uint32_t cellproof_zpow(uint32_t cell, uint32_t e) { return (e * cellproof_brp7(cell)) & 127u; }
+// a pair of the select calls' list (cellproof_plan.hpp): 128 * item + cell, the item counted within its pass
+KZG_HD uint32_t cellproof_pair_item(uint32_t pair) { return pair >> 7; }
+KZG_HD uint32_t cellproof_pair_cell(uint32_t pair) { return pair & 127u; }
 
 // the eight elements base + i S of thread t in the pass of stride S = 8^p
 KZG_HD void cellproof_get8(fr29 (&x)[8], const uint32_t* img, uint32_t base, uint32_t sh) {

@@ -589,6 +589,10 @@ extern "C" void kzg_ctx_destroy(kzg_ctx* ctx) {
   if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   for (auto e : ctx->proof_events) (void)hipEventDestroy(e);
+  for (auto& pin : ctx->pair_pins) {
+    if (pin.p) (void)hipHostFree(pin.p);
+    if (pin.ev) (void)hipEventDestroy(pin.ev);
+  }
   for (auto& pe : ctx->prof_events) {
     (void)hipEventDestroy(pe.e0);
     (void)hipEventDestroy(pe.e1);

@@ -255,6 +255,15 @@ struct kzg_ctx {
   mutable std::mutex cellproof_mu;
   mutable std::atomic<bool> cellproof_ready{false};
   mutable uint32_t* d_cellproof_tab = nullptr;
+  mutable std::atomic<uint64_t> cellproof_vectors{0};  // quotient vectors committed by the cell-proof calls so far, by launch size (kzg_ctx_cellproof_vectors)
+  // Pinned host buffers of the select calls' pair lists (engine_proof.hip: pair_pin_take), guarded by `lock`.  A *_dev call fills one on
+  // the host, enqueues its upload and returns: the buffer is the call's until `ev`, recorded behind that copy, has completed.
+  struct PairPin {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipEvent_t ev = nullptr;
+  };
+  mutable std::vector<PairPin> pair_pins;
   uint4* d_gen_affine = nullptr; // G1 generator and its [z^2]-image (GLV cross-check path), affine, 2^392-Montgomery (2 x 96 B): a term of batch verification's second lincomb
   host::pairing_ctx* pairing = nullptr;  // host: Frobenius constants + Miller lines of G2 and [tau]_2
   uint64_t table_bytes = 0;
@@ -316,14 +325,17 @@ int32_t sidecar_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8
 //   present       16-byte masks: recover the absent cells; null: compute the cells of blobs
 //   out_cells     the 128 cells of every item; null (compute with proofs only): no cells wanted
 //   out_proofs48  the 128 proofs of every item, 6,144 bytes; null: cells only -- the call takes neither ctx->lock nor a workspace slot
+//   want          HOST memory in either form, 16-byte masks: the select calls -- only the wanted proofs are computed and written, the rest
+//                 of out_proofs48 stays as the caller laid it down; null: the full call
 struct CellCall {
   const uint8_t *in, *present;
   uint8_t *out_cells, *out_proofs48;
   int32_t* status;
+  const uint8_t* want = nullptr;
   CellCall advanced(uint64_t first) const {  // the same call from item `first` on
     return CellCall{in + first * (present ? KZG_BYTES_PER_CELL_SET : (size_t)KZG_BYTES_PER_BLOB), present ? present + first * 16 : nullptr,
                     out_cells ? out_cells + first * KZG_BYTES_PER_CELL_SET : nullptr,
-                    out_proofs48 ? out_proofs48 + first * (KZG_CELLS_PER_EXT_BLOB * 48) : nullptr, status + first};
+                    out_proofs48 ? out_proofs48 + first * (KZG_CELLS_PER_EXT_BLOB * 48) : nullptr, status + first, want ? want + first * 16 : nullptr};
   }
 };
 int32_t das_host(const kzg_ctx* ctx, const CellCall& call, uint64_t n);                // engine_proof.hip

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "engine_internal.hpp"
+#include "cellproof_plan.hpp"  // the select calls' pair list and pass plan: host logic
 #include "poly_kernels.cuh"  // this translation unit owns the quotient / evaluation kernels of the proof path
 #include "cells_kernels.cuh"  // ... and the blob extension kernel of compute_cells
 #include "cellproof_kernels.cuh"  // ... and the quotient vectors of the cell proofs
@@ -417,6 +418,7 @@ static int32_t cellproof_dev_locked(const kzg_ctx* ctx, const uint8_t* d_items, 
   for (uint64_t base = 0; base < n; base += P) {
     const uint64_t m = std::min(n - base, P), vectors = m * KZG_CELLS_PER_EXT_BLOB;
     const CellProofLayout L = cellproof_layout(ctx, m);
+    ctx->cellproof_vectors.fetch_add(vectors, std::memory_order_relaxed);
     uint32_t* coeffs = reinterpret_cast<uint32_t*>(ws + L.o_coeff);
     int32_t* vstatus = reinterpret_cast<int32_t*>(ws + L.o_vst);
     uint32_t* q = reinterpret_cast<uint32_t*>(ws + L.o_q);
@@ -460,13 +462,138 @@ static int32_t cellproofs_locked(const kzg_ctx* ctx, const CellCall& d, uint64_t
                               src.proofs_of_own_cells, n, d.out_proofs48, d.status, st);
 }
 
+// ---- the select calls: the proofs of chosen (item, cell) pairs only ----
+// The host turns the `want` masks (host memory in every form) into the pass plan and the pair list (cellproof_plan.hpp).  A pass packs
+// consecutive items while its wanted vectors stay <= 128 cellproof_pass, so a pass's MSM is never larger than a full call's, and with
+// all-ones masks the passes ARE the full call's.  Workspace of a call: the pair lists of all its passes (a *_dev call; the host-buffer call
+// keeps them in the host-i/o pool), then, for a pass of m items and V vectors, the m coefficient sets and 128 m vector statuses as in
+// cellproof_layout, the V compact statuses, V x 128 KiB of vectors, 48 V bytes of compact proofs and the MSM's buffers for V vectors.
+using cellplan::Pass;
+struct CellSelLayout {
+  size_t o_pairs = 0, o_coeff = 0, o_vst = 0, o_cst = 0, o_q = 0, o_prf = 0, total = 0;
+  MsmBufs msm;
+};
+static CellSelLayout cellsel_layout(const kzg_ctx* ctx, uint64_t call_pairs, const Pass& p) {
+  CellSelLayout L;
+  Carve ws;
+  L.o_pairs = ws.take(call_pairs * sizeof(uint32_t));
+  L.o_coeff = ws.take(p.items * (size_t)CELLPROOF_COEFF_BYTES);
+  L.o_vst = ws.take(p.items * KZG_CELLS_PER_EXT_BLOB * sizeof(int32_t));
+  L.o_cst = ws.take(p.vectors * sizeof(int32_t));
+  L.o_q = ws.take(p.vectors * 4096 * sizeof(fr_t));
+  L.o_prf = ws.take(p.vectors * 48);
+  if (p.vectors) L.msm = msm_carve(ctx, ws, p.vectors);
+  L.total = ws.off;
+  return L;
+}
+static size_t cellsel_ws_bytes(const kzg_ctx* ctx, uint64_t call_pairs, const std::vector<Pass>& plan) {
+  size_t need = 0;
+  for (const Pass& p : plan) need = std::max(need, cellsel_layout(ctx, call_pairs, p).total);
+  return need;
+}
+// One pass: p.items items from d_items on (stride, skip_rejected: cellproof_dev_locked's), their p.vectors pairs at d_pairs on the device.
+// The compact proofs go to d_compact (null: the workspace's own buffer) and, with d_scatter_to -- the caller's proof buffer at the pass's
+// first item --, from there to their places.  A pass nobody wants a proof of launches k_cell_coeffs alone, and only where no earlier kernel
+// has written the statuses (status_written).
+static int32_t cellsel_pass(const kzg_ctx* ctx, const uint8_t* d_items, uint64_t stride, bool skip_rejected, bool status_written, const Pass& p,
+                            const uint32_t* d_pairs, uint8_t* d_compact, uint8_t* d_scatter_to, int32_t* d_status, const CellSelLayout& L, uint8_t* ws,
+                            hipStream_t st) {
+  const uint64_t m = p.items, V = p.vectors;
+  if (V == 0 && status_written) return 0;
+  uint32_t* coeffs = reinterpret_cast<uint32_t*>(ws + L.o_coeff);
+  int32_t* vstatus = reinterpret_cast<int32_t*>(ws + L.o_vst);
+  int32_t* cstat = reinterpret_cast<int32_t*>(ws + L.o_cst);
+  uint32_t* q = reinterpret_cast<uint32_t*>(ws + L.o_q);
+  if (!d_compact) d_compact = ws + L.o_prf;
+  ctx->cellproof_vectors.fetch_add(V, std::memory_order_relaxed);
+  {
+    ProfScope ps(ctx, PROF_POLY, st);
+    hipLaunchKernelGGL(k_cell_coeffs, dim3((unsigned)std::min<uint64_t>(m, ctx->num_cus)), dim3(CELLS_THREADS), 0, st, d_items, stride, m, skip_rejected,
+                       ctx->d_cells_tab, coeffs, d_status, vstatus);
+    if (V)
+      hipLaunchKernelGGL(k_cell_quotients_sel, dim3((unsigned)V), dim3(CELLS_THREADS), 0, st, coeffs, ctx->d_cells_tab, ctx->d_cellproof_tab, vstatus, d_pairs,
+                         cstat, q);
+  }
+  if (V == 0) return 0;
+  const int32_t rc = msm_pipeline(ctx, false, reinterpret_cast<const uint8_t*>(q), V, d_compact, nullptr, cstat, L.msm, ws, st);
+  if (rc) return rc;
+  if (d_scatter_to)
+    hipLaunchKernelGGL(k_cellproof_scatter, dim3(blocks_for(V, 256)), dim3(256), 0, st, reinterpret_cast<const uint4*>(d_compact), d_pairs, (uint32_t)V,
+                       reinterpret_cast<uint4*>(d_scatter_to));
+  return 0;
+}
+// A pinned host buffer of at least `bytes` for the pair list of the *_dev call being enqueued (the caller holds ctx->lock): one whose
+// last upload has completed, else a new one while fewer than eight exist, else the first, once its upload has run -- only a ninth call
+// behind eight unfinished ones waits.  The caller records pin->ev behind its copy.
+static int32_t pair_pin_take(const kzg_ctx* ctx, size_t bytes, kzg_ctx::PairPin** out) {
+  constexpr size_t MAX_PINS = 8;
+  std::vector<kzg_ctx::PairPin>& pins = ctx->pair_pins;
+  kzg_ctx::PairPin* pick = nullptr;
+  for (size_t k = 0; k < pins.size() && !pick; k++) {
+    if (hipEventQuery(pins[k].ev) == hipSuccess) pick = &pins[k];
+    else (void)hipGetLastError();  // hipErrorNotReady is not an error of this call
+  }
+  if (!pick && pins.size() < MAX_PINS) {
+    kzg_ctx::PairPin fresh;
+    HIP_TRY(hipEventCreateWithFlags(&fresh.ev, hipEventDisableTiming));
+    pins.push_back(fresh);
+    pick = &pins.back();
+  }
+  if (!pick) {
+    pick = &pins[0];
+    HIP_TRY(hipEventSynchronize(pick->ev));
+  }
+  if (pick->bytes < bytes) {
+    if (pick->p) (void)hipHostFree(pick->p);
+    pick->p = nullptr;
+    pick->bytes = 0;
+    const size_t room = std::max<size_t>(bytes + bytes / 4, 65536);
+    if (hipHostMalloc(&pick->p, room, hipHostMallocDefault) != hipSuccess) return fail(KZG_FAIL_HIP, "hipHostMalloc(pair list) failed");
+    pick->bytes = room;
+  }
+  *out = pick;
+  return 0;
+}
+// the select proofs of n device-resident items whose cells kernel has been enqueued; the caller holds a workspace (with_workspace).  `d.want` is
+// read here, before the call returns: the pair list goes up from a pinned buffer of the context's.
+static int32_t cellsel_dev_locked(const kzg_ctx* ctx, const CellCall& d, uint64_t n, hipStream_t st) {
+  const CellSource& src = cell_source(d);
+  const uint8_t* d_items = src.proofs_of_own_cells ? d.out_cells : d.in;
+  const uint64_t stride = src.proofs_of_own_cells ? KZG_BYTES_PER_CELL_SET : src.up_bytes;
+  const bool status_written = src.proofs_of_own_cells || d.out_cells != nullptr;
+  const std::vector<Pass> plan = cellplan::plan(d.want, n, cellproof_pass(ctx));
+  const uint64_t call_pairs = cellplan::total_vectors(plan);
+  int32_t rc = ws_reserve(ctx, cellsel_ws_bytes(ctx, call_pairs, plan), st);
+  if (rc) return rc;
+  uint8_t* ws = ws_ptr(ctx);
+  const uint32_t* d_pairs = reinterpret_cast<const uint32_t*>(ws);  // o_pairs == 0 in every pass's layout
+  if (call_pairs) {
+    kzg_ctx::PairPin* pin = nullptr;
+    rc = pair_pin_take(ctx, call_pairs * sizeof(uint32_t), &pin);
+    if (rc) return rc;
+    cellplan::write_all_pairs(d.want, plan, static_cast<uint32_t*>(pin->p));
+    HIP_TRY(hipMemcpyAsync(ws, pin->p, call_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(pin->ev, st));
+  }
+  uint64_t base = 0, voff = 0;
+  for (const Pass& p : plan) {
+    rc = cellsel_pass(ctx, d_items + base * stride, stride, src.proofs_of_own_cells, status_written, p, d_pairs + voff, nullptr,
+                      d.out_proofs48 + base * (KZG_CELLS_PER_EXT_BLOB * 48), d.status + base, cellsel_layout(ctx, call_pairs, p), ws, st);
+    if (rc) return rc;
+    base += p.items;
+    voff += p.vectors;
+  }
+  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "cell-proof pipeline launch failed");
+  return 0;
+}
+
 // The device-resident cell call: the cells by their kernel, launched first and outside the lock, then the proofs under a workspace slot.
 int32_t das_dev(const kzg_ctx* ctx, const CellCall& d, uint64_t n, hipStream_t st) {
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(ctx->device));
   int32_t rc = d.out_proofs48 ? ensure_cellproof_tab(ctx) : 0;
   if (rc == 0 && d.out_cells) rc = cells_of(ctx, d, n, st);
-  if (rc == 0 && d.out_proofs48) rc = with_workspace(ctx, st, [&] { return cellproofs_locked(ctx, d, n, st); });
+  if (rc == 0 && d.out_proofs48) rc = with_workspace(ctx, st, [&] { return d.want ? cellsel_dev_locked(ctx, d, n, st) : cellproofs_locked(ctx, d, n, st); });
   return rc;
 }
 
@@ -479,28 +606,61 @@ static void cells_first_halves(const uint8_t* blobs, uint64_t n, const int32_t* 
       memset(out_cells + i * KZG_BYTES_PER_CELL_SET, 0, KZG_BYTES_PER_BLOB);
   }
 }
+// A select call's compact proofs to their places in the caller's buffer, with the pair lists the device walked and the statuses now on the
+// host: the wanted positions of a rejected item get zero bytes, and no other position is written.
+static void cellsel_scatter_host(const std::vector<Pass>& plan, const uint32_t* pairs, const uint8_t* compact, const int32_t* status, uint8_t* out_proofs48) {
+  uint64_t base = 0, s = 0;
+  for (const Pass& p : plan) {
+    for (uint64_t v = 0; v < p.vectors; v++, s++) {
+      const uint64_t item = base + cellproof_pair_item(pairs[s]);
+      uint8_t* dst = out_proofs48 + 48 * (KZG_CELLS_PER_EXT_BLOB * item + cellproof_pair_cell(pairs[s]));
+      if (status[item] == 0)
+        memcpy(dst, compact + 48 * s, 48);
+      else
+        memset(dst, 0, 48);
+    }
+    base += p.items;
+  }
+}
 // The host-buffer cell call.  The input crosses PCIe in passes through the staging ring.  The masks of the whole call go up once, and
 // the proofs (6 KiB per item) and the statuses come down once, through the host-i/o pool.  A pass's cells come down behind its kernel,
 // and its slot is free again behind all the pass enqueued.  With proofs a staging pass is a pass of the device path (about 28 ms of
 // MSM each at the default of 32, so a pass's copy hides behind its predecessor), and one workspace slot serves all passes, sized
-// before anything is in flight.
+// before anything is in flight.  A select call (c.want) walks cellplan's passes instead, sends its pair lists up with the masks and
+// brings only its 48 V selected proofs down, compact: the host puts them in their places once the statuses are there.
 int32_t das_host(const kzg_ctx* ctx, const CellCall& c, uint64_t n) {
   if (n == 0) return 0;
   const CellSource& src = cell_source(c);
-  const bool proofs = c.out_proofs48 != nullptr;
+  const bool proofs = c.out_proofs48 != nullptr, sel = proofs && c.want != nullptr;
   int32_t rc = proofs ? ensure_cellproof_tab(ctx) : 0;
   if (rc) return rc;
+  // a select call: its plan and pair lists, and the compact proofs as they come down; all three live until close() has synchronised
+  std::vector<Pass> sel_plan;
+  std::vector<uint32_t> pairs;
+  std::vector<uint8_t> compact;
+  std::vector<uint64_t> items_plan;
+  if (sel) {
+    sel_plan = cellplan::plan(c.want, n, cellproof_pass(ctx));
+    pairs.resize(cellplan::total_vectors(sel_plan));
+    cellplan::write_all_pairs(c.want, sel_plan, pairs.data());
+    compact.resize(pairs.size() * 48);
+    for (const Pass& p : sel_plan) items_plan.push_back(p.items);
+  }
   HostCall hc(ctx);
-  const int a_mask = hc.upload(c.present, n * 16), a_prf = hc.download(c.out_proofs48, n * (KZG_CELLS_PER_EXT_BLOB * 48)),
-            a_st = hc.download(c.status, n * sizeof(int32_t));
+  // the full-size proof download would overwrite the positions a select call must leave alone: its 48 V selected proofs come down instead
+  const int a_mask = hc.upload(c.present, n * 16), a_prf = sel ? -1 : hc.download(c.out_proofs48, n * (KZG_CELLS_PER_EXT_BLOB * 48)),
+            a_st = hc.download(c.status, n * sizeof(int32_t)), a_pairs = hc.upload(pairs.empty() ? nullptr : pairs.data(), pairs.size() * sizeof(uint32_t)),
+            a_cmp = hc.download(compact.empty() ? nullptr : compact.data(), compact.size());
   const uint64_t pass = proofs ? cellproof_pass(ctx) : ctx->knobs.cells_pass ? ctx->knobs.cells_pass : src.cells_pass;
-  rc = hc.open(even_plan(n, pass), src.up_bytes + (c.out_cells ? KZG_BYTES_PER_CELL_SET : 0));
+  rc = hc.open(sel ? items_plan : even_plan(n, pass), src.up_bytes + (c.out_cells ? KZG_BYTES_PER_CELL_SET : 0));
   if (rc) return rc;
   const uint8_t* d_present = hc.dev(a_mask);  // resolved after open(): opening may move the pools
-  uint8_t* d_prf = hc.dev(a_prf);
+  uint8_t *d_prf = hc.dev(a_prf), *d_cmp = hc.dev(a_cmp);
+  const uint32_t* d_pairs = hc.dev<uint32_t>(a_pairs);
   int32_t* d_status = hc.dev<int32_t>(a_st);
+  uint64_t voff = 0;  // vectors of the select passes enqueued so far
   auto enqueue = [&] {
-    return hc.passes(c.in, src.up_bytes, [&](size_t, uint64_t base, uint64_t m, uint8_t* d_in) {
+    return hc.passes(c.in, src.up_bytes, [&](size_t k, uint64_t base, uint64_t m, uint8_t* d_in) {
       const CellCall d{d_in, d_present ? d_present + base * 16 : nullptr, c.out_cells ? d_in + hc.max_pass * src.up_bytes : nullptr,
                        d_prf ? d_prf + base * (KZG_CELLS_PER_EXT_BLOB * 48) : nullptr, d_status + base};
       if (d.out_cells) {
@@ -512,18 +672,28 @@ int32_t das_host(const kzg_ctx* ctx, const CellCall& c, uint64_t n) {
                                                   : hipMemcpyAsync(out, d.out_cells, m * KZG_BYTES_PER_CELL_SET, hipMemcpyDeviceToHost, hc.st);
         if (down != hipSuccess) return fail(KZG_FAIL_HIP, "device-to-host copy failed");
       }
+      if (sel) {
+        const Pass& p = sel_plan[k];
+        const int32_t e = cellsel_pass(ctx, src.proofs_of_own_cells ? d.out_cells : d.in, src.proofs_of_own_cells ? KZG_BYTES_PER_CELL_SET : src.up_bytes,
+                                       src.proofs_of_own_cells, src.proofs_of_own_cells || d.out_cells != nullptr, p, d_pairs + voff, d_cmp + voff * 48, nullptr,
+                                       d.status, cellsel_layout(ctx, 0, p), ws_ptr(ctx), hc.st);
+        voff += p.vectors;
+        return e;
+      }
       return proofs ? cellproofs_locked(ctx, d, m, hc.st) : 0;
     });
   };
   if (proofs)
     rc = with_workspace(ctx, hc.st, [&] {
-      const int32_t e = ws_reserve(ctx, cellproof_ws_bytes(ctx, n), hc.st);
+      const int32_t e = ws_reserve(ctx, sel ? cellsel_ws_bytes(ctx, 0, sel_plan) : cellproof_ws_bytes(ctx, n), hc.st);
       return e ? e : enqueue();
     });
   else
     rc = enqueue();
+  if (rc == 0 && sel && hipGetLastError() != hipSuccess) rc = fail(KZG_FAIL_HIP, "cell-proof pipeline launch failed");
   rc = hc.close(rc);
   if (rc == 0 && src.ext_half_down && c.out_cells) cells_first_halves(c.in, n, c.status, c.out_cells);
+  if (rc == 0 && sel) cellsel_scatter_host(sel_plan, pairs.data(), compact.data(), c.status, c.out_proofs48);
   return rc;
 }
 
@@ -586,6 +756,47 @@ extern "C" int32_t kzg_recover_cells_and_proofs_batch(const kzg_ctx* ctx, const 
   return das_on_members(ctx, cell_call(cells, present, out_cells, out_proofs48, status), n);
 } catch (...) {
   return abi_exception();
+}
+
+// The select forms: `want` is host memory in all four, and a null `want` is an argument error, not the full call
+static CellCall cell_call_select(const void* in, const void* present, const uint8_t* want, void* out_cells, void* inout_proofs48, void* status) {
+  CellCall c = cell_call(in, present, out_cells, inout_proofs48, status);
+  c.want = want;
+  return c;
+}
+extern "C" int32_t kzg_compute_cells_and_proofs_select_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* want, uint64_t n, uint8_t* out_cells,
+                                                             uint8_t* inout_proofs48, int32_t* status) try {
+  if (!ctx || (n && (!blobs || !want || !inout_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return das_on_members(ctx, cell_call_select(blobs, nullptr, want, out_cells, inout_proofs48, status), n);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_compute_cells_and_proofs_select_batch_dev(const kzg_ctx* ctx, const void* d_blobs, const uint8_t* want, uint64_t n, void* d_out_cells,
+                                                                 void* d_inout_proofs48, void* d_status, void* hip_stream) try {
+  if (!ctx || (n && (!d_blobs || !want || !d_inout_proofs48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return das_dev(ctx, cell_call_select(d_blobs, nullptr, want, d_out_cells, d_inout_proofs48, d_status), n, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_recover_cells_and_proofs_select_batch(const kzg_ctx* ctx, const uint8_t* cells, const uint8_t* present, const uint8_t* want, uint64_t n,
+                                                             uint8_t* out_cells, uint8_t* inout_proofs48, int32_t* status) try {
+  if (!ctx || (n && (!cells || !present || !want || !out_cells || !inout_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return das_on_members(ctx, cell_call_select(cells, present, want, out_cells, inout_proofs48, status), n);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_recover_cells_and_proofs_select_batch_dev(const kzg_ctx* ctx, const void* d_cells, const void* d_present, const uint8_t* want, uint64_t n,
+                                                                 void* d_out_cells, void* d_inout_proofs48, void* d_status, void* hip_stream) try {
+  if (!ctx || (n && (!d_cells || !d_present || !want || !d_out_cells || !d_inout_proofs48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return das_dev(ctx, cell_call_select(d_cells, d_present, want, d_out_cells, d_inout_proofs48, d_status), n, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" uint64_t kzg_ctx_cellproof_vectors(const kzg_ctx* ctx) {
+  if (!ctx) return 0;
+  uint64_t total = ctx->cellproof_vectors.load(std::memory_order_relaxed);
+  for (const kzg_ctx* p : ctx->peers) total += p->cellproof_vectors.load(std::memory_order_relaxed);
+  return total;
 }
 
 void warm_code_object_proof() {

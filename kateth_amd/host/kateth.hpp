@@ -362,6 +362,40 @@ class Setup {
     if (status) throw Error(static_cast<ErrorKind>(status));
     return out;
   }
+  // The proofs of the cells `cell_indices` of one blob, 48 bytes each in the order given: one MSM per distinct cell instead of 128
+  // (kzg_compute_cells_and_proofs_select_batch).  Errors as compute_cells; an index >= 128 is std::invalid_argument.
+  std::vector<Bytes48> compute_cell_proofs(const uint8_t* blob, size_t len, const std::vector<uint64_t>& cell_indices) const {
+    if (len != BLOB_BYTES) throw Error(ErrorKind::BlobInvalidLen);
+    std::array<uint8_t, 16> want{};
+    for (uint64_t c : cell_indices) {
+      if (c >= CELLS_PER_EXT_BLOB) throw std::invalid_argument("compute_cell_proofs: cell index out of range");
+      want[c >> 3] |= static_cast<uint8_t>(1u << (c & 7));
+    }
+    std::vector<uint8_t> all(CELLS_PER_EXT_BLOB * 48);
+    int32_t status = 0;
+    check(kzg_compute_cells_and_proofs_select_batch(ctx_.get(), blob, want.data(), 1, nullptr, all.data(), &status), "kzg_compute_cells_and_proofs_select_batch");
+    if (status) throw Error(static_cast<ErrorKind>(status));
+    std::vector<Bytes48> out(cell_indices.size());
+    for (size_t i = 0; i < cell_indices.size(); i++) std::memcpy(out[i].data(), all.data() + 48 * cell_indices[i], 48);
+    return out;
+  }
+  // recover_cells_and_proofs for a node that received its cells WITH their proofs (`proofs`: 48 bytes per given cell, in their order): all
+  // 128 cells and all 128 proofs, the given proofs kept as they came and only the absent cells' computed.  Arguments and errors as recover_cells.
+  CellsAndProofs recover_cells_and_missing_proofs(const std::vector<uint64_t>& cell_indices, const uint8_t* cells, size_t len, const uint8_t* proofs,
+                                                  size_t proofs_len) const {
+    std::vector<uint8_t> in;
+    std::array<uint8_t, 16> present{}, want{};
+    cell_set(cell_indices, cells, len, in, present);
+    if (proofs_len != cell_indices.size() * 48) throw std::invalid_argument("recover_cells_and_missing_proofs: one 48-byte proof per cell");
+    CellsAndProofs out{std::vector<uint8_t>(CELLS_PER_EXT_BLOB * BYTES_PER_CELL), std::vector<uint8_t>(CELLS_PER_EXT_BLOB * 48)};
+    for (size_t i = 0; i < cell_indices.size(); i++) std::memcpy(out.proofs.data() + 48 * cell_indices[i], proofs + 48 * i, 48);
+    for (size_t b = 0; b < 16; b++) want[b] = static_cast<uint8_t>(~present[b]);
+    int32_t status = 0;
+    check(kzg_recover_cells_and_proofs_select_batch(ctx_.get(), in.data(), present.data(), want.data(), 1, out.cells.data(), out.proofs.data(), &status),
+          "kzg_recover_cells_and_proofs_select_batch");
+    if (status) throw Error(static_cast<ErrorKind>(status));
+    return out;
+  }
 
   // (proof, y)
   std::pair<Bytes48, Bytes32> proof(const uint8_t* blob, size_t len, const Bytes32& point) const {

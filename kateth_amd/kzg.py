@@ -193,6 +193,17 @@ _SIGNATURES = {
         ctypes.c_int32,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     ),
+    "kzg_compute_cells_and_proofs_select_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
+    "kzg_compute_cells_and_proofs_select_batch_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "kzg_recover_cells_and_proofs_select_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
+    "kzg_recover_cells_and_proofs_select_batch_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "kzg_ctx_cellproof_vectors": (ctypes.c_uint64, [ctypes.c_void_p]),
     "kzg_compute_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
     "kzg_verify_blob_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
     "kzg_verify_blob_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
@@ -667,6 +678,37 @@ class Setup:
             raise ValueError("recover_cells_and_proofs_batch: n * 262144 bytes of cells and n * 16 bytes of mask")
         return self._produce("kzg_recover_cells_and_proofs_batch", [cells, present], n, [CELLS_PER_EXT_BLOB * BYTES_PER_CELL, CELLS_PER_EXT_BLOB * 48])
 
+    def _select_call(self, what: str, inputs, n: int, proofs, want_cells: bool):
+        """a select call `what`(handle, *inputs, n, out_cells, inout_proofs, status): the proof buffer starts as `proofs` (zero bytes when None)"""
+        size = n * CELLS_PER_EXT_BLOB * 48
+        if proofs is not None and len(_buf(proofs)) != size:
+            raise ValueError("%s: the proof buffer is n * 6144 bytes" % what)
+        io = ctypes.create_string_buffer(bytes(_buf(proofs)) if proofs is not None else bytes(size), size)
+        cells = ctypes.create_string_buffer(n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL) if want_cells else None
+        status = (ctypes.c_int32 * n)()
+        rc = getattr(self._lib, what)(self._h, *inputs, n, None if cells is None else ctypes.cast(cells, ctypes.c_void_p), ctypes.cast(io, ctypes.c_void_p), status)
+        self._check(rc, what)
+        return (None if cells is None else cells.raw), io.raw, list(status)
+
+    def compute_cells_and_proofs_select_batch(self, blobs: bytes, want: bytes, proofs: Optional[bytes] = None, want_cells: bool = True):
+        """`compute_cells_and_proofs_batch` for CHOSEN cells: `want` is n 16-byte masks (cell c wanted iff bit c & 7 of byte c >> 3) ->
+        (cells or None, n * 128 * 48 bytes of proofs, [status]).  The wanted proofs stand where the full call puts them; every other
+        position keeps the bytes of `proofs` (zero bytes when None).  A rejected blob's wanted positions are zero bytes."""
+        blobs, want = _buf(blobs), _buf(want)
+        n = len(want) // 16
+        if len(blobs) != n * BYTES_PER_BLOB or len(want) != n * 16:
+            raise ValueError("compute_cells_and_proofs_select_batch: n * 131072 bytes of blobs and n * 16 bytes of mask")
+        return self._select_call("kzg_compute_cells_and_proofs_select_batch", [blobs, want], n, proofs, want_cells)
+
+    def recover_cells_and_proofs_select_batch(self, cells: bytes, present: bytes, want: bytes, proofs: Optional[bytes] = None):
+        """`recover_cells_and_proofs_batch` for CHOSEN cells: `want` as in `compute_cells_and_proofs_select_batch`, independent of
+        `present` -> (cells, proofs, [status]).  A node passes the proofs it received in `proofs` and wants the absent cells'."""
+        cells, present, want = _buf(cells), _buf(present), _buf(want)
+        n = len(present) // 16
+        if len(cells) != n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL or len(present) != n * 16 or len(want) != n * 16:
+            raise ValueError("recover_cells_and_proofs_select_batch: n * 262144 bytes of cells and two n * 16 bytes of masks")
+        return self._select_call("kzg_recover_cells_and_proofs_select_batch", [cells, present, want], n, proofs, True)
+
     def compute_proof_batch(self, blobs: bytes, zs: bytes):
         blobs, zs = _buf(blobs), _buf(zs)
         n = len(zs) // 32
@@ -814,6 +856,40 @@ class Setup:
             raise error_from_status(status[0])
         return ([out[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)],
                 [proofs[48 * c:48 * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)])
+
+    def compute_cell_proofs(self, blob: bytes, cell_indices: Sequence[int]) -> List[bytes]:
+        """The proofs of the cells `cell_indices` of one blob (each what `compute_cells_and_proofs` returns for that cell), in the order
+        given, at one MSM per distinct cell; raises what `compute_cells` raises, ValueError for an index out of range."""
+        blob = _buf(blob)
+        if len(blob) != BYTES_PER_BLOB:
+            raise BlobError("InvalidLen")
+        cell_indices = [int(c) for c in cell_indices]
+        if any(not 0 <= c < CELLS_PER_EXT_BLOB for c in cell_indices):
+            raise ValueError("compute_cell_proofs: cell index out of range")
+        mask = bytearray(16)
+        for c in cell_indices:
+            mask[c >> 3] |= 1 << (c & 7)
+        _, proofs, status = self.compute_cells_and_proofs_select_batch(blob, bytes(mask), want_cells=False)
+        if status[0]:
+            raise error_from_status(status[0])
+        return [proofs[48 * c:48 * (c + 1)] for c in cell_indices]
+
+    def recover_cells_and_missing_proofs(self, cell_indices: Sequence[int], cells: Sequence[bytes], proofs: Sequence[bytes]):
+        """`recover_cells_and_proofs` for a node that received the cells WITH their proofs: (all 128 cells, all 128 proofs), the given
+        proofs kept as they came and only the absent cells' computed.  Arguments and errors as `recover_cells`; one 48-byte proof per cell."""
+        flat, mask = self._cell_set(cell_indices, cells)
+        proofs = [_buf(p) for p in proofs]
+        if len(proofs) != len(cells) or any(len(p) != 48 for p in proofs):
+            raise ValueError("recover_cells_and_missing_proofs: one 48-byte proof per cell")
+        held = bytearray(CELLS_PER_EXT_BLOB * 48)
+        for c, p in zip(cell_indices, proofs):
+            held[48 * int(c):48 * (int(c) + 1)] = p
+        want = bytes(b ^ 0xFF for b in mask)
+        out, all_proofs, status = self.recover_cells_and_proofs_select_batch(flat, mask, want, bytes(held))
+        if status[0]:
+            raise error_from_status(status[0])
+        return ([out[BYTES_PER_CELL * c:BYTES_PER_CELL * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)],
+                [all_proofs[48 * c:48 * (c + 1)] for c in range(CELLS_PER_EXT_BLOB)])
 
     def blob_proof(self, blob: bytes, commitment: bytes) -> bytes:
         """`Setup::blob_proof` + `compress` (kzg::Error on bad input)."""
@@ -1137,6 +1213,28 @@ class Setup:
     def verify_proof_batch_each_dev(self, d_proofs: int, d_commitments: int, d_points: int, d_evals: int, n: int, stream: int = 0):
         """-> (ok_each: List[bool], status: List[int], ok: bool); synchronous, results in host memory"""
         return self._verdicts("kzg_verify_proof_batch_each_dev", (d_proofs, d_commitments, d_points, d_evals), n, (stream,))
+
+    def compute_cells_and_proofs_select_batch_dev(self, d_blobs: int, want: bytes, n: int, d_out_cells: int, d_inout_proofs: int, d_status: int, stream: int = 0):
+        """Device-resident select call: `want` is n * 16 bytes of HOST memory, read before this returns; enqueues on `stream` and returns
+        without synchronising.  d_out_cells may be 0 (proofs only).  Positions of d_inout_proofs nobody wants are not written."""
+        want = _buf(want)
+        if len(want) != n * 16:
+            raise ValueError("compute_cells_and_proofs_select_batch_dev: n * 16 bytes of mask")
+        rc = self._lib.kzg_compute_cells_and_proofs_select_batch_dev(self._h, d_blobs, want, n, d_out_cells or None, d_inout_proofs, d_status, stream)
+        self._check(rc, "kzg_compute_cells_and_proofs_select_batch_dev")
+
+    def recover_cells_and_proofs_select_batch_dev(self, d_cells: int, d_present: int, want: bytes, n: int, d_out_cells: int, d_inout_proofs: int, d_status: int,
+                                                  stream: int = 0):
+        """Device-resident select call of recovery: `want` is HOST memory as above, `d_present` device memory as in the full call."""
+        want = _buf(want)
+        if len(want) != n * 16:
+            raise ValueError("recover_cells_and_proofs_select_batch_dev: n * 16 bytes of mask")
+        rc = self._lib.kzg_recover_cells_and_proofs_select_batch_dev(self._h, d_cells, d_present, want, n, d_out_cells, d_inout_proofs, d_status, stream)
+        self._check(rc, "kzg_recover_cells_and_proofs_select_batch_dev")
+
+    def cellproof_vectors(self) -> int:
+        """quotient vectors this context (all members) has committed in cell-proof calls so far, 128 per item of a full call (measurement aid)"""
+        return int(self._lib.kzg_ctx_cellproof_vectors(self._h))
 
     def verify_each_checks(self) -> int:
         """two-pairing checks the per-item verdict calls have spent on this context so far"""
