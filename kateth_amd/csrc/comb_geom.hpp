@@ -34,6 +34,64 @@ KZG_HD CombGeom comb_make_geom(uint32_t nb, uint32_t G) {
   return g;
 }
 KZG_HD uint64_t comb_table_entries(const CombGeom& g) { return (uint64_t)g.G * g.epg; }
+
+// ---- the lane walk of k_msm_comb30 --------------------------------------------------------------------------------------
+// A lane owns blocks [b0, b0 + bpo) of the 64 nb blocks and visits them once per plane, planes counting down.  CombWalk is
+// the part of a position that is THE SAME IN EVERY LANE of a wave -- plane h, block counter s -- and, when every lane's
+// first block opens a chunk (b0 % nb == 0: "wide" shapes, bpo a multiple of 4 nb, every production shape), also the block
+// within its chunk r and the number of chunks dq past the lane's first chunk q0 = b0 / nb.  The kernel keeps it in scalar
+// registers and adds the lane's q0 where a position is used.  CombLanePos is the per-lane (chunk, block in chunk) the other
+// shapes need instead of (dq, r).
+struct CombWalk {
+  uint32_t h, s, r, dq;
+};
+// blocks per lane of a launch shape, and whether the shape is wide
+KZG_HD uint32_t comb_blocks_per_lane(const CombGeom& g, uint32_t splits, uint32_t lpb) { return (64u * g.nb) / (splits * (lpb / g.G)); }
+KZG_HD bool comb_shape_is_wide(const CombGeom& g, uint32_t splits, uint32_t lpb) { return comb_blocks_per_lane(g, splits, lpb) % (4u * g.nb) == 0u; }
+// k_msm_comb30 is compiled per kind of shape, so that neither instance carries the other's registers and branches: the product
+// launches COMB_SHAPE_WIDE or COMB_SHAPE_NARROW; COMB_SHAPE_ANY decides at run time (the test-only timed instance).
+enum : int { COMB_SHAPE_ANY = 0, COMB_SHAPE_WIDE = 1, COMB_SHAPE_NARROW = 2 };
+struct CombLanePos {
+  uint32_t q, r;
+};
+KZG_HD void comb_walk_start(CombWalk& w, uint32_t H) {
+  w.h = H - 1u;
+  w.s = 0;
+  w.r = 0;
+  w.dq = 0;
+}
+// to the next step; true when the lane wrapped to its first block on the next plane down
+KZG_HD bool comb_walk_advance(CombWalk& w, uint32_t nb, uint32_t bpo) {
+  w.s++;
+  w.r++;
+  if (w.r == nb) {
+    w.r = 0;
+    w.dq++;
+  }
+  if (w.s != bpo) return false;
+  w.s = 0;
+  w.r = 0;
+  w.dq = 0;
+  w.h--;
+  return true;
+}
+KZG_HD void comb_lane_advance(CombLanePos& p, uint32_t nb, bool wrapped, uint32_t b0) {
+  p.r++;
+  if (p.r == nb) {
+    p.r = 0;
+    p.q++;
+  }
+  if (wrapped) {
+    p.q = b0 / nb;
+    p.r = b0 % nb;
+  }
+}
+// Wide shapes: a lane's chunks come in aligned groups of four whose masks are ONE 32-byte load (mb0..mb3), issued when w opens
+// a group; the step at w cuts its pattern from slot dq % 4 of them.
+KZG_HD bool comb_walk_loads_masks(const CombWalk& w) { return w.r == 0u && (w.dq & 3u) == 0u; }
+KZG_HD uint32_t comb_walk_mask_slot(const CombWalk& w) { return w.dq & 3u; }
+// Horner doubling in front of the step at w: on a lane's first block of every plane but the first
+KZG_HD bool comb_walk_doubles(const CombWalk& w, uint32_t H) { return w.s == 0u && w.h != H - 1u; }
 // largest `splits` the geometry supports: a lane must own a whole number of blocks
 KZG_HD uint32_t comb_max_splits(const CombGeom& g) { return (64u * g.nb) / g.lpg; }
 

@@ -1144,8 +1144,13 @@ int32_t msm_launch(const kzg_ctx* ctx, bool be_bytes, const uint8_t* d_scalars, 
   const bool lat = msm_uses_lat(ctx, splits);
   const uint4* table = lat ? ctx->d_table_lat : ctx->d_table;
   const CombGeom geom = lat ? ctx->comb_lat : ctx->comb;
-  hipLaunchKernelGGL(k_msm_comb30<false>, dim3((unsigned)msm_units(n, splits, lpb)), dim3(64), 0, st, masks, n, splits, lpb, table, geom, partials,
-                     (const uint4*)(lat ? ctx->d_comb_k_lat : ctx->d_comb_k), (uint64_t*)nullptr);
+  const uint4* comb_k = (const uint4*)(lat ? ctx->d_comb_k_lat : ctx->d_comb_k);
+  if (comb_shape_is_wide(geom, splits, lpb))
+    hipLaunchKernelGGL((k_msm_comb30<false, COMB_SHAPE_WIDE>), dim3((unsigned)msm_units(n, splits, lpb)), dim3(64), 0, st, masks, n, splits, lpb, table, geom,
+                       partials, comb_k, (uint64_t*)nullptr);
+  else
+    hipLaunchKernelGGL((k_msm_comb30<false, COMB_SHAPE_NARROW>), dim3((unsigned)msm_units(n, splits, lpb)), dim3(64), 0, st, masks, n, splits, lpb, table, geom,
+                       partials, comb_k, (uint64_t*)nullptr);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -180,8 +180,10 @@ namespace kzg {
 // every generated statement, so that a CPU test runs f30_prod::step and f30_run2 THEMSELVES against f30_mul_core_c.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define KZG_F30_ATOM_FENCE() __builtin_amdgcn_sched_barrier(0)
+#define KZG_F30_OPAQUE(x) asm("" : "+v"(x))  // the value stays in its register; the compiler forgets how it was computed
 #else
 #define KZG_F30_ATOM_FENCE() ((void)0)
+#define KZG_F30_OPAQUE(x) ((void)0)
 #endif
 #if defined(__HIP_DEVICE_COMPILE__) || defined(KZG_FP30_HOST_ATOMS)
 // Device version: every column is issued as explicit v_mad_i64_i32 chains that START from the carry of the previous column
@@ -273,6 +275,10 @@ struct f30_prod {
       mad30_col<folds(K), L, k2_of(K)>::run(A, cy, folds(K) ? q[K - 1] : 0, f30_p(0), xs, ys, qs, ps);
     } else if constexpr (folds(K)) {
       mad30_fold<L>::run(A, cy, q[K - 1], f30_p(0), xs, ys);
+    } else if constexpr (K == 0) {
+      // the accumulator starts here: the first multiply-add takes the constant 0 as its addend, no register is cleared for it
+      A = (int64_t)xs[0] * ys[0];
+      if constexpr (L > 1) mad30_chain<L - 1, false>::run(A, cy, xs + 1, ys + 1);
     } else {
       mad30_chain<L, false>::run(A, cy, xs, ys);
     }
@@ -336,6 +342,10 @@ struct f30_prod {
         r.l[K - N_] = (int32_t)((uint32_t)A & F30_MASK);
       } else {
         r.l[K - N_] = f30_sbfe((uint32_t)A);  // r may alias an operand: limb K-13 of every operand was last read in column K-1
+        // The digit as the compiler must take it: a later squaring doubles it (a2), and the compiler, seeing through the field
+        // extraction, formed the doubled limb from A again -- shift left by two, arithmetic shift right by one -- beside the
+        // digit: three instructions per limb where the digit and its shift are two.
+        KZG_F30_OPAQUE(r.l[K - N_]);
       }
     } else if constexpr (PH == 4) {
       if constexpr (K < N_)
@@ -594,6 +604,16 @@ KZG_HD void f30_load_entry(fp30& x, fp30& y, const uint32_t* wx, const uint32_t*
   const uint32_t m = neg ? 0xffffffffu : 0u, one = neg ? 1u : 0u;
   KZG_UNROLL_FULL
   for (int i = 0; i < F30_N; i++) y.l[i] = (int32_t)(((uint32_t)t.l[i] ^ m) + one);  // two's complement, one v_xad_u32 per limb
+}
+// The digits are computed HERE, not where they are first used: a caller that refills the packed words' registers next (the
+// hot loop's gather of the following entry) then needs no second set of registers for them and no copies at the loop's edge.
+KZG_HD void f30_pin(fp30& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  KZG_UNROLL_FULL
+  for (int i = 0; i < F30_N; i++) asm volatile("" : "+v"(a.l[i]));
+#else
+  (void)a;
+#endif
 }
 
 // ---- XYZZ accumulator ---------------------------------------------------------------------------------------------------------

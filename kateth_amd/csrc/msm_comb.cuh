@@ -99,10 +99,98 @@ static __global__ __launch_bounds__(512) void k_comb_transpose(const uint8_t* __
   }
 }
 
-// lane-walker of k_msm_comb30: position = (plane h counting down, block counter s, chunk q, block-in-chunk r)
-struct CombWalker {
-  uint32_t h, s, q, r;
+// (uint32_t)(m >> off) for a wave-uniform off: written as the instruction itself, so that a scalar branch which picks m among
+// several registers stays a branch (the compiler would fold it into selects between them, two per register pair)
+// SLOT: which of the registers, as a comment in the statement -- four statements with the same text would be merged into one
+// behind the branch again, reading its operand through a pointer chosen by the branch, which puts the registers into memory.
+template <int SLOT>
+__device__ __forceinline__ uint32_t comb_mask_bits(uint64_t m, uint32_t off) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint64_t r;
+  if constexpr (SLOT == 0) asm volatile("v_lshrrev_b64 %0, %1, %2 ; mask slot 0" : "=v"(r) : "s"(off), "v"(m));
+  if constexpr (SLOT == 1) asm volatile("v_lshrrev_b64 %0, %1, %2 ; mask slot 1" : "=v"(r) : "s"(off), "v"(m));
+  if constexpr (SLOT == 2) asm volatile("v_lshrrev_b64 %0, %1, %2 ; mask slot 2" : "=v"(r) : "s"(off), "v"(m));
+  if constexpr (SLOT == 3) asm volatile("v_lshrrev_b64 %0, %1, %2 ; mask slot 3" : "=v"(r) : "s"(off), "v"(m));
+  return (uint32_t)r;
+#else
+  return (uint32_t)(m >> off);
+#endif
+}
+
+// A lane of k_msm_comb30 on its walk (comb_geom.hpp).  w = the step whose mask is fetched next, p1 = the step whose entry is
+// gathered next.  Plane and block counter are wave-uniform; in wide shapes so are the block within its chunk and the chunk's
+// distance from the lane's first chunk -- scalar registers and scalar branches; only the first chunk and the pattern cut from
+// the mask are the lane's own.  The other shapes carry a per-lane (chunk, block) beside it (lw, lp1).
+// Pipeline registers: mb* = mask(s) covering the step at p1; (nx, ny) = table entry of the step after the one being added.
+// A lane's chunks are consecutive, so when they come in aligned groups of four (bpo a multiple of 4 nb: every production
+// shape) the four masks are ONE 32-byte load per group instead of an 8-byte load per step: with [plane][chunk] rows a
+// 128-byte line holds 16 chunks of one plane = 4 owners x 4 groups, and the table gathers (20 GB per launch through a
+// 4-MB L2) evicted it between a lane's visits -- FETCH_SIZE counted 7.9 GB of mask re-fetches per 4,096 blobs.
+// Plain forced-inline functions on one struct, not closures over locals: every field must become a register of its own before
+// the compiler starts merging the stores of two branches into one store through a chosen pointer (which had put two of the
+// masks into scratch).
+struct CombLane {
+  const uint64_t* mrow;   // the blob's masks, [plane][chunk]
+  const uint64_t* mlane;  // ... at the lane's group's plane 0 and the lane's first chunk
+  const uint4* tgrp;      // the group's table
+  uint32_t nb, bpo, b0, kbase, H, ep64;
+  uint32_t q0e;  // the lane's first chunk in table entries
+  bool wide;
+  CombWalk w, p1;
+  CombLanePos lw, lp1;
+  uint64_t mb0, mb1, mb2, mb3;
+  fp_t nx, ny;
+  bool nneg, ndbl;
+  uint32_t nidx;
 };
+// the mask of the step at w (in wide shapes only when w opens a new group of four chunks); then w is the next step
+__device__ __forceinline__ void comb_next_mask(CombLane& s) {
+  if (s.wide) {
+    if (comb_walk_loads_masks(s.w)) {
+      const uint4* src = reinterpret_cast<const uint4*>(s.mlane + (s.w.h * 64u + s.w.dq));
+      const uint4 lo = src[0], hi = src[1];
+      s.mb0 = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
+      s.mb1 = (uint64_t)lo.z | ((uint64_t)lo.w << 32);
+      s.mb2 = (uint64_t)hi.x | ((uint64_t)hi.y << 32);
+      s.mb3 = (uint64_t)hi.z | ((uint64_t)hi.w << 32);
+    }
+  } else {
+    s.mb0 = s.mrow[(s.kbase + s.w.h) * 64u + s.lw.q];
+  }
+  s.p1 = s.w;
+  const bool wrapped = comb_walk_advance(s.w, s.nb, s.bpo);
+  if (!s.wide) {
+    s.lp1 = s.lw;
+    comb_lane_advance(s.lw, s.nb, wrapped, s.b0);
+  }
+}
+// the entry of block r of the chunk whose entries start at qe; bits = the chunk's mask from the block's first point on
+__device__ __forceinline__ void comb_cut(CombLane& s, uint32_t bits, uint32_t qe, uint32_t r) {
+  const uint32_t tb = comb_tbits(s.nb, r);
+  const uint32_t pat = bits & ((1u << tb) - 1u);
+  s.nneg = (pat >> (tb - 1u)) != 0u;  // top sign +1: the table holds the mirrored pattern, negated
+  const uint32_t m = s.nneg ? (~pat & ((1u << (tb - 1u)) - 1u)) : pat;
+  s.nidx = qe + comb_entry_off(s.nb, r) + m;
+  load_affine96(s.nx, s.ny, s.tgrp, s.nidx);
+}
+// entry of the step at p1
+__device__ __forceinline__ void comb_gather(CombLane& s) {
+  if (s.wide) {
+    // the slot is the same in every lane: a scalar branch to the shift that reads it, no select between the four registers
+    const uint32_t off = comb_point_off(s.nb, s.p1.r);
+    uint32_t bits;
+    switch (comb_walk_mask_slot(s.p1)) {
+      case 0: bits = comb_mask_bits<0>(s.mb0, off); break;
+      case 1: bits = comb_mask_bits<1>(s.mb1, off); break;
+      case 2: bits = comb_mask_bits<2>(s.mb2, off); break;
+      default: bits = comb_mask_bits<3>(s.mb3, off); break;
+    }
+    comb_cut(s, bits, s.q0e + s.p1.dq * s.ep64, s.p1.r);
+  } else {
+    comb_cut(s, (uint32_t)(s.mb0 >> comb_point_off(s.nb, s.lp1.r)), s.lp1.q * s.ep64, s.lp1.r);
+  }
+  s.ndbl = comb_walk_doubles(s.p1, s.H);
+}
 
 // One wave per unit.  lpb = 64 lanes per blob: unit = (blob, split).  lpb = 32 (large batches, splits = 1): a wave carries
 // TWO blobs on its two halves -- every lane owns twice the blocks for the same H - 1 doublings, which halves the Horner
@@ -111,7 +199,8 @@ struct CombWalker {
 // of the 64 nb blocks.
 // TIMED: instantiated only by the test-only library (tests/window_msm): every unit records {wall start, wall end, cycles,
 // hw id} into wave_times (tools/gpu_wave_times.py); the product instantiates <false> and passes nullptr.
-template <bool TIMED>
+// SHAPE (comb_geom.hpp): the kind of shape the instance is launched with; the launcher's choice must be the shape's.
+template <bool TIMED, int SHAPE = COMB_SHAPE_ANY>
 static __global__ __launch_bounds__(64, 2) void k_msm_comb30(const uint64_t* __restrict__ masks, uint64_t n, uint32_t splits, uint32_t lpb,
                                                              const uint4* __restrict__ table, CombGeom g, g1_xyzz* __restrict__ partials,
                                                              const uint4* __restrict__ comb_k, uint64_t* __restrict__ wave_times) {
@@ -134,7 +223,7 @@ static __global__ __launch_bounds__(64, 2) void k_msm_comb30(const uint64_t* __r
   const uint32_t lpg = lpb / g.G;
   const uint32_t grp = l / lpg;
   const uint32_t owner = split * lpg + l % lpg;
-  const uint32_t bpo = (64u * g.nb) / (splits * lpg);
+  const uint32_t bpo = comb_blocks_per_lane(g, splits, lpb);
   const uint32_t b0 = owner * bpo;
   const uint64_t* mrow = masks + blob * (64u * 256u);  // [plane][chunk]
   const uint32_t kbase = grp * g.H;
@@ -157,70 +246,29 @@ static __global__ __launch_bounds__(64, 2) void k_msm_comb30(const uint64_t* __r
     acc.inf = 0;
   }
 
-  CombWalker w;  // next mask to load
-  w.h = g.H - 1u;
-  w.s = 0;
-  w.q = b0 / nb;
-  w.r = b0 % nb;
-  auto advance = [&]() {
-    w.s++;
-    w.r++;
-    if (w.r == nb) {
-      w.r = 0;
-      w.q++;
-    }
-    if (w.s == bpo) {
-      w.s = 0;
-      w.h--;
-      w.q = b0 / nb;
-      w.r = b0 % nb;
-    }
-  };
-  // pipeline registers: mb* = mask(s) covering step t+1 with its walker position p1; (nx, ny) = table entry of step t.
-  // A lane's chunks are consecutive, so when they come in aligned groups of four (bpo a multiple of 4 nb: every production
-  // shape) the four masks are ONE 32-byte load per group instead of an 8-byte load per step: with [plane][chunk] rows a
-  // 128-byte line holds 16 chunks of one plane = 4 owners x 4 groups, and the table gathers (20 GB per launch through a
-  // 4-MB L2) evicted it between a lane's visits -- FETCH_SIZE counted 7.9 GB of mask re-fetches per 4,096 blobs.
-  const bool wide = (bpo % (4u * nb)) == 0u;
+  CombLane s;
+  s.mrow = mrow;
+  s.tgrp = tgrp;
+  s.nb = nb;
+  s.bpo = bpo;
+  s.b0 = b0;
+  s.kbase = kbase;
+  s.H = g.H;
+  s.ep64 = g.ep64;
+  s.wide = SHAPE == COMB_SHAPE_WIDE ? true : (SHAPE == COMB_SHAPE_NARROW ? false : comb_shape_is_wide(g, splits, lpb));
   const uint32_t q0 = b0 / nb;
-  uint64_t mb0 = 0, mb1 = 0, mb2 = 0, mb3 = 0;
-  auto fetch_mask = [&]() {  // the mask of the step at w; in wide mode only when w enters a new group of four chunks
-    if (wide) {
-      if (w.r == 0u && ((w.q - q0) & 3u) == 0u) {
-        const uint4* src = reinterpret_cast<const uint4*>(mrow + (kbase + w.h) * 64u + w.q);
-        const uint4 lo = src[0], hi = src[1];
-        mb0 = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
-        mb1 = (uint64_t)lo.z | ((uint64_t)lo.w << 32);
-        mb2 = (uint64_t)hi.x | ((uint64_t)hi.y << 32);
-        mb3 = (uint64_t)hi.z | ((uint64_t)hi.w << 32);
-      }
-    } else {
-      mb0 = mrow[(kbase + w.h) * 64u + w.q];
-    }
-  };
-  fetch_mask();
-  CombWalker p1 = w;
-  advance();
-  fp_t nx, ny;
-  bool nneg = false, ndbl = false;
-  uint32_t nidx = 0;
-  auto gather = [&]() {  // entry of the step at p1 from its mask
-    const uint32_t k = wide ? ((p1.q - q0) & 3u) : 0u;
-    const uint64_t m1 = k == 0u ? mb0 : (k == 1u ? mb1 : (k == 2u ? mb2 : mb3));
-    const uint32_t tb = comb_tbits(nb, p1.r);
-    const uint32_t pat = (uint32_t)(m1 >> comb_point_off(nb, p1.r)) & ((1u << tb) - 1u);
-    nneg = (pat >> (tb - 1u)) != 0u;  // top sign +1: the table holds the mirrored pattern, negated
-    const uint32_t m = nneg ? (~pat & ((1u << (tb - 1u)) - 1u)) : pat;
-    nidx = p1.q * g.ep64 + comb_entry_off(nb, p1.r) + m;
-    ndbl = (p1.s == 0u) && (p1.h != g.H - 1u);
-    load_affine96(nx, ny, tgrp, nidx);
-  };
-  gather();  // always before the next fetch_mask(): a new group's load overwrites masks whose patterns are already cut out
-  if (total > 1u) {
-    fetch_mask();
-    p1 = w;
-    advance();
-  }
+  s.q0e = q0 * g.ep64;
+  s.mlane = mrow + kbase * 64u + q0;
+  comb_walk_start(s.w, g.H);
+  s.lw.q = q0;
+  s.lw.r = b0 % nb;
+  s.lp1 = s.lw;
+  s.mb0 = s.mb1 = s.mb2 = s.mb3 = 0;
+  s.nneg = s.ndbl = false;
+  s.nidx = 0;
+  comb_next_mask(s);
+  comb_gather(s);  // always before the next mask: a new group's load overwrites masks whose patterns are already cut out
+  if (total > 1u) comb_next_mask(s);
 
   // The two waves of a SIMD trade issue priority every 2^g.fair shader cycles (issue_fair.cuh).  Measured at 4,096 blobs = one
   // round of 2,048 waves: left to the hardware the older wave of every pair finished after 18.0 ms and the younger after
@@ -230,16 +278,14 @@ static __global__ __launch_bounds__(64, 2) void k_msm_comb30(const uint64_t* __r
   for (uint32_t t = 0; t < total; t++) {
     if (g.fair) issue_fair_tick_low(g.fair);
     fp30 cx, cy;
-    f30_load_entry(cx, cy, nx.v, ny.v, xyzz30_entry_neg(acc, nneg));
-    const bool cneg = nneg, cdbl = ndbl;
-    const uint32_t cidx = nidx;
+    f30_load_entry(cx, cy, s.nx.v, s.ny.v, xyzz30_entry_neg(acc, s.nneg));
+    f30_pin(cx);  // unpacked before the gather below loads the next entry into the same registers
+    f30_pin(cy);
+    const bool cneg = s.nneg, cdbl = s.ndbl;
+    const uint32_t cidx = s.nidx;
     if (t + 1u < total) {
-      gather();
-      if (t + 2u < total) {
-        fetch_mask();
-        p1 = w;
-        advance();
-      }
+      comb_gather(s);
+      if (t + 2u < total) comb_next_mask(s);
     }
     if (cdbl && !acc.inf) {  // Horner step between two planes: out of line, on a copy (63 times per lane at G = 4)
       g1_xyzz30 tmp = acc;
