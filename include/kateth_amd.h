@@ -72,6 +72,8 @@ extern "C" {
 #define KZG_ERR_CELLS_INCONSISTENT 9         /* the present cells are not the evaluations of one polynomial of degree < 4096 */
 /* kzg_verify_cell_proof_batch only */
 #define KZG_ERR_CELL_INDEX 10                /* a cell index >= 128 */
+/* kzg_verify_cell_proof_batch_rows, kzg_cell_row_weights only */
+#define KZG_ERR_COMMITMENT_INDEX 11          /* a commitment index >= the number of commitments given */
 
 #define KZG_FAIL_ARGUMENT (-1)
 #define KZG_FAIL_HIP (-2)
@@ -499,13 +501,57 @@ int32_t kzg_ctx_g1_monomial(const kzg_ctx* ctx, uint32_t first, uint32_t count, 
  * On a GROUP context the host-buffer call cuts the batch into contiguous shares, one per member, like kzg_verify_proof_batch; every
  * member's partial second lincomb carries its own monomial terms, so the partials add.  The *_dev call acts on member 0.
  * Per-item verdicts: kzg_verify_cell_proof_batch_each[_dev], below with the other *_each calls.
- * Not here: a sharded phase-1 entry point for cells, a *_group_dev form, and deduplicating the commitments before they are decoded
- * (the decoder runs on 2n points where 128 cells of one blob need n + 1).
+ * Not here: a sharded phase-1 entry point for cells and a *_group_dev form.  A caller who holds a block's list of commitments and not
+ * one per cell uses kzg_verify_cell_proof_batch_rows, below: the commitments are decoded once each.
  */
 int32_t kzg_verify_cell_proof_batch(const kzg_ctx* ctx, const uint8_t* commitments48, const uint64_t* cell_indices, const uint8_t* cells /* n * 2048 */,
                                     const uint8_t* proofs48, uint64_t n, int32_t* ok);
 int32_t kzg_verify_cell_proof_batch_dev(const kzg_ctx* ctx, const void* d_commitments48, const void* d_cell_indices, const void* d_cells,
                                         const void* d_proofs48, uint64_t n, int32_t* ok, void* hip_stream);
+
+/*
+ * THE ROW-INDEXED FORM of kzg_verify_cell_proof_batch: what a PeerDAS node holds is a block's list of u commitments (one per blob) and
+ * column sidecars whose cells each belong to one of them -- the consensus specs' earlier argument shape (row_commitments, row_indices,
+ * column_indices, cells, proofs).  Tuple k is (commitments48[commitment_indices[k]], cell_indices[k], cells[k], proofs48[k]); the
+ * commitments are u x 48 bytes, both index arrays n native uint64, cells and proofs as above.  Device pointers (*_dev) are resident on
+ * ctx's device and 16-byte aligned.  u may exceed n, a commitment may be listed twice, and the point at infinity is a valid commitment.
+ *   The check: with w_c = sum_{k : commitment_indices[k] = c} r^k,  sum_k r^k C_{index_k} = sum_{c<u} w_c C_c, so it is the check above
+ *   with u commitment terms in place of n: the decoder runs on n + u points and the second lincomb has n + u + 64 terms.
+ *   The transcript: leaf k stays SHA-256(commitment48 || cell index || cell || proof48) with the commitment looked up through the index,
+ *   so root, seed and r are those of kzg_verify_cell_proof_batch on the expanded arrays and both sums are the same points: *ok and the
+ *   return code are EXACTLY that call's whenever every commitment index is in range and every listed commitment is referenced.  The
+ *   two calls are interchangeable.
+ *   n == 0   *ok = 1, whatever u is.  u == 0 with n > 0 returns KZG_ERR_COMMITMENT_INDEX without a launch.  A null required pointer with
+ *            n > 0 returns KZG_FAIL_ARGUMENT; commitments48 may be null only when u == 0.
+ *   rejected inputs: first-error-wins over four entries, in this order, the lowest position within the first entry that has an error:
+ *              1. indices, per item: commitment index >= u  KZG_ERR_COMMITMENT_INDEX, else cell index >= 128  KZG_ERR_CELL_INDEX
+ *                 (an item with a bad commitment index is hashed with commitment 0; nothing is read out of bounds)
+ *              2. commitments: ALL u, in list order, referenced or not   KZG_ERR_EC_* as kzg_g1_decompress_batch reports them
+ *              3. cell: an element >= r             KZG_ERR_BLOB_INVALID_FIELD_ELEMENT
+ *              4. proof                             KZG_ERR_EC_*
+ * On a GROUP context the host-buffer call cuts the ITEMS into the members' usual contiguous shares; every member gets all u
+ * commitments (each validates them: the merged record takes the list positions from the first share) and its slice of both index
+ * arrays; the powers of r run over global item indices.  The *_dev call acts on member 0.
+ * Cost of the weights: n u / 64 wave-steps of an index compare -- nothing for a block's shape (u up to a few hundred), about a
+ * millisecond in the degenerate u ~ n = 65,536 case: there, use the per-cell call.
+ * Not here: a *_each form (a caller who gets false expands the commitments and calls kzg_verify_cell_proof_batch_each), a *_group_dev
+ * form, and the GLV route (KATETH_AMD_VAR_GLV does not apply to this form).
+ */
+int32_t kzg_verify_cell_proof_batch_rows(const kzg_ctx* ctx, const uint8_t* commitments48 /* u * 48 */, uint64_t u, const uint64_t* commitment_indices /* n */,
+                                         const uint64_t* cell_indices /* n */, const uint8_t* cells /* n * 2048 */, const uint8_t* proofs48 /* n * 48 */,
+                                         uint64_t n, int32_t* ok);
+int32_t kzg_verify_cell_proof_batch_rows_dev(const kzg_ctx* ctx, const void* d_commitments48, uint64_t u, const void* d_commitment_indices,
+                                             const void* d_cell_indices, const void* d_cells, const void* d_proofs48, uint64_t n, int32_t* ok,
+                                             void* hip_stream);
+/*
+ * Introspection: the row-indexed form's commitment scalars.  out_w32[c] = sum_{k<n, commitment_indices[k] = c} r^(first_index + k) mod
+ * the group order, c < u, 32 bytes big-endian canonical; an unreferenced commitment gives zero.  It runs through the launch sequence
+ * phase 2 uses -- k_batch_scalars for the powers, then k_cells_row_weights and its reduce launch -- which pins that kernel exactly.
+ * Host memory in and out; synchronous; a group context answers from member 0.  r >= the modulus: KZG_ERR_FF_NOT_IN_FIELD; an index
+ * >= u: KZG_ERR_COMMITMENT_INDEX.
+ */
+int32_t kzg_cell_row_weights(const kzg_ctx* ctx, const uint8_t* r32, uint64_t first_index, const uint64_t* commitment_indices /* n, HOST */, uint64_t n,
+                             uint64_t u, uint8_t* out_w32 /* u * 32 */);
 
 /*
  * PER-ITEM VERDICTS: which items of a batch are bad.  What a caller of the reference does when Setup::verify_blob_proof_batch is

@@ -1,6 +1,8 @@
 // verify_cell_kzg_proof_batch (EIP-7594): the kernels of the cells kind of batch verification (compiled once: engine_verify.hip owns
 // this header).  k_cells_leaves is the front; k_cells_interp and k_cells_reduce run once the challenge r is known and leave the 64
-// scalars -S_j of lincomb B's monomial terms (arithmetic and layout: cellverify_math.cuh).  The per-item verdicts add k_cells_each_leaves,
+// scalars -S_j of lincomb B's monomial terms (arithmetic and layout: cellverify_math.cuh).  The row-indexed form
+// (kzg_verify_cell_proof_batch_rows) adds k_cells_rows_leaves, the front with the commitment read through an index, and
+// k_cells_row_weights / k_cells_roww_reduce, lincomb B's commitment scalars.  The per-item verdicts add k_cells_each_leaves,
 // k_each_vec_level and k_each_gather_cells (at the end of this file).
 #pragma once
 #include "cellverify_math.cuh"
@@ -18,15 +20,26 @@ namespace kzg {
 // words of the index (KZG_ERR_CELL_INDEX) and of the cell (KZG_ERR_BLOB_INVALID_FIELD_ELEMENT), and the leaf.
 // Like k_points_leaves it runs beside two decoder waves per SIMD: sha256_block_rolled, 64 VGPRs, no scratch.
 // hipcc -Rpass-analysis=kernel-resource-usage (gfx950): the figures are in DESIGN.md and asserted by tests/test_cellverify_host.py.
-static __global__ __launch_bounds__(256, 8) void k_cells_leaves(const uint8_t* __restrict__ commitments48, const unsigned long long* __restrict__ cell_indices,
-                                                                const uint8_t* __restrict__ cells, const uint8_t* __restrict__ proofs48, uint64_t n,
-                                                                const fr_t* __restrict__ h64_plain, fr_t* __restrict__ z_plain, fr_t* __restrict__ y_plain,
-                                                                int32_t* __restrict__ status_index, int32_t* __restrict__ status_cell,
-                                                                uint32_t* __restrict__ leaves /* n x 8 words */) {
+//
+// ROWS (k_cells_rows_leaves, the row-indexed form): the commitment is commitments48[commitment_indices[i]] of a list of `ncom` -- the
+// row index is read and the address formed right where the twelve words are loaded, so nothing of it lives through the hash; an index
+// >= ncom reads commitment 0 and is rejected below (KZG_ERR_COMMITMENT_INDEX, ahead of the cell index's code).  The body is shared;
+// k_cells_leaves is its ROWS = false instance and compiles to what it was.
+template <bool ROWS>
+__device__ __forceinline__ void cells_leaves_body(const uint8_t* __restrict__ commitments48, const unsigned long long* __restrict__ commitment_indices, uint64_t ncom,
+                                                  const unsigned long long* __restrict__ cell_indices, const uint8_t* __restrict__ cells,
+                                                  const uint8_t* __restrict__ proofs48, uint64_t n, const fr_t* __restrict__ h64_plain, fr_t* __restrict__ z_plain,
+                                                  fr_t* __restrict__ y_plain, int32_t* __restrict__ status_index, int32_t* __restrict__ status_cell,
+                                                  uint32_t* __restrict__ leaves /* n x 8 words */) {
   issue_priority_latency();
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t* c = reinterpret_cast<const uint32_t*>(commitments48 + i * 48);
+  uint64_t row = i;
+  if (ROWS) {
+    const unsigned long long r = commitment_indices[i];
+    row = r < ncom ? r : 0;
+  }
+  const uint32_t* c = reinterpret_cast<const uint32_t*>(commitments48 + row * 48);
   const uint4* cell = reinterpret_cast<const uint4*>(cells + i * (uint64_t)KZG_BYTES_PER_CELL);
   const unsigned long long index = cell_indices[i];
   // The range check rides on the words as they pass, most significant first: `cmp` is the comparison of the current element's words so
@@ -122,8 +135,59 @@ static __global__ __launch_bounds__(256, 8) void k_cells_leaves(const uint8_t* _
     zd[1] = make_uint4(h1.x & keep, h1.y & keep, h1.z & keep, h1.w & keep);
     yd[0] = zero;
     yd[1] = zero;
-    status_index[k] = good ? 0 : KZG_ERR_CELL_INDEX;
+    int32_t code = good ? 0 : KZG_ERR_CELL_INDEX;
+    if (ROWS && commitment_indices[k] >= ncom) code = KZG_ERR_COMMITMENT_INDEX;
+    status_index[k] = code;
   }
+}
+static __global__ __launch_bounds__(256, 8) void k_cells_leaves(const uint8_t* __restrict__ commitments48, const unsigned long long* __restrict__ cell_indices,
+                                                                const uint8_t* __restrict__ cells, const uint8_t* __restrict__ proofs48, uint64_t n,
+                                                                const fr_t* __restrict__ h64_plain, fr_t* __restrict__ z_plain, fr_t* __restrict__ y_plain,
+                                                                int32_t* __restrict__ status_index, int32_t* __restrict__ status_cell,
+                                                                uint32_t* __restrict__ leaves /* n x 8 words */) {
+  cells_leaves_body<false>(commitments48, nullptr, 0, cell_indices, cells, proofs48, n, h64_plain, z_plain, y_plain, status_index, status_cell, leaves);
+}
+// the row-indexed form's front (kzg_verify_cell_proof_batch_rows): the same budget beside two decoder waves, asserted by
+// tests/test_cellverify_rows_host.py
+static __global__ __launch_bounds__(256, 8) void k_cells_rows_leaves(const uint8_t* __restrict__ commitments48 /* ncom x 48 */,
+                                                                     const unsigned long long* __restrict__ commitment_indices, uint64_t ncom,
+                                                                     const unsigned long long* __restrict__ cell_indices, const uint8_t* __restrict__ cells,
+                                                                     const uint8_t* __restrict__ proofs48, uint64_t n, const fr_t* __restrict__ h64_plain,
+                                                                     fr_t* __restrict__ z_plain, fr_t* __restrict__ y_plain, int32_t* __restrict__ status_index,
+                                                                     int32_t* __restrict__ status_cell, uint32_t* __restrict__ leaves /* n x 8 words */) {
+  cells_leaves_body<true>(commitments48, commitment_indices, ncom, cell_indices, cells, proofs48, n, h64_plain, z_plain, y_plain, status_index, status_cell, leaves);
+}
+
+// The row-indexed form's commitment scalars  w_c = sum_{k : index_k = c} r^k  (cellverify_math.cuh), commitment-major: workgroup
+// (c, tile) -- lane t strides over the tile's indices (8-byte coalesced loads, the same lines for every c: the L2 serves them), adds
+// r^k (plain, k_batch_scalars' lincomb A scalar) on a match, then an LDS tree.  No atomics: every sum has a fixed order, and Fr addition
+// is exact, so any order gives the same canonical value.  An item whose index status is non-zero is skipped (an index >= ncom matches
+// no workgroup anyway); nothing is indexed BY an index.  n u / 64 wave-steps: nothing for a block's shape, about a millisecond at
+// u = n = 65,536, where the per-cell call is the one to use.
+static __global__ __launch_bounds__(CELLV_ROWW_THREADS) void k_cells_row_weights(const unsigned long long* __restrict__ commitment_indices,
+                                                                                 const int32_t* __restrict__ status_index /* null: none */,
+                                                                                 const fr_t* __restrict__ rpow_plain, uint64_t n, uint64_t tile,
+                                                                                 fr_t* __restrict__ partials /* gridDim.x x gridDim.y */) {
+  __shared__ fr_t red[CELLV_ROWW_THREADS];
+  const uint32_t t = threadIdx.x;
+  const uint64_t lo = (uint64_t)blockIdx.y * tile, hi = lo + tile < n ? lo + tile : n;
+  fr_t acc;
+  cellv_roww_thread(acc, commitment_indices, status_index, rpow_plain, lo, hi, t, (uint64_t)blockIdx.x);
+  red[t] = acc;
+  __syncthreads();
+  for (uint32_t w = CELLV_ROWW_THREADS / 2; w >= 1; w >>= 1) {
+    if (t < w) cellv_roww_fold(red, t, w);
+    __syncthreads();
+  }
+  if (t == 0) partials[(uint64_t)blockIdx.x * gridDim.y + blockIdx.y] = red[0];
+}
+// w_c = the sum of commitment c's tile partials in tile order, into lincomb B's commitment slots: one thread per commitment
+static __global__ __launch_bounds__(256) void k_cells_roww_reduce(const fr_t* __restrict__ partials, uint32_t tiles, uint64_t ncom, fr_t* __restrict__ out_plain) {
+  const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncom) return;
+  fr_t out;
+  cellv_roww_sum(out, partials + c * tiles, tiles);
+  out_plain[c] = out;
 }
 
 // elements 8 t .. 8 t + 7 of cell k as they lie in memory (256 consecutive bytes, big-endian) -> plain limbs; zero for a cell that

@@ -179,4 +179,46 @@ KZG_HD void cellv_neg_sum(fr_t& out, const fr_t* partials, uint32_t count, uint3
   fr_neg(out, acc);
 }
 
+// ---- the row-indexed form (kzg_verify_cell_proof_batch_rows): commitment c of a list of u takes ONE scalar in lincomb B ---------------
+//   w_c = sum over the items k with commitment index c of r^(first_index + k)        (zero for a commitment nobody references)
+// k_cells_row_weights runs one workgroup of CELLV_ROWW_THREADS threads per (commitment, tile of items): thread t takes the tile's items
+// t, t + 256, ..., a tree in LDS sums the threads, k_cells_roww_reduce sums a commitment's tiles.  All values plain and canonical:
+// fr_add is exact, every order gives the same value.  tests/hostcpp/cellv_rows.cpp walks these functions thread by thread.
+constexpr int CELLV_ROWW_THREADS = 256;
+// items per tile: at least 2,048 (eight per thread), a multiple of the workgroup, and never more than 32 tiles
+KZG_HD uint64_t cellv_roww_tile(uint64_t n) {
+  const uint64_t t = ((n + 31) / 32 + 255) / 256 * 256;
+  return t < 2048 ? 2048 : t;
+}
+KZG_HD uint32_t cellv_roww_tiles(uint64_t n) {
+  const uint64_t tile = cellv_roww_tile(n);
+  return (uint32_t)((n + tile - 1) / tile);
+}
+// thread t's sum over items lo + t, lo + t + 256, ... < hi of commitment c; status_index (may be null): items rejected for an index
+KZG_HD void cellv_roww_thread(fr_t& acc, const unsigned long long* commitment_indices, const int32_t* status_index, const fr_t* rpow_plain, uint64_t lo,
+                              uint64_t hi, uint32_t t, uint64_t c) {
+  KZG_UNROLL_FULL
+  for (int q = 0; q < 8; q++) acc.v[q] = 0;
+  for (uint64_t k = lo + t; k < hi; k += (uint64_t)CELLV_ROWW_THREADS) {
+    if (commitment_indices[k] != c) continue;
+    if (status_index && status_index[k] != 0) continue;
+    fr_add(acc, acc, rpow_plain[k]);
+  }
+}
+// one step of the tree: thread t < w adds its neighbour at distance w
+KZG_HD void cellv_roww_fold(fr_t* red, uint32_t t, uint32_t w) {
+  const fr_t a = red[t], b = red[t + w];
+  fr_t s;
+  fr_add(s, a, b);
+  red[t] = s;
+}
+// a commitment's tile partials in tile order
+KZG_HD void cellv_roww_sum(fr_t& out, const fr_t* partials, uint32_t tiles) {
+  fr_t acc;
+  KZG_UNROLL_FULL
+  for (int q = 0; q < 8; q++) acc.v[q] = 0;
+  for (uint32_t k = 0; k < tiles; k++) fr_add(acc, acc, partials[k]);
+  out = acc;
+}
+
 }  // namespace kzg

@@ -370,14 +370,21 @@ struct VerifyInputs {
   bool on_host;
   const uint64_t* cell_indices = nullptr;
   const uint8_t* cells = nullptr;
+  // CELLS, the row-indexed form (kzg_verify_cell_proof_batch_rows): commitments48 is a LIST of ncom points and item k's commitment is
+  // entry commitment_indices[k] of it.  Null: the per-cell form, one commitment per item.
+  const uint64_t* commitment_indices = nullptr;
+  uint64_t ncom = 0;
+  bool rows() const { return commitment_indices != nullptr; }
   bool any_null() const {
     return !commitments48 || !proofs48 || (kind == VerifyKind::BLOBS ? !blobs : kind == VerifyKind::POINTS ? (!z32 || !y32) : (!cell_indices || !cells));
   }
-  VerifyInputs advanced(uint64_t first) const {  // the same inputs from item `first` on
-    VerifyInputs a{kind, blobs ? blobs + first * (size_t)KZG_BYTES_PER_BLOB : nullptr, commitments48 + first * 48, proofs48 + first * 48,
+  VerifyInputs advanced(uint64_t first) const {  // the same inputs from item `first` on (the row-indexed form's commitment list stays whole)
+    VerifyInputs a{kind, blobs ? blobs + first * (size_t)KZG_BYTES_PER_BLOB : nullptr, rows() ? commitments48 : commitments48 + first * 48, proofs48 + first * 48,
                    z32 ? z32 + first * 32 : nullptr, y32 ? y32 + first * 32 : nullptr, on_host};
     a.cell_indices = cell_indices ? cell_indices + first : nullptr;
     a.cells = cells ? cells + first * (size_t)KZG_BYTES_PER_CELL : nullptr;
+    a.commitment_indices = rows() ? commitment_indices + first : nullptr;
+    a.ncom = ncom;
     return a;
   }
 };
@@ -391,6 +398,13 @@ static inline VerifyInputs cell_inputs(const void* commitments48, const void* ce
   VerifyInputs in{VerifyKind::CELLS, nullptr, (const uint8_t*)commitments48, (const uint8_t*)proofs48, nullptr, nullptr, on_host};
   in.cell_indices = (const uint64_t*)cell_indices;
   in.cells = (const uint8_t*)cells;
+  return in;
+}
+static inline VerifyInputs cell_rows_inputs(const void* commitments48, uint64_t ncom, const void* commitment_indices, const void* cell_indices, const void* cells,
+                                            const void* proofs48, bool on_host) {
+  VerifyInputs in = cell_inputs(commitments48, cell_indices, cells, proofs48, on_host);
+  in.commitment_indices = (const uint64_t*)commitment_indices;
+  in.ncom = ncom;
   return in;
 }
 // the wanted ending of a batch call: one boolean (no VerifyEach), or the per-item verdicts of kzg_verify_*_batch_each beside it

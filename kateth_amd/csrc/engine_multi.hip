@@ -92,6 +92,10 @@ int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t 
     if (hipSetDevice(m->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
     return verify_phase1(m, in.advanced(shares[j].first), shares[j].count, nullptr, roots.data() + 32 * (size_t)j, err.data() + stride * j, &sessions[j]);
   });
+  // the row-indexed cells form: every member validated the WHOLE commitment list, so that entry of a record carries list positions,
+  // not item positions -- it must not get a share's offset: the first share's (offset 0) stands for all
+  if (rc == 0 && in.rows())
+    for (uint32_t j = 1; j < W; j++) err[stride * j + 2] = -1;
   const int32_t code = rc ? 0 : merged_first_error(shares, err.data(), kinds);
   if (rc == 0 && code == 0)
     rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {

@@ -20,6 +20,12 @@
 struct kzg_verify_session {
   const kzg_ctx* ctx = nullptr;
   uint64_t n = 0;
+  // The commitments of the current use: ncom == n and rows == false in every form but the cells kind's row-indexed one
+  // (kzg_verify_cell_proof_batch_rows), where the call brings a LIST of ncom commitments and an index per item.  Wherever "proofs then
+  // commitments" are laid out the count is n + ncom; with ncom == n every size, offset and launch is the per-item form's.
+  uint64_t ncom = 0;
+  bool rows = false;
+  uint64_t stride = 0;         // words per status array: max(n, ncom)
   hipStream_t st = nullptr;    // the caller's stream of the current use
   hipStream_t side = nullptr;  // owned: the point decoder
   hipStream_t aux = nullptr;   // owned: lincomb A (the decoder may still hold `side` when its sorting starts)
@@ -29,20 +35,20 @@ struct kzg_verify_session {
   size_t cap = 0;
   VerifyKind kind = VerifyKind::BLOBS;  // set when the session is acquired: every kind-dependent site below reads verify_kind.hpp's row of it
   uint64_t tail = 1;       // facts(kind).tail_terms: lincomb B's terms behind the 2n points, the generator or the cells kind's 64 monomial points
-  uint4* aff = nullptr;    // [2n+tail] affine points: proofs, commitments, generator | monomial points
-  uint8_t* inf = nullptr;  // [2n+tail]
+  uint4* aff = nullptr;    // [n+ncom+tail] affine points: proofs, commitments, generator | monomial points
+  uint8_t* inf = nullptr;  // [n+ncom+tail]
   fr_t* z = nullptr;       // [n] plain
   fr_t* y = nullptr;       // [n] plain
-  fr_t* scal = nullptr;    // [2n+tail] plain: r_i*z_i (n), r_i (n), -sum r_i*y_i | cells: -S_j (64)
+  fr_t* scal = nullptr;    // [n+ncom+tail] plain: r_i*z_i (n), r_i (n) | rows: w_c (ncom), -sum r_i*y_i | cells: -S_j (64)
   bool glv = false;        // n >= 32,768: both lincombs on GLV-split scalars (use_glv)
   fr_t* glv_b = nullptr;   // [2 (2n+tail)]: k1 | k2 of scal
   fr_t* glv_a = nullptr;   // [2n]: k1 | k2 of the r_i
-  int32_t* stat = nullptr;   // [4n] one status array per entry of the kind's error record (stat_of)
+  int32_t* stat = nullptr;   // [4 stride] one status array per entry of the kind's error record (stat_of)
   unsigned long long* first4 = nullptr;  // verify_proof_batch: (index << 32) | code of the first rejected proof, commitment, z, y (k_first_errors)
   uint32_t* leaves = nullptr;  // transcript: n leaves, ceil(n / 16) mid digests, ceil(n / 256) nodes
   uint32_t* mids = nullptr;
   uint32_t* nodes = nullptr;
-  uint8_t* pts48 = nullptr;  // [2n * 48] device copy of proofs || commitments (host-buffer entry points)
+  uint8_t* pts48 = nullptr;  // [(n + ncom) * 48] device copy of proofs || commitments (host-buffer entry points)
   uint8_t* zy32 = nullptr;   // [2n * 32] device copy of z || y as given (host-buffer verify_proof_batch)
   uint8_t* msm_a = nullptr;  // scratch of the two lincomb MSMs (carved from buf: no allocation in phase 2)
   uint8_t* msm_b = nullptr;
@@ -57,7 +63,11 @@ struct kzg_verify_session {
   const uint8_t* d_cells = nullptr;  // the cells kind (front_enqueue records them): phase 2 reads the cells again
   const uint64_t* d_cell_indices = nullptr;
   fr_t* cell_part = nullptr;   // [ceil(n / CELLV_CELLS) x 64] k_cells_interp's partial coefficient vectors
-  uint8_t* cells_in = nullptr; // [n * 2048 | n * 8] device copy of cells || cell indices (host-buffer entry point)
+  uint8_t* cells_in = nullptr; // [n * 2048 | n * 8 | rows: n * 8] device copy of cells || cell indices || commitment indices (host-buffer entry point)
+  // the row-indexed form only: lincomb A's scalars r^k cannot live in B's commitment slots (those hold the ncom weights w_c)
+  const uint64_t* d_com_indices = nullptr;  // front_enqueue records them: phase 2 reads them again
+  fr_t* rpow = nullptr;        // [n] plain r^k: k_batch_scalars' sa, k_cells_interp's rpow_plain, lincomb A's scalars
+  fr_t* roww_part = nullptr;   // [ncom x cellv_roww_tiles(n)] k_cells_row_weights' tile partials
   // per-item verdicts (kzg_verify_*_batch_each, kzg_verify_session_tree): a device allocation of its own (owned), made on first use
   // and kept with the pooled session; carved by each_carve for the current n
   uint8_t* tree = nullptr;
@@ -86,7 +96,7 @@ static void session_free(kzg_verify_session* s) {
 // the status array of entry `entry` of the session's error record (verify_kind.hpp); null for an entry the record does not have
 static int32_t* stat_of(const kzg_verify_session* s, int entry) {
   const int slot = facts(s->kind).slot[entry];
-  return slot < 0 ? nullptr : s->stat + (uint64_t)slot * s->n;
+  return slot < 0 ? nullptr : s->stat + (uint64_t)slot * s->stride;
 }
 static const host::miller_lines& lines_against_a(const kzg_ctx* ctx, VerifyKind kind) {  // the G2 point of the pairing against A
   return facts(kind).pair_tau64 ? ctx->pairing->lines_tau64 : ctx->pairing->lines_tau;
@@ -156,7 +166,9 @@ struct SessionUse {
 // workgroups whether there are 260 or 130 of them, and half the windows means half as many bucket THREADS with chains twice as
 // long (A: 40,960 threads x 32 entries instead of 81,920 x 16 on a chip with 131,072 lanes at this register budget): the bucket
 // kernels went from 1.13 / 0.53 ms to 1.43 / 1.26 ms, against 0.1 ms saved in the host's Horner loops.
-static bool use_glv(const kzg_ctx* ctx, uint64_t n_items) { return n_items >= 32768 && !ctx->knobs.var_msm_classic && ctx->knobs.var_glv; }
+static bool use_glv(const kzg_ctx* ctx, uint64_t n_items, bool rows = false) {  // not for the cells kind's row-indexed form
+  return !rows && n_items >= 32768 && !ctx->knobs.var_msm_classic && ctx->knobs.var_glv;
+}
 // seg_total: the terms of ALL the lincombs whose bucket kernels run side by side (batch verification: n + 2 n + 1), so that their
 // lanes together are one round of the chip: 0 = this lincomb alone.
 static VarGeom choose_var_geom(const kzg_ctx* ctx, uint64_t nterms, bool glv = false, uint64_t seg_total = 0) {
@@ -451,52 +463,60 @@ static void scan_first_error(const int32_t* st, uint64_t n, int32_t* idx, int32_
 // ---- session set-up -----------------------------------------------------------------------------------------------
 struct SessionLayout {
   size_t o_aff, o_inf, o_z, o_y, o_scal, o_glv_b, o_glv_a, o_stat, o_first4, o_leaves, o_mids, o_nodes, o_pts, o_zy, o_msm_a, o_msm_b, o_rpow, o_ysum, o_cell_part,
-      o_cells_in, total;
+      o_cells_in, o_rpow_n, o_roww, total;
 };
 // `staged`: room for the device copies of a host-buffer cells call's cells and indices (points_stage_host); the other kinds have nothing
 // that is carved on demand.  With one tail term the layout of the blob and points kinds is what it always was.
-static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n, VerifyKind kind, bool staged) {
+// `rows`: the cells kind's row-indexed form with a list of `ncom` commitments (n otherwise): n + ncom points, status arrays of
+// max(n, ncom) words, and behind everything else the n powers r^k and the weights' tile partials.
+static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n, VerifyKind kind, bool staged, bool rows, uint64_t ncom) {
   SessionLayout L{};
   const bool is_cells = kind == VerifyKind::CELLS;
+  const uint64_t np = n + ncom, stride = std::max(n, ncom);  // proofs then commitments
   const uint64_t tail = facts(kind).tail_terms;
   const uint64_t groups = (n + 255) / 256;
   Carve pool;
-  const bool glv = use_glv(ctx, n);
-  L.o_aff = pool.take((glv ? 2 : 1) * (2 * n + tail) * 96);  // GLV: the [z^2]-images behind the points
-  L.o_inf = pool.take(2 * n + tail);
+  const bool glv = use_glv(ctx, n, rows);
+  L.o_aff = pool.take((glv ? 2 : 1) * (np + tail) * 96);  // GLV: the [z^2]-images behind the points
+  L.o_inf = pool.take(np + tail);
   L.o_z = pool.take(n * 32 + 32);
   L.o_y = pool.take(n * 32 + 32);
-  L.o_scal = pool.take((2 * n + tail) * 32);
-  L.o_glv_b = pool.take(glv ? 2 * (2 * n + tail) * 32 : 0);
+  L.o_scal = pool.take((np + tail) * 32);
+  L.o_glv_b = pool.take(glv ? 2 * (np + tail) * 32 : 0);
   L.o_glv_a = pool.take(glv ? 2 * n * 32 : 0);
-  L.o_stat = pool.take(4 * n * 4 + 4);
+  L.o_stat = pool.take(4 * stride * 4 + 4);
   L.o_first4 = pool.take(4 * sizeof(unsigned long long));
   L.o_leaves = pool.take(n * 32 + 32);
   L.o_mids = pool.take((n / 16 + 1) * 32 + 32);
   L.o_nodes = pool.take(groups * 32 + 32);
-  L.o_pts = pool.take(2 * n * 48 + 48);
+  L.o_pts = pool.take(np * 48 + 48);
   L.o_zy = pool.take(2 * n * 32 + 32);
-  L.o_msm_a = pool.take((glv ? msm_var_layout(ctx, 2 * n, true) : msm_var_layout(ctx, n, false, 3 * n + tail)).total + 256);
-  L.o_msm_b = pool.take((glv ? msm_var_layout(ctx, 2 * (2 * n + tail), true) : msm_var_layout(ctx, 2 * n + tail, false, 3 * n + tail)).total + 256);
+  L.o_msm_a = pool.take((glv ? msm_var_layout(ctx, 2 * n, true) : msm_var_layout(ctx, n, false, n + np + tail)).total + 256);
+  L.o_msm_b = pool.take((glv ? msm_var_layout(ctx, 2 * (np + tail), true) : msm_var_layout(ctx, np + tail, false, n + np + tail)).total + 256);
   L.o_rpow = pool.take(64 * 32);
   L.o_ysum = pool.take(((n + 255) / 256 + 1) * 32);
   L.o_cell_part = pool.take(is_cells ? blocks_for(n, CELLV_CELLS) * (size_t)64 * sizeof(fr_t) : 0);
-  L.o_cells_in = pool.take(is_cells && staged ? n * ((size_t)KZG_BYTES_PER_CELL + 8) : 0);
+  L.o_cells_in = pool.take(is_cells && staged ? n * ((size_t)KZG_BYTES_PER_CELL + 8 + (rows ? 8 : 0)) : 0);
+  L.o_rpow_n = pool.take(rows ? n * 32 : 0);
+  L.o_roww = pool.take(rows ? ncom * (size_t)cellv_roww_tiles(n) * 32 : 0);
   L.total = pool.off;
   return L;
 }
 
 // Takes a session from the context's pool (or creates one), sized for n items of `kind`, and enqueues its initialisation on `st`.
-// `staged`: session_layout's.  The caller has set the device.
-static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, VerifyKind kind, bool staged, kzg_verify_session** out) {
+// `staged`: session_layout's; `rows_ncom`: null, or the commitment count of the cells kind's row-indexed form.  The caller has set the device.
+static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, VerifyKind kind, bool staged, kzg_verify_session** out,
+                               const uint64_t* rows_ncom = nullptr) {
   *out = nullptr;
   const bool is_cells = kind == VerifyKind::CELLS;
+  const bool rows = rows_ncom != nullptr;
+  const uint64_t ncom = rows ? *rows_ncom : n, np = n + ncom;
   if (is_cells) {  // lincomb B's fixed terms, copied in below: derived by this member's first cells session
     const int32_t rc = ensure_g1_monomial(ctx);
     if (rc) return rc;
   }
   const uint64_t tail = facts(kind).tail_terms;
-  const SessionLayout L = session_layout(ctx, n, kind, staged);
+  const SessionLayout L = session_layout(ctx, n, kind, staged, rows, ncom);
   kzg_verify_session* s = nullptr;
   {
     std::lock_guard<std::mutex> guard(ctx->pool_lock);
@@ -566,18 +586,22 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, V
   }
   if (st == KZG_SESSION_STREAM) st = s->side;
   s->n = n;
+  s->ncom = ncom;
+  s->rows = rows;
+  s->stride = std::max(n, ncom);
   s->st = st;
   s->kind = kind;
   s->tail = tail;
   s->d_cells = nullptr;
   s->d_cell_indices = nullptr;
+  s->d_com_indices = nullptr;
   s->tree_n = 0;
   s->aff = (uint4*)(s->buf + L.o_aff);
   s->inf = s->buf + L.o_inf;
   s->z = (fr_t*)(s->buf + L.o_z);
   s->y = (fr_t*)(s->buf + L.o_y);
   s->scal = (fr_t*)(s->buf + L.o_scal);
-  s->glv = use_glv(ctx, n);
+  s->glv = use_glv(ctx, n, rows);
   s->glv_b = (fr_t*)(s->buf + L.o_glv_b);
   s->glv_a = (fr_t*)(s->buf + L.o_glv_a);
   s->stat = (int32_t*)(s->buf + L.o_stat);
@@ -593,11 +617,13 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, V
   s->ysum = (fr_t*)(s->buf + L.o_ysum);
   s->cell_part = (fr_t*)(s->buf + L.o_cell_part);
   s->cells_in = s->buf + L.o_cells_in;
+  s->rpow = (fr_t*)(s->buf + L.o_rpow_n);
+  s->roww_part = (fr_t*)(s->buf + L.o_roww);
   // generator term (cells: the monomial terms), cleared flags and statuses
   const uint4* fixed = is_cells ? ctx->d_g1_monomial : ctx->d_gen_affine;  // `tail` points, their [z^2]-images behind them
-  if (hipMemcpyAsync(s->aff + (2 * n) * 6, fixed, tail * 96, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-      (s->glv && hipMemcpyAsync(s->aff + ((2 * n + tail) + 2 * n) * 6, fixed + tail * 6, tail * 96, hipMemcpyDeviceToDevice, st) != hipSuccess) ||  // [z^2]G
-      hipMemsetAsync(s->inf, 0, 2 * n + tail, st) != hipSuccess || hipMemsetAsync(s->stat, 0, 4 * n * 4 + 4, st) != hipSuccess) {
+  if (hipMemcpyAsync(s->aff + np * 6, fixed, tail * 96, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+      (s->glv && hipMemcpyAsync(s->aff + ((np + tail) + np) * 6, fixed + tail * 6, tail * 96, hipMemcpyDeviceToDevice, st) != hipSuccess) ||  // [z^2]G
+      hipMemsetAsync(s->inf, 0, np + tail, st) != hipSuccess || hipMemsetAsync(s->stat, 0, 4 * s->stride * 4 + 4, st) != hipSuccess) {
     kzg_verify_session_destroy(s);
     return fail(KZG_FAIL_HIP, "verify session init failed");
   }
@@ -611,24 +637,25 @@ static bool one_item_on_host(const kzg_verify_session* s) { return s->n == 1 && 
 
 // The point decoder beside the caller's stream.  `side` -- the session's side stream, or the caller's own under verify_serial -- waits
 // for what the caller's stream holds at the fork (ev_fork: session initialised, inputs resident) and decodes points
-// [first, first + count) of the 2n: proofs, then commitments.  `how`:
+// [first, first + count) of the n + ncom: proofs, then commitments.  `how`:
 //   DECODE_FORKED  the caller recorded ev_fork itself, earlier on its stream (phase1_items: ahead of the hash)
 //   DECODE_WHOLE   all 2n points with the one-launch decoder (k_g1_decompress) instead of a range
 //   DECODE_FINISH  nothing is decoded after this: the [z^2]-images under GLV right behind the decoder (one product per point), then ev_join
 enum : unsigned { DECODE_FORKED = 1u, DECODE_WHOLE = 2u, DECODE_FINISH = 4u };
 static void decode_on_side(kzg_verify_session* s, hipStream_t side, uint64_t first, uint64_t count, const uint8_t* prf, const uint8_t* com, unsigned how) {
-  const uint64_t n = s->n;
+  const uint64_t n = s->n, nc = s->ncom, np = n + nc;
+  int32_t *stat_prf = s->stat + 2 * s->stride, *stat_com = s->stat + s->stride;  // slots 2 and 1 in every kind (verify_kind.hpp)
   if (!(how & DECODE_FORKED)) (void)hipEventRecord(s->ev_fork, s->st);
   (void)hipStreamWaitEvent(side, s->ev_fork, 0);
   {
     ProfScope ps(s->ctx, PROF_DECODE, side);
     if (how & DECODE_WHOLE)
-      launch_g1_decompress(side, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
+      launch_g1_decompress(side, prf, n, stat_prf, com, nc, stat_com, s->aff, s->inf);
     else
-      launch_g1_decompress_range(side, first, count, prf, n, s->stat + 2 * n, com, n, s->stat + n, s->aff, s->inf);
+      launch_g1_decompress_range(side, first, count, prf, n, stat_prf, com, nc, stat_com, s->aff, s->inf);
   }
   if (!(how & DECODE_FINISH)) return;
-  if (s->glv) hipLaunchKernelGGL(k_glv_points, dim3(blocks_for(2 * n, 64)), dim3(64), 0, side, s->aff, 2 * n, 2 * n + s->tail);
+  if (s->glv) hipLaunchKernelGGL(k_glv_points, dim3(blocks_for(np, 64)), dim3(64), 0, side, s->aff, np, np + s->tail);
   (void)hipEventRecord(s->ev_join, side);
 }
 
@@ -727,7 +754,9 @@ static VerifyInputs staged_inputs(const kzg_verify_session* s) {
     case VerifyKind::POINTS: return point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32, false);
     case VerifyKind::CELLS: break;
   }
-  return cell_inputs(s->pts48 + n * 48, s->cells_in + n * (size_t)KZG_BYTES_PER_CELL, s->cells_in, s->pts48, false);
+  const uint8_t* idx = s->cells_in + n * (size_t)KZG_BYTES_PER_CELL;
+  if (s->rows) return cell_rows_inputs(s->pts48 + n * 48, s->ncom, idx + n * 8, idx, s->cells_in, s->pts48, false);
+  return cell_inputs(s->pts48 + n * 48, idx, s->cells_in, s->pts48, false);
 }
 static void err_clear(int32_t* err, int kinds) {
   for (int k = 0; k < 2 * kinds; k++) err[k] = (k % 2 == 0) ? -1 : 0;
@@ -761,11 +790,16 @@ static int32_t front_enqueue(kzg_verify_session* s, const VerifyInputs& in) {
       // z = h^64 and y = 0, and hashes the 34-block leaf; the cells are read again in phase 2
       s->d_cells = in.cells;
       s->d_cell_indices = in.cell_indices;
+      s->d_com_indices = in.commitment_indices;
       // the decoder is ONE launch over proofs and commitments: no event after the proof half for lincomb A to wait on instead of ev_join
-      decode_on_side(s, s->side, 0, 2 * n, prf, com, DECODE_FINISH | (fused_prep_fits(ctx, n, 2 * n) ? DECODE_WHOLE : 0u));
+      decode_on_side(s, s->side, 0, n + s->ncom, prf, com, DECODE_FINISH | (fused_prep_fits(ctx, n, n + s->ncom) ? DECODE_WHOLE : 0u));
       if (hipMemsetAsync(s->first4, 0xff, 4 * sizeof(unsigned long long), s->side) != hipSuccess)  // for k_first_errors, later on this stream
         return fail(KZG_FAIL_HIP, "verify_proof_batch: fork failed");
-      if (s->kind == VerifyKind::CELLS)
+      if (s->rows)  // the row-indexed form: the commitment through the item's index, the index's status with the cell index's
+        hipLaunchKernelGGL(k_cells_rows_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, reinterpret_cast<const unsigned long long*>(in.commitment_indices),
+                           s->ncom, reinterpret_cast<const unsigned long long*>(in.cell_indices), in.cells, prf, n, ctx->d_cellv_h64, s->z, s->y,
+                           stat_of(s, kzg::verify::CELLS_INDEX), stat_of(s, kzg::verify::CELLS_CELL), s->leaves);
+      else if (s->kind == VerifyKind::CELLS)
         hipLaunchKernelGGL(k_cells_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, reinterpret_cast<const unsigned long long*>(in.cell_indices), in.cells, prf, n,
                            ctx->d_cellv_h64, s->z, s->y, stat_of(s, kzg::verify::CELLS_INDEX), stat_of(s, kzg::verify::CELLS_CELL), s->leaves);
       else
@@ -794,7 +828,9 @@ static int32_t front_status(kzg_verify_session* s, int32_t* err) {
     case VerifyKind::POINTS:
     case VerifyKind::CELLS:
       if (hipStreamWaitEvent(side, s->ev_nodes, 0) != hipSuccess) return fail(KZG_FAIL_HIP, "verify_proof_batch: status wait failed");
-      hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(n, 256)), dim3(256), 0, side, stat_of(s, 0), stat_of(s, 1), stat_of(s, 2), stat_of(s, 3), n, s->first4);
+      // over the arrays' stride: the row-indexed form's commitment statuses are ncom words, which may be more than n (the rest is clear)
+      hipLaunchKernelGGL(k_first_errors, dim3(blocks_for(s->stride, 256)), dim3(256), 0, side, stat_of(s, 0), stat_of(s, 1), stat_of(s, 2), stat_of(s, 3), s->stride,
+                         s->first4);
       if (hipGetLastError() != hipSuccess || hipMemcpyAsync(s->h_first4, s->first4, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, side) != hipSuccess ||
           hipEventRecord(s->ev_stat, side) != hipSuccess || hipEventSynchronize(s->ev_stat) != hipSuccess)
         return fail(KZG_FAIL_HIP, "verify_proof_batch: status readback failed");
@@ -920,11 +956,13 @@ static int32_t points_stage_host(const kzg_ctx* ctx, const VerifyInputs& in, uin
   }
   SessionUse use;
   const bool is_cells = in.kind == VerifyKind::CELLS;
-  const int32_t rc = session_acquire(ctx, n, ctx->verify_stream, in.kind, true, &use.s);
+  const int32_t rc = session_acquire(ctx, n, ctx->verify_stream, in.kind, true, &use.s, in.rows() ? &in.ncom : nullptr);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   if (hipMemcpyAsync(s->pts48, in.proofs48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-      hipMemcpyAsync(s->pts48 + n * 48, in.commitments48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess)
+      hipMemcpyAsync(s->pts48 + n * 48, in.commitments48, s->ncom * 48, hipMemcpyHostToDevice, s->st) != hipSuccess)
+    return fail(KZG_FAIL_HIP, "host-to-device copy failed");
+  if (s->rows && hipMemcpyAsync(s->cells_in + n * ((size_t)KZG_BYTES_PER_CELL + 8), in.commitment_indices, n * 8, hipMemcpyHostToDevice, s->st) != hipSuccess)
     return fail(KZG_FAIL_HIP, "host-to-device copy failed");
   if (is_cells ? (hipMemcpyAsync(s->cells_in, in.cells, n * (size_t)KZG_BYTES_PER_CELL, hipMemcpyHostToDevice, s->st) != hipSuccess ||
                hipMemcpyAsync(s->cells_in + n * (size_t)KZG_BYTES_PER_CELL, in.cell_indices, n * 8, hipMemcpyHostToDevice, s->st) != hipSuccess)
@@ -945,7 +983,7 @@ int32_t verify_phase1(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hi
   TraceTimer tt(ctx->knobs.trace, "phase1");
   err_clear(err, facts(in.kind).entries);
   SessionUse use;
-  int32_t rc = in.on_host ? points_stage_host(ctx, in, n, &use.s) : session_acquire(ctx, n, st, in.kind, false, &use.s);
+  int32_t rc = in.on_host ? points_stage_host(ctx, in, n, &use.s) : session_acquire(ctx, n, st, in.kind, false, &use.s, in.rows() ? &in.ncom : nullptr);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   tt.mark("session");
@@ -1147,16 +1185,26 @@ static int32_t p2_scalars(kzg_verify_session* s, const uint8_t* roots32, uint64_
   const int32_t rc = p2_seed(s, roots32, world, n_total);
   if (rc) return rc;
   const unsigned nblk = blocks_for(n, 256);
-  hipLaunchKernelGGL(k_batch_scalars, dim3(nblk), dim3(256), 0, st, s->rpow2, s->z, s->y, n, first_index, s->scal + n, s->scal, s->ysum);
+  // lincomb A's scalars r^k: B's commitment slots, or in the row-indexed form (whose ncom slots take the weights) an array of their own
+  fr_t* rk = s->rows ? s->rpow : s->scal + n;
+  fr_t* tail_scal = s->scal + n + s->ncom;
+  hipLaunchKernelGGL(k_batch_scalars, dim3(nblk), dim3(256), 0, st, s->rpow2, s->z, s->y, n, first_index, rk, s->scal, s->ysum);
+  if (s->rows) {  // w_c = sum of the r^k whose item points at commitment c: B's ncom commitment scalars
+    const uint32_t tiles = cellv_roww_tiles(n);
+    ProfScope ps(s->ctx, PROF_POLY, st);  // no class of their own: a verification call launches nothing else of the k_poly class
+    hipLaunchKernelGGL(k_cells_row_weights, dim3((unsigned)s->ncom, tiles), dim3(CELLV_ROWW_THREADS), 0, st, reinterpret_cast<const unsigned long long*>(s->d_com_indices),
+                       stat_of(s, kzg::verify::CELLS_INDEX), rk, n, cellv_roww_tile(n), s->roww_part);
+    hipLaunchKernelGGL(k_cells_roww_reduce, dim3(blocks_for(s->ncom, 256)), dim3(256), 0, st, s->roww_part, tiles, s->ncom, s->scal + n);
+  }
   if (s->kind == VerifyKind::CELLS) {
     // y = 0: the generator's slot is S_0's.  The 64 scalars -S_j of the monomial terms: r^k (s->scal + n, just written) times the
     // interpolation polynomial of cell k, summed per workgroup, then over the workgroups
     const unsigned ngrp = blocks_for(n, CELLV_CELLS);
     hipLaunchKernelGGL(k_cells_interp, dim3(ngrp), dim3(CELLV_THREADS), 0, st, s->d_cells, reinterpret_cast<const unsigned long long*>(s->d_cell_indices),
-                       stat_of(s, kzg::verify::CELLS_INDEX), stat_of(s, kzg::verify::CELLS_CELL), s->scal + n, n, s->ctx->d_cells_tab, s->ctx->d_cellv_tab, s->cell_part);
-    hipLaunchKernelGGL(k_cells_reduce, dim3(1), dim3(256), 0, st, s->cell_part, ngrp, s->scal + 2 * n);
+                       stat_of(s, kzg::verify::CELLS_INDEX), stat_of(s, kzg::verify::CELLS_CELL), rk, n, s->ctx->d_cells_tab, s->ctx->d_cellv_tab, s->cell_part);
+    hipLaunchKernelGGL(k_cells_reduce, dim3(1), dim3(256), 0, st, s->cell_part, ngrp, tail_scal);
   } else {
-    hipLaunchKernelGGL(k_batch_ysum_finish, dim3(1), dim3(256), 0, st, s->ysum, nblk, s->scal + 2 * n);
+    hipLaunchKernelGGL(k_batch_ysum_finish, dim3(1), dim3(256), 0, st, s->ysum, nblk, tail_scal);
   }
   if (s->glv) hipLaunchKernelGGL(k_glv_split, dim3(blocks_for(2 * n + s->tail, 256)), dim3(256), 0, st, s->scal, n, s->tail, s->glv_b, s->glv_a);
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "verify phase 2 launch failed");
@@ -1168,7 +1216,7 @@ static int32_t p2_scalars(kzg_verify_session* s, const uint8_t* roots32, uint64_
 //     infinity flags (which the decoder may not have written yet).
 static int32_t p2_sort(kzg_verify_session* s, Phase2& p2, bool beside_decoder) {
   const kzg_ctx* ctx = s->ctx;
-  const uint64_t n = s->n, nb = 2 * n + s->tail;  // lincomb B's terms
+  const uint64_t n = s->n, nb = n + s->ncom + s->tail;  // lincomb B's terms
   (void)hipEventRecord(s->ev_aux, s->st);
   (void)hipStreamWaitEvent(s->aux, s->ev_aux, 0);
   const uint8_t* inf = beside_decoder ? nullptr : s->inf;
@@ -1190,7 +1238,7 @@ static int32_t p2_sort(kzg_verify_session* s, Phase2& p2, bool beside_decoder) {
   }
   if (rc == 0) {
     ProfScope psa(ctx, PROF_VAR_MSM, s->aux);
-    rc = msm_var_sort(ctx, p2.ja, inf, s->scal + n, n, s->aux, s->msm_a, beside_decoder, false, 0, 0, n + nb);
+    rc = msm_var_sort(ctx, p2.ja, inf, s->rows ? s->rpow : s->scal + n, n, s->aux, s->msm_a, beside_decoder, false, 0, 0, n + nb);
   }
   return rc;
 }
@@ -1847,7 +1895,7 @@ int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t
   const bool front_done = in.on_host && blobs;
   int32_t rc = front_done   ? verify_phase1_host(ctx, in.blobs, in.commitments48, in.proofs48, n, root, each ? err6 : nullptr, &use.s)
                : in.on_host ? points_stage_host(ctx, in, n, &use.s)
-                            : session_acquire(ctx, n, st, in.kind, false, &use.s);
+                            : session_acquire(ctx, n, st, in.kind, false, &use.s, in.rows() ? &in.ncom : nullptr);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   const VerifyInputs dev = in.on_host ? staged_inputs(s) : in;
@@ -1907,6 +1955,90 @@ extern "C" int32_t kzg_verify_cell_proof_batch_dev(const kzg_ctx* ctx, const voi
 extern "C" int32_t kzg_verify_cell_proof_batch(const kzg_ctx* ctx, const uint8_t* commitments48, const uint64_t* cell_indices, const uint8_t* cells,
                                                const uint8_t* proofs48, uint64_t n, int32_t* ok) try {
   return batch_entry(ctx, cell_inputs(commitments48, cell_indices, cells, proofs48, true), n, nullptr, ok, nullptr);
+} catch (...) {
+  return abi_exception();
+}
+
+// ---- the row-indexed form: a block's list of u commitments and an index per item (include/kateth_amd.h) ------------------------------
+// The cells kind with ncom = u in the session: the front reads the commitment through the index (k_cells_rows_leaves), the decoder runs
+// on n + u points, lincomb B has n + u + 64 terms whose u commitment scalars are the weights w_c (k_cells_row_weights), and lincomb A's
+// scalars r^k live in an array of their own.  Transcript, r and both sums are the per-cell call's on the expanded arrays.
+static int32_t rows_entry(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, int32_t* ok, hipStream_t st) {
+  if (!ctx || !ok) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (n == 0) return empty_batch(ok);
+  *ok = 0;
+  if (!in.commitment_indices || !in.cell_indices || !in.cells || !in.proofs48 || (in.ncom && !in.commitments48)) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (in.ncom == 0) return KZG_ERR_COMMITMENT_INDEX;  // every index is out of range: nothing is launched
+  if (in.ncom >> 31) return fail(KZG_FAIL_ARGUMENT, "too many commitments");  // one workgroup column per commitment
+  return batch_entry(ctx, in, n, nullptr, ok, st);
+}
+extern "C" int32_t kzg_verify_cell_proof_batch_rows(const kzg_ctx* ctx, const uint8_t* commitments48, uint64_t u, const uint64_t* commitment_indices,
+                                                    const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs48, uint64_t n, int32_t* ok) try {
+  return rows_entry(ctx, cell_rows_inputs(commitments48, u, commitment_indices, cell_indices, cells, proofs48, true), n, ok, nullptr);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_verify_cell_proof_batch_rows_dev(const kzg_ctx* ctx, const void* d_commitments48, uint64_t u, const void* d_commitment_indices,
+                                                        const void* d_cell_indices, const void* d_cells, const void* d_proofs48, uint64_t n, int32_t* ok,
+                                                        void* hip_stream) try {
+  return rows_entry(ctx, cell_rows_inputs(d_commitments48, u, d_commitment_indices, d_cell_indices, d_cells, d_proofs48, false), n, ok, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+
+// Introspection: the weights through phase 2's launch sequence -- k_batch_scalars (with z = y = 0: only its r^k are read), then
+// k_cells_row_weights and its reduce launch.  Scratch of its own, freed here; member 0 of a group.
+extern "C" int32_t kzg_cell_row_weights(const kzg_ctx* ctx, const uint8_t* r32, uint64_t first_index, const uint64_t* commitment_indices, uint64_t n, uint64_t u,
+                                        uint8_t* out_w32) try {
+  if (!ctx || !r32 || (n && !commitment_indices) || (u && !out_w32)) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  fr_t r;
+  fr_from_be_bytes_plain(r, r32);
+  if (!fr_is_canonical(r)) return KZG_ERR_FF_NOT_IN_FIELD;
+  for (uint64_t k = 0; k < n; k++)
+    if (commitment_indices[k] >= u) return KZG_ERR_COMMITMENT_INDEX;
+  if (u == 0) return 0;
+  if (n == 0) {
+    memset(out_w32, 0, (size_t)u * 32);
+    return 0;
+  }
+  if (u >> 31) return fail(KZG_FAIL_ARGUMENT, "too many commitments");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const uint32_t tiles = cellv_roww_tiles(n);
+  const unsigned nblk = blocks_for(n, 256);
+  Carve c;
+  const size_t o_rpow2 = c.take(64 * sizeof(fr_t)), o_zero = c.take(n * sizeof(fr_t)), o_rk = c.take(n * sizeof(fr_t)), o_sb = c.take(n * sizeof(fr_t)),
+               o_ysum = c.take(((size_t)nblk + 1) * sizeof(fr_t)), o_idx = c.take(n * 8), o_part = c.take((size_t)u * tiles * sizeof(fr_t)),
+               o_w = c.take((size_t)u * sizeof(fr_t));
+  struct Scratch {
+    uint8_t* p = nullptr;
+    ~Scratch() {
+      if (p) (void)hipFree(p);
+    }
+  } d;
+  HIP_TRY(hipMalloc(&d.p, c.off));
+  to_mont<FrParams>(r, r);
+  fr_t rpow2[64];
+  rpow2[0] = r;
+  for (int k = 1; k < 64; k++) fr_sqr(rpow2[k], rpow2[k - 1]);
+  hipStream_t st = nullptr;  // an introspection call, waited for here
+  fr_t *d_rpow2 = (fr_t*)(d.p + o_rpow2), *d_zero = (fr_t*)(d.p + o_zero), *d_rk = (fr_t*)(d.p + o_rk), *d_sb = (fr_t*)(d.p + o_sb), *d_ysum = (fr_t*)(d.p + o_ysum),
+       *d_part = (fr_t*)(d.p + o_part), *d_w = (fr_t*)(d.p + o_w);
+  unsigned long long* d_idx = (unsigned long long*)(d.p + o_idx);
+  HIP_TRY(hipMemcpyAsync(d_rpow2, rpow2, sizeof(rpow2), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_idx, commitment_indices, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(d_zero, 0, n * sizeof(fr_t), st));
+  hipLaunchKernelGGL(k_batch_scalars, dim3(nblk), dim3(256), 0, st, d_rpow2, d_zero, d_zero, n, first_index, d_rk, d_sb, d_ysum);
+  {
+    ProfScope ps(ctx, PROF_POLY, st);
+    hipLaunchKernelGGL(k_cells_row_weights, dim3((unsigned)u, tiles), dim3(CELLV_ROWW_THREADS), 0, st, d_idx, (const int32_t*)nullptr, d_rk, n, cellv_roww_tile(n), d_part);
+    hipLaunchKernelGGL(k_cells_roww_reduce, dim3(blocks_for(u, 256)), dim3(256), 0, st, d_part, tiles, u, d_w);
+  }
+  HIP_TRY(hipGetLastError());
+  std::vector<fr_t> w(u);
+  HIP_TRY(hipMemcpyAsync(w.data(), d_w, (size_t)u * sizeof(fr_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (uint64_t k = 0; k < u; k++) fr_to_be_bytes_plain(out_w32 + 32 * k, w[k]);
+  return 0;
 } catch (...) {
   return abi_exception();
 }

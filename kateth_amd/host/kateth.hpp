@@ -12,6 +12,7 @@
 //   verify_proof_batch(ps, cs, zs, ys)   <- src/kzg/setup.rs:115-161 behind :96-113 per tuple
 //   verify_cell_proof_batch(cs, idx, cells, ps) <- EIP-7594 verify_cell_kzg_proof_batch (specs/fulu/polynomial-commitments-sampling.md)
 //   verify_cell_proof_batch_each(...)    <- the same, one Verdict per tuple
+//   verify_cell_proof_batch_rows(cs, rows, idx, cells, ps) <- the same check on a block's commitment list and an index per cell
 //   decompress(bytes48) -> P1            <- P1::decompress, src/bls.rs:505-531
 //   verify_blob_proof(blob, c, p)        <- src/kzg/setup.rs:208-221
 //   verify_blob_proof_batch(blobs,cs,ps) <- src/kzg/setup.rs:247-275
@@ -54,6 +55,7 @@ enum class ErrorKind : int32_t {
   CellsNotEnough = KZG_ERR_CELLS_NOT_ENOUGH,                     // recover_cells: fewer than 64 cells
   CellsInconsistent = KZG_ERR_CELLS_INCONSISTENT,                // recover_cells: the cells do not lie on one polynomial of degree < 4096
   CellIndex = KZG_ERR_CELL_INDEX,                                // verify_cell_proof_batch: a cell index >= 128
+  CommitmentIndex = KZG_ERR_COMMITMENT_INDEX,                    // verify_cell_proof_batch_rows: a commitment index past the list
 };
 
 class Error : public std::runtime_error {
@@ -529,6 +531,22 @@ class Setup {
     int32_t ok = 0;
     int32_t rc = kzg_verify_cell_proof_batch(ctx_.get(), cs.data(), cell_indices.data(), cells, ps.data(), n, &ok);
     return finish(rc, ok, "kzg_verify_cell_proof_batch");
+  }
+
+  // The row-indexed form: a block's LIST of commitments and, per cell, the position of its commitment in it (what a PeerDAS node holds:
+  // no repeated commitments).  Verdict and errors are verify_cell_proof_batch's on the expanded lists; an index past the list throws
+  // CommitmentIndex, and every listed commitment is validated, referenced or not.
+  bool verify_cell_proof_batch_rows(const std::vector<Bytes48>& commitments, const std::vector<uint64_t>& commitment_indices,
+                                    const std::vector<uint64_t>& cell_indices, const uint8_t* cells, size_t cells_len, const std::vector<Bytes48>& proofs) const {
+    const size_t n = proofs.size(), u = commitments.size();
+    if (commitment_indices.size() != n || cell_indices.size() != n || cells_len != n * BYTES_PER_CELL)
+      throw std::invalid_argument("verify_cell_proof_batch_rows: one commitment index, one cell index and one 2048-byte cell per proof");
+    std::vector<uint8_t> cs(u * 48), ps(n * 48);
+    for (size_t i = 0; i < u; i++) std::copy(commitments[i].begin(), commitments[i].end(), cs.begin() + i * 48);
+    for (size_t i = 0; i < n; i++) std::copy(proofs[i].begin(), proofs[i].end(), ps.begin() + i * 48);
+    int32_t ok = 0;
+    int32_t rc = kzg_verify_cell_proof_batch_rows(ctx_.get(), u ? cs.data() : nullptr, u, commitment_indices.data(), cell_indices.data(), cells, ps.data(), n, &ok);
+    return finish(rc, ok, "kzg_verify_cell_proof_batch_rows");
   }
 
   // the first 64 monomial G1 setup points [tau^j]_1 the context derives on first use, 48 bytes each

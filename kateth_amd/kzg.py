@@ -15,6 +15,8 @@ Method names, argument meaning and error behaviour follow the reference:
     Setup.verify_proof_batch(ps, cs, zs, ys)     src/kzg/setup.rs:115-161 behind :96-113 per tuple
     Setup.verify_cell_proof_batch(cs, idx, cells, ps)  EIP-7594 verify_cell_kzg_proof_batch (same document as compute_cells)
     Setup.verify_cell_proof_batch_each(cs, idx, cells, ps)  the same, one verdict (or error) per tuple
+    Setup.verify_cell_proof_batch_rows(cs, rows, idx, cells, ps)  the same check on a block's commitment LIST and an index per cell
+    Setup.verify_data_columns(cs, columns)  ... built from column sidecars (column index, cells, proofs)
 
 Points cross this boundary in their 48-byte compressed form (what every caller
 of the reference does next: benches/kzg.rs:25-32, src/kzg/setup.rs:341-343).
@@ -77,7 +79,8 @@ class LoadSetupError(Exception):
 
 
 class CellsError(Exception):
-    """rejections of `recover_cells` and of a cell index in `verify_cell_proof_batch` (EIP-7594); the reference has no counterpart."""
+    """rejections of `recover_cells`, of a cell index in `verify_cell_proof_batch` and of a commitment index in its row-indexed form
+    (EIP-7594); the reference has no counterpart."""
 
     def __init__(self, kind: str):
         super().__init__("cells::Error::" + kind)
@@ -99,6 +102,7 @@ _STATUS = {
     8: lambda: CellsError("NotEnoughCells"),
     9: lambda: CellsError("Inconsistent"),
     10: lambda: CellsError("CellIndex"),
+    11: lambda: CellsError("CommitmentIndex"),
 }
 
 
@@ -112,7 +116,7 @@ def _kzg_error(code: int) -> KzgError:
 
 
 def _cell_verify_error(code: int) -> Exception:
-    """verify_cell_proof_batch's rejections: CellsError for a cell index, KzgError for a commitment, a cell or a proof"""
+    """verify_cell_proof_batch[_rows]'s rejections: CellsError for a cell or commitment index, KzgError for a commitment, a cell or a proof"""
     inner = error_from_status(code)
     return inner if isinstance(inner, CellsError) else _kzg_error(code)
 
@@ -229,6 +233,11 @@ _SIGNATURES = {
         ctypes.c_int32,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p, _i32p, ctypes.c_void_p],
     ),
+    "kzg_verify_cell_proof_batch_rows": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u64p, _u64p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
+    "kzg_verify_cell_proof_batch_rows_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
+    "kzg_cell_row_weights": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u64p, ctypes.c_uint64, ctypes.c_uint64, _u8p]),
     "kzg_verify_cell_proof_batch_each": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u64p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p, _i32p]),
     "kzg_verify_cell_proof_batch_each_dev": (
         ctypes.c_int32,
@@ -1011,6 +1020,71 @@ class Setup:
         idx = self._cell_index_array(cell_indices, n)
         com, cells, prf = self._host_args(commitments, cells, proofs)
         return self._verdict("kzg_verify_cell_proof_batch", (com, idx, cells, prf, n), to_error=_cell_verify_error)
+
+    def verify_cell_proof_batch_rows(self, commitments: Sequence[bytes], commitment_indices: Sequence[int], cell_indices: Sequence[int],
+                                     cells: Sequence[bytes], proofs: Sequence[bytes]) -> bool:
+        """`verify_cell_kzg_proof_batch` (EIP-7594) in the row-indexed form: a block's LIST of commitments, and per cell the position of
+        its commitment in that list.  The verdict and the errors are verify_cell_proof_batch's on the expanded lists; an index past the
+        list raises CellsError CommitmentIndex, and EVERY listed commitment is validated, referenced or not.  Unequal lengths, an item
+        of the wrong size and an index that is no uint64 are a ValueError."""
+        what = "verify_cell_proof_batch_rows"
+        n = len(cells)
+        if not (len(commitment_indices) == n and len(cell_indices) == n and len(proofs) == n):
+            raise ValueError("%s: %d commitment indices, %d cell indices, %d cells, %d proofs" % (what, len(commitment_indices), len(cell_indices), n, len(proofs)))
+        commitments, cells, proofs = [_buf(v) for v in commitments], [_buf(v) for v in cells], [_buf(v) for v in proofs]
+        commitment_indices, cell_indices = [int(c) for c in commitment_indices], [int(c) for c in cell_indices]
+        if any(len(v) != 48 for v in commitments) or any(len(v) != 48 for v in proofs):
+            raise ValueError("%s: a commitment or proof is 48 bytes" % what)
+        if any(len(v) != BYTES_PER_CELL for v in cells):
+            raise ValueError("%s: a cell is %d bytes" % (what, BYTES_PER_CELL))
+        if any(not 0 <= c < 1 << 64 for c in commitment_indices + cell_indices):
+            raise ValueError("%s: an index is a uint64" % what)
+        return self.verify_cell_proof_batch_rows_host(b"".join(commitments), len(commitments), commitment_indices, cell_indices, b"".join(cells), b"".join(proofs), n)
+
+    def verify_cell_proof_batch_rows_host(self, commitments, u: int, commitment_indices, cell_indices, cells, proofs, n: int) -> bool:
+        """kzg_verify_cell_proof_batch_rows on u CONTIGUOUS commitments and n contiguous (commitment index, cell index, cell, proof) in host
+        memory: bytes-like objects or raw host addresses (ints); either index array as in verify_cell_proof_batch_host"""
+        cidx, idx = self._cell_index_array(commitment_indices, n), self._cell_index_array(cell_indices, n)
+        com, cells, prf = self._host_args(commitments, cells, proofs)
+        if not isinstance(com, int) and len(com) == 0:
+            com = None  # an empty list: the ABI takes a null pointer with u == 0
+        return self._verdict("kzg_verify_cell_proof_batch_rows", (com, u, cidx, idx, cells, prf, n), to_error=_cell_verify_error)
+
+    def verify_cell_proof_batch_rows_dev(self, d_commitments: int, u: int, d_commitment_indices: int, d_cell_indices: int, d_cells: int, d_proofs: int, n: int,
+                                         stream: int = 0) -> bool:
+        """kzg_verify_cell_proof_batch_rows_dev: device pointers (16-byte aligned) to u commitments, n + n uint64 indices, n cells, n proofs"""
+        return self._verdict("kzg_verify_cell_proof_batch_rows_dev", (d_commitments, u, d_commitment_indices, d_cell_indices, d_cells, d_proofs, n), (stream,),
+                             to_error=_cell_verify_error)
+
+    def verify_data_columns(self, commitments: Sequence[bytes], columns) -> bool:
+        """What a PeerDAS node holds: a block's commitments (one per blob) and column sidecars.  `columns` is a list of
+        (column_index, cells, proofs), cells and proofs with one entry per commitment, in the commitments' order.  Builds the two index
+        arrays and calls verify_cell_proof_batch_rows."""
+        u = len(commitments)
+        rows, cols, cells, proofs = [], [], [], []
+        for column_index, col_cells, col_proofs in columns:
+            if len(col_cells) != u or len(col_proofs) != u:
+                raise ValueError("verify_data_columns: column %d has %d cells and %d proofs for %d commitments" % (column_index, len(col_cells), len(col_proofs), u))
+            rows += range(u)
+            cols += [int(column_index)] * u
+            cells += list(col_cells)
+            proofs += list(col_proofs)
+        return self.verify_cell_proof_batch_rows(commitments, rows, cols, cells, proofs)
+
+    def cell_row_weights(self, r: int, commitment_indices: Sequence[int], u: int, first_index: int = 0) -> List[int]:
+        """w_c = sum over the items k with commitment_indices[k] == c of r^(first_index + k) mod the group order, c < u, through the kernel
+        behind the row-indexed form's commitment scalars (kzg_cell_row_weights).  r >= the modulus raises KzgError, an index >= u
+        CellsError CommitmentIndex."""
+        n = len(commitment_indices)
+        if not 0 <= r < 1 << 256 or any(not 0 <= int(c) < 1 << 64 for c in commitment_indices) or not 0 <= first_index < 1 << 64:
+            raise ValueError("cell_row_weights: r is 32 bytes, indices are uint64")
+        out = (ctypes.c_uint8 * (32 * max(u, 1)))()
+        rc = self._lib.kzg_cell_row_weights(self._h, int(r).to_bytes(32, "big"), first_index, self._cell_index_array(commitment_indices, n), n, u, ctypes.cast(out, _u8p))
+        self._check(rc, "kzg_cell_row_weights")
+        if rc > 0:
+            raise _cell_verify_error(rc)
+        res = bytes(out)
+        return [int.from_bytes(res[32 * k:32 * k + 32], "big") for k in range(u)]
 
     def g1_monomial(self, first: int = 0, count: int = 64) -> List[bytes]:
         """the 48-byte encodings of the monomial G1 setup points [tau^j]_1, first <= j < first + count <= 64, which the context derives
