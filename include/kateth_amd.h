@@ -194,6 +194,12 @@ uint64_t kzg_ctx_table_bytes(const kzg_ctx* ctx);
 /* bytes of commitment / proof workspace slot `slot` (0..2) as allocated so far: a caller that runs one call at a time only ever
  * grows slot 0; slots 1 and 2 are allocated when calls are found in flight side by side (tests, memory accounting) */
 uint64_t kzg_ctx_workspace_bytes(const kzg_ctx* ctx, uint32_t slot);
+/* The balance plan of the fixed-base MSM's two-blobs-per-wave launches (KATETH_AMD_COMB_BALANCE=off|auto|<partner>:<shed>) and the
+ * newest timing record a launch has taken, as 44 words: [0..7] partner and [8..15] steps shed of the eight unit classes (unit
+ * index mod 8) as the next launch would get them; [16] the record's sequence number (0: none yet), [17] earliest start and
+ * [18..25] latest end per class on the device's 100-MHz counter, [26] units that reported, [27] units launched; [28..43] the
+ * partner and shed words that launch ran under. */
+int32_t kzg_ctx_comb_balance(const kzg_ctx* ctx, uint64_t* out44);
 
 /*
  * Replaces Setup::blob_to_commitment + Compress::compress for n blobs

@@ -95,4 +95,52 @@ KZG_HD bool comb_walk_doubles(const CombWalk& w, uint32_t H) { return w.s == 0u 
 // largest `splits` the geometry supports: a lane must own a whole number of blocks
 KZG_HD uint32_t comb_max_splits(const CombGeom& g) { return (64u * g.nb) / g.lpg; }
 
+// ---- a walk that starts at step t (the second pass of a balanced launch, below) ----------------------------------------------
+// the position of step t of a lane's bpo * H steps; the lane's own (chunk, block) there for the shapes that carry one
+KZG_HD void comb_walk_at(CombWalk& w, uint32_t H, uint32_t nb, uint32_t bpo, uint32_t t) {
+  w.h = H - 1u - t / bpo;
+  w.s = t % bpo;
+  w.r = w.s % nb;  // meaningful in wide shapes only (b0 % nb == 0)
+  w.dq = w.s / nb;
+}
+KZG_HD void comb_lane_at(CombLanePos& p, uint32_t nb, uint32_t b0, const CombWalk& w) {
+  p.q = (b0 + w.s) / nb;
+  p.r = (b0 + w.s) % nb;
+}
+// Wide shapes: the first of the four chunks (counted from the lane's first chunk, like dq) whose masks the 32-byte load covering
+// the step at w holds.  A walk that starts inside a group of four issues that load itself; from then on comb_walk_loads_masks.
+KZG_HD uint32_t comb_walk_mask_base(const CombWalk& w) { return w.dq & ~3u; }
+
+// ---- balance plan of a half-wave launch (lpb = 32, splits = 1) ------------------------------------------------------------
+// Workgroups are dealt round-robin to the chip's eight XCDs, which do not clock alike: CLASS r = unit % 8 ends early or late as
+// a whole.  A plan pairs classes (partner is an involution) and lets the slower member of a pair leave out its LAST shed[r]
+// steps -- plane 0 of the lane's group, blocks [bpo - d, bpo): nothing is doubled after them, so d <= bpo - 1 -- which the unit
+// of class partner[r] of the same group of eight consecutive units then walks in a second pass, from the identity, on the
+// giver's two blobs, into a second array of lane sums.  No wave reads what another wave of the launch writes.  One byte per
+// class, packed: by value in two scalar register pairs.
+struct CombBalance {
+  uint64_t partner;  // byte r = partner of class r
+  uint64_t shed;     // byte r = steps class r leaves to its partner (non-zero for at most one member of a pair)
+};
+constexpr uint64_t COMB_BALANCE_IDENTITY = 0x0706050403020100ull;
+KZG_HD CombBalance comb_balance_none() { return CombBalance{COMB_BALANCE_IDENTITY, 0}; }
+KZG_HD uint32_t comb_balance_partner(const CombBalance& b, uint32_t r) { return (uint32_t)(b.partner >> (8u * r)) & 0xffu; }
+KZG_HD uint32_t comb_balance_shed(const CombBalance& b, uint32_t r) { return (uint32_t)(b.shed >> (8u * r)) & 0xffu; }
+KZG_HD bool comb_balance_empty(const CombBalance& b) { return b.shed == 0; }
+// a plan the kernel may run with lanes of bpo blocks: an involution without fixed points that shed, sheds <= bpo - 1 and on one side only
+KZG_HD bool comb_balance_valid(const CombBalance& b, uint32_t bpo) {
+  for (uint32_t r = 0; r < 8u; r++) {
+    const uint32_t p = comb_balance_partner(b, r), d = comb_balance_shed(b, r);
+    if (p >= 8u || comb_balance_partner(b, p) != r) return false;
+    if (d != 0u && (p == r || d + 1u > bpo || comb_balance_shed(b, p) != 0u)) return false;
+  }
+  return true;
+}
+// The timing record of one launch, 64-bit words: earliest start and, per class, latest end of its units on the constant 100-MHz
+// counter, and how many units reported.  k_msm_comb30 folds into it, the lane-sum kernel behind it hands it to the host and
+// clears it (msm_reduce_kernels.cuh).
+enum : uint32_t { COMB_REC_START = 0, COMB_REC_END = 1, COMB_REC_UNITS = 9, COMB_REC_WORDS = 10 };
+// units [0, comb_balance_units(n)) of a half-wave launch over n blobs take part: whole groups of eight units with all sixteen blobs
+KZG_HD uint64_t comb_balance_units(uint64_t n) { return (n / 16u) * 8u; }
+
 }  // namespace kzg

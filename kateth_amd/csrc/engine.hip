@@ -383,7 +383,7 @@ static MsmShapeCost msm_shape(const kzg_ctx* ctx, uint64_t n) {
   const bool half_ok = !ctx->knobs.comb_full_wave && ctx->comb.G <= 32 && (64u * ctx->comb.nb) % (32u / ctx->comb.G) == 0;
   if (half_ok && n >= 2) {
     const double c = rounds((double)((n + 1) / 2)) * (2.0 * A + D + 10.0);
-    if (c < best.cost) best = MsmShapeCost{1, 32, c};
+    if (c < best.cost || ctx->knobs.comb_half_wave) best = MsmShapeCost{1, 32, c};
   }
   return best;
 }
@@ -432,6 +432,21 @@ extern "C" int32_t kzg_ctx_plane_groups(const kzg_ctx* ctx) try {
   if (!ctx || !ctx->use_comb) return 0;
   std::lock_guard<std::mutex> guard(ctx->lock);
   return (int32_t)ctx->comb.G;
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_ctx_comb_balance(const kzg_ctx* ctx, uint64_t* out44) try {
+  if (!ctx || !out44) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  std::lock_guard<std::mutex> guard(ctx->bal_lock);
+  const CombBalance now = ctx->knobs.comb_balance == 2 ? ctx->knobs.comb_balance_forced : (ctx->knobs.comb_balance == 1 ? ctx->bal_plan : comb_balance_none());
+  for (uint32_t r = 0; r < 8u; r++) {
+    out44[r] = comb_balance_partner(now, r);
+    out44[8u + r] = comb_balance_shed(now, r);
+    out44[28u + r] = comb_balance_partner(ctx->bal_last_ran, r);
+    out44[36u + r] = comb_balance_shed(ctx->bal_last_ran, r);
+  }
+  for (uint32_t i = 0; i < COMB_REC_WORDS + 2u; i++) out44[16u + i] = ctx->bal_last[i];
+  return 0;
 } catch (...) {
   return abi_exception();
 }
@@ -514,6 +529,13 @@ EnvKnobs read_env_knobs() {
     if (const char* e = getenv("KATETH_AMD_VERIFY_STREAMS")) k.verify_streams = (uint32_t)atoi(e) <= (uint32_t)KZG_STAGE_STREAMS ? (uint32_t)atoi(e) : 0u;
     if (const char* e = getenv("KATETH_AMD_VERIFY_CHUNK")) k.verify_chunk = (uint64_t)atoll(e) > 0 ? (uint64_t)atoll(e) : 0;
     k.comb_full_wave = getenv("KATETH_AMD_COMB_FULL_WAVE") != nullptr;
+    if (const char* e = getenv("KATETH_AMD_COMB_HALF_WAVE")) k.comb_half_wave = atoi(e) != 0;
+    if (const char* e = getenv("KATETH_AMD_COMB_BALANCE")) {
+      if (std::string(e) == "off")
+        k.comb_balance = 0;
+      else if (comb_balance_parse(e, k.comb_balance_forced))
+        k.comb_balance = 2;  // anything else, "auto" included, leaves the default
+    }
     if (const char* e = getenv("KATETH_AMD_LAT_TABLE")) k.lat_table = atoi(e) != 0;
     if (const char* e = getenv("KATETH_AMD_COMB_FAIR")) k.comb_fair = (uint32_t)atoi(e) < 40u ? (uint32_t)atoi(e) : 0u;
     if (const char* e = getenv("KATETH_AMD_MSM_SPLITS")) {
@@ -578,6 +600,8 @@ extern "C" void kzg_ctx_destroy(kzg_ctx* ctx) {
   if (ctx->d_gen_affine) (void)hipFree(ctx->d_gen_affine);
   if (ctx->d_comb_k) (void)hipFree(ctx->d_comb_k);
   if (ctx->d_comb_k_lat) (void)hipFree(ctx->d_comb_k_lat);
+  if (ctx->d_bal_rec) (void)hipFree(ctx->d_bal_rec);
+  if (ctx->h_bal_msg) (void)hipHostFree(ctx->h_bal_msg);
   if (ctx->msm_override && ctx->msm_override->destroy) ctx->msm_override->destroy(ctx);
   delete ctx->pairing;
   for (WsSlot& w : ctx->wss) {
@@ -875,6 +899,14 @@ static int32_t ctx_build(kzg_ctx* ctx, const uint8_t* g1_lagrange, const uint8_t
     int32_t rcc = comb_build_tables(ctx, c, G, t, st, nullptr);
     if (rcc) return rcc;
     tables_install(ctx, t);
+    // the timing records of the balanced launches and the pinned ring they are forwarded to (engine_internal.hpp: bal_lock)
+    unsigned long long init[kzg_ctx::KZG_BAL_RING * COMB_REC_WORDS] = {};
+    for (uint32_t i = 0; i < kzg_ctx::KZG_BAL_RING; i++) init[i * COMB_REC_WORDS + COMB_REC_START] = ~0ull;
+    HIP_TRY(hipMalloc(&ctx->d_bal_rec, sizeof(init)));
+    HIP_TRY(hipMemcpy(ctx->d_bal_rec, init, sizeof(init), hipMemcpyHostToDevice));
+    const size_t msg_bytes = kzg_ctx::KZG_BAL_RING * (COMB_REC_WORDS + 2) * sizeof(unsigned long long);
+    HIP_TRY(hipHostMalloc(&ctx->h_bal_msg, msg_bytes, hipHostMallocDefault));
+    memset(ctx->h_bal_msg, 0, msg_bytes);
   }
   HIP_TRY(hipDeviceSynchronize());
   return 0;
@@ -1124,8 +1156,54 @@ extern "C" int32_t kzg_ctx_create_multi(const uint8_t* g1_lagrange, const uint8_
 // partials[unit * 64 + lane].  `scratch`: msm_scratch_bytes(ctx, n) bytes.  `scalars_consumed` (optional): recorded on `st` as
 // soon as d_scalars is no longer read (after the bit-plane transposition; the MSM kernel reads the masks), so that a staging
 // buffer can be refilled while the MSM runs.
+// The plan and the timing record of a launch (engine_internal.hpp: bal_lock).  A plan applies where it is simple: two blobs per
+// wave, one split, a wide shape (every production shape at lpb = 32), at least one whole group of eight units; the kernels leave
+// a ragged last group alone.  A forced plan goes to every such launch it is valid for.  The automatic plan is learnt from, and
+// given to, launches of ONE round that fill more than half the chip in whole groups: there a class is an XCD under full load, and
+// its end time says how that XCD clocks; a few waves on an idle chip, or a second round dealt as slots free up, say something else.
+static void balance_begin(const kzg_ctx* ctx, uint64_t n, uint32_t splits, uint32_t lpb, const CombGeom& geom, bool lat, MsmCall& call) {
+  call = MsmCall{};
+  if (lat || lpb != 32u || splits != 1u || !comb_shape_is_wide(geom, splits, lpb) || comb_balance_units(n) == 0u) return;
+  const uint32_t bpo = comb_blocks_per_lane(geom, splits, lpb), total = geom.H * bpo;
+  if (ctx->knobs.comb_balance == 2 && comb_balance_valid(ctx->knobs.comb_balance_forced, bpo)) call.plan = ctx->knobs.comb_balance_forced;
+  const uint64_t units = msm_units(n, splits, lpb), round = (uint64_t)ctx->num_cus * 8u;
+  if (n % 16u != 0u || units > round || 2u * units <= round || ctx->d_bal_rec == nullptr) return;
+  constexpr uint32_t R = kzg_ctx::KZG_BAL_RING, W = COMB_REC_WORDS + 2u;
+  std::lock_guard<std::mutex> guard(ctx->bal_lock);
+  // the newest forwarded record that is whole, if it is newer than the one taken last
+  for (uint64_t s = ctx->bal_seq; s > ctx->bal_seen && s + R > ctx->bal_seq; s--) {
+    const kzg_ctx::BalIssued& was = ctx->bal_issued[s % R];
+    volatile const unsigned long long* msg = ctx->h_bal_msg + (s % R) * W;
+    unsigned long long w[W];
+    w[W - 1u] = __atomic_load_n(&msg[W - 1u], __ATOMIC_ACQUIRE);
+    for (uint32_t i = 1; i + 1u < W; i++) w[i] = msg[i];
+    w[0] = __atomic_load_n(&msg[0], __ATOMIC_ACQUIRE);
+    if (was.seq != s || w[0] != s || w[W - 1u] != s || w[1u + COMB_REC_UNITS] != was.units) continue;
+    ctx->bal_seen = s;
+    ctx->bal_last[0] = s;
+    for (uint32_t i = 0; i < COMB_REC_WORDS; i++) ctx->bal_last[1u + i] = w[1u + i];
+    ctx->bal_last[1u + COMB_REC_WORDS] = was.units;
+    ctx->bal_last_ran = was.ran;
+    if (ctx->knobs.comb_balance == 1) {
+      double t[8];
+      for (uint32_t r = 0; r < 8u; r++) t[r] = (double)(int64_t)(w[1u + COMB_REC_END + r] - w[1u + COMB_REC_START]);
+      ctx->bal_plan = comb_balance_next(was.ran, t, was.total, was.bpo);
+    }
+    break;
+  }
+  if (ctx->knobs.comb_balance == 1 && comb_balance_valid(ctx->bal_plan, bpo)) call.plan = ctx->bal_plan;
+  call.seq = ++ctx->bal_seq;
+  kzg_ctx::BalIssued& now = ctx->bal_issued[call.seq % R];
+  now.seq = call.seq;
+  now.units = units;
+  now.total = total;
+  now.bpo = bpo;
+  now.ran = call.plan;
+}
+
 int32_t msm_launch(const kzg_ctx* ctx, bool be_bytes, const uint8_t* d_scalars, uint64_t n, int32_t* d_status, g1_xyzz* partials, uint32_t splits, uint32_t lpb,
-                   void* scratch, hipStream_t st, hipEvent_t scalars_consumed) {
+                   void* scratch, hipStream_t st, MsmCall& call, hipEvent_t scalars_consumed) {
+  call = MsmCall{};
   if (ctx->msm_override) {
     int32_t rco = ctx->msm_override->launch(ctx, be_bytes, d_scalars, n, d_status, partials, splits, lpb, scratch, st);
     if (rco == 0 && scalars_consumed) HIP_TRY(hipEventRecord(scalars_consumed, st));
@@ -1145,12 +1223,15 @@ int32_t msm_launch(const kzg_ctx* ctx, bool be_bytes, const uint8_t* d_scalars, 
   const uint4* table = lat ? ctx->d_table_lat : ctx->d_table;
   const CombGeom geom = lat ? ctx->comb_lat : ctx->comb;
   const uint4* comb_k = (const uint4*)(lat ? ctx->d_comb_k_lat : ctx->d_comb_k);
+  balance_begin(ctx, n, splits, lpb, geom, lat, call);
+  call.partials2 = reinterpret_cast<g1_xyzz*>(reinterpret_cast<uint8_t*>(scratch) + (size_t)n * KZG_BYTES_PER_BLOB);
+  unsigned long long* rec = call.seq ? ctx->d_bal_rec + (call.seq % kzg_ctx::KZG_BAL_RING) * COMB_REC_WORDS : nullptr;
   if (comb_shape_is_wide(geom, splits, lpb))
     hipLaunchKernelGGL((k_msm_comb30<false, COMB_SHAPE_WIDE>), dim3((unsigned)msm_units(n, splits, lpb)), dim3(64), 0, st, masks, n, splits, lpb, table, geom,
-                       partials, comb_k, (uint64_t*)nullptr);
+                       partials, comb_k, (uint64_t*)nullptr, call.plan, call.partials2, rec);
   else
     hipLaunchKernelGGL((k_msm_comb30<false, COMB_SHAPE_NARROW>), dim3((unsigned)msm_units(n, splits, lpb)), dim3(64), 0, st, masks, n, splits, lpb, table, geom,
-                       partials, comb_k, (uint64_t*)nullptr);
+                       partials, comb_k, (uint64_t*)nullptr, comb_balance_none(), (g1_xyzz*)nullptr, (unsigned long long*)nullptr);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1158,13 +1239,16 @@ int32_t msm_launch(const kzg_ctx* ctx, bool be_bytes, const uint8_t* d_scalars, 
 // of a blob -- 6 + log2(splits) levels of latency instead of the splits + 5 a sequential walk over the splits costs (a
 // single blob uses up to 256 units on the latency comb).  `partials` must have room for n * splits unit sums after the n * splits * 64 lane sums.
 int32_t msm_finish(const kzg_ctx* ctx, uint64_t n, uint8_t* d_out48, uint8_t* d_out_affine96, const int32_t* d_status, g1_xyzz* partials,
-                                 g1_xyzz* sums, uint32_t splits, uint32_t lpb, hipStream_t st) {
+                                 g1_xyzz* sums, uint32_t splits, uint32_t lpb, hipStream_t st, const MsmCall& call) {
   ProfScope ps(ctx, PROF_REDUCE_COMPRESS, st);
   g1_xyzz* unit_sums = (splits == 1) ? sums : partials + (size_t)n * splits * 64;
   const uint64_t units = msm_units(n, splits, lpb);
-  if (lpb == 32)  // half-wave mode: four blobs per reducing wave
-    hipLaunchKernelGGL(k_msm_reduce_half4, dim3((unsigned)((units + 1) / 2)), dim3(64), 0, st, partials, units, unit_sums, n);
-  else
+  if (lpb == 32) {  // half-wave mode: four blobs per reducing wave
+    const uint64_t slot = call.seq % kzg_ctx::KZG_BAL_RING;
+    hipLaunchKernelGGL(k_msm_reduce_half4, dim3((unsigned)((units + 1) / 2)), dim3(64), 0, st, partials, units, unit_sums, n, (const g1_xyzz*)call.partials2,
+                       call.plan, call.seq ? ctx->d_bal_rec + slot * COMB_REC_WORDS : (unsigned long long*)nullptr,
+                       call.seq ? ctx->h_bal_msg + slot * (COMB_REC_WORDS + 2u) : (unsigned long long*)nullptr, (unsigned long long)call.seq);
+  } else
     hipLaunchKernelGGL(k_msm_reduce, dim3((unsigned)units), dim3(64), 0, st, partials, units, lpb, unit_sums, units);
   if (splits > 64) {  // latency shape (a few blobs over up to 256 units each): tree + constant term + encoding in one launch
     hipLaunchKernelGGL((k_msm_reduce_splits<true>), dim3((unsigned)n), dim3(64), 0, st, unit_sums, splits, n, sums, d_status, d_out48, d_out_affine96);
@@ -1183,9 +1267,10 @@ int32_t msm_pipeline(const kzg_ctx* ctx, bool be_bytes, const uint8_t* d_scalars
                      const MsmBufs& bufs, uint8_t* ws, hipStream_t st) {
   g1_xyzz* partials = reinterpret_cast<g1_xyzz*>(ws + bufs.o_part);
   const uint32_t lpb = msm_lanes_per_blob(ctx, n, bufs.splits);
-  int32_t rc = msm_launch(ctx, be_bytes, d_scalars, n, d_status, partials, bufs.splits, lpb, ws + bufs.o_scratch, st);
+  MsmCall call;
+  int32_t rc = msm_launch(ctx, be_bytes, d_scalars, n, d_status, partials, bufs.splits, lpb, ws + bufs.o_scratch, st, call);
   if (rc) return rc;
-  return msm_finish(ctx, n, d_out48, d_out_affine96, d_status, partials, reinterpret_cast<g1_xyzz*>(ws + bufs.o_sum), bufs.splits, lpb, st);
+  return msm_finish(ctx, n, d_out48, d_out_affine96, d_status, partials, reinterpret_cast<g1_xyzz*>(ws + bufs.o_sum), bufs.splits, lpb, st, call);
 }
 
 // ---------------------------------------------------------------------------
@@ -1368,10 +1453,11 @@ int32_t commit_host(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_
     uint8_t* d_chunk = nullptr;
     rc = hc.ring.feed(k, blobs + base * (size_t)KZG_BYTES_PER_BLOB, m * (size_t)KZG_BYTES_PER_BLOB, comp[slot], &d_chunk);
     // msm_launch records done_event(k) behind the bit-plane transposition
-    if (rc == 0) rc = msm_launch(ctx, true, d_chunk, m, d_status + base, partials, splits, lpb, wslot + o_masks, comp[slot], hc.ring.done_event(k));
+    MsmCall call;
+    if (rc == 0) rc = msm_launch(ctx, true, d_chunk, m, d_status + base, partials, splits, lpb, wslot + o_masks, comp[slot], call, hc.ring.done_event(k));
     if (rc == 0)
       rc = msm_finish(ctx, m, out48 ? d_res + base * 48 : nullptr, out_affine96 ? d_res + base * 96 : nullptr, d_status + base, partials, sums, splits, lpb,
-                      comp[slot]);
+                      comp[slot], call);
   }
   if (rc == 0 && piped) rc = stream_after(comp[0], comp[1], ctx->stage_join[1]);
   if (rc == 0) rc = ws.end();

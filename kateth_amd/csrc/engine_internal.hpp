@@ -29,6 +29,7 @@
 //   engine_proof.hip  poly_kernels.cuh, cells_kernels.cuh, cellproof_kernels.cuh   (its only user)
 //   engine_verify.hip verify_kernels.cuh, cellverify_kernels.cuh      (its only user)      -> launch_glv_points
 #include "comb_geom.hpp"
+#include "comb_balance.hpp"
 #include "g1.cuh"
 #include "sha256.cuh"
 #include "pairing.hpp"
@@ -135,6 +136,9 @@ struct EnvKnobs {
   uint32_t comb_fair = 20;       // KATETH_AMD_COMB_FAIR=s: the MSM waves of a SIMD trade issue priority every 2^s cycles; 0 = hardware default (measurement aid)
   bool lat_table = true;         // KATETH_AMD_LAT_TABLE=0: no latency comb beside a class-22 table (measurement aid)
   bool comb_full_wave = false;   // KATETH_AMD_COMB_FULL_WAVE: never use the comb's two-blobs-per-wave mode (measurement aid)
+  bool comb_half_wave = false;   // KATETH_AMD_COMB_HALF_WAVE=1: two blobs per wave from two blobs on, not only where msm_shape finds it cheaper (tests of the half-wave paths at small batches)
+  int comb_balance = 1;          // KATETH_AMD_COMB_BALANCE=off|auto|<partner>:<shed> -> 0 | 1 | 2: the balance plan of half-wave launches (comb_balance.hpp); 2 = comb_balance_forced on every
+  CombBalance comb_balance_forced = comb_balance_none();  // launch it is valid for (tests, A/B runs)
   uint32_t msm_splits = 0;       // KATETH_AMD_MSM_SPLITS: force the (blob, split) decomposition of the fixed-base MSM (power of two <= 64; 0 = automatic)
   uint64_t challenge_split_max = 0;  // KATETH_AMD_CHALLENGE_SPLIT_MAX: largest batch hashed by the two-wave SHA-256 kernel (0 = default)
   uint64_t sidecar_pass = 0;     // KATETH_AMD_SIDECAR_PASS: blobs per staging pass of kzg_blob_sidecar_batch (0 = the plan of the host-buffer proof call)
@@ -271,6 +275,27 @@ struct kzg_ctx {
   hipStream_t side_stream = nullptr;  // non-blocking stream for work that overlaps the caller's stream
   hipStream_t copy_stream = nullptr;  // non-blocking stream for the chunked host-to-device copies of the host-buffer entry points
   EnvKnobs knobs;  // read once at kzg_ctx_create
+  // Balance of the comb's half-wave launches (msm_launch / msm_finish, engine.hip; comb_balance.hpp), guarded by bal_lock.  Every
+  // launch that fills most of one round takes the next sequence number and with it one of KZG_BAL_RING device records, which its
+  // waves fold their times into and its lane-sum kernel forwards to the pinned ring entry of the same index; the host remembers
+  // what it issued there.  The next such launch takes the newest entry that is complete (both sequence words, all units
+  // reported) -- it never waits for one -- and, with KATETH_AMD_COMB_BALANCE=auto, moves bal_plan by it.  Each launch carries its
+  // own copy of the plan by value, so calls in flight on several streams do not see each other's.
+  static constexpr uint32_t KZG_BAL_RING = 16;
+  struct BalIssued {
+    uint64_t seq = 0, units = 0;
+    uint32_t total = 0, bpo = 0;
+    CombBalance ran = comb_balance_none();
+  };
+  mutable std::mutex bal_lock;
+  mutable CombBalance bal_plan = comb_balance_none();
+  mutable uint64_t bal_seq = 0;   // records issued so far
+  mutable uint64_t bal_seen = 0;  // newest record taken
+  mutable BalIssued bal_issued[KZG_BAL_RING];
+  mutable unsigned long long bal_last[COMB_REC_WORDS + 2] = {};  // that record: its sequence number, the COMB_REC_ words, its units (kzg_ctx_comb_balance)
+  mutable CombBalance bal_last_ran = comb_balance_none();
+  unsigned long long* d_bal_rec = nullptr;  // KZG_BAL_RING x COMB_REC_WORDS, cleared by the kernel that forwards them
+  unsigned long long* h_bal_msg = nullptr;  // pinned: KZG_BAL_RING x {seq, COMB_REC_WORDS, seq}
   // workspace (grown on demand, guarded by lock)
   mutable std::mutex lock;
   // KZG_WS_SLOTS workspaces for commitment / proof calls: a call takes the LOWEST slot whose previous user has completed or ran
@@ -642,7 +667,17 @@ uint32_t msm_lanes_per_blob(const kzg_ctx* ctx, uint64_t n, uint32_t splits);  /
 static inline uint64_t msm_units(uint64_t n, uint32_t splits, uint32_t lpb) { return lpb == 64 ? n * splits : (n + 1) / 2; }
 
 // Scratch the fixed-base MSM needs besides the lane sums: the comb's bit-plane masks (the blob transposed, 128 KiB per blob).
-static inline size_t msm_scratch_bytes(const kzg_ctx* ctx, uint64_t n) { return ctx->use_comb ? (size_t)n * KZG_BYTES_PER_BLOB : 0; }
+// Behind them, the second lane sums of a balanced half-wave launch (comb_geom.hpp CombBalance): one row of 64 per unit, 6 KiB per blob.
+static inline size_t msm_scratch_bytes(const kzg_ctx* ctx, uint64_t n) {
+  return ctx->use_comb ? (size_t)n * KZG_BYTES_PER_BLOB + (size_t)((n + 1) / 2) * 64 * sizeof(g1_xyzz) : 0;
+}
+// What msm_launch decided for one launch and msm_finish must know: the plan the launch runs under, its second lane sums, and the
+// timing record it folds into (seq = 0: none).
+struct MsmCall {
+  CombBalance plan = comb_balance_none();
+  g1_xyzz* partials2 = nullptr;
+  uint64_t seq = 0;
+};
 
 // ---- launchers of engine.hip (fixed-base MSM: msm_comb.cuh, msm_fixed.cuh) ---------------------------------------------------
 // The fixed-base MSM alone over `n` scalar vectors on the device: 64 lane sums per (blob, split) unit into
@@ -651,11 +686,11 @@ static inline size_t msm_scratch_bytes(const kzg_ctx* ctx, uint64_t n) { return 
 // soon as d_scalars is no longer read (after the bit-plane transposition; the MSM kernel reads the masks), so that a staging
 // buffer can be refilled while the MSM runs.
 int32_t msm_launch(const kzg_ctx* ctx, bool be_bytes, const uint8_t* d_scalars, uint64_t n, int32_t* d_status, g1_xyzz* partials, uint32_t splits, uint32_t lpb,
-                   void* scratch, hipStream_t st, hipEvent_t scalars_consumed = nullptr);
+                   void* scratch, hipStream_t st, MsmCall& call, hipEvent_t scalars_consumed = nullptr);
 // Lane sums of n blobs -> 48-byte encodings.  Two tree stages: the 64 lane sums of every (blob, split) unit, then the units
-// of a blob.  `partials` must have room for n * splits unit sums after the n * splits * 64 lane sums.
+// of a blob.  `partials` must have room for n * splits unit sums after the n * splits * 64 lane sums.  `call`: as msm_launch left it.
 int32_t msm_finish(const kzg_ctx* ctx, uint64_t n, uint8_t* d_out48, uint8_t* d_out_affine96, const int32_t* d_status, g1_xyzz* partials, g1_xyzz* sums,
-                   uint32_t splits, uint32_t lpb, hipStream_t st);
+                   uint32_t splits, uint32_t lpb, hipStream_t st, const MsmCall& call);
 // The buffers of one MSM + reduce + compress over up to n scalar vectors, as offsets into a workspace: the lane sums (64 lane sums + 1 unit
 // sum per (vector, split)), the n sums and msm_scratch_bytes; `splits` is choose_splits(ctx, n).
 struct MsmBufs {

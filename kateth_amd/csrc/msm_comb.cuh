@@ -144,10 +144,12 @@ struct CombLane {
   uint32_t nidx;
 };
 // the mask of the step at w (in wide shapes only when w opens a new group of four chunks); then w is the next step
+// FIRST: the walk starts at w, which may lie inside a group of four: the group's load is issued whatever w is
+template <bool FIRST = false>
 __device__ __forceinline__ void comb_next_mask(CombLane& s) {
   if (s.wide) {
-    if (comb_walk_loads_masks(s.w)) {
-      const uint4* src = reinterpret_cast<const uint4*>(s.mlane + (s.w.h * 64u + s.w.dq));
+    if (FIRST || comb_walk_loads_masks(s.w)) {
+      const uint4* src = reinterpret_cast<const uint4*>(s.mlane + (s.w.h * 64u + (FIRST ? comb_walk_mask_base(s.w) : s.w.dq)));
       const uint4 lo = src[0], hi = src[1];
       s.mb0 = (uint64_t)lo.x | ((uint64_t)lo.y << 32);
       s.mb1 = (uint64_t)lo.z | ((uint64_t)lo.w << 32);
@@ -200,10 +202,16 @@ __device__ __forceinline__ void comb_gather(CombLane& s) {
 // TIMED: instantiated only by the test-only library (tests/window_msm): every unit records {wall start, wall end, cycles,
 // hw id} into wave_times (tools/gpu_wave_times.py); the product instantiates <false> and passes nullptr.
 // SHAPE (comb_geom.hpp): the kind of shape the instance is launched with; the launcher's choice must be the shape's.
+// bal, partials2 (comb_geom.hpp CombBalance): the launch's balance plan and the second lane sums a taker's second pass writes,
+// partials2[giver's unit * 64 + lane]; an empty plan (every launch but the half-wave ones the host plans for) touches neither.
+// rec: the launch's timing record (COMB_REC_*) or null.  The three default to "no plan, no record": the test-only timed launch
+// (tests/window_msm) passes none of them and times the unbalanced walk.
 template <bool TIMED, int SHAPE = COMB_SHAPE_ANY>
 static __global__ __launch_bounds__(64, 2) void k_msm_comb30(const uint64_t* __restrict__ masks, uint64_t n, uint32_t splits, uint32_t lpb,
                                                              const uint4* __restrict__ table, CombGeom g, g1_xyzz* __restrict__ partials,
-                                                             const uint4* __restrict__ comb_k, uint64_t* __restrict__ wave_times) {
+                                                             const uint4* __restrict__ comb_k, uint64_t* __restrict__ wave_times,
+                                                             CombBalance bal = CombBalance{COMB_BALANCE_IDENTITY, 0}, g1_xyzz* __restrict__ partials2 = nullptr,
+                                                             unsigned long long* __restrict__ rec = nullptr) {
   const int lane = threadIdx.x;
   const uint64_t unit = blockIdx.x;
   uint64_t wt_wall0 = 0, wt_cyc0 = 0;
@@ -211,23 +219,17 @@ static __global__ __launch_bounds__(64, 2) void k_msm_comb30(const uint64_t* __r
     wt_wall0 = wall_clock64();
     wt_cyc0 = clock64();
   }
-  const uint32_t l = (uint32_t)lane % lpb;
-  const uint64_t blob = (lpb == 64u) ? unit / splits : unit * (64u / lpb) + (uint32_t)lane / lpb;
+  // the launch's timing record (COMB_REC_*): lane 0 of every unit -- always a live lane -- folds in its start here and its end below
+  if (rec != nullptr && lane == 0) atomicMin(&rec[COMB_REC_START], (unsigned long long)wall_clock64());
   const uint32_t split = (lpb == 64u) ? (uint32_t)(unit % splits) : 0u;
-  if (blob >= n) {  // odd batch in half-wave mode: the idle half contributes the identity
+  if (((lpb == 64u) ? unit / splits : unit * (64u / lpb) + (uint32_t)lane / lpb) >= n) {  // odd batch in half-wave mode: the idle half contributes the identity
     g1_xyzz none;
     xyzz_set_inf(none);
     partials[unit * 64 + lane] = none;
     return;
   }
   const uint32_t lpg = lpb / g.G;
-  const uint32_t grp = l / lpg;
-  const uint32_t owner = split * lpg + l % lpg;
   const uint32_t bpo = comb_blocks_per_lane(g, splits, lpb);
-  const uint32_t b0 = owner * bpo;
-  const uint64_t* mrow = masks + blob * (64u * 256u);  // [plane][chunk]
-  const uint32_t kbase = grp * g.H;
-  const uint4* tgrp = table + (uint64_t)grp * g.epg * 6u;
   const uint32_t total = g.H * bpo;
   const uint32_t nb = g.nb;
 
@@ -236,7 +238,7 @@ static __global__ __launch_bounds__(64, 2) void k_msm_comb30(const uint64_t* __r
   // The recoding's constant term K = [c0] * (sum of the setup points) is the STARTING VALUE of one lane per blob -- lane 0 of
   // the blob's first unit, plane group 0 -- so no later step has to add it.  The lane doubles its accumulator H - 1 times on
   // its way down the planes: comb_k holds [c0 / 2^(H-1)] * sum (affine, table format; null when it is the identity).
-  if (comb_k != nullptr && l == 0u && split == 0u) {
+  if (comb_k != nullptr && (uint32_t)lane % lpb == 0u && split == 0u) {
     fp_t kx, ky;
     load_affine96(kx, ky, comb_k, 0);
     f30_unpack(acc.x, kx.v);
@@ -246,67 +248,106 @@ static __global__ __launch_bounds__(64, 2) void k_msm_comb30(const uint64_t* __r
     acc.inf = 0;
   }
 
-  CombLane s;
-  s.mrow = mrow;
-  s.tgrp = tgrp;
-  s.nb = nb;
-  s.bpo = bpo;
-  s.b0 = b0;
-  s.kbase = kbase;
-  s.H = g.H;
-  s.ep64 = g.ep64;
-  s.wide = SHAPE == COMB_SHAPE_WIDE ? true : (SHAPE == COMB_SHAPE_NARROW ? false : comb_shape_is_wide(g, splits, lpb));
-  const uint32_t q0 = b0 / nb;
-  s.q0e = q0 * g.ep64;
-  s.mlane = mrow + kbase * 64u + q0;
-  comb_walk_start(s.w, g.H);
-  s.lw.q = q0;
-  s.lw.r = b0 % nb;
-  s.lp1 = s.lw;
-  s.mb0 = s.mb1 = s.mb2 = s.mb3 = 0;
-  s.nneg = s.ndbl = false;
-  s.nidx = 0;
-  comb_next_mask(s);
-  comb_gather(s);  // always before the next mask: a new group's load overwrites masks whose patterns are already cut out
-  if (total > 1u) comb_next_mask(s);
-
-  // The two waves of a SIMD trade issue priority every 2^g.fair shader cycles (issue_fair.cuh).  Measured at 4,096 blobs = one
-  // round of 2,048 waves: left to the hardware the older wave of every pair finished after 18.0 ms and the younger after
-  // 29.7 ms; with a period of 2^16 cycles 24.7 / 29.2 ms (a low-priority wave's steps are 4x as long, it notices its turn
-  // late); with 2^20 cycles 27.8 / 28.4 ms and the launch takes 29.2 instead of 30.7 ms (profiles/r02/wave_fairness_sweep.json).
-#pragma unroll 1
-  for (uint32_t t = 0; t < total; t++) {
-    if (g.fair) issue_fair_tick_low(g.fair);
-    fp30 cx, cy;
-    f30_load_entry(cx, cy, s.nx.v, s.ny.v, xyzz30_entry_neg(acc, s.nneg));
-    f30_pin(cx);  // unpacked before the gather below loads the next entry into the same registers
-    f30_pin(cy);
-    const bool cneg = s.nneg, cdbl = s.ndbl;
-    const uint32_t cidx = s.nidx;
-    if (t + 1u < total) {
-      comb_gather(s);
-      if (t + 2u < total) comb_next_mask(s);
-    }
-    if (cdbl && !acc.inf) {  // Horner step between two planes: out of line, on a copy (63 times per lane at G = 4)
-      g1_xyzz30 tmp = acc;
-      xyzz30_dbl(tmp);
-      acc = tmp;
-    }
-    bool done = false;
-    if (!acc.inf) done = xyzz30_madd_fast(acc, cx, cy);
-    if (!done) {
-      g1_xyzz30 tmp = acc;
-      fp_t rx, ry;
-      load_affine96(rx, ry, tgrp, cidx);
-      fp30 sx, sy;  // separate objects: the call takes their address
-      f30_load_entry(sx, sy, rx.v, ry.v, xyzz30_entry_neg(tmp, cneg));
-      xyzz30_madd_complete(tmp, sx, sy);
-      acc = tmp;
-    }
+  // Balance plan (comb_geom.hpp; the host passes a non-empty one only with lpb == 32, splits == 1 and a wide shape): this unit
+  // walks steps [0, cnt) of its own two blobs and then, in a second pass through the same loop, the last d2 steps its partner
+  // left out, on the partner's blobs -- lane for lane the partner's geometry, which depends on the lane alone.
+  uint32_t first = 0, cnt = total, d2 = 0;
+  uint64_t unit2 = unit;
+  if (!comb_balance_empty(bal) && unit < comb_balance_units(n)) {
+    const uint32_t cls = (uint32_t)unit & 7u, pr = comb_balance_partner(bal, cls);
+    cnt = total - comb_balance_shed(bal, cls);
+    d2 = comb_balance_shed(bal, pr);
+    unit2 = (unit & ~(uint64_t)7) | pr;
   }
-  g1_xyzz out;
-  xyzz30_to_xyzz(out, acc);  // back to canonical 2^384-Montgomery limbs for k_msm_reduce
-  partials[unit * 64 + lane] = out;
+  uint64_t wunit = unit;  // the unit whose blobs the pass walks
+  g1_xyzz* outp = partials + unit * 64;
+#pragma unroll 1
+  for (;;) {
+    // The lane's geometry, derived in each pass from a lane index the compiler cannot tie to the other pass's, so that none of it
+    // is carried in vector registers across the conversion that ends a pass (profiles/comb_balance/comb30_slots.json has the counts).
+    uint32_t ln = (uint32_t)lane;
+    asm volatile("" : "+v"(ln));
+    const uint32_t l = ln % lpb;
+    const uint64_t blob = (lpb == 64u) ? wunit / splits : wunit * (64u / lpb) + ln / lpb;
+    const uint32_t grp = l / lpg;
+    const uint32_t owner = split * lpg + l % lpg;
+    const uint32_t b0 = owner * bpo;
+    const uint64_t* mrow = masks + blob * (64u * 256u);  // [plane][chunk]
+    const uint32_t kbase = grp * g.H;
+    CombLane s;
+    s.mrow = mrow;
+    s.tgrp = table + (uint64_t)grp * g.epg * 6u;
+    s.nb = nb;
+    s.bpo = bpo;
+    s.b0 = b0;
+    s.kbase = kbase;
+    s.H = g.H;
+    s.ep64 = g.ep64;
+    s.wide = SHAPE == COMB_SHAPE_WIDE ? true : (SHAPE == COMB_SHAPE_NARROW ? false : comb_shape_is_wide(g, splits, lpb));
+    const uint32_t q0 = b0 / nb;
+    s.q0e = q0 * g.ep64;
+    s.mlane = mrow + kbase * 64u + q0;
+    s.mb0 = s.mb1 = s.mb2 = s.mb3 = 0;
+    s.nneg = s.ndbl = false;
+    s.nidx = 0;
+    comb_walk_at(s.w, g.H, nb, bpo, first);
+    comb_lane_at(s.lw, nb, b0, s.w);
+    s.lp1 = s.lw;
+    comb_next_mask<true>(s);
+    comb_gather(s);  // always before the next mask: a new group's load overwrites masks whose patterns are already cut out
+    if (cnt > 1u) comb_next_mask(s);
+
+    // The two waves of a SIMD trade issue priority every 2^g.fair shader cycles (issue_fair.cuh).  Measured at 4,096 blobs = one
+    // round of 2,048 waves: left to the hardware the older wave of every pair finished after 18.0 ms and the younger after
+    // 29.7 ms; with a period of 2^16 cycles 24.7 / 29.2 ms (a low-priority wave's steps are 4x as long, it notices its turn
+    // late); with 2^20 cycles 27.8 / 28.4 ms and the launch takes 29.2 instead of 30.7 ms (profiles/r02/wave_fairness_sweep.json).
+#pragma unroll 1
+    for (uint32_t t = 0; t < cnt; t++) {
+      if (g.fair) issue_fair_tick_low(g.fair);
+      fp30 cx, cy;
+      f30_load_entry(cx, cy, s.nx.v, s.ny.v, xyzz30_entry_neg(acc, s.nneg));
+      f30_pin(cx);  // unpacked before the gather below loads the next entry into the same registers
+      f30_pin(cy);
+      const bool cneg = s.nneg, cdbl = s.ndbl;
+      const uint32_t cidx = s.nidx;
+      if (t + 1u < cnt) {
+        comb_gather(s);
+        if (t + 2u < cnt) comb_next_mask(s);
+      }
+      if (cdbl && !acc.inf) {  // Horner step between two planes: out of line, on a copy (63 times per lane at G = 4)
+        g1_xyzz30 tmp = acc;
+        xyzz30_dbl(tmp);
+        acc = tmp;
+      }
+      bool done = false;
+      if (!acc.inf) done = xyzz30_madd_fast(acc, cx, cy);
+      if (!done) {
+        g1_xyzz30 tmp = acc;
+        fp_t rx, ry;
+        load_affine96(rx, ry, s.tgrp, cidx);
+        fp30 sx, sy;  // separate objects: the call takes their address
+        f30_load_entry(sx, sy, rx.v, ry.v, xyzz30_entry_neg(tmp, cneg));
+        xyzz30_madd_complete(tmp, sx, sy);
+        acc = tmp;
+      }
+    }
+    g1_xyzz out;
+    xyzz30_to_xyzz(out, acc);  // back to canonical 2^384-Montgomery limbs for k_msm_reduce
+    outp[lane] = out;
+    if (d2 == 0u) break;
+    // second pass: the partner's blobs, its last d2 steps, from the identity -- the constant term K is the giver's -- into the
+    // second lane sums of the GIVER's unit
+    wunit = unit2;
+    first = total - d2;
+    cnt = d2;
+    d2 = 0;
+    xyzz30_set_inf(acc);
+    outp = partials2 + unit2 * 64;
+  }
+  if (rec != nullptr && lane == 0) {
+    atomicMax(&rec[COMB_REC_END + ((uint32_t)unit & 7u)], (unsigned long long)wall_clock64());
+    atomicAdd(&rec[COMB_REC_UNITS], 1ull);
+  }
   if (TIMED) {
     if (wave_times && lane == 0) {
       uint32_t hwid, xcc;

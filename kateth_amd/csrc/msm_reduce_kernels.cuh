@@ -1,5 +1,6 @@
 // Lane-sum trees and point encoding behind the fixed-base MSM (compiled once: engine.hip owns this header).
 #pragma once
+#include "comb_geom.hpp"
 #include "msm_fixed.cuh"
 
 namespace kzg {
@@ -44,11 +45,29 @@ static __global__ __launch_bounds__(64) void k_msm_reduce(const g1_xyzz* __restr
 // j + 16 (j = l % 16) of blob l / 16 as it loads them, then a 4-level tree over 16 lanes.  The same five dependent additions per
 // blob as k_msm_reduce, but n / 4 waves instead of n / 2: at 4,096 blobs one wave per SIMD instead of two, whose interleaved
 // issue made every level 1.5 times as long (0.25 -> 0.13 ms per 4,096 blobs).
+// Balanced launches (comb_geom.hpp CombBalance): a blob whose unit shed steps has second lane sums in partials2, rows as in
+// partials, written by its partner's unit: its lanes add four lane sums instead of two as they load (two more additions in
+// front of the tree, for those blobs only).
+// rec / msg / seq: the MSM launch's timing record (COMB_REC_*), handed to the host here -- no launch and no synchronisation of
+// its own: the first wave copies it into the pinned ring entry msg = {seq, record, seq} and clears it for its next launch; the
+// host takes an entry only when both sequence words name the launch it looks for.
 static __global__ __launch_bounds__(64) void k_msm_reduce_half4(const g1_xyzz* __restrict__ partials, uint64_t units, g1_xyzz* __restrict__ unit_sums,
-                                                                uint64_t n_out) {
+                                                                uint64_t n_out, const g1_xyzz* __restrict__ partials2, CombBalance bal,
+                                                                unsigned long long* __restrict__ rec, volatile unsigned long long* msg,
+                                                                unsigned long long seq) {
   __shared__ g1_xyzz28 lds[32];
   issue_priority_latency();
   const int lane = threadIdx.x;
+  if (rec != nullptr && blockIdx.x == 0) {
+    if (lane == 0) msg[0] = seq;
+    __threadfence_system();
+    if (lane < (int)COMB_REC_WORDS) {
+      msg[1 + lane] = rec[lane];
+      rec[lane] = lane == (int)COMB_REC_START ? ~0ull : 0ull;
+    }
+    __threadfence_system();
+    if (lane == 0) msg[1 + COMB_REC_WORDS] = seq;
+  }
   const int q = lane >> 4, j = lane & 15;
   const uint64_t u = (uint64_t)blockIdx.x * 2 + (uint32_t)(q >> 1);  // unit of this lane's blob
   const uint64_t slot = u * 2 + (uint32_t)(q & 1);                   // = blob index
@@ -57,11 +76,18 @@ static __global__ __launch_bounds__(64) void k_msm_reduce_half4(const g1_xyzz* _
   xyzz28_set_inf(acc);
   if (live) {
     const g1_xyzz* row = partials + u * 64 + (uint32_t)(q & 1) * 32u;
-    const g1_xyzz a = row[j], b = row[j + 16];
-    g1_xyzz28 other;
+    const g1_xyzz* row2 = partials2 + u * 64 + (uint32_t)(q & 1) * 32u;
+    const bool giver = !comb_balance_empty(bal) && u < comb_balance_units(n_out) && comb_balance_shed(bal, (uint32_t)u & 7u) != 0u;
+    const int terms = giver ? 4 : 2;  // lane sums j and j + 16, then their second parts: one addition in the code
+    const g1_xyzz a = row[j];
     xyzz28_from_xyzz(acc, a);
-    xyzz28_from_xyzz(other, b);
-    xyzz28_add_complete_inl<true>(acc, other);
+#pragma unroll 1
+    for (int k = 1; k < terms; k++) {
+      const g1_xyzz b = ((k & 2) ? row2 : row)[j + 16 * (k & 1)];
+      g1_xyzz28 other;
+      xyzz28_from_xyzz(other, b);
+      xyzz28_add_complete_inl<true>(acc, other);
+    }
   }
 #pragma unroll 1
   for (int step = 1; step < 16; step <<= 1) {

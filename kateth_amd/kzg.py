@@ -168,6 +168,7 @@ _SIGNATURES = {
     "kzg_ctx_msm_kernel_name": (ctypes.c_char_p, [ctypes.c_void_p]),
     "kzg_ctx_plane_groups": (ctypes.c_int32, [ctypes.c_void_p]),
     "kzg_ctx_table_bytes": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "kzg_ctx_comb_balance": (ctypes.c_int32, [ctypes.c_void_p, _u64p]),
     "kzg_blob_to_commitment_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
     "kzg_blob_to_commitment_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kzg_blob_to_commitment_batch_affine": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _i32p]),
@@ -575,6 +576,17 @@ class Setup:
     def workspace_bytes(self):
         """bytes of the three commitment / proof workspace slots as allocated so far"""
         return [int(self._lib.kzg_ctx_workspace_bytes(self._h, k)) for k in range(3)]
+
+    def comb_balance(self) -> dict:
+        """the balance plan of the two-blobs-per-wave MSM launches and the newest timing record taken (kzg_ctx_comb_balance)"""
+        w = (ctypes.c_uint64 * 44)()
+        self._check(self._lib.kzg_ctx_comb_balance(self._h, w), "kzg_ctx_comb_balance")
+        w = [int(x) for x in w]
+        rec = None
+        if w[16]:
+            rec = {"seq": w[16], "start": w[17], "end": w[18:26], "end_us": [(e - w[17]) / 100.0 for e in w[18:26]], "units": w[27],
+                   "ran": {"partner": w[28:36], "shed": w[36:44]}}
+        return {"partner": w[0:8], "shed": w[8:16], "record": rec}
 
     def _check(self, rc: int, what: str):
         if rc < 0:

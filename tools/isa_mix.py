@@ -3,6 +3,7 @@
 
   isa_mix.py <listing.s> [name ...]                  one line per function, the 18 commonest opcodes of the named ones
   isa_mix.py --slots <listing.s> [kernel] [--json]   issue slots of a kernel's hot loop (default k_msm_comb30)
+  isa_mix.py --spans <listing.s> [kernel]            every backward-branch span of the kernel, one JSON line each, shortest first
 
 --slots takes the kernel's longest backward-branch span (the label a branch jumps back to .. that branch) and counts, for the
 span and for its fast-addition block (the first product's opening multiply-add .. the last multiply-add before the span's first
@@ -101,8 +102,36 @@ def hot_loop_slots(path, kernel="k_msm_comb30"):
     return out
 
 
+def backward_spans(path, kernel="k_msm_comb30"):
+    """every backward-branch span of the kernel, outermost last: its counts, multiply-adds, scratch instructions and calls.  A
+    kernel that wraps its hot loop in another loop (k_msm_comb30's two passes of a balanced launch) has the wrapping loop as its
+    longest span; the hot loop is then read off this list"""
+    s = open(path).read()
+    names = [n for n in re.findall(r"^(_Z\w+):", s, flags=re.M) if kernel in n]
+    if not names:
+        raise SystemExit("no function matching %r in %s" % (kernel, path))
+    a = s.index("\n" + names[0] + ":")
+    b = s.find(".Lfunc_end", a)
+    ins, labels = _instructions(s[a:b if b > 0 else len(s)])
+    out = []
+    for k, (n, op, args) in enumerate(ins):
+        if op.startswith(("s_cbranch", "s_branch")):
+            tgt = labels.get(args.strip())
+            if tgt is not None and tgt < n:
+                first = next(i for i, (m, _o, _a) in enumerate(ins) if m > tgt)
+                loop = ins[first:k + 1]
+                row = _count(loop)
+                row.update(first=first, last=k, v_mad_i64_i32=sum(1 for _n, o, _a in loop if o.startswith("v_mad_i64_i32")),
+                           scratch=sum(1 for _n, o, _a in loop if "scratch" in o), calls=sum(1 for _n, o, _a in loop if o.startswith("s_swappc")))
+                out.append(row)
+    return sorted(out, key=lambda r: r["slots"])
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "--slots":
+    if len(sys.argv) > 1 and sys.argv[1] == "--spans":
+        for r in backward_spans(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else "k_msm_comb30"):
+            print(json.dumps(r))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--slots":
         rest = [x for x in sys.argv[2:] if x != "--json"]
         res = hot_loop_slots(rest[0], rest[1] if len(rest) > 1 else "k_msm_comb30")
         if "--json" in sys.argv:
