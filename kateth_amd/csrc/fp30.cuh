@@ -622,6 +622,9 @@ KZG_HD void f30_pin(fp30& a) {
 // flips the flag; an entry to add is therefore loaded with the sign xyzz30_entry_neg() gives.  Doubling and the complete addition
 // work on the raw coordinates and keep the flag.
 // Invariant between additions: y C-form, zz and zzz C- or U-form, |value| < 0.53 p; x L-form (a sum of two C-forms), |value| < 3.3 p.
+// Right after the complete addition's identity branch y, zz and zzz are a table entry and the constant one instead -- canonical
+// residues or their negation, |value| < p: inside every product's operand contract too (tests/fp30_adder_cases.py runs both states at
+// their extremes under the 128-bit column check).
 struct g1_xyzz30 {
   fp30 x, y, zz, zzz;
   uint32_t inf;

@@ -617,6 +617,62 @@ extern "C" int32_t hm_g1_sum30(uint8_t* out48, const uint8_t* pts48, const uint8
   return 0;
 }
 
+// the adder on RAW accumulators, n cases: acc = x, y, zz, zzz limbs (4 x 13), inf, yneg (54 int32); entry = x2, y2 limbs (26).  The CPU
+// counterpart of tests/device_atoms/device_atoms.hip's da_xyzz30_op (same layout, same ops), so that Python can feed the invariant's
+// extremes and a built false alarm of the cheap zero test, with every column and limb bound checked along the chain.
+// op 0: xyzz30_madd_fast (flag_out = its return), 1: xyzz30_madd_complete, 2: xyzz30_dbl, 3: xyzz30_mdbl(acc, x2, y2),
+// 4: xyzz30_to_xyzz (x, y, zz, zzz as 12 words each in the first 48 words of acc_out)
+extern "C" int32_t hm_xyzz30_op(int op, uint32_t n, const int32_t* acc_in, const int32_t* entry_in, int32_t* acc_out, int32_t* flag_out) {
+  for (uint32_t i = 0; i < n; i++) {
+    const int32_t* a = acc_in + (size_t)i * 54;
+    const int32_t* e = entry_in + (size_t)i * 26;
+    int32_t* o = acc_out + (size_t)i * 54;
+    g1_xyzz30 p;
+    fp30 x2, y2;
+    for (int k = 0; k < 13; k++) {
+      p.x.l[k] = a[k];
+      p.y.l[k] = a[13 + k];
+      p.zz.l[k] = a[26 + k];
+      p.zzz.l[k] = a[39 + k];
+      x2.l[k] = e[k];
+      y2.l[k] = e[13 + k];
+    }
+    p.inf = (uint32_t)a[52];
+    p.yneg = (uint32_t)a[53];
+    int32_t flag = 0;
+    switch (op) {
+      case 0: flag = xyzz30_madd_fast(p, x2, y2) ? 1 : 0; break;
+      case 1: xyzz30_madd_complete(p, x2, y2); break;
+      case 2: xyzz30_dbl(p); break;
+      case 3: xyzz30_mdbl(p, x2, y2); break;
+      case 4: {
+        g1_xyzz r;
+        xyzz30_to_xyzz(r, p);
+        for (int k = 0; k < 12; k++) {
+          o[k] = (int32_t)r.x.v[k];
+          o[12 + k] = (int32_t)r.y.v[k];
+          o[24 + k] = (int32_t)r.zz.v[k];
+          o[36 + k] = (int32_t)r.zzz.v[k];
+        }
+        for (int k = 48; k < 54; k++) o[k] = 0;
+        flag_out[i] = 0;
+        continue;
+      }
+      default: return -1;
+    }
+    for (int k = 0; k < 13; k++) {
+      o[k] = p.x.l[k];
+      o[13 + k] = p.y.l[k];
+      o[26 + k] = p.zz.l[k];
+      o[39 + k] = p.zzz.l[k];
+    }
+    o[52] = (int32_t)p.inf;
+    o[53] = (int32_t)p.yneg;
+    flag_out[i] = flag;
+  }
+  return 0;
+}
+
 // ---- GLV split of a scalar (kateth_amd/csrc/glv.cuh): k (32 B little-endian) -> k1 || k2 (32 B each, little-endian) -------------
 extern "C" void hm_glv_split(uint8_t* out64, const uint8_t* k32) {
   fr_t k, k1, k2;

@@ -11,10 +11,12 @@ smallest table (class 8, 100 MB) and on class 16 (three blocks per chunk: the ot
     the CPU build, test_fp30_madd_complete); what a blob can force is the identity branch of the complete addition at every
     lane's first step, the out-of-line doubling at every plane change, and long runs of one repeated table pattern with
     alternating sign (scalars 0x5555.. and 0xaaaa.. mod r in every position).
-    THE GAP THIS LEAVES: on the device, xyzz30_madd_complete's P == Q branch into xyzz30_mdbl and its P == -Q branch are run by no
-    GPU test, here or elsewhere; their formulas are checked on the CPU build only, where f30_mul_core_c stands in for the generated
-    statements.  What the GPU does run of the same code is the products themselves (f30_mul, f30_sqr, f30_mul2 issued alone, in
-    xyzz30_dbl at every plane change and in xyzz30_madd_complete's generic branch after a false alarm of the cheap test).
+    THE GAP THIS LEAVES: through the public API, xyzz30_madd_complete's P == Q branch into xyzz30_mdbl, its P == -Q branch and its
+    generic branch after a false alarm of the cheap test cannot be reached here.  tests/test_gpu_fp30_device.py runs all of them on
+    the device -- on raw accumulators and on point sums, with the products at their operand extremes -- but in a test-only
+    translation unit that compiles its OWN instances of fp30.cuh's inline functions.  What remains unpinned is therefore only
+    k_msm_comb30's instance of those branches: the compiler's register allocation around the same statements inside that kernel,
+    of which the whole-commitment comparisons here and in test_gpu_comb_walk.py / test_gpu_comb_balance.py are the one check.
 Every case is compared byte for byte; nothing here is timed."""
 import json
 import os

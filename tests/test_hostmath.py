@@ -528,6 +528,26 @@ def test_fp30_madd_complete(hm):
     assert hm.hm_f28_violations() == before
 
 
+def test_fp30_adder_chain_at_the_invariants_extremes(hm):
+    """the adder as a CHAIN on raw accumulators (xyzz30_madd_fast / _complete / _dbl / _mdbl / _to_xyzz through hm_xyzz30_op), every
+    column formed in 128 bits and every limb bound checked by this build: random accumulators inside g1_xyzz30's invariant, the
+    invariant's extremes in all sign combinations (x limbs at +-(2^30 + 4), y and the entry at +-(2^29 + 2), zz / zzz all-ones
+    U-form, every limb 12 as large as the |value| bounds allow), a BUILT false alarm of the cheap zero test (k = -7, 0, 7; k = +-8
+    must not alarm; one whose X3 limbs lie where only the wide carry pass is right), P + P, P - P, the identity and y = 0 given
+    as 0, p and -p.  No bound may be reported: that is what says every input is inside the documented contract -- the device test
+    (tests/test_gpu_fp30_device.py) feeds the same list -- and every output must match the formulas' residues from Python integers."""
+    import fp30_adder_cases as AC
+
+    cases = AC.adder_cases()
+    assert len({c["id"] for c in cases}) == len(cases)
+    assert {"fast", "alarm", "false_alarm_generic", "p_plus_p", "p_minus_p", "identity", "y_zero", "dbl", "mdbl", "to_xyzz", "to_xyzz_identity"} == {c["branch"] for c in cases}
+    before = hm.hm_f28_violations()
+    got = AC.run_cases(hm.hm_xyzz30_op, cases)
+    assert hm.hm_f28_violations() == before
+    for c in cases:
+        AC.check(c, *got[c["id"]])
+
+
 def test_glv_split_of_a_scalar(hm):
     """glv.cuh: k = k1 + k2 z^2 with k1 < z^2 < 2^128 and k2 = floor(k / z^2) < 2^128, for random scalars, the extremes of the field,
     multiples of z^2 and their neighbours (the Barrett estimate is corrected up to twice); and [z^2]P = (beta x, -y) on the curve"""
