@@ -540,8 +540,8 @@ int32_t kzg_verify_cell_proof_batch_dev(const kzg_ctx* ctx, const void* d_commit
  * arrays; the powers of r run over global item indices.  The *_dev call acts on member 0.
  * Cost of the weights: n u / 64 wave-steps of an index compare -- nothing for a block's shape (u up to a few hundred), about a
  * millisecond in the degenerate u ~ n = 65,536 case: there, use the per-cell call.
- * Not here: a *_each form (a caller who gets false expands the commitments and calls kzg_verify_cell_proof_batch_each), a *_group_dev
- * form, and the GLV route (KATETH_AMD_VAR_GLV does not apply to this form).
+ * Per-item verdicts: kzg_verify_cell_proof_batch_rows_each[_dev], below behind the other *_each calls.
+ * Not here: a *_group_dev form, and the GLV route (KATETH_AMD_VAR_GLV does not apply to this form).
  */
 int32_t kzg_verify_cell_proof_batch_rows(const kzg_ctx* ctx, const uint8_t* commitments48 /* u * 48 */, uint64_t u, const uint64_t* commitment_indices /* n */,
                                          const uint64_t* cell_indices /* n */, const uint8_t* cells /* n * 2048 */, const uint8_t* proofs48 /* n * 48 */,
@@ -623,6 +623,48 @@ int32_t kzg_verify_cell_proof_batch_each(const kzg_ctx* ctx, const uint8_t* comm
                                          const uint8_t* proofs48, uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok);
 int32_t kzg_verify_cell_proof_batch_each_dev(const kzg_ctx* ctx, const void* d_commitments48, const void* d_cell_indices, const void* d_cells,
                                              const void* d_proofs48, uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream);
+
+/*
+ * PER-ITEM VERDICTS FOR THE ROW-INDEXED FORM: which cells of a kzg_verify_cell_proof_batch_rows are bad, from the shape block import
+ * holds -- the list of u commitments is decoded once and nothing is expanded.  Inputs exactly as kzg_verify_cell_proof_batch_rows(_dev);
+ * ok_each (n bytes), status (n x int32), commitment_status (u x int32, may be NULL) and ok are HOST memory; the *_dev call is synchronous.
+ *   status[i]  commitment_indices[i] >= u: KZG_ERR_COMMITMENT_INDEX.  Otherwise what kzg_verify_cell_proof_batch returns for the
+ *              expanded tuple (commitments48[commitment_indices[i]], cell_indices[i], cells[i], proofs48[i]) ALONE: 0, or its first
+ *              rejection in the order cell index (KZG_ERR_CELL_INDEX), commitment (KZG_ERR_EC_*), cell
+ *              (KZG_ERR_BLOB_INVALID_FIELD_ELEMENT), proof (KZG_ERR_EC_*).  A listed commitment that item i does not reference never
+ *              touches item i -- the deliberate difference from the boolean rows call, which validates the whole list.
+ *   ok_each[i] that call's *ok; 0 whenever status[i] != 0.
+ *   commitment_status[c]  c < u: the decoder's code for listed commitment c, 0 or KZG_ERR_EC_*, referenced or not: how a caller learns
+ *              that the LIST is bad.  May be NULL.
+ *   *ok        1 iff every ok_each[i] == 1 AND every listed commitment is valid: 1 exactly when kzg_verify_cell_proof_batch_rows on the
+ *              same arguments returns KZG_OK with *ok = 1, whether or not commitment_status is NULL.
+ *   return     0, or a negative KZG_FAIL_*.  A rejected item or commitment never makes the call return a positive code.
+ *   n == 0     *ok = 1, no launch, no output array is written, whatever u is.  u == 0 with n > 0: every status[i] =
+ *              KZG_ERR_COMMITMENT_INDEX, every ok_each[i] = 0, *ok = 0, return 0, no launch.  u >= 2^31: KZG_FAIL_ARGUMENT.  A null
+ *              required pointer with n > 0 returns KZG_FAIL_ARGUMENT; commitments48 may be null only when u == 0; only
+ *              commitment_status is optional.  n == 1 obeys the same contract: the item sees only its own commitment.
+ * Whenever every commitment index is in range, ok_each and status are byte for byte those of kzg_verify_cell_proof_batch_each on the
+ * expanded arrays (the challenge is the same, so are both trees), and the bound on the two-pairing checks is the same
+ * 1 + 2 k ceil(log2 n) (kzg_verify_each_checks).
+ * How: the rows call's session (n + u decoded points).  No item and no listed commitment rejected -> the rows batch check runs first
+ * and true settles every item.  Otherwise -- also when only an unreferenced commitment is bad: the batch check is never asked to sum a
+ * rejected point -- the per-item terms are built with the commitment gathered through the item's index, and the descent is that of
+ * the *_each calls above.
+ * GROUP context: the host-buffer call cuts the ITEMS into the members' usual shares; every member gets all u commitments and its slice
+ * of both index arrays, runs the single-device call on its share with its own challenge and writes ok_each and status in place;
+ * commitment_status is written once, by the member that serves the first share (every member validates the same list); *ok is the AND.
+ * The *_dev call acts on member 0.  Not here: a *_group_dev form, a kzg_verify_session_tree form, and the GLV route
+ * (KATETH_AMD_VAR_GLV does not apply to this form).
+ */
+int32_t kzg_verify_cell_proof_batch_rows_each(const kzg_ctx* ctx, const uint8_t* commitments48 /* u * 48 */, uint64_t u,
+                                              const uint64_t* commitment_indices /* n */, const uint64_t* cell_indices /* n */,
+                                              const uint8_t* cells /* n * 2048 */, const uint8_t* proofs48 /* n * 48 */, uint64_t n,
+                                              uint8_t* ok_each /* n, HOST */, int32_t* status /* n, HOST */,
+                                              int32_t* commitment_status /* u, HOST, may be NULL */, int32_t* ok);
+int32_t kzg_verify_cell_proof_batch_rows_each_dev(const kzg_ctx* ctx, const void* d_commitments48, uint64_t u, const void* d_commitment_indices,
+                                                  const void* d_cell_indices, const void* d_cells, const void* d_proofs48, uint64_t n,
+                                                  uint8_t* ok_each /* n, HOST */, int32_t* status /* n, HOST */,
+                                                  int32_t* commitment_status /* u, HOST, may be NULL */, int32_t* ok, void* hip_stream);
 
 /*
  * Introspection: out96[k] = sum_{j<64} s_kj [tau^j]_1 for m vectors of 64 scalars (scalars32: m x 64 x 32 bytes big-endian, canonical;

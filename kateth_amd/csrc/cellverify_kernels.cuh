@@ -3,7 +3,7 @@
 // scalars -S_j of lincomb B's monomial terms (arithmetic and layout: cellverify_math.cuh).  The row-indexed form
 // (kzg_verify_cell_proof_batch_rows) adds k_cells_rows_leaves, the front with the commitment read through an index, and
 // k_cells_row_weights / k_cells_roww_reduce, lincomb B's commitment scalars.  The per-item verdicts add k_cells_each_leaves,
-// k_each_vec_level and k_each_gather_cells (at the end of this file).
+// k_each_vec_level and k_each_gather_cells (at the end of this file); the row-indexed form's verdicts add k_each_rows_status.
 #pragma once
 #include "cellverify_math.cuh"
 #include "verify_kernels.cuh"
@@ -188,6 +188,24 @@ static __global__ __launch_bounds__(256) void k_cells_roww_reduce(const fr_t* __
   fr_t out;
   cellv_roww_sum(out, partials + c * tiles, tiles);
   out_plain[c] = out;
+}
+
+// The row-indexed form's k_each_status (kzg_verify_cell_proof_batch_rows_each): ONE launch over max(n, ncom) threads.  Thread i < n
+// folds item i's code THROUGH its commitment index (cellv_rows_item_status: the commitment slot is read only behind a clear index slot)
+// and counts the rejected items in counts[0], as k_each_status does; thread c < ncom counts the rejected LISTED commitments in
+// counts[1], referenced or not -- the driver must not hand a rejected point to the batch check's lincomb, and the call's *ok is 0 for a
+// bad list.  The ncom commitment statuses themselves are read back from the session's array, only when the caller asks for them.
+static __global__ __launch_bounds__(256) void k_each_rows_status(const int32_t* __restrict__ st_index, const int32_t* __restrict__ st_com,
+                                                                const int32_t* __restrict__ st_cell, const int32_t* __restrict__ st_proof,
+                                                                const unsigned long long* __restrict__ commitment_indices, uint64_t ncom, uint64_t n,
+                                                                int32_t* __restrict__ status /* n */, uint32_t* __restrict__ counts /* 2 */) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const int32_t c = cellv_rows_item_status(st_index, st_com, st_cell, st_proof, commitment_indices, ncom, i);
+    status[i] = c;
+    if (c) atomicAdd(counts, 1u);
+  }
+  if (i < ncom && st_com[i]) atomicAdd(counts + 1, 1u);
 }
 
 // elements 8 t .. 8 t + 7 of cell k as they lie in memory (256 consecutive bytes, big-endian) -> plain limbs; zero for a cell that

@@ -17,6 +17,7 @@
 // Bounds (units of r): the passes are cells_math.cuh's with normalised inputs < 2 and a cells_reduce behind each; both products take
 // an operand < 2 and a canonical one; a sum takes two normalised values < 2 (limbs < 2^30, value < 4) into cells_reduce.
 #pragma once
+#include "../../include/kateth_amd.h"  // KZG_ERR_COMMITMENT_INDEX (cellv_rows_item_status)
 #include "cells_math.cuh"
 
 namespace kzg {
@@ -219,6 +220,26 @@ KZG_HD void cellv_roww_sum(fr_t& out, const fr_t* partials, uint32_t tiles) {
   for (int q = 0; q < 8; q++) acc.v[q] = 0;
   for (uint32_t k = 0; k < tiles; k++) fr_add(acc, acc, partials[k]);
   out = acc;
+}
+
+// ---- per-item verdicts of the row-indexed form (kzg_verify_cell_proof_batch_rows_each): item i's code ----------------------------------
+// What kzg_verify_cell_proof_batch returns for the expanded tuple alone, in its parse order: the index slot (KZG_ERR_COMMITMENT_INDEX
+// ahead of KZG_ERR_CELL_INDEX, as the front wrote it), else the commitment slot AT commitment_indices[i] -- the list's other entries
+// never touch the item -- else the cell slot, else the proof slot.  The index is read, and the commitment slot indexed by it, only when
+// the index slot is clear: the front clears it only for a row below ncom, and a row that is not below ncom is answered with the front's
+// code all the same, so nothing is indexed by an unchecked value.  The four arrays are the session's (stride max(n, ncom) apart there;
+// here just four pointers): st_com has ncom words, the others n.  k_each_rows_status runs it per item, tests/hostcpp/cellv_rows_status.cpp
+// on the host.
+KZG_HD int32_t cellv_rows_item_status(const int32_t* st_index, const int32_t* st_com, const int32_t* st_cell, const int32_t* st_proof,
+                                      const unsigned long long* commitment_indices, uint64_t ncom, uint64_t i) {
+  int32_t c = st_index[i];
+  if (c) return c;
+  const unsigned long long row = commitment_indices[i];
+  if (row >= ncom) return KZG_ERR_COMMITMENT_INDEX;
+  c = st_com[row];
+  if (!c) c = st_cell[i];
+  if (!c) c = st_proof[i];
+  return c;
 }
 
 }  // namespace kzg

@@ -436,6 +436,9 @@ static inline VerifyInputs cell_rows_inputs(const void* commitments48, uint64_t 
 struct VerifyEach {
   uint8_t* ok_each;
   int32_t* status;
+  // the row-indexed cells form (kzg_verify_cell_proof_batch_rows_each) only: the decoder's code per LISTED commitment (ncom words), or
+  // null for a caller who does not ask -- a rejected listed commitment makes the call's *ok 0 either way
+  int32_t* commitment_status = nullptr;
 };
 // The single-device batch call behind every route -- {blobs, points} x {host buffers, device pointers} x {one boolean, per-item verdicts};
 // n >= 1, `st`: the caller's stream of the device routes -- and phase 1 alone, whose session becomes the caller's (engine_verify.hip).

@@ -111,14 +111,16 @@ int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t 
 }
 
 // Per-item verdicts (kzg_verify_*_batch_each) over the members: the same contiguous shares, each member's share its own batch with its
-// own challenge -- an item's verdict does not depend on r, so the outputs land in place and nothing is merged but the AND.
+// own challenge -- an item's verdict does not depend on r, so the outputs land in place and nothing is merged but the AND.  The
+// row-indexed cells form: every member gets the whole commitment list and validates it, so each member's boolean already carries the
+// list's verdict and the list's statuses are written once, by the member that serves the first share.
 int32_t multi_verify_each(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, const VerifyEach& each, int32_t* ok) {
   *ok = 0;
   const std::vector<Share> shares = shares_of(ctx, n);
   std::vector<int32_t> oks(shares.size(), 0);
   const int32_t rc = run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
     const Share& sh = shares[j];
-    const VerifyEach out{each.ok_each + sh.first, each.status + sh.first};
+    const VerifyEach out{each.ok_each + sh.first, each.status + sh.first, j == 0 ? each.commitment_status : nullptr};
     return verify_batch_single(member_of(ctx, sh.member), in.advanced(sh.first), sh.count, nullptr, &out, &oks[j]);
   });
   if (rc) return rc;

@@ -74,7 +74,7 @@ struct kzg_verify_session {
   size_t tree_cap = 0;
   uint64_t tree_n = 0;             // items the trees stand for; 0 = not built in this use of the session
   int32_t* t_status = nullptr;     // [n] the single-item call's code per item (k_each_status)
-  uint32_t* t_rejected = nullptr;  // [1] how many of them are non-zero
+  uint32_t* t_rejected = nullptr;  // [2] how many of them are non-zero; rows: [1] = how many LISTED commitments the decoder rejected
   g1_xyzz28* t_a = nullptr;        // both trees, level after level from the leaves (EachGeom::off)
   g1_xyzz28* t_b = nullptr;
   uint32_t* t_idx = nullptr;       // [EACH_GATHER] node positions of one fetch
@@ -1663,7 +1663,7 @@ static int32_t each_reserve(kzg_verify_session* s, const EachGeom& g) {
   const uint64_t n = s->n, total = g.off[g.height + 1];
   if (total >> 32) return fail(KZG_FAIL_ARGUMENT, "per-item verdicts: batch too large");
   Carve c;
-  const size_t o_status = c.take(n * sizeof(int32_t)), o_rej = c.take(sizeof(uint32_t)), o_a = c.take(total * sizeof(g1_xyzz28)),
+  const size_t o_status = c.take(n * sizeof(int32_t)), o_rej = c.take(2 * sizeof(uint32_t)), o_a = c.take(total * sizeof(g1_xyzz28)),
                o_b = c.take(total * sizeof(g1_xyzz28)), o_idx = c.take(EACH_GATHER * sizeof(uint32_t)), o_out = c.take(2 * EACH_GATHER * sizeof(g1_xyzz));
   const bool is_cells = s->kind == VerifyKind::CELLS;
   const size_t o_vec = is_cells ? c.take(total * 64 * sizeof(fr_t)) : 0;
@@ -1689,8 +1689,14 @@ static int32_t each_reserve(kzg_verify_session* s, const EachGeom& g) {
 static int32_t each_status_enqueue(kzg_verify_session* s) {
   const uint64_t n = s->n;
   hipStream_t st = s->st;
-  if (hipStreamWaitEvent(st, s->ev_join, 0) != hipSuccess || hipMemsetAsync(s->t_rejected, 0, sizeof(uint32_t), st) != hipSuccess)
+  if (hipStreamWaitEvent(st, s->ev_join, 0) != hipSuccess || hipMemsetAsync(s->t_rejected, 0, (s->rows ? 2 : 1) * sizeof(uint32_t), st) != hipSuccess)
     return fail(KZG_FAIL_HIP, "per-item verdicts: status enqueue failed");
+  if (s->rows) {  // the commitment's code through the item's index, and the rejected entries of the list counted beside the rejected items
+    hipLaunchKernelGGL(k_each_rows_status, dim3(blocks_for(s->stride, 256)), dim3(256), 0, st, stat_of(s, 0), stat_of(s, 1), stat_of(s, 2), stat_of(s, 3),
+                       reinterpret_cast<const unsigned long long*>(s->d_com_indices), s->ncom, n, s->t_status, s->t_rejected);
+    if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "per-item verdicts: status launch failed");
+    return 0;
+  }
   hipLaunchKernelGGL(k_each_status, dim3(blocks_for(n, 256)), dim3(256), 0, st, stat_of(s, 0), stat_of(s, 1), stat_of(s, 2), stat_of(s, 3), n, s->t_status,
                      s->t_rejected);
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "per-item verdicts: status launch failed");
@@ -1700,7 +1706,11 @@ static int32_t each_status_enqueue(kzg_verify_session* s) {
 static int32_t each_build(kzg_verify_session* s, const EachGeom& g, uint64_t first_index) {
   const uint64_t n = s->n;
   hipStream_t st = s->st;
-  hipLaunchKernelGGL(k_each_terms, dim3(2 * blocks_for(n, 64)), dim3(64), 0, st, s->rpow2, s->z, s->y, s->aff, s->t_status, n, first_index, s->t_a, s->t_b);
+  if (s->rows)  // the commitment gathered through the item's index out of the list behind the n proofs
+    hipLaunchKernelGGL(k_each_rows_terms, dim3(2 * blocks_for(n, 64)), dim3(64), 0, st, s->rpow2, s->z, s->y, s->aff, s->t_status,
+                       reinterpret_cast<const unsigned long long*>(s->d_com_indices), s->ncom, n, first_index, s->t_a, s->t_b);
+  else
+    hipLaunchKernelGGL(k_each_terms, dim3(2 * blocks_for(n, 64)), dim3(64), 0, st, s->rpow2, s->z, s->y, s->aff, s->t_status, n, first_index, s->t_a, s->t_b);
   for (uint32_t l = 0; l < g.height; l++) {
     const uint64_t cin = g.off[l + 1] - g.off[l], cout = g.off[l + 2] - g.off[l + 1];
     hipLaunchKernelGGL(k_each_level, dim3(blocks_for(2 * cout, 64)), dim3(64), 0, st, s->t_a + g.off[l], s->t_b + g.off[l], cin, s->t_a + g.off[l + 1],
@@ -1834,20 +1844,25 @@ extern "C" uint64_t kzg_ctx_sessions_created(const kzg_ctx* ctx) {
   return total;
 }
 
-// The ending of the per-item calls: the session's front is enqueued and its root taken (n >= 2).
+// The ending of the per-item calls: the session's front is enqueued and its root taken (n >= 2; the row-indexed form: n >= 1).
+// The row-indexed form (s->rows): a rejected LISTED commitment, referenced or not, makes *ok 0 and keeps the batch check from running
+// -- it would sum a rejected point -- while an item's verdict depends on its own commitment alone: the tree settles the items.
 static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, const VerifyEach& out, int32_t* ok) {
   const uint64_t n = s->n;
   *ok = 0;
   const EachGeom g = each_geom(n);
-  uint32_t rejected = 0;
+  uint32_t counts[2] = {0, 0};  // rejected items; rows: rejected listed commitments
   int32_t rc = each_reserve(s, g);
   if (rc == 0) rc = each_status_enqueue(s);
   if (rc == 0 && (hipMemcpyAsync(out.status, s->t_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
-                  hipMemcpyAsync(&rejected, s->t_rejected, sizeof(uint32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+                  hipMemcpyAsync(counts, s->t_rejected, (s->rows ? 2 : 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+                  (s->rows && out.commitment_status &&
+                   hipMemcpyAsync(out.commitment_status, stat_of(s, 1), s->ncom * sizeof(int32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess) ||
                   hipStreamSynchronize(s->st) != hipSuccess))
     rc = fail(KZG_FAIL_HIP, "per-item verdicts: status read-back failed");
   if (rc) return rc;
-  if (rejected == 0) {  // today's batch check first: true = every item true
+  const uint32_t rejected = counts[0], bad_list = counts[1];
+  if (rejected == 0 && bad_list == 0) {  // today's batch check first: true = every item true
     Phase2 p2(s);
     int32_t all = 0;
     rc = p2_scalars(s, root, 1, 0, n);
@@ -1868,7 +1883,7 @@ static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, const Ver
   if (rc) return rc;
   for (uint64_t i = 0; i < n; i++)
     if (out.status[i]) out.ok_each[i] = 0;
-  return 0;  // *ok = 0: an item was rejected, or the batch check was false
+  return 0;  // *ok = 0: an item or a listed commitment was rejected, or the batch check was false
 }
 
 // The single-device batch call (engine_internal.hpp).  What differs between the routes: how the session with device-resident inputs
@@ -1876,7 +1891,9 @@ static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, const Ver
 int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hipStream_t st, const VerifyEach* each, int32_t* ok) {
   *ok = 0;
   const bool blobs = in.kind == VerifyKind::BLOBS;
-  if (each && n == 1) {  // per-item verdicts of one item: the boolean call's answer in the per-item outputs
+  // (not the row-indexed form: its boolean call validates the whole LIST, and a listed commitment the item does not reference must not
+  // become the item's status -- one item goes through each_finish like any other count)
+  if (each && n == 1 && !in.rows()) {  // per-item verdicts of one item: the boolean call's answer in the per-item outputs
     int32_t one = 0;
     const int32_t rc = verify_batch_single(ctx, in, 1, st, nullptr, &one);
     if (rc < 0) return rc;
@@ -1963,25 +1980,56 @@ extern "C" int32_t kzg_verify_cell_proof_batch(const kzg_ctx* ctx, const uint8_t
 // The cells kind with ncom = u in the session: the front reads the commitment through the index (k_cells_rows_leaves), the decoder runs
 // on n + u points, lincomb B has n + u + 64 terms whose u commitment scalars are the weights w_c (k_cells_row_weights), and lincomb A's
 // scalars r^k live in an array of their own.  Transcript, r and both sums are the per-cell call's on the expanded arrays.
-static int32_t rows_entry(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, int32_t* ok, hipStream_t st) {
+// `each`: the per-item form's outputs (kzg_verify_cell_proof_batch_rows_each), null for the boolean call.
+static int32_t rows_entry(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, const VerifyEach* each, int32_t* ok, hipStream_t st) {
   if (!ctx || !ok) return fail(KZG_FAIL_ARGUMENT, "null argument");
   if (n == 0) return empty_batch(ok);
   *ok = 0;
-  if (!in.commitment_indices || !in.cell_indices || !in.cells || !in.proofs48 || (in.ncom && !in.commitments48)) return fail(KZG_FAIL_ARGUMENT, "null argument");
-  if (in.ncom == 0) return KZG_ERR_COMMITMENT_INDEX;  // every index is out of range: nothing is launched
+  if (!in.commitment_indices || !in.cell_indices || !in.cells || !in.proofs48 || (in.ncom && !in.commitments48) || (each && (!each->ok_each || !each->status)))
+    return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (in.ncom == 0) {  // every index is out of range: nothing is launched
+    if (!each) return KZG_ERR_COMMITMENT_INDEX;
+    for (uint64_t i = 0; i < n; i++) {
+      each->status[i] = KZG_ERR_COMMITMENT_INDEX;
+      each->ok_each[i] = 0;
+    }
+    return 0;
+  }
   if (in.ncom >> 31) return fail(KZG_FAIL_ARGUMENT, "too many commitments");  // one workgroup column per commitment
-  return batch_entry(ctx, in, n, nullptr, ok, st);
+  return batch_entry(ctx, in, n, each, ok, st);
 }
 extern "C" int32_t kzg_verify_cell_proof_batch_rows(const kzg_ctx* ctx, const uint8_t* commitments48, uint64_t u, const uint64_t* commitment_indices,
                                                     const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs48, uint64_t n, int32_t* ok) try {
-  return rows_entry(ctx, cell_rows_inputs(commitments48, u, commitment_indices, cell_indices, cells, proofs48, true), n, ok, nullptr);
+  return rows_entry(ctx, cell_rows_inputs(commitments48, u, commitment_indices, cell_indices, cells, proofs48, true), n, nullptr, ok, nullptr);
 } catch (...) {
   return abi_exception();
 }
 extern "C" int32_t kzg_verify_cell_proof_batch_rows_dev(const kzg_ctx* ctx, const void* d_commitments48, uint64_t u, const void* d_commitment_indices,
                                                         const void* d_cell_indices, const void* d_cells, const void* d_proofs48, uint64_t n, int32_t* ok,
                                                         void* hip_stream) try {
-  return rows_entry(ctx, cell_rows_inputs(d_commitments48, u, d_commitment_indices, d_cell_indices, d_cells, d_proofs48, false), n, ok, (hipStream_t)hip_stream);
+  return rows_entry(ctx, cell_rows_inputs(d_commitments48, u, d_commitment_indices, d_cell_indices, d_cells, d_proofs48, false), n, nullptr, ok, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+
+// Per-item verdicts of the row-indexed form: the rows session as it stands through each_finish.  What learns the indirection is the
+// status fold (k_each_rows_status: the commitment's code through the item's index, the list's rejected entries counted beside) and the
+// terms kernel (k_each_rows_terms: the commitment gathered out of the list); levels, vector tree, fetches and descent are the per-cell
+// form's.  The challenge is the rows call's, which is the per-cell call's on the expanded arrays, so are both trees.
+extern "C" int32_t kzg_verify_cell_proof_batch_rows_each(const kzg_ctx* ctx, const uint8_t* commitments48, uint64_t u, const uint64_t* commitment_indices,
+                                                         const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs48, uint64_t n, uint8_t* ok_each,
+                                                         int32_t* status, int32_t* commitment_status, int32_t* ok) try {
+  const VerifyEach each{ok_each, status, commitment_status};
+  return rows_entry(ctx, cell_rows_inputs(commitments48, u, commitment_indices, cell_indices, cells, proofs48, true), n, &each, ok, nullptr);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_verify_cell_proof_batch_rows_each_dev(const kzg_ctx* ctx, const void* d_commitments48, uint64_t u, const void* d_commitment_indices,
+                                                             const void* d_cell_indices, const void* d_cells, const void* d_proofs48, uint64_t n, uint8_t* ok_each,
+                                                             int32_t* status, int32_t* commitment_status, int32_t* ok, void* hip_stream) try {
+  const VerifyEach each{ok_each, status, commitment_status};
+  return rows_entry(ctx, cell_rows_inputs(d_commitments48, u, d_commitment_indices, d_cell_indices, d_cells, d_proofs48, false), n, &each, ok,
+                    (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }

@@ -1186,9 +1186,17 @@ static __global__ __launch_bounds__(256) void k_each_status(const int32_t* __res
 // and nothing else.  Radix-2^28 point arithmetic with the complete adder behind the cheap one, as in var_bucket_chain: proof_i
 // = +-commitment_i, +-G and the identity partway through all occur.  A point at infinity is an all-zero entry and is skipped; a
 // rejected item (status != 0) writes the identity to both trees.
-static __global__ __launch_bounds__(64, 2) void k_each_terms(const fr_t* __restrict__ rpow2, const fr_t* __restrict__ z_plain, const fr_t* __restrict__ y_plain,
-                                                            const uint4* __restrict__ aff, const int32_t* __restrict__ status, uint64_t n,
-                                                            uint64_t first_index, g1_xyzz28* __restrict__ leaves_a, g1_xyzz28* __restrict__ leaves_b) {
+//
+// ROWS (k_each_rows_terms, the cells kind's row-indexed form): the session holds the n proofs, then a LIST of ncom commitments, then the
+// tail; item i's commitment is aff[n + commitment_indices[i]].  The row is one 8-byte load ahead of the ladder -- behind the status
+// test, so a rejected item (a row >= ncom among them: its status is KZG_ERR_COMMITMENT_INDEX) reads neither the index nor a base -- and
+// the commitment's position is the one 64-bit value the loop carries beyond the sibling's.  The body is shared; k_each_terms is its
+// ROWS = false instance with the figures it had (238 VGPRs, the adder's 352-byte frame, occupancy 2).
+template <bool ROWS>
+__device__ __forceinline__ void each_terms_body(const fr_t* __restrict__ rpow2, const fr_t* __restrict__ z_plain, const fr_t* __restrict__ y_plain,
+                                                const uint4* __restrict__ aff, const int32_t* __restrict__ status,
+                                                const unsigned long long* __restrict__ commitment_indices, uint64_t ncom, uint64_t n, uint64_t first_index,
+                                                g1_xyzz28* __restrict__ leaves_a, g1_xyzz28* __restrict__ leaves_b) {
   const uint32_t half = gridDim.x / 2u;
   const bool is_b = blockIdx.x >= half;  // uniform over the workgroup
   const uint64_t i = (uint64_t)(blockIdx.x - (is_b ? half : 0u)) * 64u + threadIdx.x;
@@ -1223,6 +1231,13 @@ static __global__ __launch_bounds__(64, 2) void k_each_terms(const fr_t* __restr
     }
   }
   const uint32_t nbases = is_b ? 3u : 1u;
+  // ROWS: where the item's commitment stands, and the tail behind the list (cells: y = 0, so the third base is never added, but its
+  // position stays inside the array); a row the front did not accept never arrives here, the clamp keeps even that one in bounds
+  uint64_t com_at = 0;
+  if (ROWS) {
+    const unsigned long long row = commitment_indices[i];
+    com_at = n + (row < ncom ? row : 0);
+  }
   // scalars are below r < 2^255: bit 255 is dropped, 255 steps
   auto shl1 = [](fr_t& s) {
 #pragma unroll
@@ -1239,7 +1254,7 @@ static __global__ __launch_bounds__(64, 2) void k_each_terms(const fr_t* __restr
     for (uint32_t k = 0; k < nbases; k++) {
       const uint32_t top = k == 0 ? s0.v[7] : (k == 1 ? s1.v[7] : s2.v[7]);
       if (!(top >> 31)) continue;
-      const uint64_t idx = k == 0 ? i : (k == 1 ? n + i : 2 * n);
+      const uint64_t idx = ROWS ? (k == 0 ? i : (k == 1 ? com_at : n + ncom)) : (k == 0 ? i : (k == 1 ? n + i : 2 * n));
       fp_t px, py;
       load_affine96(px, py, aff, idx);
       if (bn_is_zero(px) && bn_is_zero(py)) continue;  // the point at infinity
@@ -1258,6 +1273,18 @@ static __global__ __launch_bounds__(64, 2) void k_each_terms(const fr_t* __restr
     shl1(s2);
   }
   *out = acc;
+}
+static __global__ __launch_bounds__(64, 2) void k_each_terms(const fr_t* __restrict__ rpow2, const fr_t* __restrict__ z_plain, const fr_t* __restrict__ y_plain,
+                                                            const uint4* __restrict__ aff, const int32_t* __restrict__ status, uint64_t n,
+                                                            uint64_t first_index, g1_xyzz28* __restrict__ leaves_a, g1_xyzz28* __restrict__ leaves_b) {
+  each_terms_body<false>(rpow2, z_plain, y_plain, aff, status, nullptr, 0, n, first_index, leaves_a, leaves_b);
+}
+// the row-indexed form's terms (kzg_verify_cell_proof_batch_rows_each): the same budget, asserted by tests/test_cellverify_rows_each_host.py
+static __global__ __launch_bounds__(64, 2) void k_each_rows_terms(const fr_t* __restrict__ rpow2, const fr_t* __restrict__ z_plain, const fr_t* __restrict__ y_plain,
+                                                                 const uint4* __restrict__ aff /* n + ncom + tail */, const int32_t* __restrict__ status,
+                                                                 const unsigned long long* __restrict__ commitment_indices, uint64_t ncom, uint64_t n,
+                                                                 uint64_t first_index, g1_xyzz28* __restrict__ leaves_a, g1_xyzz28* __restrict__ leaves_b) {
+  each_terms_body<true>(rpow2, z_plain, y_plain, aff, status, commitment_indices, ncom, n, first_index, leaves_a, leaves_b);
 }
 
 // one level of both sum trees: out[j] = in[2 j] + in[2 j + 1], a missing sibling being the identity; lanes [0, cnt_out) take

@@ -13,6 +13,7 @@
 //   verify_cell_proof_batch(cs, idx, cells, ps) <- EIP-7594 verify_cell_kzg_proof_batch (specs/fulu/polynomial-commitments-sampling.md)
 //   verify_cell_proof_batch_each(...)    <- the same, one Verdict per tuple
 //   verify_cell_proof_batch_rows(cs, rows, idx, cells, ps) <- the same check on a block's commitment list and an index per cell
+//   verify_cell_proof_batch_rows_each(...) <- that form, one Verdict per cell (and the list's own statuses)
 //   decompress(bytes48) -> P1            <- P1::decompress, src/bls.rs:505-531
 //   verify_blob_proof(blob, c, p)        <- src/kzg/setup.rs:208-221
 //   verify_blob_proof_batch(blobs,cs,ps) <- src/kzg/setup.rs:247-275
@@ -626,6 +627,31 @@ class Setup {
     int32_t ok = 0;
     check(kzg_verify_cell_proof_batch_each(ctx_.get(), cs.data(), cell_indices.data(), cells, ps.data(), n, ok_each.data(), status.data(), &ok),
           "kzg_verify_cell_proof_batch_each");
+    std::vector<Verdict> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = Verdict{ok_each[i] != 0, status[i]};
+    return out;
+  }
+  // The row-indexed form's verdicts: entry i is what verify_cell_proof_batch returns for the expanded tuple i alone (status:
+  // CommitmentIndex for an index past the list, else as verify_cell_proof_batch_each); a listed commitment touches only the cells that
+  // reference it.  commitment_status, if wanted, receives the decoder's code per LISTED commitment, referenced or not; all_ok, if wanted,
+  // is verify_cell_proof_batch_rows' verdict.  Arguments and length checks as verify_cell_proof_batch_rows.
+  std::vector<Verdict> verify_cell_proof_batch_rows_each(const std::vector<Bytes48>& commitments, const std::vector<uint64_t>& commitment_indices,
+                                                         const std::vector<uint64_t>& cell_indices, const uint8_t* cells, size_t cells_len,
+                                                         const std::vector<Bytes48>& proofs, std::vector<int32_t>* commitment_status = nullptr,
+                                                         bool* all_ok = nullptr) const {
+    const size_t n = proofs.size(), u = commitments.size();
+    if (commitment_indices.size() != n || cell_indices.size() != n || cells_len != n * BYTES_PER_CELL)
+      throw std::invalid_argument("verify_cell_proof_batch_rows_each: one commitment index, one cell index and one 2048-byte cell per proof");
+    std::vector<uint8_t> cs(u * 48), ps(n * 48), ok_each(n);
+    std::vector<int32_t> status(n);
+    for (size_t i = 0; i < u; i++) std::copy(commitments[i].begin(), commitments[i].end(), cs.begin() + i * 48);
+    for (size_t i = 0; i < n; i++) std::copy(proofs[i].begin(), proofs[i].end(), ps.begin() + i * 48);
+    if (commitment_status) commitment_status->assign(u, 0);
+    int32_t ok = 0;
+    check(kzg_verify_cell_proof_batch_rows_each(ctx_.get(), u ? cs.data() : nullptr, u, commitment_indices.data(), cell_indices.data(), cells, ps.data(), n,
+                                                ok_each.data(), status.data(), commitment_status && u ? commitment_status->data() : nullptr, &ok),
+          "kzg_verify_cell_proof_batch_rows_each");
+    if (all_ok) *all_ok = ok != 0;
     std::vector<Verdict> out(n);
     for (size_t i = 0; i < n; i++) out[i] = Verdict{ok_each[i] != 0, status[i]};
     return out;

@@ -16,6 +16,7 @@ Method names, argument meaning and error behaviour follow the reference:
     Setup.verify_cell_proof_batch(cs, idx, cells, ps)  EIP-7594 verify_cell_kzg_proof_batch (same document as compute_cells)
     Setup.verify_cell_proof_batch_each(cs, idx, cells, ps)  the same, one verdict (or error) per tuple
     Setup.verify_cell_proof_batch_rows(cs, rows, idx, cells, ps)  the same check on a block's commitment LIST and an index per cell
+    Setup.verify_cell_proof_batch_rows_each(cs, rows, idx, cells, ps)  that form with one verdict (or error) per cell
     Setup.verify_data_columns(cs, columns)  ... built from column sidecars (column index, cells, proofs)
 
 Points cross this boundary in their 48-byte compressed form (what every caller
@@ -238,6 +239,13 @@ _SIGNATURES = {
     "kzg_verify_cell_proof_batch_rows_dev": (
         ctypes.c_int32,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
+    "kzg_verify_cell_proof_batch_rows_each": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u64p, _u64p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p, _i32p, _i32p]),
+    "kzg_verify_cell_proof_batch_rows_each_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p,
+         _i32p, _i32p, ctypes.c_void_p]),
     "kzg_cell_row_weights": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u64p, ctypes.c_uint64, ctypes.c_uint64, _u8p]),
     "kzg_verify_cell_proof_batch_each": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u64p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p, _i32p]),
     "kzg_verify_cell_proof_batch_each_dev": (
@@ -1039,7 +1047,13 @@ class Setup:
         its commitment in that list.  The verdict and the errors are verify_cell_proof_batch's on the expanded lists; an index past the
         list raises CellsError CommitmentIndex, and EVERY listed commitment is validated, referenced or not.  Unequal lengths, an item
         of the wrong size and an index that is no uint64 are a ValueError."""
-        what = "verify_cell_proof_batch_rows"
+        n, commitments, commitment_indices, cell_indices, cells, proofs = self._cell_rows_lists("verify_cell_proof_batch_rows", commitments, commitment_indices,
+                                                                                                cell_indices, cells, proofs)
+        return self.verify_cell_proof_batch_rows_host(b"".join(commitments), len(commitments), commitment_indices, cell_indices, b"".join(cells), b"".join(proofs), n)
+
+    @staticmethod
+    def _cell_rows_lists(what, commitments, commitment_indices, cell_indices, cells, proofs):
+        """the row-indexed list forms' length and size checks (ValueError) -> (n, the five lists as bytes / ints)"""
         n = len(cells)
         if not (len(commitment_indices) == n and len(cell_indices) == n and len(proofs) == n):
             raise ValueError("%s: %d commitment indices, %d cell indices, %d cells, %d proofs" % (what, len(commitment_indices), len(cell_indices), n, len(proofs)))
@@ -1051,7 +1065,7 @@ class Setup:
             raise ValueError("%s: a cell is %d bytes" % (what, BYTES_PER_CELL))
         if any(not 0 <= c < 1 << 64 for c in commitment_indices + cell_indices):
             raise ValueError("%s: an index is a uint64" % what)
-        return self.verify_cell_proof_batch_rows_host(b"".join(commitments), len(commitments), commitment_indices, cell_indices, b"".join(cells), b"".join(proofs), n)
+        return n, commitments, commitment_indices, cell_indices, cells, proofs
 
     def verify_cell_proof_batch_rows_host(self, commitments, u: int, commitment_indices, cell_indices, cells, proofs, n: int) -> bool:
         """kzg_verify_cell_proof_batch_rows on u CONTIGUOUS commitments and n contiguous (commitment index, cell index, cell, proof) in host
@@ -1072,16 +1086,66 @@ class Setup:
         """What a PeerDAS node holds: a block's commitments (one per blob) and column sidecars.  `columns` is a list of
         (column_index, cells, proofs), cells and proofs with one entry per commitment, in the commitments' order.  Builds the two index
         arrays and calls verify_cell_proof_batch_rows."""
-        u = len(commitments)
+        return self.verify_cell_proof_batch_rows(commitments, *self._data_column_lists("verify_data_columns", len(commitments), columns))
+
+    @staticmethod
+    def _data_column_lists(what, u, columns):
+        """column sidecars -> (commitment indices, cell indices, cells, proofs), column after column, a column's rows in the commitments' order"""
         rows, cols, cells, proofs = [], [], [], []
         for column_index, col_cells, col_proofs in columns:
             if len(col_cells) != u or len(col_proofs) != u:
-                raise ValueError("verify_data_columns: column %d has %d cells and %d proofs for %d commitments" % (column_index, len(col_cells), len(col_proofs), u))
+                raise ValueError("%s: column %d has %d cells and %d proofs for %d commitments" % (what, column_index, len(col_cells), len(col_proofs), u))
             rows += range(u)
             cols += [int(column_index)] * u
             cells += list(col_cells)
             proofs += list(col_proofs)
-        return self.verify_cell_proof_batch_rows(commitments, rows, cols, cells, proofs)
+        return rows, cols, cells, proofs
+
+    def _rows_verdicts(self, what: str, head, n: int, u: int, tail=()):
+        """a row-indexed per-item call `what`(handle, *head, n, ok_each, status, commitment_status, &ok, *tail)
+        -> (ok_each, status, commitment_status, ok)"""
+        ok_each, status, ok = ctypes.create_string_buffer(max(n, 1)), (ctypes.c_int32 * max(n, 1))(), ctypes.c_int32(0)
+        com_status = (ctypes.c_int32 * max(u, 1))()
+        rc = getattr(self._lib, what)(self._h, *head, n, ctypes.cast(ok_each, _u8p), status, com_status, ctypes.byref(ok), *tail)
+        self._check(rc, what)
+        if rc > 0:  # the ABI reports rejected items and commitments in its arrays, never as the call's code
+            raise EngineError("%s returned %d" % (what, rc))
+        return [bool(b) for b in ok_each.raw[:n]], list(status[:n]), list(com_status[:u]), bool(ok.value)
+
+    def verify_cell_proof_batch_rows_each(self, commitments: Sequence[bytes], commitment_indices: Sequence[int], cell_indices: Sequence[int],
+                                          cells: Sequence[bytes], proofs: Sequence[bytes]) -> List[Union[bool, CellsError, KzgError]]:
+        """verify_cell_proof_batch_rows with one verdict per cell: True / False, or IN PLACE the error the per-cell call raises for that
+        cell's expanded tuple alone -- CellsError CommitmentIndex / CellIndex, or KzgError for its commitment, cell or proof.  A listed
+        commitment touches only the cells that reference it (verify_cell_proof_batch_rows_each_host also returns the list's own
+        statuses).  Length and size checks are a ValueError, exactly as in verify_cell_proof_batch_rows."""
+        n, commitments, commitment_indices, cell_indices, cells, proofs = self._cell_rows_lists("verify_cell_proof_batch_rows_each", commitments,
+                                                                                                commitment_indices, cell_indices, cells, proofs)
+        ok_each, status, _, _ = self.verify_cell_proof_batch_rows_each_host(b"".join(commitments), len(commitments), commitment_indices, cell_indices,
+                                                                            b"".join(cells), b"".join(proofs), n)
+        return [_cell_verify_error(status[i]) if status[i] else ok_each[i] for i in range(n)]
+
+    def verify_cell_proof_batch_rows_each_host(self, commitments, u: int, commitment_indices, cell_indices, cells, proofs, n: int):
+        """kzg_verify_cell_proof_batch_rows_each on host memory (arguments as verify_cell_proof_batch_rows_host)
+        -> (ok_each: List[bool], status: List[int], commitment_status: List[int], ok: bool)"""
+        cidx, idx = self._cell_index_array(commitment_indices, n), self._cell_index_array(cell_indices, n)
+        com, cells, prf = self._host_args(commitments, cells, proofs)
+        if not isinstance(com, int) and len(com) == 0:
+            com = None  # an empty list: the ABI takes a null pointer with u == 0
+        return self._rows_verdicts("kzg_verify_cell_proof_batch_rows_each", (com, u, cidx, idx, cells, prf), n, u)
+
+    def verify_cell_proof_batch_rows_each_dev(self, d_commitments: int, u: int, d_commitment_indices: int, d_cell_indices: int, d_cells: int, d_proofs: int,
+                                              n: int, stream: int = 0):
+        """kzg_verify_cell_proof_batch_rows_each_dev: device pointers as verify_cell_proof_batch_rows_dev
+        -> (ok_each, status, commitment_status, ok); synchronous, results in host memory"""
+        return self._rows_verdicts("kzg_verify_cell_proof_batch_rows_each_dev", (d_commitments, u, d_commitment_indices, d_cell_indices, d_cells, d_proofs), n, u,
+                                   (stream,))
+
+    def verify_data_columns_each(self, commitments: Sequence[bytes], columns) -> List[list]:
+        """verify_data_columns with the bad cells named: one list per column, in the given order, of the per-row results of
+        verify_cell_proof_batch_rows_each (True / False / the error in place) -- which sidecar, and which cell of it, to drop."""
+        u, columns = len(commitments), list(columns)
+        res = self.verify_cell_proof_batch_rows_each(commitments, *self._data_column_lists("verify_data_columns_each", u, columns))
+        return [res[u * k: u * (k + 1)] for k in range(len(columns))]
 
     def cell_row_weights(self, r: int, commitment_indices: Sequence[int], u: int, first_index: int = 0) -> List[int]:
         """w_c = sum over the items k with commitment_indices[k] == c of r^(first_index + k) mod the group order, c < u, through the kernel
