@@ -415,6 +415,53 @@ int32_t kzg_recover_cells_and_proofs_select_batch_dev(const kzg_ctx* ctx, const 
 uint64_t kzg_ctx_cellproof_vectors(const kzg_ctx* ctx);
 
 /*
+ * The data column forms of the cell calls: cells and proofs as COLUMN MATRICES, the layout a block producer's column sidecars and
+ * kzg_verify_cell_proof_batch_rows' callers hold.  The consensus specs' compute_matrix / get_data_column_sidecars (produce) and
+ * recover_matrix (recover) for one block.
+ *   n                : the number of rows: the block's blobs, in order.
+ *   column matrix    : of cells, 128 * n * 2048 bytes, the cell of column c, row b at 2048 * (c * n + b); of proofs, 128 * n * 48
+ *                      bytes, the proof of (c, b) at 48 * (c * n + b).  Column c's sidecar payload is one run of n * 2048 and one of
+ *                      n * 48 bytes.  With T the permutation from the blob-major layout of the cell calls to this one:
+ * kzg_compute_data_columns_batch: out_column_cells, out_column_proofs48 and status are byte for byte T of
+ *   kzg_compute_cells_and_proofs_batch(blobs), out_commitments48 (n * 48, may be NULL) byte for byte kzg_blob_to_commitment_batch(blobs).
+ *   A rejected blob: KZG_ERR_BLOB_INVALID_FIELD_ELEMENT, its row zero bytes in all 128 columns of cells and of proofs, its commitment 48
+ *   zero bytes; the other rows are untouched by it.  The blobs cross PCIe once for the three results.
+ * kzg_recover_data_columns_batch: a node holds whole columns, so the masks are given ONCE and apply to every row (a caller with ragged
+ *   cell sets keeps to the blob-major calls).
+ *   present16, want16 : one 16-byte mask each, the bit order of `present` and `want` above.  HOST memory in every form, the *_dev ones
+ *                      included: they travel as kernel arguments and through the pass plan and are read before the call returns.
+ *   want16 == NULL   : cells only -- inout_column_proofs48 must be NULL too (and only then): no cell-proof table is built and no
+ *                      workspace slot taken, as in kzg_recover_cells_batch.
+ *   With the two masks repeated n times, out_column_cells, inout_column_proofs48 and status are exactly T of
+ *   kzg_recover_cells_and_proofs_select_batch(T^-1 column_cells, present x n, want x n, T^-1 inout_column_proofs48): all 128 columns of
+ *   an accepted row are written, the present ones byte for byte as they came; wanted proof positions hold the full call's bytes, those of
+ *   a rejected row 48 zero bytes; unwanted proof positions keep the caller's bytes; status precedence, the consistency check and the
+ *   zeroing of a rejected row's cells are that call's.  The bytes of an absent column are never interpreted.  out_column_cells must not
+ *   overlap column_cells.
+ * Bounds: nothing outside the matrices, the n commitments and the n statuses is written; n == 0 returns 0.  A null required pointer with
+ *   n > 0 returns KZG_FAIL_ARGUMENT; only out_commitments48, and want16 together with the proofs, may be null.
+ * The *_dev forms take HIP device pointers resident on ctx's device (16-byte aligned) for the matrices, commitments and statuses,
+ *   enqueue on `hip_stream` and return without synchronising on the device.  They take a workspace slot only when proofs or commitments
+ *   are computed.
+ * Group contexts: the host-buffer forms cut the ROWS into the members' usual contiguous shares, and each member writes its rows of every
+ *   column straight into the caller's matrices; the *_dev forms act on member 0.
+ * Passes are those of the select calls above (KATETH_AMD_CELLPROOF_PASS); a pass of m rows writes rows [base, base + m) of every column.
+ *   kzg_ctx_cellproof_vectors counts these calls like the others.
+ * Not here: per-row masks, a device-resident want16, *_group_dev forms, a verification call with implicit indices
+ *   (kzg_verify_cell_proof_batch_rows serves).
+ */
+int32_t kzg_compute_data_columns_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48 /* n * 48, may be NULL */,
+                                       uint8_t* out_column_cells /* 128 * n * 2048 */, uint8_t* out_column_proofs48 /* 128 * n * 48 */, int32_t* status);
+int32_t kzg_compute_data_columns_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_commitments48 /* may be NULL */,
+                                           void* d_out_column_cells, void* d_out_column_proofs48, void* d_status, void* hip_stream);
+int32_t kzg_recover_data_columns_batch(const kzg_ctx* ctx, const uint8_t* column_cells /* 128 * n * 2048 */, const uint8_t* present16 /* 16, HOST */,
+                                       const uint8_t* want16 /* 16, HOST, may be NULL */, uint64_t n, uint8_t* out_column_cells /* 128 * n * 2048 */,
+                                       uint8_t* inout_column_proofs48 /* 128 * n * 48; NULL iff want16 is NULL */, int32_t* status);
+int32_t kzg_recover_data_columns_batch_dev(const kzg_ctx* ctx, const void* d_column_cells, const uint8_t* present16 /* 16, HOST */,
+                                           const uint8_t* want16 /* 16, HOST, may be NULL */, uint64_t n, void* d_out_column_cells,
+                                           void* d_inout_column_proofs48 /* NULL iff want16 is NULL */, void* d_status, void* hip_stream);
+
+/*
  * Replaces Setup::proof for n (blob, z) pairs (src/kzg/setup.rs:185-194):
  *   z32 : n * 32 bytes big-endian ; out_proof48 : n * 48 ; out_y32 : n * 32
  *   status : per item 0, KZG_ERR_BLOB_*, KZG_ERR_FF_NOT_IN_FIELD for z

@@ -132,5 +132,59 @@ static __global__ __launch_bounds__(256) void k_cellproof_scatter(const uint4* _
   dst[2] = c;
 }
 
+// ---- the data column forms: siblings of k_cell_coeffs and k_cellproof_scatter, whose code they leave as it was ----
+// k_cell_coeffs' load out of a column matrix (recovery with proofs): item b is cells 0..63 of row row0 + b of `cells`, a matrix of
+// `rows` rows (cells_column_major: a wave reads one cell, 2 KiB in a row).  status[b] is k_columns_recover's verdict and is only read; a
+// row it rejected is not looked at.  Coefficients and vector statuses as k_cell_coeffs writes them.
+// gfx950: 159 VGPRs, scratch 0, LDS 131,080 B, two waves per SIMD (tests/test_datacolumns_host.py).
+static __global__ __launch_bounds__(CELLS_THREADS) void k_columns_coeffs(const uint8_t* __restrict__ cells, uint64_t rows, uint64_t row0, uint64_t n,
+                                                                      const uint32_t* __restrict__ tab, uint32_t* __restrict__ coeffs,
+                                                                      const int32_t* __restrict__ status, int32_t* __restrict__ vstatus) {
+  __shared__ uint32_t img[CELLS_IMAGE_DWORDS];
+  __shared__ int sh_pre, sh_bad;
+  for (uint64_t b = blockIdx.x; b < n; b += gridDim.x) {
+    uint32_t t = threadIdx.x;  // opaque per item, as in k_compute_cells
+    asm volatile("" : "+v"(t));
+    if (t == 0) {
+      sh_pre = status[b];
+      sh_bad = 0;
+    }
+    __syncthreads();
+    int code = sh_pre;
+    if (code == 0) {  // block-uniform
+      if (cellproof_load_blob(img, cells, t, cells_column_major{rows, row0 + b})) sh_bad = KZG_ERR_BLOB_INVALID_FIELD_ELEMENT;
+      __syncthreads();
+      code = sh_bad;
+    }
+    if (t < 128) vstatus[b * 128u + t] = code;
+    if (code == 0) {
+#pragma unroll 1
+      for (int p = 0; p < CELLPROOF_PASSES; p++) {
+        cellproof_inv_pass(img, tab, t, p);
+        __syncthreads();
+      }
+      uint32_t ts = t;
+      asm volatile("" : "+v"(ts));
+      cellproof_store_words(coeffs + b * (uint64_t)(CELLPROOF_COEFF_BYTES / 4), img, ts);
+    }
+    __syncthreads();
+  }
+}
+
+// k_cellproof_scatter into a column matrix of proofs of `rows` rows: slot s goes to the proof of (cell, row row0 + item) of pairs[s] =
+// 128 item + cell, at 48 (cell rows + row0 + item).  Positions no pair names are not touched.
+static __global__ __launch_bounds__(256) void k_columns_scatter(const uint4* __restrict__ compact, const uint32_t* __restrict__ pairs, uint32_t nslots,
+                                                                uint8_t* __restrict__ proofs, uint64_t rows, uint64_t row0) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nslots) return;
+  const uint32_t pair = pairs[s];
+  const uint4* src = compact + (uint64_t)s * 3u;
+  uint4* dst = reinterpret_cast<uint4*>(proofs + proofs_column_at(rows, row0 + cellproof_pair_item(pair), cellproof_pair_cell(pair)));
+  const uint4 a = src[0], b = src[1], c = src[2];
+  dst[0] = a;
+  dst[1] = b;
+  dst[2] = c;
+}
+
 #endif
 }  // namespace kzg

@@ -98,14 +98,16 @@ KZG_HD void cellproof_fwd_pass(uint32_t* img, const uint32_t* tab, uint32_t t, i
 }
 
 // the blob (4096 x 32 big-endian bytes, 16-byte aligned) into the image, element i 512 + t as k_compute_cells reads it; returns whether
-// one of this thread's elements is >= r
-KZG_HD bool cellproof_load_blob(uint32_t* img, const uint8_t* blob, uint32_t t) {
+// one of this thread's elements is >= r.  Under the column map (cells_math.cuh) `blob` is a column matrix of cells and the item is cells
+// 0..63 of one of its rows.
+template <class Map = cells_blob_major>
+KZG_HD bool cellproof_load_blob(uint32_t* img, const uint8_t* blob, uint32_t t, const Map map = Map()) {
   bool bad = false;
   KZG_UNROLL_FULL
   for (int i = 0; i < 8; i++) {
     const uint32_t e = (uint32_t)i * CELLS_THREADS + t;
     fr_t v;
-    recover_ld(v, blob + (size_t)e * 32u);
+    recover_ld(v, blob + map((size_t)e * 32u));
     bad |= !fr_is_canonical(v);
     cells_put(img, e, v);
   }

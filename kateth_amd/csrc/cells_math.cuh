@@ -48,6 +48,29 @@ KZG_CELLS_TABLE(cells_16r_t1, KZG_FR29_16R_T1)
 KZG_CELLS_TABLE(cells_neg_mod, KZG_FR29_NEG_MOD)
 #undef KZG_CELLS_TABLE
 
+// Where byte `at` of an item's 262,144-byte cell set lies, as an offset from the pointer the map goes with.  Blob-major (the cell
+// calls): the pointer is the item's own cell set and the offset is `at`.  Column-major (the data column calls): the pointer is a
+// column matrix of `rows` rows -- the cell of column c, row b at 2048 (c rows + b) -- and the item is row `row` of it.  A piece that
+// does not cross a cell boundary (every 16- and 32-byte piece the kernels move) stays in one run of bytes under either map.
+struct cells_blob_major {
+  KZG_HD size_t operator()(size_t at) const { return at; }
+};
+struct cells_column_major {
+  uint64_t rows, row;
+  KZG_HD size_t operator()(size_t at) const {
+    uint32_t cell = (uint32_t)(at >> 11);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // Every phase that moves cells has the 64 lanes of a wave inside ONE cell (tests/hostcpp/datacolumns_addr.cpp walks them all), so
+    // the column's base is scalar arithmetic and the lanes differ in the low eleven bits only: the accesses are as coalesced as
+    // blob-major ones, and no strided address is kept in vector registers.
+    cell = __builtin_amdgcn_readfirstlane(cell);
+#endif
+    return (size_t)(((uint64_t)cell * rows + row) << 11) + (at & 2047u);
+  }
+};
+// the same for proofs: the 48 bytes of (cell c, row b) of a column matrix of proofs
+KZG_HD size_t proofs_column_at(uint64_t rows, uint64_t row, uint32_t cell) { return (size_t)((uint64_t)cell * rows + row) * 48u; }
+
 // Dword index of element e in a word plane.  A 32-lane group of ds_read_b32 / ds_write_b32 is conflict-free when its indices differ
 // mod 32; the lanes of a group vary bits 3..7 of e at stride 1, bits 0..2 and 6..7 at stride 8, bits 0..4 at strides 64 and 512 and in
 // the coalesced load and store -- folding bits 5..7 onto bits 0..2 and bits 6..7 onto bits 3..4 makes all of them 32 different banks.

@@ -320,6 +320,15 @@ int32_t StageRing::feed(uint64_t k, const uint8_t* host_src, size_t bytes, hipSt
   HIP_TRY(hipMemcpyAsync(*d_chunk, host_src, bytes, hipMemcpyHostToDevice, copy_st));
   return copy_st != comp ? stream_after(comp, copy_st, ctx->stage_copied[slot]) : 0;
 }
+int32_t StageRing::feed_pitched(uint64_t k, const uint8_t* host_src, size_t host_pitch, size_t width, size_t height, hipStream_t comp, uint8_t** d_chunk) {
+  const uint64_t slot = k % slots;
+  hipStream_t copy_st = overlap ? ctx->stage_copy_stream : comp;
+  if (width * height > slot_bytes) return fail(KZG_FAIL_ARGUMENT, "staging ring: chunk larger than its slot");
+  *d_chunk = ctx->stage + slot * slot_bytes;
+  if (copy_st != comp && k >= slots) HIP_TRY(hipStreamWaitEvent(copy_st, ctx->stage_done[slot], 0));
+  HIP_TRY(hipMemcpy2DAsync(*d_chunk, width, host_src, host_pitch, width, height, hipMemcpyHostToDevice, copy_st));
+  return copy_st != comp ? stream_after(comp, copy_st, ctx->stage_copied[slot]) : 0;
+}
 hipEvent_t StageRing::done_event(uint64_t k) const { return ctx->stage_done[k % slots]; }
 int32_t StageRing::consumed(uint64_t k, hipStream_t comp) {
   HIP_TRY(hipEventRecord(done_event(k), comp));

@@ -490,6 +490,8 @@ struct StageRing {
   bool overlap = true;
   int32_t open(const kzg_ctx* c, uint64_t nslots, size_t bytes_per_slot, size_t io_bytes, bool overlap_copies);  // stage_init + stage_reserve
   int32_t feed(uint64_t k, const uint8_t* host_src, size_t bytes, hipStream_t comp, uint8_t** d_chunk);
+  // feed() of a chunk that lies in the caller's memory as `height` runs of `width` bytes, host_pitch apart; it arrives packed (pitch = width)
+  int32_t feed_pitched(uint64_t k, const uint8_t* host_src, size_t host_pitch, size_t width, size_t height, hipStream_t comp, uint8_t** d_chunk);
   hipEvent_t done_event(uint64_t k) const;
   int32_t consumed(uint64_t k, hipStream_t comp);
 };
@@ -536,6 +538,20 @@ struct HostCall {
     for (size_t k = 0; k < plan.size() && rc == 0; base += plan[k], k++) {
       uint8_t* d_chunk = nullptr;
       rc = ring.feed(k, src + base * item_bytes, plan[k] * item_bytes, st, &d_chunk);
+      if (rc == 0) rc = body(k, base, plan[k], d_chunk);
+      if (rc == 0) rc = ring.consumed(k, st);
+    }
+    return rc;
+  }
+  // passes() over the rows of a column matrix of `rows` rows in the caller's memory (`columns` columns of piece_bytes per row): a pass of
+  // m rows from row `base` on arrives as a column matrix of m rows
+  template <class Body>
+  int32_t passes_of_rows(const uint8_t* matrix, size_t piece_bytes, size_t columns, uint64_t rows, Body&& body) {
+    int32_t rc = 0;
+    uint64_t base = 0;
+    for (size_t k = 0; k < plan.size() && rc == 0; base += plan[k], k++) {
+      uint8_t* d_chunk = nullptr;
+      rc = ring.feed_pitched(k, matrix + base * piece_bytes, rows * piece_bytes, plan[k] * piece_bytes, columns, st, &d_chunk);
       if (rc == 0) rc = body(k, base, plan[k], d_chunk);
       if (rc == 0) rc = ring.consumed(k, st);
     }

@@ -495,9 +495,14 @@ static size_t cellsel_ws_bytes(const kzg_ctx* ctx, uint64_t call_pairs, const st
 // The compact proofs go to d_compact (null: the workspace's own buffer) and, with d_scatter_to -- the caller's proof buffer at the pass's
 // first item --, from there to their places.  A pass nobody wants a proof of launches k_cell_coeffs alone, and only where no earlier kernel
 // has written the statuses (status_written).
+// `col` (the data column calls): d_scatter_to is a column matrix of proofs of col->rows rows and the pass's first item its row col->row0;
+// with skip_rejected, d_items is the column matrix of cells the items are rows of, in the same way, and `stride` is not used.
+struct ColumnRows {
+  uint64_t rows, row0;
+};
 static int32_t cellsel_pass(const kzg_ctx* ctx, const uint8_t* d_items, uint64_t stride, bool skip_rejected, bool status_written, const Pass& p,
                             const uint32_t* d_pairs, uint8_t* d_compact, uint8_t* d_scatter_to, int32_t* d_status, const CellSelLayout& L, uint8_t* ws,
-                            hipStream_t st) {
+                            hipStream_t st, const ColumnRows* col = nullptr) {
   const uint64_t m = p.items, V = p.vectors;
   if (V == 0 && status_written) return 0;
   uint32_t* coeffs = reinterpret_cast<uint32_t*>(ws + L.o_coeff);
@@ -508,8 +513,12 @@ static int32_t cellsel_pass(const kzg_ctx* ctx, const uint8_t* d_items, uint64_t
   ctx->cellproof_vectors.fetch_add(V, std::memory_order_relaxed);
   {
     ProfScope ps(ctx, PROF_POLY, st);
-    hipLaunchKernelGGL(k_cell_coeffs, dim3((unsigned)std::min<uint64_t>(m, ctx->num_cus)), dim3(CELLS_THREADS), 0, st, d_items, stride, m, skip_rejected,
-                       ctx->d_cells_tab, coeffs, d_status, vstatus);
+    if (col && skip_rejected)
+      hipLaunchKernelGGL(k_columns_coeffs, dim3((unsigned)std::min<uint64_t>(m, ctx->num_cus)), dim3(CELLS_THREADS), 0, st, d_items, col->rows, col->row0, m,
+                         ctx->d_cells_tab, coeffs, d_status, vstatus);
+    else
+      hipLaunchKernelGGL(k_cell_coeffs, dim3((unsigned)std::min<uint64_t>(m, ctx->num_cus)), dim3(CELLS_THREADS), 0, st, d_items, stride, m, skip_rejected,
+                         ctx->d_cells_tab, coeffs, d_status, vstatus);
     if (V)
       hipLaunchKernelGGL(k_cell_quotients_sel, dim3((unsigned)V), dim3(CELLS_THREADS), 0, st, coeffs, ctx->d_cells_tab, ctx->d_cellproof_tab, vstatus, d_pairs,
                          cstat, q);
@@ -517,7 +526,10 @@ static int32_t cellsel_pass(const kzg_ctx* ctx, const uint8_t* d_items, uint64_t
   if (V == 0) return 0;
   const int32_t rc = msm_pipeline(ctx, false, reinterpret_cast<const uint8_t*>(q), V, d_compact, nullptr, cstat, L.msm, ws, st);
   if (rc) return rc;
-  if (d_scatter_to)
+  if (d_scatter_to && col)
+    hipLaunchKernelGGL(k_columns_scatter, dim3(blocks_for(V, 256)), dim3(256), 0, st, reinterpret_cast<const uint4*>(d_compact), d_pairs, (uint32_t)V,
+                       d_scatter_to, col->rows, col->row0);
+  else if (d_scatter_to)
     hipLaunchKernelGGL(k_cellproof_scatter, dim3(blocks_for(V, 256)), dim3(256), 0, st, reinterpret_cast<const uint4*>(d_compact), d_pairs, (uint32_t)V,
                        reinterpret_cast<uint4*>(d_scatter_to));
   return 0;
@@ -789,6 +801,250 @@ extern "C" int32_t kzg_recover_cells_and_proofs_select_batch_dev(const kzg_ctx* 
                                                                  void* d_out_cells, void* d_inout_proofs48, void* d_status, void* hip_stream) try {
   if (!ctx || (n && (!d_cells || !d_present || !want || !d_out_cells || !d_inout_proofs48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
   return das_dev(ctx, cell_call_select(d_cells, d_present, want, d_out_cells, d_inout_proofs48, d_status), n, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+// ---------------------------------------------------------------------------
+// the data column calls: the producer's and the reconstructing node's cell calls, cells and proofs as COLUMN MATRICES
+// ---------------------------------------------------------------------------
+// A column matrix of a call over n rows (the block's blobs, in order) puts the cell of column c, row b at 2048 (c n + b) and its proof at
+// 48 (c n + b): column c's sidecar payload is one run of bytes.  The kernels do the addressing (cells_column_major, cells_math.cuh; the
+// k_columns_* siblings), a pass of m rows writes rows [base, base + m) of every column, and everything else -- pass plan, pair lists,
+// workspace, MSM -- is the select calls': the ONE `want` mask of a call, repeated for its rows, goes through cellplan like n masks would,
+// and the producer is the all-ones plan, whose passes are the full call's.
+//   in        produce: the n blobs, blob-major.  recover (`present`): the column matrix of cells
+//   present   HOST memory in either form: the call's one 16-byte mask, a kernel argument of k_columns_recover
+//   want      HOST memory: the one mask of the proofs to compute; null: all of them (produce), or none (recover: out_proofs48 is null too)
+struct ColumnCall {
+  const uint8_t *in, *present, *want;
+  uint8_t *out_commitments48, *out_cells, *out_proofs48;
+  int32_t* status;
+};
+static std::vector<uint8_t> column_want_masks(const ColumnCall& c, uint64_t n) {
+  std::vector<uint8_t> want(n * cellplan::MASK_BYTES, 0xff);
+  for (uint64_t i = 0; c.want && i < n; i++) memcpy(want.data() + i * cellplan::MASK_BYTES, c.want, cellplan::MASK_BYTES);
+  return want;
+}
+// the cells of n rows, row0 on, of column matrices of `rows` rows: either kernel writes every byte of its rows and every status
+static int32_t columns_cells_enqueue(const kzg_ctx* ctx, const ColumnCall& c, const uint8_t* d_in, uint64_t n, uint8_t* d_out_cells, uint64_t rows, uint64_t row0,
+                                     int32_t* d_status, hipStream_t st) {
+  const unsigned grid = (unsigned)std::min<uint64_t>(n, ctx->num_cus);
+  if (c.present) {
+    uint4 mask;
+    memcpy(&mask, c.present, sizeof mask);
+    hipLaunchKernelGGL(k_columns_recover, dim3(grid), dim3(CELLS_THREADS), 0, st, d_in, mask, n, ctx->d_cells_tab, ctx->d_recover_tab, d_out_cells, rows, row0,
+                       d_status);
+  } else {
+    hipLaunchKernelGGL(k_columns_compute, dim3(grid), dim3(CELLS_THREADS), 0, st, d_in, n, ctx->d_cells_tab, d_out_cells, rows, row0, d_status);
+  }
+  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "data column cells launch failed");
+  return 0;
+}
+// The commitments of n resident blobs by the commitment path (the blobs' bytes as the MSM's scalars, chunks of 16,384 as
+// kzg_blob_to_commitment_batch_dev takes them), in the workspace from ws_off on.  The statuses hold the cells kernel's verdicts already: the
+// MSM's own range check finds the same blobs, and a rejected blob's commitment is 48 zero bytes.
+constexpr uint64_t COLUMNS_COMMIT_CHUNK = 16384;
+static size_t columns_commit_ws(const kzg_ctx* ctx, uint64_t n, size_t ws_off) {
+  Carve carve;
+  carve.off = ws_off;
+  (void)msm_carve(ctx, carve, std::min(n, COLUMNS_COMMIT_CHUNK));
+  return carve.off;
+}
+static int32_t columns_commit(const kzg_ctx* ctx, const uint8_t* d_blobs, uint64_t n, uint8_t* d_out48, int32_t* d_status, size_t ws_off, hipStream_t st) {
+  const uint64_t cn = std::min(n, COLUMNS_COMMIT_CHUNK);
+  Carve carve;
+  carve.off = ws_off;
+  const MsmBufs bufs = msm_carve(ctx, carve, cn);
+  for (uint64_t base = 0; base < n; base += cn) {
+    const int32_t rc =
+        msm_pipeline(ctx, true, d_blobs + base * (uint64_t)KZG_BYTES_PER_BLOB, std::min(n - base, cn), d_out48 + base * 48, nullptr, d_status + base, bufs, ws_ptr(ctx), st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// The device-resident call: the cells by their kernel, launched first and outside the lock (das_dev's order); commitments and proofs
+// under one workspace slot, which a call that wants neither does not take.  Both masks are read here, before the call returns.
+static int32_t columns_dev(const kzg_ctx* ctx, const ColumnCall& c, uint64_t n, hipStream_t st) {
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const bool recover = c.present != nullptr;
+  int32_t rc = c.out_proofs48 ? ensure_cellproof_tab(ctx) : 0;
+  if (rc == 0) rc = columns_cells_enqueue(ctx, c, c.in, n, c.out_cells, n, 0, c.status, st);
+  if (rc || (!c.out_proofs48 && !c.out_commitments48)) return rc;
+  return with_workspace(ctx, st, [&] {
+    const std::vector<uint8_t> want = column_want_masks(c, n);
+    const std::vector<Pass> plan = cellplan::plan(want.data(), n, cellproof_pass(ctx));
+    const uint64_t call_pairs = cellplan::total_vectors(plan);
+    Carve head;
+    head.take(call_pairs * sizeof(uint32_t));  // the pair list stays in front of everything, as in every pass's layout
+    const size_t need = std::max(cellsel_ws_bytes(ctx, call_pairs, plan), c.out_commitments48 ? columns_commit_ws(ctx, n, head.off) : (size_t)0);
+    int32_t e = ws_reserve(ctx, need, st);
+    if (e) return e;
+    uint8_t* ws = ws_ptr(ctx);
+    const uint32_t* d_pairs = reinterpret_cast<const uint32_t*>(ws);
+    if (call_pairs) {
+      kzg_ctx::PairPin* pin = nullptr;
+      e = pair_pin_take(ctx, call_pairs * sizeof(uint32_t), &pin);
+      if (e) return e;
+      cellplan::write_all_pairs(want.data(), plan, static_cast<uint32_t*>(pin->p));
+      HIP_TRY(hipMemcpyAsync(ws, pin->p, call_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipEventRecord(pin->ev, st));
+    }
+    if (c.out_commitments48) {
+      e = columns_commit(ctx, c.in, n, c.out_commitments48, c.status, head.off, st);
+      if (e) return e;
+    }
+    uint64_t base = 0, voff = 0;
+    for (const Pass& p : plan) {
+      const ColumnRows rows{n, base};
+      e = cellsel_pass(ctx, recover ? c.out_cells : c.in + base * (uint64_t)KZG_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB, recover, true, p, d_pairs + voff, nullptr,
+                       c.out_proofs48, c.status + base, cellsel_layout(ctx, call_pairs, p), ws, st, &rows);
+      if (e) return e;
+      base += p.items;
+      voff += p.vectors;
+    }
+    if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "data column pipeline launch failed");
+    return 0;
+  });
+}
+
+// The host-buffer call on one device, over rows [first, first + n) of the caller's matrices of `rows` rows (a group member's share; the
+// whole call on a single device).  A staging slot holds a pass of m rows column-major with pitch m -- the input (recover) and the cells
+// behind it -- and the copies between it and the caller's matrices are 2-D, between pitch 2048 m and pitch 2048 rows: the rows of every
+// column go straight to their places.  produce: the blobs go up once, blob-major, for cells, commitments and proofs alike; only columns
+// 64..127 come down, and columns 0..63 are copied from the caller's blobs on the host once the statuses are there (cells_first_halves'
+// reason).  Proofs: a pass's compact proofs are put column-major with pitch m in the workspace, and the wanted columns -- `want` is one
+// mask, so a column is wanted for all rows or for none -- come down in runs of consecutive columns, 48 m bytes per column; the wanted
+// positions of a rejected row arrive as the zero bytes the MSM's encoder wrote, and no other position of the caller's matrix is written.
+static int32_t columns_host(const kzg_ctx* ctx, const ColumnCall& c, uint64_t rows, uint64_t first, uint64_t n) {
+  if (n == 0) return 0;
+  const bool recover = c.present != nullptr, proofs = c.out_proofs48 != nullptr;
+  int32_t rc = proofs ? ensure_cellproof_tab(ctx) : 0;
+  if (rc) return rc;
+  std::vector<uint8_t> want;
+  std::vector<Pass> sel_plan;
+  std::vector<uint32_t> pairs;  // lives until close() has synchronised
+  std::vector<uint64_t> items_plan;
+  if (proofs) {
+    want = column_want_masks(c, n);
+    sel_plan = cellplan::plan(want.data(), n, cellproof_pass(ctx));
+    pairs.resize(cellplan::total_vectors(sel_plan));
+    cellplan::write_all_pairs(want.data(), sel_plan, pairs.data());
+    for (const Pass& p : sel_plan) items_plan.push_back(p.items);
+  } else {
+    items_plan = even_plan(n, ctx->knobs.cells_pass ? ctx->knobs.cells_pass : CELLS_OF_CELL_SETS.cells_pass);
+  }
+  const size_t up_bytes = recover ? KZG_BYTES_PER_CELL_SET : (size_t)KZG_BYTES_PER_BLOB;
+  HostCall hc(ctx);
+  const int a_com = hc.download(c.out_commitments48 ? c.out_commitments48 + first * 48 : nullptr, n * 48), a_st = hc.download(c.status + first, n * sizeof(int32_t)),
+            a_pairs = hc.upload(pairs.empty() ? nullptr : pairs.data(), pairs.size() * sizeof(uint32_t));
+  rc = hc.open(items_plan, up_bytes + KZG_BYTES_PER_CELL_SET);
+  if (rc) return rc;
+  uint8_t* d_com = hc.dev(a_com);
+  const uint32_t* d_pairs = hc.dev<uint32_t>(a_pairs);
+  int32_t* d_status = hc.dev<int32_t>(a_st);
+  // workspace of a pass: the select pass's layout (no pair list: it is in the host-i/o pool) and behind it the pass's proofs, column-major
+  auto colprf_off = [&](const Pass& p) { return cellsel_layout(ctx, 0, p).total; };
+  uint64_t voff = 0;
+  auto pass_body = [&](size_t k, uint64_t base, uint64_t m, uint8_t* d_in) -> int32_t {
+    uint8_t* d_cells = d_in + hc.max_pass * up_bytes;
+    int32_t e = columns_cells_enqueue(ctx, c, d_in, m, d_cells, m, 0, d_status + base, hc.st);
+    if (e) return e;
+    const uint64_t col0 = recover ? 0 : KZG_CELLS_PER_EXT_BLOB / 2;  // produce: the extension half only
+    if (hipMemcpy2DAsync(c.out_cells + (col0 * rows + first + base) * KZG_BYTES_PER_CELL, rows * KZG_BYTES_PER_CELL, d_cells + col0 * m * KZG_BYTES_PER_CELL,
+                         m * KZG_BYTES_PER_CELL, m * KZG_BYTES_PER_CELL, KZG_CELLS_PER_EXT_BLOB - col0, hipMemcpyDeviceToHost, hc.st) != hipSuccess)
+      return fail(KZG_FAIL_HIP, "device-to-host copy failed");
+    if (d_com) {
+      e = columns_commit(ctx, d_in, m, d_com + base * 48, d_status + base, 0, hc.st);
+      if (e) return e;
+    }
+    if (!proofs) return 0;
+    const Pass& p = sel_plan[k];
+    uint8_t* d_colprf = ws_ptr(ctx) + colprf_off(p);
+    const ColumnRows pass_rows{m, 0};
+    e = cellsel_pass(ctx, recover ? d_cells : d_in, KZG_BYTES_PER_BLOB, recover, true, p, d_pairs + voff, nullptr, d_colprf, d_status + base, cellsel_layout(ctx, 0, p),
+                     ws_ptr(ctx), hc.st, &pass_rows);
+    voff += p.vectors;
+    if (e || p.vectors == 0) return e;
+    for (uint32_t c0 = 0; c0 < cellplan::CELLS;) {  // runs of wanted columns
+      if (!cellplan::wanted(want.data(), c0)) {
+        c0++;
+        continue;
+      }
+      uint32_t c1 = c0 + 1;
+      while (c1 < cellplan::CELLS && cellplan::wanted(want.data(), c1)) c1++;
+      if (hipMemcpy2DAsync(c.out_proofs48 + ((uint64_t)c0 * rows + first + base) * 48, rows * 48, d_colprf + (uint64_t)c0 * m * 48, m * 48, m * 48, c1 - c0,
+                           hipMemcpyDeviceToHost, hc.st) != hipSuccess)
+        return fail(KZG_FAIL_HIP, "device-to-host copy failed");
+      c0 = c1;
+    }
+    return 0;
+  };
+  auto enqueue = [&] {
+    return recover ? hc.passes_of_rows(c.in + first * KZG_BYTES_PER_CELL, KZG_BYTES_PER_CELL, KZG_CELLS_PER_EXT_BLOB, rows, pass_body)
+                   : hc.passes(c.in + first * (size_t)KZG_BYTES_PER_BLOB, KZG_BYTES_PER_BLOB, pass_body);
+  };
+  if (proofs || d_com)
+    rc = with_workspace(ctx, hc.st, [&] {
+      size_t need = 0;  // sized before anything is in flight, for the pass that asks most: a short last pass may take more splits than a full one
+      for (uint64_t m : hc.plan) need = std::max(need, d_com ? columns_commit_ws(ctx, m, 0) : (size_t)0);
+      for (const Pass& p : sel_plan) need = std::max(need, colprf_off(p) + p.items * (size_t)(KZG_CELLS_PER_EXT_BLOB * 48));
+      const int32_t e = ws_reserve(ctx, need, hc.st);
+      return e ? e : enqueue();
+    });
+  else
+    rc = enqueue();
+  if (rc == 0 && hipGetLastError() != hipSuccess) rc = fail(KZG_FAIL_HIP, "data column pipeline launch failed");
+  rc = hc.close(rc);
+  if (rc == 0 && !recover) {  // columns 0..63 of every row: the caller's blob, or zero bytes
+    for (uint64_t b = first; b < first + n; b++)
+      for (uint64_t col = 0; col < KZG_CELLS_PER_EXT_BLOB / 2; col++) {
+        uint8_t* dst = c.out_cells + (col * rows + b) * KZG_BYTES_PER_CELL;
+        if (c.status[b] == 0)
+          memcpy(dst, c.in + b * (size_t)KZG_BYTES_PER_BLOB + col * KZG_BYTES_PER_CELL, KZG_BYTES_PER_CELL);
+        else
+          memset(dst, 0, KZG_BYTES_PER_CELL);
+      }
+  }
+  return rc;
+}
+static int32_t columns_on_members(const kzg_ctx* ctx, const ColumnCall& c, uint64_t n) {
+  return on_members(ctx, n, [&](const kzg_ctx* m, uint64_t first, uint64_t count) { return columns_host(m, c, n, first, count); });
+}
+
+extern "C" int32_t kzg_compute_data_columns_batch(const kzg_ctx* ctx, const uint8_t* blobs, uint64_t n, uint8_t* out_commitments48, uint8_t* out_column_cells,
+                                                  uint8_t* out_column_proofs48, int32_t* status) try {
+  if (!ctx || (n && (!blobs || !out_column_cells || !out_column_proofs48 || !status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return columns_on_members(ctx, ColumnCall{blobs, nullptr, nullptr, out_commitments48, out_column_cells, out_column_proofs48, status}, n);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_compute_data_columns_batch_dev(const kzg_ctx* ctx, const void* d_blobs, uint64_t n, void* d_out_commitments48, void* d_out_column_cells,
+                                                      void* d_out_column_proofs48, void* d_status, void* hip_stream) try {
+  if (!ctx || (n && (!d_blobs || !d_out_column_cells || !d_out_column_proofs48 || !d_status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return columns_dev(ctx, ColumnCall{(const uint8_t*)d_blobs, nullptr, nullptr, (uint8_t*)d_out_commitments48, (uint8_t*)d_out_column_cells,
+                                     (uint8_t*)d_out_column_proofs48, (int32_t*)d_status},
+                     n, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+// recover: the proofs pointer is null iff want16 is -- then it is kzg_recover_cells_batch in the column layout, with no table built and no workspace
+extern "C" int32_t kzg_recover_data_columns_batch(const kzg_ctx* ctx, const uint8_t* column_cells, const uint8_t* present16, const uint8_t* want16, uint64_t n,
+                                                  uint8_t* out_column_cells, uint8_t* inout_column_proofs48, int32_t* status) try {
+  if (!ctx || (n && (!column_cells || !present16 || !out_column_cells || !status || (want16 == nullptr) != (inout_column_proofs48 == nullptr))))
+    return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return columns_on_members(ctx, ColumnCall{column_cells, present16, want16, nullptr, out_column_cells, inout_column_proofs48, status}, n);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_recover_data_columns_batch_dev(const kzg_ctx* ctx, const void* d_column_cells, const uint8_t* present16, const uint8_t* want16, uint64_t n,
+                                                      void* d_out_column_cells, void* d_inout_column_proofs48, void* d_status, void* hip_stream) try {
+  if (!ctx || (n && (!d_column_cells || !present16 || !d_out_column_cells || !d_status || (want16 == nullptr) != (d_inout_column_proofs48 == nullptr))))
+    return fail(KZG_FAIL_ARGUMENT, "null argument");
+  return columns_dev(ctx, ColumnCall{(const uint8_t*)d_column_cells, present16, want16, nullptr, (uint8_t*)d_out_column_cells, (uint8_t*)d_inout_column_proofs48,
+                                     (int32_t*)d_status},
+                     n, (hipStream_t)hip_stream);
 } catch (...) {
   return abi_exception();
 }

@@ -120,8 +120,10 @@ KZG_HD void recover_prep_combine(uint32_t* zs, const uint32_t* part, uint32_t t)
 }
 
 // image = the present elements of cells 64 half .. 64 half + 63 times Z_c, zero where the cell is absent -- an absent cell's bytes are
-// not read.  Returns whether one of this thread's present elements is >= r.
-KZG_HD bool recover_load_half(uint32_t* img, const uint32_t* zs, const uint8_t* cells, const uint32_t* mask, uint32_t t, uint32_t half) {
+// not read.  Returns whether one of this thread's present elements is >= r.  `map` (cells_math.cuh) says where a byte of the item lies
+// from `cells` on: a wave's 64 lanes read one cell, 2 KiB in a row under either map.
+template <class Map = cells_blob_major>
+KZG_HD bool recover_load_half(uint32_t* img, const uint32_t* zs, const uint8_t* cells, const uint32_t* mask, uint32_t t, uint32_t half, const Map map = Map()) {
   bool bad = false;
   KZG_UNROLL_FULL
   for (int i = 0; i < 8; i++) {
@@ -130,7 +132,7 @@ KZG_HD bool recover_load_half(uint32_t* img, const uint32_t* zs, const uint8_t* 
     KZG_UNROLL_FULL
     for (int q = 0; q < 8; q++) v.v[q] = 0;
     if (recover_present(mask, c)) {
-      recover_ld(v, cells + ((size_t)half * 4096u + e) * 32u);
+      recover_ld(v, cells + map(((size_t)half * 4096u + e) * 32u));
       bad |= !fr_is_canonical(v);
       fr29 x, w;
       f29_from_bn(x, v);
@@ -144,8 +146,10 @@ KZG_HD bool recover_load_half(uint32_t* img, const uint32_t* zs, const uint8_t* 
   return bad;
 }
 
-// the image (canonical) -> cells 64 half .. of `out`; returns whether it differs from one of this thread's present elements
-KZG_HD bool recover_store_half(const uint32_t* img, const uint8_t* cells, uint8_t* out, const uint32_t* mask, uint32_t t, uint32_t half) {
+// the image (canonical) -> cells 64 half .. of `out`; returns whether it differs from one of this thread's present elements.  `map`
+// goes with `cells` and with `out` alike.
+template <class Map = cells_blob_major>
+KZG_HD bool recover_store_half(const uint32_t* img, const uint8_t* cells, uint8_t* out, const uint32_t* mask, uint32_t t, uint32_t half, const Map map = Map()) {
   uint32_t diff = 0;
   KZG_UNROLL_FULL
   for (int i = 0; i < 8; i++) {
@@ -155,19 +159,27 @@ KZG_HD bool recover_store_half(const uint32_t* img, const uint8_t* cells, uint8_
     cells_get(v, img, e);
     if (recover_present(mask, c)) {
       fr_t u;
-      recover_ld(u, cells + at);
+      recover_ld(u, cells + map(at));
       KZG_UNROLL_FULL
       for (int q = 0; q < 8; q++) diff |= u.v[q] ^ v.v[q];
     }
-    recover_st(out + at, v);
+    recover_st(out + map(at), v);
   }
   return diff != 0;
 }
 
+// the eight words of the stash's piece e
+template <class Map>
+KZG_HD uint32_t* recover_stash_piece(uint32_t* stash, uint32_t e, const Map map) {
+  return stash + map((size_t)e * 32u) / 4u;
+}
 // Step k = 0..17 of thread t (the list at the top).  Like cells_step it reads and writes the thread's own eight elements of the image,
 // so one barrier between steps is enough; `stash` is 131,072 bytes of global memory that only steps 3 (write) and 7 (read) touch, each
-// thread its own 8 x 32 bytes.
-KZG_HD void recover_step(uint32_t* img, const uint32_t* zs, uint32_t* stash, const uint32_t* tab, const uint32_t* rtab, uint32_t t, int k) {
+// thread its own 8 x 32 bytes.  The stash is cells 0..63 of the item's own output under `map`: piece e is the 32 bytes at offset 32 e
+// of the item, inside cell e >> 6, so under the column map it is row `row` of the output matrix's first 64 columns -- no two threads
+// share a piece, and none leaves the item's own cells.
+template <class Map = cells_blob_major>
+KZG_HD void recover_step(uint32_t* img, const uint32_t* zs, uint32_t* stash, const uint32_t* tab, const uint32_t* rtab, uint32_t t, int k, const Map map = Map()) {
   const bool inv = k <= 7 || (k >= 11 && k <= 14), fwd = (k >= 7 && k <= 10) || k >= 14;
   const int p = k <= 3 ? k : (k <= 7 ? k - 4 : (k <= 10 ? 10 - k : (k <= 14 ? k - 11 : 17 - k)));
   const uint32_t sh = 3u * (uint32_t)p, S = 1u << sh;
@@ -199,7 +211,7 @@ KZG_HD void recover_step(uint32_t* img, const uint32_t* zs, uint32_t* stash, con
     for (int i = 0; i < 8; i++) {
       fr_t v;
       f29_to_bn(v, x[i]);
-      uint32_t* s = static_cast<uint32_t*>(__builtin_assume_aligned(stash + (size_t)(base + ((uint32_t)i << sh)) * 8u, 16));
+      uint32_t* s = static_cast<uint32_t*>(__builtin_assume_aligned(recover_stash_piece(stash, base + ((uint32_t)i << sh), map), 16));
       KZG_UNROLL_FULL
       for (int q = 0; q < 8; q++) s[q] = v.v[q];
     }
@@ -209,7 +221,7 @@ KZG_HD void recover_step(uint32_t* img, const uint32_t* zs, uint32_t* stash, con
     KZG_UNROLL_FULL
     for (int i = 0; i < 8; i++) {
       const uint32_t e = base + ((uint32_t)i << sh);
-      const uint32_t* s = static_cast<const uint32_t*>(__builtin_assume_aligned(stash + (size_t)e * 8u, 16));
+      const uint32_t* s = static_cast<const uint32_t*>(__builtin_assume_aligned(recover_stash_piece(stash, e, map), 16));
       fr_t v;
       KZG_UNROLL_FULL
       for (int q = 0; q < 8; q++) v.v[q] = s[q];

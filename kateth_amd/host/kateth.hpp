@@ -400,6 +400,56 @@ class Setup {
     return out;
   }
 
+  // Data columns: what a block's column sidecars carry, as COLUMN MATRICES of `rows` rows (the block's blobs, in order) -- the cell of
+  // column c, row b at cells[2048 (c rows + b)], its proof at proofs[48 (c rows + b)] -- so that column c's payload is the run
+  // cells[2048 c rows ..], proofs[48 c rows ..].  `commitments` is 48 bytes per row.
+  struct DataColumns {
+    size_t rows = 0;
+    std::vector<uint8_t> commitments, cells, proofs;
+    const uint8_t* column_cells(size_t c) const { return cells.data() + c * rows * BYTES_PER_CELL; }
+    const uint8_t* column_proofs(size_t c) const { return proofs.data() + c * rows * 48; }
+  };
+  // The consensus specs' compute_matrix + get_data_column_sidecars for one block of len / 131,072 concatenated blobs: commitments, cells
+  // and cell proofs in one call, the blobs uploaded once (kzg_compute_data_columns_batch).  Errors as compute_cells, for the first
+  // rejected blob.
+  DataColumns data_column_sidecars(const uint8_t* blobs, size_t len) const {
+    if (len % BLOB_BYTES) throw Error(ErrorKind::BlobInvalidLen);
+    DataColumns out;
+    out.rows = len / BLOB_BYTES;
+    out.commitments.resize(out.rows * 48);
+    out.cells.resize(out.rows * CELLS_PER_EXT_BLOB * BYTES_PER_CELL);
+    out.proofs.resize(out.rows * CELLS_PER_EXT_BLOB * 48);
+    std::vector<int32_t> status(out.rows);
+    check(kzg_compute_data_columns_batch(ctx_.get(), blobs, out.rows, out.commitments.data(), out.cells.data(), out.proofs.data(), status.data()),
+          "kzg_compute_data_columns_batch");
+    for (int32_t code : status)
+      if (code) throw Error(static_cast<ErrorKind>(code));
+    return out;
+  }
+  // The consensus specs' recover_matrix for one block, with the proofs: `held` carries the columns `column_indices` (at least 64,
+  // distinct, < 128, in any order) in their places -- cells and proofs; its other columns may hold anything, its commitments are not
+  // looked at.  Returns all 128 columns: the held ones as they came, and only the absent columns' proofs are computed
+  // (kzg_recover_data_columns_batch).  Errors as recover_cells, for the first row that cannot be recovered.
+  DataColumns recover_data_columns(const DataColumns& held, const std::vector<uint64_t>& column_indices) const {
+    const size_t rows = held.rows;
+    if (held.cells.size() != rows * CELLS_PER_EXT_BLOB * BYTES_PER_CELL || held.proofs.size() != rows * CELLS_PER_EXT_BLOB * 48)
+      throw std::invalid_argument("recover_data_columns: the matrices are 128 * rows * 2048 and 128 * rows * 48 bytes");
+    std::array<uint8_t, 16> present{}, want{};
+    for (uint64_t c : column_indices) {
+      if (c >= CELLS_PER_EXT_BLOB || ((present[c >> 3] >> (c & 7)) & 1)) throw std::invalid_argument("recover_data_columns: column indices are distinct and below 128");
+      present[c >> 3] |= static_cast<uint8_t>(1u << (c & 7));
+    }
+    if (column_indices.size() < CELLS_PER_EXT_BLOB / 2) throw Error(ErrorKind::CellsNotEnough);
+    for (size_t b = 0; b < 16; b++) want[b] = static_cast<uint8_t>(~present[b]);
+    DataColumns out{rows, held.commitments, std::vector<uint8_t>(held.cells.size()), held.proofs};
+    std::vector<int32_t> status(rows);
+    check(kzg_recover_data_columns_batch(ctx_.get(), held.cells.data(), present.data(), want.data(), rows, out.cells.data(), out.proofs.data(), status.data()),
+          "kzg_recover_data_columns_batch");
+    for (int32_t code : status)
+      if (code) throw Error(static_cast<ErrorKind>(code));
+    return out;
+  }
+
   // (proof, y)
   std::pair<Bytes48, Bytes32> proof(const uint8_t* blob, size_t len, const Bytes32& point) const {
     if (len != BLOB_BYTES) throw Error(ErrorKind::BlobInvalidLen);

@@ -210,6 +210,16 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     ),
     "kzg_ctx_cellproof_vectors": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "kzg_compute_data_columns_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, _i32p]),
+    "kzg_compute_data_columns_batch_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "kzg_recover_data_columns_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
+    "kzg_recover_data_columns_batch_dev": (
+        ctypes.c_int32,
+        [ctypes.c_void_p, ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
     "kzg_compute_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p, _i32p]),
     "kzg_verify_blob_proof_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
     "kzg_verify_blob_proof_batch_dev": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
@@ -737,6 +747,94 @@ class Setup:
         if len(cells) != n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL or len(present) != n * 16 or len(want) != n * 16:
             raise ValueError("recover_cells_and_proofs_select_batch: n * 262144 bytes of cells and two n * 16 bytes of masks")
         return self._select_call("kzg_recover_cells_and_proofs_select_batch", [cells, present, want], n, proofs, True)
+
+    # -- data columns: cells and proofs as COLUMN MATRICES of n rows -- the cell of (column c, row b) at 2048 * (c * n + b), its proof at
+    # 48 * (c * n + b) -- so that column c's sidecar payload is one run of bytes
+    def compute_data_columns_batch(self, blobs: bytes, n: Optional[int] = None, want_commitments: bool = True):
+        """A block's n blobs -> (n * 48 bytes of commitments, or None without `want_commitments`; the column matrix of cells,
+        128 * n * 2048 bytes; the column matrix of proofs, 128 * n * 48 bytes; [status]).  Cells, proofs and statuses are
+        `compute_cells_and_proofs_batch`'s in the column layout, the commitments `blob_to_commitment_batch`'s; the blobs are uploaded
+        once.  A rejected blob's row is zero bytes in every column, and so is its commitment."""
+        blobs = _buf(blobs)
+        n = len(blobs) // BYTES_PER_BLOB if n is None else n
+        if len(blobs) != n * BYTES_PER_BLOB:
+            raise BlobError("InvalidLen")
+        coms = ctypes.create_string_buffer(n * 48) if want_commitments else None
+        cells = ctypes.create_string_buffer(n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL)
+        proofs = ctypes.create_string_buffer(n * CELLS_PER_EXT_BLOB * 48)
+        status = (ctypes.c_int32 * max(n, 1))()
+        rc = self._lib.kzg_compute_data_columns_batch(self._h, blobs, n, None if coms is None else ctypes.cast(coms, _u8p), ctypes.cast(cells, _u8p),
+                                                      ctypes.cast(proofs, _u8p), status)
+        self._check(rc, "kzg_compute_data_columns_batch")
+        return (None if coms is None else coms.raw), cells.raw, proofs.raw, list(status[:n])
+
+    def recover_data_columns_batch(self, column_cells: bytes, present: bytes, want: Optional[bytes] = None, n: Optional[int] = None,
+                                   proofs: Optional[bytes] = None):
+        """The column matrix of cells of n rows with the columns of the ONE 16-byte mask `present` filled in (absent columns may hold
+        anything) -> (the column matrix of all 128 columns, the column matrix of proofs or None, [status]).  `want` is the one mask of
+        the columns whose proofs to compute, into a copy of `proofs` (zero bytes when None) whose other positions stay; want = None:
+        cells only.  Statuses per row as `recover_cells_batch`; a rejected row is zero bytes in every column."""
+        column_cells, present = _buf(column_cells), _buf(present)
+        n = len(column_cells) // (CELLS_PER_EXT_BLOB * BYTES_PER_CELL) if n is None else n
+        size = n * CELLS_PER_EXT_BLOB * 48
+        if len(column_cells) != n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL or len(present) != 16 or (want is not None and len(_buf(want)) != 16):
+            raise ValueError("recover_data_columns_batch: n * 262144 bytes of cells and 16-byte masks")
+        if proofs is not None and (want is None or len(_buf(proofs)) != size):
+            raise ValueError("recover_data_columns_batch: the proof matrix is n * 6144 bytes and goes with `want`")
+        out = ctypes.create_string_buffer(n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL)
+        io = None if want is None else ctypes.create_string_buffer(bytes(_buf(proofs)) if proofs is not None else bytes(size), size)
+        status = (ctypes.c_int32 * max(n, 1))()
+        rc = self._lib.kzg_recover_data_columns_batch(self._h, column_cells, present, None if want is None else _buf(want), n, ctypes.cast(out, _u8p),
+                                                      None if io is None else ctypes.cast(io, _u8p), status)
+        self._check(rc, "kzg_recover_data_columns_batch")
+        return out.raw, (None if io is None else io.raw), list(status[:n])
+
+    def data_column_sidecars(self, blobs):
+        """The consensus specs' compute_matrix + get_data_column_sidecars for one block: `blobs` (a list of blobs, or their
+        concatenation) -> (commitments, columns), `columns` the list of 128 (column_index, cells, proofs) that `verify_data_columns`
+        takes, cells and proofs with one entry per blob in the blobs' order.  Raises what `compute_cells` raises for a rejected blob."""
+        blobs = b"".join(bytes(_buf(b)) for b in blobs) if isinstance(blobs, (list, tuple)) else _buf(blobs)
+        if len(blobs) % BYTES_PER_BLOB:
+            raise BlobError("InvalidLen")
+        n = len(blobs) // BYTES_PER_BLOB
+        coms, cells, proofs, status = self.compute_data_columns_batch(blobs, n)
+        for code in status:
+            if code:
+                raise error_from_status(code)
+        return [coms[48 * b:48 * (b + 1)] for b in range(n)], self._column_lists(n, range(CELLS_PER_EXT_BLOB), cells, proofs)
+
+    @staticmethod
+    def _column_lists(n, column_indices, cells, proofs):
+        """column matrices -> [(column_index, [n cells], [n proofs])] for the columns named"""
+        return [(c, [cells[BYTES_PER_CELL * (c * n + b):BYTES_PER_CELL * (c * n + b + 1)] for b in range(n)],
+                 [proofs[48 * (c * n + b):48 * (c * n + b + 1)] for b in range(n)]) for c in column_indices]
+
+    def recover_data_columns(self, n_rows: int, columns):
+        """The consensus specs' recover_matrix for one block, with the proofs: at least 64 column sidecars (column_index, cells,
+        proofs) of n_rows rows each, in any order -> all 128, in column order.  The given columns come back as they came and only the
+        absent columns' proofs are computed.  ValueError for a malformed list; BlobError / CellsError as `recover_cells` for a row that
+        cannot be recovered."""
+        n, columns = int(n_rows), list(columns)
+        seen = sorted(int(c) for c, _, _ in columns)
+        if any(not 0 <= c < CELLS_PER_EXT_BLOB for c in seen) or any(a == b for a, b in zip(seen, seen[1:])):
+            raise ValueError("recover_data_columns: column indices are distinct and below 128")
+        if len(seen) < CELLS_PER_EXT_BLOB // 2:
+            raise ValueError("recover_data_columns: %d columns, need 64..128" % len(seen))
+        cells, proofs, mask = bytearray(n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL), bytearray(n * CELLS_PER_EXT_BLOB * 48), bytearray(16)
+        for c, col_cells, col_proofs in columns:
+            c, col_cells, col_proofs = int(c), [_buf(v) for v in col_cells], [_buf(v) for v in col_proofs]
+            if len(col_cells) != n or len(col_proofs) != n or any(len(v) != BYTES_PER_CELL for v in col_cells) or any(len(v) != 48 for v in col_proofs):
+                raise ValueError("recover_data_columns: column %d needs %d cells of %d bytes and as many 48-byte proofs" % (c, n, BYTES_PER_CELL))
+            cells[BYTES_PER_CELL * c * n:BYTES_PER_CELL * (c + 1) * n] = b"".join(bytes(v) for v in col_cells)
+            proofs[48 * c * n:48 * (c + 1) * n] = b"".join(bytes(v) for v in col_proofs)
+            mask[c >> 3] |= 1 << (c & 7)
+        if n == 0:
+            return self._column_lists(0, range(CELLS_PER_EXT_BLOB), b"", b"")
+        out, all_proofs, status = self.recover_data_columns_batch(bytes(cells), bytes(mask), bytes(b ^ 0xFF for b in mask), n, bytes(proofs))
+        for code in status:
+            if code:
+                raise error_from_status(code)
+        return self._column_lists(n, range(CELLS_PER_EXT_BLOB), out, all_proofs)
 
     def compute_proof_batch(self, blobs: bytes, zs: bytes):
         blobs, zs = _buf(blobs), _buf(zs)
@@ -1381,6 +1479,25 @@ class Setup:
             raise ValueError("recover_cells_and_proofs_select_batch_dev: n * 16 bytes of mask")
         rc = self._lib.kzg_recover_cells_and_proofs_select_batch_dev(self._h, d_cells, d_present, want, n, d_out_cells, d_inout_proofs, d_status, stream)
         self._check(rc, "kzg_recover_cells_and_proofs_select_batch_dev")
+
+    def compute_data_columns_batch_dev(self, d_blobs: int, n: int, d_out_commitments: int, d_out_column_cells: int, d_out_column_proofs: int, d_status: int,
+                                       stream: int = 0):
+        """n blobs resident on the device -> n * 48 bytes of commitments (d_out_commitments = 0: not wanted), the column matrices of cells
+        (128 * n * 2048 bytes) and proofs (128 * n * 48) and n int32 statuses; enqueues on `stream` and returns"""
+        rc = self._lib.kzg_compute_data_columns_batch_dev(self._h, d_blobs, n, d_out_commitments or None, d_out_column_cells, d_out_column_proofs, d_status, stream)
+        self._check(rc, "kzg_compute_data_columns_batch_dev")
+
+    def recover_data_columns_batch_dev(self, d_column_cells: int, present: bytes, want: Optional[bytes], n: int, d_out_column_cells: int,
+                                       d_inout_column_proofs: int, d_status: int, stream: int = 0):
+        """Device-resident column recovery: `present` and `want` are ONE 16-byte mask each, HOST memory, read before this returns; want =
+        None goes with d_inout_column_proofs = 0 (cells only).  `d_out_column_cells` must not overlap `d_column_cells`.  Enqueues on
+        `stream` and returns."""
+        present, want = _buf(present), (None if want is None else _buf(want))
+        if len(present) != 16 or (want is not None and len(want) != 16):
+            raise ValueError("recover_data_columns_batch_dev: 16-byte masks")
+        rc = self._lib.kzg_recover_data_columns_batch_dev(self._h, d_column_cells, present, want, n, d_out_column_cells, d_inout_column_proofs or None, d_status,
+                                                          stream)
+        self._check(rc, "kzg_recover_data_columns_batch_dev")
 
     def cellproof_vectors(self) -> int:
         """quotient vectors this context (all members) has committed in cell-proof calls so far, 128 per item of a full call (measurement aid)"""
