@@ -538,9 +538,13 @@ KZG_HD void mont_mul(bn<F::N>& r, const bn<F::N>& a, const bn<F::N>& b) {
 }
 
 // ---- lazy-reduction variants: representatives in [0, 2m) -------------------------------------
-// Valid because 4m < 2^(32N) for both fields (p < 2^381, r < 2^255):  a, b < 2m  =>
+// Valid for Fp because 4p < 2^384 (p < 2^381):  a, b < 2m  =>
 // (a*b + q*m) / 2^(32N) < m (4m / 2^(32N) + 1) < 2m, so the Montgomery product needs no final
 // subtraction; add/sub fold back into [0, 2m) with one conditional +-2m.
+// NOT for Fr with both operands in [0, 2r): r = 0.9 * 2^255, so 4r = 1.8 * 2^256 and the product of two such operands
+// reaches 2.8r > 2^256 and loses its top bit (found by tests/test_gpu_fp28_device.py).  The lazy variants are used for Fp
+// only (g1.cuh); an Fr caller would have to keep one operand canonical (a < 2r, b < r: 2r / 2^256 + 1 < 2).
+// add_lazy, sub_lazy, canonicalize and is_zero_lazy hold on [0, 2m) for both fields (add_lazy through its carry term).
 template <class F>
 KZG_HD void mont_mul_lazy(bn<F::N>& r, const bn<F::N>& a, const bn<F::N>& b) {
   mont_mul_core<F, true>(r, a, b);
@@ -555,10 +559,13 @@ KZG_HD bn<F::N> modulus2() {
 template <class F>
 KZG_HD void add_lazy(bn<F::N>& r, const bn<F::N>& a, const bn<F::N>& b) {
   bn<F::N> t, s2;
-  bn_add(t, a, b);  // < 4m: no carry out of the top limb
+  // Fp: a + b < 4p < 2^384, no carry.  Fr: 4r > 2^256, so the sum can carry out of the top limb; it is then >= 2r and
+  // t - 2r mod 2^256 is the answer (a + b - 2r < 2r < 2^256).  Without the carry term Fr returned the wrapped sum.
+  uint32_t carry = bn_add(t, a, b);
   uint32_t borrow = bn_sub(s2, t, modulus2<F>());
+  const bool use_t = borrow && !carry;
   KZG_UNROLL_FULL
-  for (int i = 0; i < F::N; i++) r.v[i] = borrow ? t.v[i] : s2.v[i];
+  for (int i = 0; i < F::N; i++) r.v[i] = use_t ? t.v[i] : s2.v[i];
 }
 template <class F>
 KZG_HD void sub_lazy(bn<F::N>& r, const bn<F::N>& a, const bn<F::N>& b) {

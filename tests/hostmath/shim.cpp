@@ -684,3 +684,62 @@ extern "C" void hm_glv_split(uint8_t* out64, const uint8_t* k32) {
       out64[32 + 4 * i + b] = (uint8_t)(k2.v[i] >> (8 * b));
     }
 }
+
+// ---- radix-2^28 / 2^29 limbs in, limbs out (tests/device_atoms/atoms28_ops.h): the CPU counterparts of device_atoms28.hip's
+// da_f28_op / da_f29_op / da_xyzz28_op / da_jac28_op, same op numbers, same layouts, so that tests/fp28_cases.py can feed lazy-form
+// operands at their stated bounds and raw accumulators at their invariants' extremes with every column and limb bound checked
+#include "../device_atoms/atoms28_ops.h"
+extern "C" int32_t hm_f28_limbs_op(int op, uint32_t n, const uint32_t* in, uint32_t* out) {
+  switch (op) {
+#define HM_CASE(OP) \
+  case atoms28::OP: for (uint32_t i = 0; i < n; i++) atoms28::f28_case<atoms28::OP>(in + (size_t)i * 56, out + (size_t)i * 28); return 0;
+    ATOMS28_F28_OPS(HM_CASE)
+#undef HM_CASE
+  }
+  return -1;
+}
+extern "C" int32_t hm_f29_limbs_op(int op, uint32_t n, const uint32_t* in, uint32_t* out) {
+  switch (op) {
+#define HM_CASE(OP) \
+  case atoms28::OP: for (uint32_t i = 0; i < n; i++) atoms28::f29_case<atoms28::OP>(in + (size_t)i * 36, out + (size_t)i * 18); return 0;
+    ATOMS28_F29_OPS(HM_CASE)
+#undef HM_CASE
+  }
+  return -1;
+}
+// field.cuh's 32-bit-limb ops on the CPU build (da_bn_op's counterpart): field 0 = Fp (12 words), 1 = Fr (8 words)
+template <class F>
+static int32_t hm_bn_dispatch(int op, uint32_t n, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t* flag) {
+  switch (op) {
+#define HM_CASE(OP) \
+  case atoms28::OP: for (uint32_t i = 0; i < n; i++) atoms28::bn_case<F, atoms28::OP>(a + (size_t)i * F::N, b + (size_t)i * F::N, out + (size_t)i * F::N, flag + i); return 0;
+    ATOMS28_BN_OPS(HM_CASE)
+#undef HM_CASE
+  }
+  return -1;
+}
+extern "C" int32_t hm_bn_op(int field, int op, uint32_t n, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t* flag) {
+  if (field == 0) return hm_bn_dispatch<FpParams>(op, n, a, b, out, flag);
+  if (field == 1) return hm_bn_dispatch<FrParams>(op, n, a, b, out, flag);
+  return -1;
+}
+extern "C" int32_t hm_xyzz28_op(int op, uint32_t n, const uint32_t* acc_in, const uint32_t* q_in, uint32_t* acc_out, uint32_t* flag_out) {
+  constexpr int A = atoms28::ACC_WORDS;
+  switch (op) {
+#define HM_CASE(OP) \
+  case atoms28::OP: for (uint32_t i = 0; i < n; i++) atoms28::xyzz28_case<atoms28::OP>(acc_in + (size_t)i * A, q_in + (size_t)i * A, acc_out + (size_t)i * A, flag_out + i); return 0;
+    ATOMS28_X28_OPS(HM_CASE)
+#undef HM_CASE
+  }
+  return -1;
+}
+extern "C" int32_t hm_jac28_op(int op, uint32_t n, const uint32_t* acc_in, const uint32_t* entry_in, uint32_t* acc_out) {
+  constexpr int J = atoms28::JAC_WORDS, E = atoms28::ENTRY_WORDS;
+  switch (op) {
+#define HM_CASE(OP) \
+  case atoms28::OP: for (uint32_t i = 0; i < n; i++) atoms28::jac28_case<atoms28::OP>(acc_in + (size_t)i * J, entry_in + (size_t)i * E, acc_out + (size_t)i * J); return 0;
+    ATOMS28_J28_OPS(HM_CASE)
+#undef HM_CASE
+  }
+  return -1;
+}
