@@ -714,6 +714,55 @@ int32_t kzg_verify_cell_proof_batch_rows_each_dev(const kzg_ctx* ctx, const void
                                                   int32_t* commitment_status /* u, HOST, may be NULL */, int32_t* ok, void* hip_stream);
 
 /*
+ * THE BLOB FORM (transaction-pool form): a blob's 128 cell proofs checked against the blob itself -- what an execution client does
+ * with a blob transaction of network wrapper version 1 (BlobsBundleV2, engine_getBlobsV2; go-ethereum's kzg4844.VerifyCellProofs)
+ * before its pool admits it.  n blobs (n * 131072 bytes), their n commitments (n * 48) and n * 128 cell proofs (n * 128 * 48; proof k
+ * of blob b at 48 (128 b + k), the layout kzg_compute_cells_and_proofs_batch writes).  Device pointers (*_dev) are resident on ctx's
+ * device and 16-byte aligned.  Synchronous like every verify call: the pairing is on the host.
+ *   Definition: for canonical blobs *ok and the return code are EXACTLY those of kzg_verify_cell_proof_batch_rows with u = n and the
+ *   same commitment list, commitment_indices[i] = i >> 7, cell_indices[i] = i & 127, cells = kzg_compute_cells_batch(blobs) and the
+ *   same proofs: leaf i of the transcript is that call's leaf of tuple i, so root, seed, r and both sums are the same points.  The
+ *   calls are interchangeable bit for bit.  What differs is what moves: no cell array and no index array exists on host or device;
+ *   cells 0..63 are read out of the blob, cells 64..127 (128 KiB per blob) are computed into the session's workspace, and the
+ *   host-buffer form uploads blobs, commitments and proofs only.
+ *   n == 0   *ok = 1.  A null required pointer with n > 0 returns KZG_FAIL_ARGUMENT; so does n >= 2^24, whose 128 n items exceed what a
+ *            cell verification session takes.
+ *   rejected inputs: first-error-wins over three entries -- every blob before any commitment, every commitment before any proof, the
+ *            lowest position within the first entry that has an error:
+ *              1. blob: an element >= r      KZG_ERR_BLOB_INVALID_FIELD_ELEMENT (never taken for a blob of zeros)
+ *              2. commitment                 KZG_ERR_EC_* as kzg_g1_decompress_batch reports them
+ *              3. proof                      KZG_ERR_EC_*
+ *            Index errors cannot occur.  The point at infinity is a valid commitment and a valid proof.
+ * PER-BLOB VERDICTS (*_each): which transaction to drop.  ok_each (n bytes), status (n x int32) and ok are HOST memory in both.
+ *   status[b]  blob b's own first code in the order blob, commitment, proof (lowest k); 0 if there is none.
+ *   ok_each[b] 1 iff status[b] == 0 and the blob's 128 tuples pass on their own: for canonical, decodable inputs the AND of
+ *              kzg_verify_cell_proof_batch_rows_each's 128 verdicts of that blob.
+ *   *ok        1 iff every ok_each[b] == 1.  A rejected blob never makes the call return a positive code.
+ *   A blob with a non-zero status contributes nothing to any sum -- all 128 of its items, not only a rejected proof's -- and its
+ *   neighbours are judged as if it were absent.  The descent stops at the blobs (level 7 of the tree over the 128 n items): k bad
+ *   blobs among n cost at most 1 + 2 k ceil(log2 n) two-pairing checks (kzg_verify_each_checks counts them with the others').
+ * GROUP context: the host-buffer forms cut the BLOBS into the members' usual contiguous shares -- a blob is never split -- each member
+ * gets its slice of commitments and proofs, and the powers of r run over global item indices; the *_each form runs each share as its
+ * own batch, as the other *_each calls do.  The *_dev forms act on member 0.  Not here: a *_group_dev form, a phase-1 / session-tree
+ * form, and the GLV route.
+ */
+int32_t kzg_verify_blob_cell_proofs_batch(const kzg_ctx* ctx, const uint8_t* blobs /* n * 131072 */, const uint8_t* commitments48 /* n * 48 */,
+                                          const uint8_t* cell_proofs48 /* n * 128 * 48 */, uint64_t n, int32_t* ok);
+int32_t kzg_verify_blob_cell_proofs_batch_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_cell_proofs48, uint64_t n,
+                                              int32_t* ok, void* hip_stream);
+int32_t kzg_verify_blob_cell_proofs_batch_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* cell_proofs48, uint64_t n,
+                                               uint8_t* ok_each /* n, HOST */, int32_t* status /* n, HOST */, int32_t* ok);
+int32_t kzg_verify_blob_cell_proofs_batch_each_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_cell_proofs48, uint64_t n,
+                                                   uint8_t* ok_each /* n, HOST */, int32_t* status /* n, HOST */, int32_t* ok, void* hip_stream);
+/*
+ * Introspection: the blob form's commitment scalars.  out_w32[b] = sum_{k<128} r^(first_index + 128 b + k) mod the group order, b <
+ * n_blobs, 32 bytes big-endian canonical: kzg_cell_row_weights' values for commitment_indices[i] = i >> 7, through the launch sequence
+ * phase 2 of the blob form uses (k_batch_scalars, then k_blob_weights).  Host memory in and out; synchronous; a group context answers
+ * from member 0.  r >= the modulus: KZG_ERR_FF_NOT_IN_FIELD.
+ */
+int32_t kzg_blob_cell_weights(const kzg_ctx* ctx, const uint8_t* r32, uint64_t first_index, uint64_t n_blobs, uint8_t* out_w32 /* n_blobs * 32 */);
+
+/*
  * Introspection: out96[k] = sum_{j<64} s_kj [tau^j]_1 for m vectors of 64 scalars (scalars32: m x 64 x 32 bytes big-endian, canonical;
  * a scalar >= r is rejected with KZG_ERR_FF_NOT_IN_FIELD), in kzg_verify_phase2_dev's point format: x || y big-endian, all-zero = the
  * point at infinity.  It runs through the kernel that computes the monomial term of a fetched node in the cells *_each calls, which

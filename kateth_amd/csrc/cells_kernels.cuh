@@ -83,6 +83,69 @@ static __global__ __launch_bounds__(CELLS_THREADS) void k_compute_cells(const ui
   }
 }
 
+// The extension half alone (kzg_verify_blob_cell_proofs_batch: cells 0..63 are the blob's own bytes and are read where they lie).  A
+// sibling of k_compute_cells, not an instantiation of a shared body, for the reason given at the data column forms below: the same load
+// phase, range check and seven steps, and ONE store phase -- cells 64..127 of blob b to out_ext + 131,072 b, coalesced through the image.
+// status[b] is the blob's entry of the caller's error record: a blob with an element >= r gets KZG_ERR_BLOB_INVALID_FIELD_ELEMENT and
+// 131,072 zero bytes, which nothing may read as cells -- the verify kernels take the status, not the bytes, for the blob's verdict.
+// Same shape and budget as k_compute_cells (asserted by tests/test_blob_cell_proofs_host.py).
+static __global__ __launch_bounds__(CELLS_THREADS) void k_compute_cells_ext(const uint8_t* __restrict__ blobs, uint64_t n, const uint32_t* __restrict__ tab,
+                                                                         uint8_t* __restrict__ out_ext, int32_t* __restrict__ status) {
+  __shared__ uint32_t img[CELLS_IMAGE_DWORDS];
+  __shared__ int sh_bad;
+  for (uint64_t b = blockIdx.x; b < n; b += gridDim.x) {
+    uint32_t t = threadIdx.x;  // opaque per blob, as in k_compute_cells
+    asm volatile("" : "+v"(t));
+    const uint4* in = reinterpret_cast<const uint4*>(blobs + b * 131072ull);
+    uint4* out = reinterpret_cast<uint4*>(out_ext + b * 131072ull);
+    if (t == 0) sh_bad = 0;
+    __syncthreads();  // also: the previous blob's last reads of the image are done
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const uint32_t e = (uint32_t)i * CELLS_THREADS + t;
+      const uint4 w0 = in[2 * e], w1 = in[2 * e + 1];
+      fr_t v;
+      v.v[7] = __builtin_bswap32(w0.x);
+      v.v[6] = __builtin_bswap32(w0.y);
+      v.v[5] = __builtin_bswap32(w0.z);
+      v.v[4] = __builtin_bswap32(w0.w);
+      v.v[3] = __builtin_bswap32(w1.x);
+      v.v[2] = __builtin_bswap32(w1.y);
+      v.v[1] = __builtin_bswap32(w1.z);
+      v.v[0] = __builtin_bswap32(w1.w);
+      bad |= !fr_is_canonical(v);
+      cells_put(img, e, v);
+    }
+    if (bad) sh_bad = 1;
+    __syncthreads();
+    if (sh_bad) {  // block-uniform
+      const uint4 zero = make_uint4(0, 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 16; i++) out[(uint32_t)i * CELLS_THREADS + t] = zero;
+      if (t == 0) status[b] = KZG_ERR_BLOB_INVALID_FIELD_ELEMENT;
+      __syncthreads();  // every wave has read sh_bad before thread 0 clears it for the next blob
+      continue;
+    }
+    if (t == 0) status[b] = 0;
+#pragma unroll 1
+    for (int k = 0; k < CELLS_STEPS; k++) {
+      cells_step(img, tab, t, k);
+      __syncthreads();
+    }
+    uint32_t ts = t;  // opaque again: the store phase's addresses are not to be computed ahead of the steps and kept
+    asm volatile("" : "+v"(ts));
+#pragma unroll
+    for (int i = 0; i < 8; i++) {  // cells 64..127: the image as 4096 x 32 big-endian bytes, coalesced like the loads
+      const uint32_t e = (uint32_t)i * CELLS_THREADS + ts;
+      fr_t v;
+      cells_get(v, img, e);
+      out[2 * e] = make_uint4(__builtin_bswap32(v.v[7]), __builtin_bswap32(v.v[6]), __builtin_bswap32(v.v[5]), __builtin_bswap32(v.v[4]));
+      out[2 * e + 1] = make_uint4(__builtin_bswap32(v.v[3]), __builtin_bswap32(v.v[2]), __builtin_bswap32(v.v[1]), __builtin_bswap32(v.v[0]));
+    }
+  }
+}
+
 // recover_cells: one 512-thread workgroup per cell set, the grid loops over the sets; the steps are those of recover_math.cuh, on the
 // same LDS image as k_compute_cells, followed by that kernel's own seven steps for cells 64..127.  Global traffic per accepted item:
 // the present cells are read twice (to be scaled into the image, and to be compared with at the end), 128 KiB go to the item's own

@@ -3,7 +3,9 @@
 // scalars -S_j of lincomb B's monomial terms (arithmetic and layout: cellverify_math.cuh).  The row-indexed form
 // (kzg_verify_cell_proof_batch_rows) adds k_cells_rows_leaves, the front with the commitment read through an index, and
 // k_cells_row_weights / k_cells_roww_reduce, lincomb B's commitment scalars.  The per-item verdicts add k_cells_each_leaves,
-// k_each_vec_level and k_each_gather_cells (at the end of this file); the row-indexed form's verdicts add k_each_rows_status.
+// k_each_vec_level and k_each_gather_cells (at the end of this file); the row-indexed form's verdicts add k_each_rows_status.  The blob
+// form (kzg_verify_blob_cell_proofs_batch: the rows form with implicit indices, cells 0..63 read out of the blob) adds the BLOB instances
+// k_blob_cells_leaves, k_blob_cells_interp and k_blob_cells_each_leaves, and the two per-blob folds k_blob_weights and k_each_blob_status.
 #pragma once
 #include "cellverify_math.cuh"
 #include "verify_kernels.cuh"
@@ -25,23 +27,33 @@ namespace kzg {
 // row index is read and the address formed right where the twelve words are loaded, so nothing of it lives through the hash; an index
 // >= ncom reads commitment 0 and is rejected below (KZG_ERR_COMMITMENT_INDEX, ahead of the cell index's code).  The body is shared;
 // k_cells_leaves is its ROWS = false instance and compiles to what it was.
-template <bool ROWS>
+//
+// BLOB (k_blob_cells_leaves, kzg_verify_blob_cell_proofs_batch): the item number IS the pair of indices -- row i >> 7, column i & 127;
+// the two index pointers are null and never read.  `cells` are the BLOBS (131,072 bytes each) and cell k of blob b lies at
+// cells + 131072 b + 2048 k for k < 64, at ext + 131072 b + 2048 (k - 64) otherwise (cellv_blob_cell): one select per item ahead of
+// the hash, the streaming loop is the sibling's.  The cell's status is the BLOB's, as k_compute_cells_ext left it in blob_status (it
+// ran ahead on the same stream) -- all 128 items of a rejected blob carry its code, its zero-filled extension is never taken for
+// cells -- so the lane's own range check has no reader and the compiler drops it.
+template <bool ROWS, bool BLOB = false>
 __device__ __forceinline__ void cells_leaves_body(const uint8_t* __restrict__ commitments48, const unsigned long long* __restrict__ commitment_indices, uint64_t ncom,
                                                   const unsigned long long* __restrict__ cell_indices, const uint8_t* __restrict__ cells,
                                                   const uint8_t* __restrict__ proofs48, uint64_t n, const fr_t* __restrict__ h64_plain, fr_t* __restrict__ z_plain,
                                                   fr_t* __restrict__ y_plain, int32_t* __restrict__ status_index, int32_t* __restrict__ status_cell,
-                                                  uint32_t* __restrict__ leaves /* n x 8 words */) {
+                                                  uint32_t* __restrict__ leaves /* n x 8 words */, const uint8_t* __restrict__ ext = nullptr,
+                                                  const int32_t* __restrict__ blob_status = nullptr) {
   issue_priority_latency();
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint64_t row = i;
-  if (ROWS) {
+  if (BLOB) {
+    row = i >> 7;
+  } else if (ROWS) {
     const unsigned long long r = commitment_indices[i];
     row = r < ncom ? r : 0;
   }
   const uint32_t* c = reinterpret_cast<const uint32_t*>(commitments48 + row * 48);
-  const uint4* cell = reinterpret_cast<const uint4*>(cells + i * (uint64_t)KZG_BYTES_PER_CELL);
-  const unsigned long long index = cell_indices[i];
+  const uint4* cell = reinterpret_cast<const uint4*>(BLOB ? cellv_blob_cell(cells, ext, i) : cells + i * (uint64_t)KZG_BYTES_PER_CELL);
+  const unsigned long long index = BLOB ? (unsigned long long)(i & 127u) : cell_indices[i];
   // The range check rides on the words as they pass, most significant first: `cmp` is the comparison of the current element's words so
   // far with r's (0 undecided, 1 below, 2 above), so that nothing of an element is kept beyond the two words a block boundary cuts off.
   uint32_t cmp = 0;
@@ -119,11 +131,11 @@ __device__ __forceinline__ void cells_leaves_body(const uint8_t* __restrict__ co
   for (int q = 11; q < 15; q++) w[q] = 0;
   w[15] = (48 + 8 + KZG_BYTES_PER_CELL + 48) * 8;
   sha256_block_rolled(s, w);
-  status_cell[k] = bad ? KZG_ERR_BLOB_INVALID_FIELD_ELEMENT : 0;
+  status_cell[k] = BLOB ? blob_status[k >> 7] : (bad ? KZG_ERR_BLOB_INVALID_FIELD_ELEMENT : 0);
 #pragma unroll
   for (int q = 0; q < 8; q++) leaves[k * 8 + q] = s.h[q];
   {  // z, y and the index's status last, from the index read anew: nothing of them is held through the hash
-    const unsigned long long column = cell_indices[k];
+    const unsigned long long column = BLOB ? (unsigned long long)(k & 127u) : cell_indices[k];
     const bool good = column < (unsigned long long)KZG_CELLS_PER_EXT_BLOB;
     const uint4* h = reinterpret_cast<const uint4*>(h64_plain + (good ? (uint32_t)column : 0u));
     const uint4 zero = make_uint4(0, 0, 0, 0);
@@ -136,7 +148,7 @@ __device__ __forceinline__ void cells_leaves_body(const uint8_t* __restrict__ co
     yd[0] = zero;
     yd[1] = zero;
     int32_t code = good ? 0 : KZG_ERR_CELL_INDEX;
-    if (ROWS && commitment_indices[k] >= ncom) code = KZG_ERR_COMMITMENT_INDEX;
+    if (ROWS && !BLOB && commitment_indices[k] >= ncom) code = KZG_ERR_COMMITMENT_INDEX;
     status_index[k] = code;
   }
 }
@@ -156,6 +168,16 @@ static __global__ __launch_bounds__(256, 8) void k_cells_rows_leaves(const uint8
                                                                      fr_t* __restrict__ z_plain, fr_t* __restrict__ y_plain, int32_t* __restrict__ status_index,
                                                                      int32_t* __restrict__ status_cell, uint32_t* __restrict__ leaves /* n x 8 words */) {
   cells_leaves_body<true>(commitments48, commitment_indices, ncom, cell_indices, cells, proofs48, n, h64_plain, z_plain, y_plain, status_index, status_cell, leaves);
+}
+// the blob form's front (kzg_verify_blob_cell_proofs_batch): the same budget beside two decoder waves, asserted by
+// tests/test_blob_cell_proofs_host.py
+static __global__ __launch_bounds__(256, 8) void k_blob_cells_leaves(const uint8_t* __restrict__ commitments48 /* n / 128 x 48 */, const uint8_t* __restrict__ blobs,
+                                                                     const uint8_t* __restrict__ ext, const int32_t* __restrict__ blob_status,
+                                                                     const uint8_t* __restrict__ proofs48, uint64_t n, const fr_t* __restrict__ h64_plain,
+                                                                     fr_t* __restrict__ z_plain, fr_t* __restrict__ y_plain, int32_t* __restrict__ status_index,
+                                                                     int32_t* __restrict__ status_cell, uint32_t* __restrict__ leaves /* n x 8 words */) {
+  cells_leaves_body<true, true>(commitments48, nullptr, n >> 7, nullptr, blobs, proofs48, n, h64_plain, z_plain, y_plain, status_index, status_cell, leaves, ext,
+                                blob_status);
 }
 
 // The row-indexed form's commitment scalars  w_c = sum_{k : index_k = c} r^k  (cellverify_math.cuh), commitment-major: workgroup
@@ -208,6 +230,46 @@ static __global__ __launch_bounds__(256) void k_each_rows_status(const int32_t* 
   if (i < ncom && st_com[i]) atomicAdd(counts + 1, 1u);
 }
 
+// The blob form's commitment scalars (kzg_verify_blob_cell_proofs_batch): with implicit indices  w_b = sum_{k<128} r^(128 b + k)  is a
+// contiguous segment sum -- one 128-thread workgroup per blob, thread k takes r^(128 b + k) (plain, k_batch_scalars' lincomb A scalar)
+// and the tree of k_cells_row_weights (cellv_roww_fold) sums them.  Fr addition is exact, so the value is the one k_cells_row_weights
+// gives for the explicit index array (kzg_blob_cell_weights against kzg_cell_row_weights: the test).
+static __global__ __launch_bounds__(CELLV_BLOB_ITEMS) void k_blob_weights(const fr_t* __restrict__ rpow_plain /* 128 x gridDim.x */,
+                                                                         fr_t* __restrict__ out_plain /* gridDim.x */) {
+  __shared__ fr_t red[CELLV_BLOB_ITEMS];
+  const uint32_t t = threadIdx.x;
+  red[t] = rpow_plain[(uint64_t)blockIdx.x * CELLV_BLOB_ITEMS + t];
+  __syncthreads();
+  for (uint32_t w = CELLV_BLOB_ITEMS / 2; w >= 1; w >>= 1) {
+    if (t < w) cellv_roww_fold(red, t, w);
+    __syncthreads();
+  }
+  if (t == 0) out_plain[blockIdx.x] = red[0];
+}
+
+// The blob form's k_each_status (kzg_verify_blob_cell_proofs_batch_each): one 128-thread workgroup per blob folds (blob status,
+// commitment status, 128 proof statuses) to the blob's code (cellv_blob_code: the lowest rejected proof through an LDS minimum) and
+// writes it to ALL 128 items of the blob -- the terms kernel and the vector tree's leaves skip every item whose status is non-zero, so
+// nothing of a rejected blob enters lincomb A, lincomb B or the vector tree -- and to blob_code[b], the caller's status[b].
+// counts[0]: the rejected BLOBS.
+static __global__ __launch_bounds__(CELLV_BLOB_ITEMS) void k_each_blob_status(const int32_t* __restrict__ st_blob, const int32_t* __restrict__ st_com,
+                                                                             const int32_t* __restrict__ st_proof, int32_t* __restrict__ status /* 128 x gridDim.x */,
+                                                                             int32_t* __restrict__ blob_code /* gridDim.x */, uint32_t* __restrict__ counts) {
+  __shared__ uint32_t first;
+  const uint32_t t = threadIdx.x;
+  const uint64_t b = blockIdx.x, i = b * CELLV_BLOB_ITEMS + t;
+  if (t == 0) first = CELLV_BLOB_ITEMS;
+  __syncthreads();
+  if (st_proof[i]) atomicMin(&first, t);
+  __syncthreads();
+  const int32_t c = cellv_blob_code(st_blob[b], st_com[b], st_proof + b * CELLV_BLOB_ITEMS, first);
+  status[i] = c;
+  if (t == 0) {
+    blob_code[b] = c;
+    if (c) atomicAdd(counts, 1u);
+  }
+}
+
 // elements 8 t .. 8 t + 7 of cell k as they lie in memory (256 consecutive bytes, big-endian) -> plain limbs; zero for a cell that
 // contributes nothing
 __device__ __forceinline__ void cellv_load_elements(fr_t (&v)[8], const uint8_t* __restrict__ cells, uint64_t k, uint32_t t, bool live) {
@@ -232,16 +294,19 @@ __device__ __forceinline__ void cellv_load_elements(fr_t (&v)[8], const uint8_t*
 // cellverify_math.cuh with a barrier between them and the first 64 threads store the workgroup's 64 partial coefficients.  A cell
 // whose index or elements were rejected (the front's status words), and the cells past the batch's end in the last workgroup,
 // contribute zero.  r^k is lincomb A's scalar of item k as k_batch_scalars left it (plain).  No atomics: every sum has a fixed order.
-static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_interp(const uint8_t* __restrict__ cells, const unsigned long long* __restrict__ cell_indices,
-                                                                   const int32_t* __restrict__ status_index, const int32_t* __restrict__ status_cell,
-                                                                   const fr_t* __restrict__ rpow_plain, uint64_t n, const uint32_t* __restrict__ ctab,
-                                                                   const uint32_t* __restrict__ vtab, fr_t* __restrict__ partials /* gridDim.x x 64 */) {
-  __shared__ uint32_t img[CELLV_IMAGE_DWORDS];
+// BLOB (k_blob_cells_interp, the blob form): the column is k & 127 and the cell lies where cellv_blob_cell says -- `cells` are the
+// blobs, `ext` the extension workspace, the index pointer is null and never read; the eight threads of a cell share the choice.  The
+// body is shared; k_cells_interp is its BLOB = false instance and compiles to what it was.
+template <bool BLOB>
+__device__ __forceinline__ void cells_interp_body(uint32_t* __restrict__ img, const uint8_t* __restrict__ cells, const uint8_t* __restrict__ ext,
+                                                  const unsigned long long* __restrict__ cell_indices, const int32_t* __restrict__ status_index,
+                                                  const int32_t* __restrict__ status_cell, const fr_t* __restrict__ rpow_plain, uint64_t n,
+                                                  const uint32_t* __restrict__ ctab, const uint32_t* __restrict__ vtab, fr_t* __restrict__ partials) {
   const uint32_t cl = threadIdx.x >> 3, t = threadIdx.x & 7u;
   const uint64_t k = (uint64_t)blockIdx.x * CELLV_CELLS + cl;
   bool live = k < n;
   if (live) live = status_index[k] == 0 && status_cell[k] == 0;
-  const uint32_t column = live ? (uint32_t)cell_indices[k] : 0u;
+  const uint32_t column = live ? (BLOB ? (uint32_t)(k & 127u) : (uint32_t)cell_indices[k]) : 0u;
   fr_t rk;
   {
     const uint4 zero = make_uint4(0, 0, 0, 0);
@@ -252,7 +317,10 @@ static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_interp(const uin
   }
   {
     fr_t v[8];
-    cellv_load_elements(v, cells, k, t, live);
+    if (BLOB)
+      cellv_load_elements(v, cellv_blob_cell(cells, ext, live ? k : 0), 0, t, live);
+    else
+      cellv_load_elements(v, cells, k, t, live);
     cellv_step_a(img, ctab, cl, t, v);
   }
   __syncthreads();
@@ -263,6 +331,21 @@ static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_interp(const uin
     cellv_step_c(sum, img, threadIdx.x);
     partials[(uint64_t)blockIdx.x * 64 + threadIdx.x] = sum;
   }
+}
+static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_interp(const uint8_t* __restrict__ cells, const unsigned long long* __restrict__ cell_indices,
+                                                                   const int32_t* __restrict__ status_index, const int32_t* __restrict__ status_cell,
+                                                                   const fr_t* __restrict__ rpow_plain, uint64_t n, const uint32_t* __restrict__ ctab,
+                                                                   const uint32_t* __restrict__ vtab, fr_t* __restrict__ partials /* gridDim.x x 64 */) {
+  __shared__ uint32_t img[CELLV_IMAGE_DWORDS];
+  cells_interp_body<false>(img, cells, nullptr, cell_indices, status_index, status_cell, rpow_plain, n, ctab, vtab, partials);
+}
+// the blob form's instance (kzg_verify_blob_cell_proofs_batch); figures asserted by tests/test_blob_cell_proofs_host.py
+static __global__ __launch_bounds__(CELLV_THREADS) void k_blob_cells_interp(const uint8_t* __restrict__ blobs, const uint8_t* __restrict__ ext,
+                                                                        const int32_t* __restrict__ status_index, const int32_t* __restrict__ status_cell,
+                                                                        const fr_t* __restrict__ rpow_plain, uint64_t n, const uint32_t* __restrict__ ctab,
+                                                                        const uint32_t* __restrict__ vtab, fr_t* __restrict__ partials /* gridDim.x x 64 */) {
+  __shared__ uint32_t img[CELLV_IMAGE_DWORDS];
+  cells_interp_body<true>(img, blobs, ext, nullptr, status_index, status_cell, rpow_plain, n, ctab, vtab, partials);
 }
 
 // -S_j = -(sum of the partial vectors), j < 64, into the 64 scalar slots of lincomb B's monomial terms.  One workgroup: four threads
@@ -293,16 +376,18 @@ static __global__ __launch_bounds__(256) void k_cells_reduce(const fr_t* __restr
 // stored per cell instead of summed.  r_i = r^(first_index + i) comes from the seed's powers r^(2^k) (Montgomery) as in k_each_terms:
 // on the rejected-items route k_batch_scalars has not run.  An item whose single-item code is non-zero (status: k_each_status' output,
 // which covers the index and the elements) contributes the zero vector.
-static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_each_leaves(const uint8_t* __restrict__ cells, const unsigned long long* __restrict__ cell_indices,
-                                                                        const int32_t* __restrict__ status, const fr_t* __restrict__ rpow2, uint64_t n,
-                                                                        uint64_t first_index, const uint32_t* __restrict__ ctab, const uint32_t* __restrict__ vtab,
-                                                                        fr_t* __restrict__ leaves /* n x 64, plain, canonical */) {
-  __shared__ uint32_t img[CELLV_IMAGE_DWORDS];
+// BLOB (k_blob_cells_each_leaves, the blob form): column and cell address as in cells_interp_body<true>; k_cells_each_leaves is the
+// BLOB = false instance and compiles to what it was.
+template <bool BLOB>
+__device__ __forceinline__ void cells_each_leaves_body(uint32_t* __restrict__ img, const uint8_t* __restrict__ cells, const uint8_t* __restrict__ ext,
+                                                       const unsigned long long* __restrict__ cell_indices, const int32_t* __restrict__ status,
+                                                       const fr_t* __restrict__ rpow2, uint64_t n, uint64_t first_index, const uint32_t* __restrict__ ctab,
+                                                       const uint32_t* __restrict__ vtab, fr_t* __restrict__ leaves) {
   const uint32_t cl = threadIdx.x >> 3, t = threadIdx.x & 7u;
   const uint64_t k = (uint64_t)blockIdx.x * CELLV_CELLS + cl;
   bool live = k < n;
   if (live) live = status[k] == 0;
-  const uint32_t column = live ? (uint32_t)cell_indices[k] : 0u;
+  const uint32_t column = live ? (BLOB ? (uint32_t)(k & 127u) : (uint32_t)cell_indices[k]) : 0u;
   fr_t rk;
   bn_zero(rk);
   if (live) {
@@ -314,7 +399,10 @@ static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_each_leaves(cons
   }
   {
     fr_t v[8];
-    cellv_load_elements(v, cells, k, t, live);
+    if (BLOB)
+      cellv_load_elements(v, cellv_blob_cell(cells, ext, live ? k : 0), 0, t, live);
+    else
+      cellv_load_elements(v, cells, k, t, live);
     cellv_step_a(img, ctab, cl, t, v);
   }
   __syncthreads();
@@ -330,6 +418,20 @@ static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_each_leaves(cons
     cellv_cell_coeff(o, img, c2, j);
     leaves[item * 64 + j] = o;
   }
+}
+static __global__ __launch_bounds__(CELLV_THREADS) void k_cells_each_leaves(const uint8_t* __restrict__ cells, const unsigned long long* __restrict__ cell_indices,
+                                                                        const int32_t* __restrict__ status, const fr_t* __restrict__ rpow2, uint64_t n,
+                                                                        uint64_t first_index, const uint32_t* __restrict__ ctab, const uint32_t* __restrict__ vtab,
+                                                                        fr_t* __restrict__ leaves /* n x 64, plain, canonical */) {
+  __shared__ uint32_t img[CELLV_IMAGE_DWORDS];
+  cells_each_leaves_body<false>(img, cells, nullptr, cell_indices, status, rpow2, n, first_index, ctab, vtab, leaves);
+}
+static __global__ __launch_bounds__(CELLV_THREADS) void k_blob_cells_each_leaves(const uint8_t* __restrict__ blobs, const uint8_t* __restrict__ ext,
+                                                                             const int32_t* __restrict__ status, const fr_t* __restrict__ rpow2, uint64_t n,
+                                                                             uint64_t first_index, const uint32_t* __restrict__ ctab,
+                                                                             const uint32_t* __restrict__ vtab, fr_t* __restrict__ leaves /* n x 64 */) {
+  __shared__ uint32_t img[CELLV_IMAGE_DWORDS];
+  cells_each_leaves_body<true>(img, blobs, ext, nullptr, status, rpow2, n, first_index, ctab, vtab, leaves);
 }
 
 // one level of the vector tree: out[j] = in[2 j] + in[2 j + 1] coefficient by coefficient, a missing sibling being zero; one thread per

@@ -242,4 +242,21 @@ KZG_HD int32_t cellv_rows_item_status(const int32_t* st_index, const int32_t* st
   return c;
 }
 
+// ---- the blob form (kzg_verify_blob_cell_proofs_batch): the row-indexed form with implicit indices ------------------------------------
+// Item i is cell i & 127 of blob i >> 7: no index array exists.  Cells 0..63 are the blob's own bytes, cells 64..127 lie in the
+// extension workspace (k_compute_cells_ext), 131,072 bytes per blob in both.  One select per item; for a wave that works on one cell
+// it is uniform.  tests/hostcpp/blob_cells.cpp walks the map against the expanded arrays.
+constexpr int CELLV_BLOB_ITEMS = 128;  // items per blob = KZG_CELLS_PER_EXT_BLOB, and the threads of the two per-blob folds below
+KZG_HD const uint8_t* cellv_blob_cell(const uint8_t* blobs, const uint8_t* ext, uint64_t i) {
+  const uint64_t b = i >> 7, k = i & 127u;
+  return (k < 64 ? blobs : ext) + b * 131072ull + (k & 63u) * (uint64_t)KZG_BYTES_PER_CELL;
+}
+// The blob's code: its own status (the extension kernel's), else its commitment's, else its lowest rejected proof's.  `first_proof`:
+// the lowest k < 128 whose proof status is non-zero, 128 for none.
+KZG_HD int32_t cellv_blob_code(int32_t st_blob, int32_t st_com, const int32_t* st_proof128, uint32_t first_proof) {
+  if (st_blob) return st_blob;
+  if (st_com) return st_com;
+  return first_proof < (uint32_t)CELLV_BLOB_ITEMS ? st_proof128[first_proof] : 0;
+}
+
 }  // namespace kzg

@@ -8,6 +8,12 @@
 // pairing value is the product of the children's), otherwise the right child is checked too.  Breadth-first: the left children
 // of all failing nodes of a level go to `check` in one call, then the right children that still need one.
 // With k failing leaves among n: at most 1 + 2 k ceil(log2 n) nodes are checked, never more than 2 n - 1 (no node twice).
+//
+// FLOOR (default 0 = the above): the descent stops at level `floor`, whose m = ceil(n / 2^floor) nodes are the GROUPS the caller wants
+// a verdict for (the blob form of cell verification: floor 7, node (7, b) = blob b's 128 cells); ok_each then has m entries and
+// ok_each[g] = 0 iff group g holds a failing leaf.  Nothing below the floor is ever checked: with k failing groups at most
+// 1 + 2 k (height(n) - floor) nodes, height(n) - floor = ceil(log2 m) -- the bound above for m leaves -- and never more than 2 m - 1.
+// A floor above the root's level asks for the one group that is the whole tree: the root's check settles it.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -26,10 +32,11 @@ inline uint64_t level_count(uint64_t n, uint32_t level) { return (n + ((uint64_t
 // check(level, idx, m, pass) -> 0 or an error code: pass[k] = 1 iff node (level, idx[k]) passes; idx ascending; never called with m = 0.
 // ok_each[i] = 1 for a leaf that passes, 0 for one that fails.  Returns the first non-zero code of `check`.
 template <class Check>
-int32_t descend(uint64_t n, uint8_t* ok_each, Check&& check) {
-  for (uint64_t i = 0; i < n; i++) ok_each[i] = 1;
+int32_t descend(uint64_t n, uint8_t* ok_each, Check&& check, uint32_t floor = 0) {
   if (n == 0) return 0;
   uint32_t level = tree_height(n);
+  if (floor > level) floor = level;
+  for (uint64_t i = 0, m = level_count(n, floor); i < m; i++) ok_each[i] = 1;
   std::vector<uint64_t> failing, next, lefts, rights;
   std::vector<uint8_t> pass(1);
   {
@@ -39,7 +46,7 @@ int32_t descend(uint64_t n, uint8_t* ok_each, Check&& check) {
     if (pass[0]) return 0;
     failing.push_back(0);
   }
-  for (; level > 0; level--) {
+  for (; level > floor; level--) {
     const uint32_t child = level - 1;
     const uint64_t cnt = level_count(n, child);
     next.clear();

@@ -399,9 +399,22 @@ struct VerifyInputs {
   // entry commitment_indices[k] of it.  Null: the per-cell form, one commitment per item.
   const uint64_t* commitment_indices = nullptr;
   uint64_t ncom = 0;
-  bool rows() const { return commitment_indices != nullptr; }
+  // CELLS, the blob form (kzg_verify_blob_cell_proofs_batch): the row-indexed form with IMPLICIT indices over `blobs` -- ncom blobs, one
+  // commitment each, 128 ncom items; item i is cell i & 127 of blob i >> 7.  No index array and no cell array exists: cells 0..63 are
+  // the blob's bytes, cells 64..127 the session's extension workspace.
+  bool from_blobs = false;
+  bool rows() const { return commitment_indices != nullptr || from_blobs; }
   bool any_null() const {
+    if (from_blobs) return !commitments48 || !proofs48 || !blobs;
     return !commitments48 || !proofs48 || (kind == VerifyKind::BLOBS ? !blobs : kind == VerifyKind::POINTS ? (!z32 || !y32) : (!cell_indices || !cells));
+  }
+  VerifyInputs blob_share(uint64_t first_blob, uint64_t count) const {  // `count` blobs of the blob form from blob `first_blob` on: every array advances
+    VerifyInputs a = *this;
+    a.ncom = count;
+    a.blobs = blobs + first_blob * (size_t)KZG_BYTES_PER_BLOB;
+    a.commitments48 = commitments48 + first_blob * 48;
+    a.proofs48 = proofs48 + first_blob * (size_t)(KZG_CELLS_PER_EXT_BLOB * 48);
+    return a;
   }
   VerifyInputs advanced(uint64_t first) const {  // the same inputs from item `first` on (the row-indexed form's commitment list stays whole)
     VerifyInputs a{kind, blobs ? blobs + first * (size_t)KZG_BYTES_PER_BLOB : nullptr, rows() ? commitments48 : commitments48 + first * 48, proofs48 + first * 48,
@@ -432,7 +445,17 @@ static inline VerifyInputs cell_rows_inputs(const void* commitments48, uint64_t 
   in.ncom = ncom;
   return in;
 }
-// the wanted ending of a batch call: one boolean (no VerifyEach), or the per-item verdicts of kzg_verify_*_batch_each beside it
+static inline VerifyInputs blob_cell_inputs(const void* blobs, uint64_t n_blobs, const void* commitments48, const void* cell_proofs48, bool on_host) {
+  VerifyInputs in{VerifyKind::CELLS, (const uint8_t*)blobs, (const uint8_t*)commitments48, (const uint8_t*)cell_proofs48, nullptr, nullptr, on_host};
+  in.from_blobs = true;
+  in.ncom = n_blobs;
+  return in;
+}
+// the blob form's way to k_compute_cells_ext (cells_kernels.cuh is compiled once, in engine_proof.hip): cells 64..127 of n blobs to
+// d_out_ext (131,072 bytes per blob) and the blobs' statuses, enqueued on `st`
+int32_t cells_ext_enqueue(const kzg_ctx* ctx, const uint8_t* d_blobs, uint64_t n, uint8_t* d_out_ext, int32_t* d_status, hipStream_t st);
+// the wanted ending of a batch call: one boolean (no VerifyEach), or the per-item verdicts of kzg_verify_*_batch_each beside it (the
+// blob form of the cells kind: per BLOB, ncom entries each)
 struct VerifyEach {
   uint8_t* ok_each;
   int32_t* status;

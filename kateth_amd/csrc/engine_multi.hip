@@ -77,9 +77,12 @@ int32_t multi_verify_proof(const kzg_ctx* ctx, const uint8_t* proof48, const uin
 // shares; one share is exactly the single-device call on that member.  Otherwise every share runs the single-device phase 1
 // (verify_phase1) on its member; the challenge is seeded by all the shares' roots, so r differs from the single-device call's while the
 // boolean and the first-error code are the same.
+// The blob form of the cells kind (in.from_blobs, kzg_verify_blob_cell_proofs_batch): the shares are cut over the BLOBS -- a blob's 128
+// items are never split -- every array advances by the share's blobs, and the powers of r still run over global item indices.
 int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, int32_t* ok) {
   *ok = 0;
-  const std::vector<Share> shares = shares_of(ctx, n);
+  const uint64_t per = in.from_blobs ? KZG_CELLS_PER_EXT_BLOB : 1;  // items per unit of the split
+  const std::vector<Share> shares = shares_of(ctx, n / per);
   if (shares.size() == 1) return verify_batch_single(member_of(ctx, shares[0].member), in, n, nullptr, nullptr, ok);
   const uint32_t W = (uint32_t)shares.size();
   const int kinds = facts(in.kind).entries;
@@ -90,16 +93,33 @@ int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t 
   int32_t rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
     const kzg_ctx* m = member_of(ctx, shares[j].member);
     if (hipSetDevice(m->device) != hipSuccess) return fail(KZG_FAIL_HIP, "hipSetDevice failed");
-    return verify_phase1(m, in.advanced(shares[j].first), shares[j].count, nullptr, roots.data() + 32 * (size_t)j, err.data() + stride * j, &sessions[j]);
+    const VerifyInputs share = in.from_blobs ? in.blob_share(shares[j].first, shares[j].count) : in.advanced(shares[j].first);
+    return verify_phase1(m, share, shares[j].count * per, nullptr, roots.data() + 32 * (size_t)j, err.data() + stride * j, &sessions[j]);
   });
   // the row-indexed cells form: every member validated the WHOLE commitment list, so that entry of a record carries list positions,
   // not item positions -- it must not get a share's offset: the first share's (offset 0) stands for all
-  if (rc == 0 && in.rows())
+  if (rc == 0 && in.rows() && !in.from_blobs)
     for (uint32_t j = 1; j < W; j++) err[stride * j + 2] = -1;
-  const int32_t code = rc ? 0 : merged_first_error(shares, err.data(), kinds);
+  int32_t code = 0;
+  if (rc == 0 && in.from_blobs) {
+    // the blob form's order over the cells kind's record: blob (the cell entry: item positions), commitment (blob positions), proof
+    // (item positions).  The shares are contiguous in blobs, so within an entry positions in either unit order the same way: all in items
+    std::vector<Share> items(shares);
+    std::vector<int32_t> err3(6 * (size_t)W);
+    for (uint32_t j = 0; j < W; j++) {
+      items[j].first *= per;
+      items[j].count *= per;
+      const int32_t* e = err.data() + stride * j;
+      const int32_t rec[6] = {e[4], e[5], e[2] < 0 ? -1 : e[2] * (int32_t)per, e[3], e[6], e[7]};
+      memcpy(err3.data() + 6 * (size_t)j, rec, sizeof rec);
+    }
+    code = merged_first_error(items, err3.data(), 3);
+  } else if (rc == 0) {
+    code = merged_first_error(shares, err.data(), kinds);
+  }
   if (rc == 0 && code == 0)
     rc = run_on_helpers(W, [&](uint32_t j) -> int32_t {
-      return kzg_verify_phase2_dev(sessions[j], roots.data(), W, shares[j].first, n, partials.data() + 192 * (size_t)j);
+      return kzg_verify_phase2_dev(sessions[j], roots.data(), W, shares[j].first * per, n, partials.data() + 192 * (size_t)j);
     });
   {  // handing a session back may fail on its own: the error the caller is told about stays the first one
     const ErrorSnapshot keep = error_snapshot();
@@ -114,14 +134,17 @@ int32_t multi_verify_batch(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t 
 // own challenge -- an item's verdict does not depend on r, so the outputs land in place and nothing is merged but the AND.  The
 // row-indexed cells form: every member gets the whole commitment list and validates it, so each member's boolean already carries the
 // list's verdict and the list's statuses are written once, by the member that serves the first share.
+// The blob form (in.from_blobs): shares of whole blobs, and the outputs are per blob.
 int32_t multi_verify_each(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, const VerifyEach& each, int32_t* ok) {
   *ok = 0;
-  const std::vector<Share> shares = shares_of(ctx, n);
+  const uint64_t per = in.from_blobs ? KZG_CELLS_PER_EXT_BLOB : 1;
+  const std::vector<Share> shares = shares_of(ctx, n / per);
   std::vector<int32_t> oks(shares.size(), 0);
   const int32_t rc = run_on_helpers((uint32_t)shares.size(), [&](uint32_t j) -> int32_t {
     const Share& sh = shares[j];
     const VerifyEach out{each.ok_each + sh.first, each.status + sh.first, j == 0 ? each.commitment_status : nullptr};
-    return verify_batch_single(member_of(ctx, sh.member), in.advanced(sh.first), sh.count, nullptr, &out, &oks[j]);
+    const VerifyInputs share = in.from_blobs ? in.blob_share(sh.first, sh.count) : in.advanced(sh.first);
+    return verify_batch_single(member_of(ctx, sh.member), share, sh.count * per, nullptr, &out, &oks[j]);
   });
   if (rc) return rc;
   *ok = 1;

@@ -343,6 +343,13 @@ static int32_t cells_enqueue(const kzg_ctx* ctx, const uint8_t* d_blobs, uint64_
   if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "compute_cells launch failed");
   return 0;
 }
+// the extension half alone into a verify session's workspace (engine_internal.hpp: the verify driver's way to the kernel)
+int32_t cells_ext_enqueue(const kzg_ctx* ctx, const uint8_t* d_blobs, uint64_t n, uint8_t* d_out_ext, int32_t* d_status, hipStream_t st) {
+  const unsigned grid = (unsigned)std::min<uint64_t>(n, ctx->num_cus);
+  hipLaunchKernelGGL(k_compute_cells_ext, dim3(grid), dim3(CELLS_THREADS), 0, st, d_blobs, n, ctx->d_cells_tab, d_out_ext, d_status);
+  if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "blob extension launch failed");
+  return 0;
+}
 static int32_t recover_enqueue(const kzg_ctx* ctx, const uint8_t* d_cells, const uint8_t* d_present, uint64_t n, uint8_t* d_out_cells, int32_t* d_status,
                                hipStream_t st) {
   const unsigned grid = (unsigned)std::min<uint64_t>(n, ctx->num_cus);

@@ -68,6 +68,12 @@ struct kzg_verify_session {
   const uint64_t* d_com_indices = nullptr;  // front_enqueue records them: phase 2 reads them again
   fr_t* rpow = nullptr;        // [n] plain r^k: k_batch_scalars' sa, k_cells_interp's rpow_plain, lincomb A's scalars
   fr_t* roww_part = nullptr;   // [ncom x cellv_roww_tiles(n)] k_cells_row_weights' tile partials
+  // the blob form only (kzg_verify_blob_cell_proofs_batch: rows with implicit indices, n = 128 ncom): no cells, no index arrays
+  bool from_blobs = false;
+  const uint8_t* d_blobs = nullptr;  // front_enqueue records them: cells 0..63 of every blob, read again in phase 2
+  uint8_t* ext = nullptr;            // [ncom * 131072] cells 64..127 (k_compute_cells_ext)
+  int32_t* blob_stat = nullptr;      // [ncom] that kernel's statuses: the blob entry of the error record
+  int32_t* blob_code = nullptr;      // [ncom] per-blob codes of the *_each form (k_each_blob_status)
   // per-item verdicts (kzg_verify_*_batch_each, kzg_verify_session_tree): a device allocation of its own (owned), made on first use
   // and kept with the pooled session; carved by each_carve for the current n
   uint8_t* tree = nullptr;
@@ -463,13 +469,15 @@ static void scan_first_error(const int32_t* st, uint64_t n, int32_t* idx, int32_
 // ---- session set-up -----------------------------------------------------------------------------------------------
 struct SessionLayout {
   size_t o_aff, o_inf, o_z, o_y, o_scal, o_glv_b, o_glv_a, o_stat, o_first4, o_leaves, o_mids, o_nodes, o_pts, o_zy, o_msm_a, o_msm_b, o_rpow, o_ysum, o_cell_part,
-      o_cells_in, o_rpow_n, o_roww, total;
+      o_cells_in, o_rpow_n, o_roww, o_ext, o_blob_stat, o_blob_code, total;
 };
 // `staged`: room for the device copies of a host-buffer cells call's cells and indices (points_stage_host); the other kinds have nothing
 // that is carved on demand.  With one tail term the layout of the blob and points kinds is what it always was.
 // `rows`: the cells kind's row-indexed form with a list of `ncom` commitments (n otherwise): n + ncom points, status arrays of
 // max(n, ncom) words, and behind everything else the n powers r^k and the weights' tile partials.
-static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n, VerifyKind kind, bool staged, bool rows, uint64_t ncom) {
+// `from_blobs`: rows with implicit indices over ncom blobs (n = 128 ncom): the staged copy is the BLOBS, the weights need no partials, and
+// behind everything the extension workspace and the per-blob status words.
+static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n, VerifyKind kind, bool staged, bool rows, uint64_t ncom, bool from_blobs = false) {
   SessionLayout L{};
   const bool is_cells = kind == VerifyKind::CELLS;
   const uint64_t np = n + ncom, stride = std::max(n, ncom);  // proofs then commitments
@@ -496,17 +504,21 @@ static SessionLayout session_layout(const kzg_ctx* ctx, uint64_t n, VerifyKind k
   L.o_rpow = pool.take(64 * 32);
   L.o_ysum = pool.take(((n + 255) / 256 + 1) * 32);
   L.o_cell_part = pool.take(is_cells ? blocks_for(n, CELLV_CELLS) * (size_t)64 * sizeof(fr_t) : 0);
-  L.o_cells_in = pool.take(is_cells && staged ? n * ((size_t)KZG_BYTES_PER_CELL + 8 + (rows ? 8 : 0)) : 0);
+  L.o_cells_in = pool.take(!(is_cells && staged) ? 0 : from_blobs ? ncom * (size_t)KZG_BYTES_PER_BLOB : n * ((size_t)KZG_BYTES_PER_CELL + 8 + (rows ? 8 : 0)));
   L.o_rpow_n = pool.take(rows ? n * 32 : 0);
-  L.o_roww = pool.take(rows ? ncom * (size_t)cellv_roww_tiles(n) * 32 : 0);
+  L.o_roww = pool.take(rows && !from_blobs ? ncom * (size_t)cellv_roww_tiles(n) * 32 : 0);
+  L.o_ext = pool.take(from_blobs ? ncom * (size_t)KZG_BYTES_PER_BLOB : 0);
+  L.o_blob_stat = pool.take(from_blobs ? ncom * sizeof(int32_t) : 0);
+  L.o_blob_code = pool.take(from_blobs ? ncom * sizeof(int32_t) : 0);
   L.total = pool.off;
   return L;
 }
 
 // Takes a session from the context's pool (or creates one), sized for n items of `kind`, and enqueues its initialisation on `st`.
 // `staged`: session_layout's; `rows_ncom`: null, or the commitment count of the cells kind's row-indexed form.  The caller has set the device.
+// `from_blobs`: the blob form of the row-indexed session (rows_ncom = its blobs, n = 128 of them each).
 static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, VerifyKind kind, bool staged, kzg_verify_session** out,
-                               const uint64_t* rows_ncom = nullptr) {
+                               const uint64_t* rows_ncom = nullptr, bool from_blobs = false) {
   *out = nullptr;
   const bool is_cells = kind == VerifyKind::CELLS;
   const bool rows = rows_ncom != nullptr;
@@ -516,7 +528,7 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, V
     if (rc) return rc;
   }
   const uint64_t tail = facts(kind).tail_terms;
-  const SessionLayout L = session_layout(ctx, n, kind, staged, rows, ncom);
+  const SessionLayout L = session_layout(ctx, n, kind, staged, rows, ncom, from_blobs);
   kzg_verify_session* s = nullptr;
   {
     std::lock_guard<std::mutex> guard(ctx->pool_lock);
@@ -595,6 +607,8 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, V
   s->d_cells = nullptr;
   s->d_cell_indices = nullptr;
   s->d_com_indices = nullptr;
+  s->from_blobs = from_blobs;
+  s->d_blobs = nullptr;
   s->tree_n = 0;
   s->aff = (uint4*)(s->buf + L.o_aff);
   s->inf = s->buf + L.o_inf;
@@ -619,6 +633,9 @@ static int32_t session_acquire(const kzg_ctx* ctx, uint64_t n, hipStream_t st, V
   s->cells_in = s->buf + L.o_cells_in;
   s->rpow = (fr_t*)(s->buf + L.o_rpow_n);
   s->roww_part = (fr_t*)(s->buf + L.o_roww);
+  s->ext = s->buf + L.o_ext;
+  s->blob_stat = (int32_t*)(s->buf + L.o_blob_stat);
+  s->blob_code = (int32_t*)(s->buf + L.o_blob_code);
   // generator term (cells: the monomial terms), cleared flags and statuses
   const uint4* fixed = is_cells ? ctx->d_g1_monomial : ctx->d_gen_affine;  // `tail` points, their [z^2]-images behind them
   if (hipMemcpyAsync(s->aff + np * 6, fixed, tail * 96, hipMemcpyDeviceToDevice, st) != hipSuccess ||
@@ -754,6 +771,7 @@ static VerifyInputs staged_inputs(const kzg_verify_session* s) {
     case VerifyKind::POINTS: return point_inputs(s->pts48, s->pts48 + n * 48, s->zy32, s->zy32 + n * 32, false);
     case VerifyKind::CELLS: break;
   }
+  if (s->from_blobs) return blob_cell_inputs(s->cells_in, s->ncom, s->pts48 + n * 48, s->pts48, false);
   const uint8_t* idx = s->cells_in + n * (size_t)KZG_BYTES_PER_CELL;
   if (s->rows) return cell_rows_inputs(s->pts48 + n * 48, s->ncom, idx + n * 8, idx, s->cells_in, s->pts48, false);
   return cell_inputs(s->pts48 + n * 48, idx, s->cells_in, s->pts48, false);
@@ -765,6 +783,15 @@ static void err_clear(int32_t* err, int kinds) {
 static int32_t first_error_code(const int32_t* err, int kinds) {
   for (int k = 0; k < 2 * kinds; k += 2)
     if (err[k] >= 0) return err[k + 1];
+  return 0;
+}
+// The code of a session's error record.  The blob form reads the cells kind's record {index, commitment, cell, proof} in ITS order: the
+// cell entry is the blob's (the front writes the extension kernel's status to all 128 items of a blob, so its lowest position is the
+// lowest rejected blob), and every blob comes before any commitment, every commitment before any proof; the index entry is never set.
+static int32_t session_error_code(const kzg_verify_session* s, const int32_t* err) {
+  if (!s->from_blobs) return first_error_code(err, facts(s->kind).entries);
+  for (int k : {(int)kzg::verify::CELLS_CELL, 1, 3})
+    if (err[2 * k] >= 0) return err[2 * k + 1];
   return 0;
 }
 // Everything of phase 1 that can be enqueued at once.  When this returns z, y and the statuses are being produced, the decoder's
@@ -795,7 +822,13 @@ static int32_t front_enqueue(kzg_verify_session* s, const VerifyInputs& in) {
       decode_on_side(s, s->side, 0, n + s->ncom, prf, com, DECODE_FINISH | (fused_prep_fits(ctx, n, n + s->ncom) ? DECODE_WHOLE : 0u));
       if (hipMemsetAsync(s->first4, 0xff, 4 * sizeof(unsigned long long), s->side) != hipSuccess)  // for k_first_errors, later on this stream
         return fail(KZG_FAIL_HIP, "verify_proof_batch: fork failed");
-      if (s->rows)  // the row-indexed form: the commitment through the item's index, the index's status with the cell index's
+      if (s->from_blobs) {  // the blob form: the extension half into the session, then the front over implicit indices
+        s->d_blobs = in.blobs;
+        const int32_t rc = cells_ext_enqueue(ctx, in.blobs, s->ncom, s->ext, s->blob_stat, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_blob_cells_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, in.blobs, s->ext, s->blob_stat, prf, n, ctx->d_cellv_h64, s->z, s->y,
+                           stat_of(s, kzg::verify::CELLS_INDEX), stat_of(s, kzg::verify::CELLS_CELL), s->leaves);
+      } else if (s->rows)  // the row-indexed form: the commitment through the item's index, the index's status with the cell index's
         hipLaunchKernelGGL(k_cells_rows_leaves, dim3(blocks_for(n, 256)), dim3(256), 0, st, com, reinterpret_cast<const unsigned long long*>(in.commitment_indices),
                            s->ncom, reinterpret_cast<const unsigned long long*>(in.cell_indices), in.cells, prf, n, ctx->d_cellv_h64, s->z, s->y,
                            stat_of(s, kzg::verify::CELLS_INDEX), stat_of(s, kzg::verify::CELLS_CELL), s->leaves);
@@ -956,12 +989,18 @@ static int32_t points_stage_host(const kzg_ctx* ctx, const VerifyInputs& in, uin
   }
   SessionUse use;
   const bool is_cells = in.kind == VerifyKind::CELLS;
-  const int32_t rc = session_acquire(ctx, n, ctx->verify_stream, in.kind, true, &use.s, in.rows() ? &in.ncom : nullptr);
+  const int32_t rc = session_acquire(ctx, n, ctx->verify_stream, in.kind, true, &use.s, in.rows() ? &in.ncom : nullptr, in.from_blobs);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   if (hipMemcpyAsync(s->pts48, in.proofs48, n * 48, hipMemcpyHostToDevice, s->st) != hipSuccess ||
       hipMemcpyAsync(s->pts48 + n * 48, in.commitments48, s->ncom * 48, hipMemcpyHostToDevice, s->st) != hipSuccess)
     return fail(KZG_FAIL_HIP, "host-to-device copy failed");
+  if (s->from_blobs) {  // the blobs, commitments and proofs are all that crosses: 128 KiB + 48 B + 6 KiB per blob
+    if (hipMemcpyAsync(s->cells_in, in.blobs, s->ncom * (size_t)KZG_BYTES_PER_BLOB, hipMemcpyHostToDevice, s->st) != hipSuccess)
+      return fail(KZG_FAIL_HIP, "host-to-device copy failed");
+    *out = use.release();
+    return 0;
+  }
   if (s->rows && hipMemcpyAsync(s->cells_in + n * ((size_t)KZG_BYTES_PER_CELL + 8), in.commitment_indices, n * 8, hipMemcpyHostToDevice, s->st) != hipSuccess)
     return fail(KZG_FAIL_HIP, "host-to-device copy failed");
   if (is_cells ? (hipMemcpyAsync(s->cells_in, in.cells, n * (size_t)KZG_BYTES_PER_CELL, hipMemcpyHostToDevice, s->st) != hipSuccess ||
@@ -983,7 +1022,7 @@ int32_t verify_phase1(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t n, hi
   TraceTimer tt(ctx->knobs.trace, "phase1");
   err_clear(err, facts(in.kind).entries);
   SessionUse use;
-  int32_t rc = in.on_host ? points_stage_host(ctx, in, n, &use.s) : session_acquire(ctx, n, st, in.kind, false, &use.s, in.rows() ? &in.ncom : nullptr);
+  int32_t rc = in.on_host ? points_stage_host(ctx, in, n, &use.s) : session_acquire(ctx, n, st, in.kind, false, &use.s, in.rows() ? &in.ncom : nullptr, in.from_blobs);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   tt.mark("session");
@@ -1189,7 +1228,10 @@ static int32_t p2_scalars(kzg_verify_session* s, const uint8_t* roots32, uint64_
   fr_t* rk = s->rows ? s->rpow : s->scal + n;
   fr_t* tail_scal = s->scal + n + s->ncom;
   hipLaunchKernelGGL(k_batch_scalars, dim3(nblk), dim3(256), 0, st, s->rpow2, s->z, s->y, n, first_index, rk, s->scal, s->ysum);
-  if (s->rows) {  // w_c = sum of the r^k whose item points at commitment c: B's ncom commitment scalars
+  if (s->from_blobs) {  // w_b = the sum of blob b's 128 consecutive powers
+    ProfScope ps(s->ctx, PROF_POLY, st);
+    hipLaunchKernelGGL(k_blob_weights, dim3((unsigned)s->ncom), dim3(CELLV_BLOB_ITEMS), 0, st, rk, s->scal + n);
+  } else if (s->rows) {  // w_c = sum of the r^k whose item points at commitment c: B's ncom commitment scalars
     const uint32_t tiles = cellv_roww_tiles(n);
     ProfScope ps(s->ctx, PROF_POLY, st);  // no class of their own: a verification call launches nothing else of the k_poly class
     hipLaunchKernelGGL(k_cells_row_weights, dim3((unsigned)s->ncom, tiles), dim3(CELLV_ROWW_THREADS), 0, st, reinterpret_cast<const unsigned long long*>(s->d_com_indices),
@@ -1200,8 +1242,12 @@ static int32_t p2_scalars(kzg_verify_session* s, const uint8_t* roots32, uint64_
     // y = 0: the generator's slot is S_0's.  The 64 scalars -S_j of the monomial terms: r^k (s->scal + n, just written) times the
     // interpolation polynomial of cell k, summed per workgroup, then over the workgroups
     const unsigned ngrp = blocks_for(n, CELLV_CELLS);
-    hipLaunchKernelGGL(k_cells_interp, dim3(ngrp), dim3(CELLV_THREADS), 0, st, s->d_cells, reinterpret_cast<const unsigned long long*>(s->d_cell_indices),
-                       stat_of(s, kzg::verify::CELLS_INDEX), stat_of(s, kzg::verify::CELLS_CELL), rk, n, s->ctx->d_cells_tab, s->ctx->d_cellv_tab, s->cell_part);
+    if (s->from_blobs)
+      hipLaunchKernelGGL(k_blob_cells_interp, dim3(ngrp), dim3(CELLV_THREADS), 0, st, s->d_blobs, s->ext, stat_of(s, kzg::verify::CELLS_INDEX),
+                         stat_of(s, kzg::verify::CELLS_CELL), rk, n, s->ctx->d_cells_tab, s->ctx->d_cellv_tab, s->cell_part);
+    else
+      hipLaunchKernelGGL(k_cells_interp, dim3(ngrp), dim3(CELLV_THREADS), 0, st, s->d_cells, reinterpret_cast<const unsigned long long*>(s->d_cell_indices),
+                         stat_of(s, kzg::verify::CELLS_INDEX), stat_of(s, kzg::verify::CELLS_CELL), rk, n, s->ctx->d_cells_tab, s->ctx->d_cellv_tab, s->cell_part);
     hipLaunchKernelGGL(k_cells_reduce, dim3(1), dim3(256), 0, st, s->cell_part, ngrp, tail_scal);
   } else {
     hipLaunchKernelGGL(k_batch_ysum_finish, dim3(1), dim3(256), 0, st, s->ysum, nblk, tail_scal);
@@ -1403,7 +1449,7 @@ static int32_t verify_fused(kzg_verify_session* s, const VerifyInputs& in, int32
   if (rc == 0) rc = p2_accumulate(s, p2);
   if (rc == 0) rc = front_status(s, err);
   tt.mark("decoder done, first errors");
-  const int32_t code = rc == 0 ? first_error_code(err, kinds) : 0;
+  const int32_t code = rc == 0 ? session_error_code(s, err) : 0;
   if (rc == 0 && code == 0) rc = p2_finish_and_pair(s, p2, ok);
   tt.mark("lincombs + host horner + pairing");
   return rc ? rc : code;  // a rejected input wins: its code is returned, the sums are discarded
@@ -1691,6 +1737,12 @@ static int32_t each_status_enqueue(kzg_verify_session* s) {
   hipStream_t st = s->st;
   if (hipStreamWaitEvent(st, s->ev_join, 0) != hipSuccess || hipMemsetAsync(s->t_rejected, 0, (s->rows ? 2 : 1) * sizeof(uint32_t), st) != hipSuccess)
     return fail(KZG_FAIL_HIP, "per-item verdicts: status enqueue failed");
+  if (s->from_blobs) {  // the blob's code (blob, commitment, lowest rejected proof) for all 128 items of it; counts[0] = the rejected blobs
+    hipLaunchKernelGGL(k_each_blob_status, dim3((unsigned)s->ncom), dim3(CELLV_BLOB_ITEMS), 0, st, s->blob_stat, stat_of(s, 1), stat_of(s, 3), s->t_status,
+                       s->blob_code, s->t_rejected);
+    if (hipGetLastError() != hipSuccess) return fail(KZG_FAIL_HIP, "per-item verdicts: status launch failed");
+    return 0;
+  }
   if (s->rows) {  // the commitment's code through the item's index, and the rejected entries of the list counted beside the rejected items
     hipLaunchKernelGGL(k_each_rows_status, dim3(blocks_for(s->stride, 256)), dim3(256), 0, st, stat_of(s, 0), stat_of(s, 1), stat_of(s, 2), stat_of(s, 3),
                        reinterpret_cast<const unsigned long long*>(s->d_com_indices), s->ncom, n, s->t_status, s->t_rejected);
@@ -1706,7 +1758,10 @@ static int32_t each_status_enqueue(kzg_verify_session* s) {
 static int32_t each_build(kzg_verify_session* s, const EachGeom& g, uint64_t first_index) {
   const uint64_t n = s->n;
   hipStream_t st = s->st;
-  if (s->rows)  // the commitment gathered through the item's index out of the list behind the n proofs
+  if (s->from_blobs)  // the commitment of blob i >> 7 out of the list behind the n proofs
+    hipLaunchKernelGGL(k_each_blob_terms, dim3(2 * blocks_for(n, 64)), dim3(64), 0, st, s->rpow2, s->z, s->y, s->aff, s->t_status, s->ncom, n, first_index, s->t_a,
+                       s->t_b);
+  else if (s->rows)  // the commitment gathered through the item's index out of the list behind the n proofs
     hipLaunchKernelGGL(k_each_rows_terms, dim3(2 * blocks_for(n, 64)), dim3(64), 0, st, s->rpow2, s->z, s->y, s->aff, s->t_status,
                        reinterpret_cast<const unsigned long long*>(s->d_com_indices), s->ncom, n, first_index, s->t_a, s->t_b);
   else
@@ -1717,9 +1772,13 @@ static int32_t each_build(kzg_verify_session* s, const EachGeom& g, uint64_t fir
                        s->t_b + g.off[l + 1], cout);
   }
   if (s->kind == VerifyKind::CELLS) {  // the monomial term's coefficient vectors r_i I_i and their sums; the points are taken per fetched node (each_fetch)
-    hipLaunchKernelGGL(k_cells_each_leaves, dim3(blocks_for(n, CELLV_CELLS)), dim3(CELLV_THREADS), 0, st, s->d_cells,
-                       reinterpret_cast<const unsigned long long*>(s->d_cell_indices), s->t_status, s->rpow2, n, first_index, s->ctx->d_cells_tab, s->ctx->d_cellv_tab,
-                       s->t_vec);
+    if (s->from_blobs)
+      hipLaunchKernelGGL(k_blob_cells_each_leaves, dim3(blocks_for(n, CELLV_CELLS)), dim3(CELLV_THREADS), 0, st, s->d_blobs, s->ext, s->t_status, s->rpow2, n,
+                         first_index, s->ctx->d_cells_tab, s->ctx->d_cellv_tab, s->t_vec);
+    else
+      hipLaunchKernelGGL(k_cells_each_leaves, dim3(blocks_for(n, CELLV_CELLS)), dim3(CELLV_THREADS), 0, st, s->d_cells,
+                         reinterpret_cast<const unsigned long long*>(s->d_cell_indices), s->t_status, s->rpow2, n, first_index, s->ctx->d_cells_tab,
+                         s->ctx->d_cellv_tab, s->t_vec);
     for (uint32_t l = 0; l < g.height; l++) {
       const uint64_t cin = g.off[l + 1] - g.off[l], cout = g.off[l + 2] - g.off[l + 1];
       hipLaunchKernelGGL(k_each_vec_level, dim3(blocks_for(cout * 64, 256)), dim3(256), 0, st, s->t_vec + g.off[l] * 64, cin, s->t_vec + g.off[l + 1] * 64, cout);
@@ -1748,7 +1807,8 @@ static int32_t each_fetch(kzg_verify_session* s, const std::vector<uint32_t>& po
   }
   return 0;
 }
-// The descent over the session's trees: ok_each[i] = the leaf check of item i.  A level's nodes come back in one fetch and are checked
+// The descent over the session's trees: ok_each[i] = the leaf check of item i -- the blob form: of BLOB i, the node (7, i); the descent
+// stops at that floor and never enters a blob's 128 cells.  A level's nodes come back in one fetch and are checked
 // side by side on the helper pool: to affine, two Miller loops, one final exponentiation each (host::verify_pairings_fixed).
 static int32_t each_descend(kzg_verify_session* s, const EachGeom& g, uint8_t* ok_each) {
   const kzg_ctx* ctx = s->ctx;
@@ -1774,7 +1834,7 @@ static int32_t each_descend(kzg_verify_session* s, const EachGeom& g, uint8_t* o
       }
       return 0;
     });
-  });
+  }, s->from_blobs ? 7u : 0u);
   ctx->each_checks.fetch_add(checks, std::memory_order_relaxed);
   tt.mark("done");
   return rc;
@@ -1849,13 +1909,14 @@ extern "C" uint64_t kzg_ctx_sessions_created(const kzg_ctx* ctx) {
 // -- it would sum a rejected point -- while an item's verdict depends on its own commitment alone: the tree settles the items.
 static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, const VerifyEach& out, int32_t* ok) {
   const uint64_t n = s->n;
+  const uint64_t verdicts = s->from_blobs ? s->ncom : n;  // the blob form answers per blob: status and ok_each have ncom entries
   *ok = 0;
   const EachGeom g = each_geom(n);
-  uint32_t counts[2] = {0, 0};  // rejected items; rows: rejected listed commitments
+  uint32_t counts[2] = {0, 0};  // rejected items (the blob form: blobs); rows: rejected listed commitments
   int32_t rc = each_reserve(s, g);
   if (rc == 0) rc = each_status_enqueue(s);
-  if (rc == 0 && (hipMemcpyAsync(out.status, s->t_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
-                  hipMemcpyAsync(counts, s->t_rejected, (s->rows ? 2 : 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+  if (rc == 0 && (hipMemcpyAsync(out.status, s->from_blobs ? s->blob_code : s->t_status, verdicts * sizeof(int32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
+                  hipMemcpyAsync(counts, s->t_rejected, (s->rows && !s->from_blobs ? 2 : 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess ||
                   (s->rows && out.commitment_status &&
                    hipMemcpyAsync(out.commitment_status, stat_of(s, 1), s->ncom * sizeof(int32_t), hipMemcpyDeviceToHost, s->st) != hipSuccess) ||
                   hipStreamSynchronize(s->st) != hipSuccess))
@@ -1871,7 +1932,7 @@ static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, const Ver
     if (rc == 0) rc = p2_finish_and_pair(s, p2, &all);
     if (rc) return rc;
     if (all) {
-      memset(out.ok_each, 1, n);
+      memset(out.ok_each, 1, verdicts);
       *ok = 1;
       return 0;
     }
@@ -1881,7 +1942,7 @@ static int32_t each_finish(kzg_verify_session* s, const uint8_t* root, const Ver
   if (rc == 0) rc = each_build(s, g, 0);
   if (rc == 0) rc = each_descend(s, g, out.ok_each);
   if (rc) return rc;
-  for (uint64_t i = 0; i < n; i++)
+  for (uint64_t i = 0; i < verdicts; i++)
     if (out.status[i]) out.ok_each[i] = 0;
   return 0;  // *ok = 0: an item or a listed commitment was rejected, or the batch check was false
 }
@@ -1912,7 +1973,7 @@ int32_t verify_batch_single(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t
   const bool front_done = in.on_host && blobs;
   int32_t rc = front_done   ? verify_phase1_host(ctx, in.blobs, in.commitments48, in.proofs48, n, root, each ? err6 : nullptr, &use.s)
                : in.on_host ? points_stage_host(ctx, in, n, &use.s)
-                            : session_acquire(ctx, n, st, in.kind, false, &use.s, in.rows() ? &in.ncom : nullptr);
+                            : session_acquire(ctx, n, st, in.kind, false, &use.s, in.rows() ? &in.ncom : nullptr, in.from_blobs);
   if (rc) return rc;
   kzg_verify_session* s = use.s;
   const VerifyInputs dev = in.on_host ? staged_inputs(s) : in;
@@ -2030,6 +2091,94 @@ extern "C" int32_t kzg_verify_cell_proof_batch_rows_each_dev(const kzg_ctx* ctx,
   const VerifyEach each{ok_each, status, commitment_status};
   return rows_entry(ctx, cell_rows_inputs(d_commitments48, u, d_commitment_indices, d_cell_indices, d_cells, d_proofs48, false), n, &each, ok,
                     (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+
+// ---- the blob form: a blob's 128 cell proofs against the blob itself (include/kateth_amd.h) -------------------------------------------
+// The row-indexed session with ncom = the blobs and n = 128 of them each, under another address map: the extension half goes into the
+// session (k_compute_cells_ext, through cells_ext_enqueue), the front, k_cells_interp and the per-item kernels run as instances that
+// take the item number for the pair of indices and read cells 0..63 out of the blob (cellv_blob_cell), the commitment scalars are
+// 128-term segment sums (k_blob_weights).  Transcript, r and both sums are the rows call's on the expanded arrays.  `each`: the
+// per-BLOB outputs of the *_each forms -- the status fold gives all 128 items of a blob its code (k_each_blob_status) and the descent
+// stops at level 7.
+static int32_t blob_cells_entry(const kzg_ctx* ctx, const VerifyInputs& in, uint64_t nblobs, const VerifyEach* each, int32_t* ok, hipStream_t st) {
+  if (!ctx || !ok) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  if (nblobs == 0) return empty_batch(ok);
+  *ok = 0;
+  if (in.any_null() || (each && (!each->ok_each || !each->status))) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  // a cells session numbers its tree nodes, about two per item, in 32 bits
+  if (nblobs >> 24) return fail(KZG_FAIL_ARGUMENT, "too many blobs: their 128 cells each exceed a cell verification session");
+  const uint64_t n = nblobs * KZG_CELLS_PER_EXT_BLOB;
+  if (in.on_host && is_group(ctx)) return each ? multi_verify_each(ctx, in, n, *each, ok) : multi_verify_batch(ctx, in, n, ok);
+  return verify_batch_single(ctx, in, n, st, each, ok);
+}
+extern "C" int32_t kzg_verify_blob_cell_proofs_batch(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* cell_proofs48, uint64_t n,
+                                                     int32_t* ok) try {
+  return blob_cells_entry(ctx, blob_cell_inputs(blobs, n, commitments48, cell_proofs48, true), n, nullptr, ok, nullptr);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_verify_blob_cell_proofs_batch_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_cell_proofs48, uint64_t n,
+                                                         int32_t* ok, void* hip_stream) try {
+  return blob_cells_entry(ctx, blob_cell_inputs(d_blobs, n, d_commitments48, d_cell_proofs48, false), n, nullptr, ok, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_verify_blob_cell_proofs_batch_each(const kzg_ctx* ctx, const uint8_t* blobs, const uint8_t* commitments48, const uint8_t* cell_proofs48,
+                                                          uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok) try {
+  const VerifyEach each{ok_each, status};
+  return blob_cells_entry(ctx, blob_cell_inputs(blobs, n, commitments48, cell_proofs48, true), n, &each, ok, nullptr);
+} catch (...) {
+  return abi_exception();
+}
+extern "C" int32_t kzg_verify_blob_cell_proofs_batch_each_dev(const kzg_ctx* ctx, const void* d_blobs, const void* d_commitments48, const void* d_cell_proofs48,
+                                                              uint64_t n, uint8_t* ok_each, int32_t* status, int32_t* ok, void* hip_stream) try {
+  const VerifyEach each{ok_each, status};
+  return blob_cells_entry(ctx, blob_cell_inputs(d_blobs, n, d_commitments48, d_cell_proofs48, false), n, &each, ok, (hipStream_t)hip_stream);
+} catch (...) {
+  return abi_exception();
+}
+
+// Introspection: the blob form's commitment scalars through phase 2's launch sequence -- k_batch_scalars for the powers, then
+// k_blob_weights.  Scratch of its own, freed here; member 0 of a group.
+extern "C" int32_t kzg_blob_cell_weights(const kzg_ctx* ctx, const uint8_t* r32, uint64_t first_index, uint64_t n_blobs, uint8_t* out_w32) try {
+  if (!ctx || !r32 || (n_blobs && !out_w32)) return fail(KZG_FAIL_ARGUMENT, "null argument");
+  fr_t r;
+  fr_from_be_bytes_plain(r, r32);
+  if (!fr_is_canonical(r)) return KZG_ERR_FF_NOT_IN_FIELD;
+  if (n_blobs == 0) return 0;
+  if (n_blobs >> 24) return fail(KZG_FAIL_ARGUMENT, "too many blobs");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const uint64_t n = n_blobs * KZG_CELLS_PER_EXT_BLOB;
+  const unsigned nblk = blocks_for(n, 256);
+  Carve c;
+  const size_t o_rpow2 = c.take(64 * sizeof(fr_t)), o_zero = c.take(n * sizeof(fr_t)), o_rk = c.take(n * sizeof(fr_t)), o_sb = c.take(n * sizeof(fr_t)),
+               o_ysum = c.take(((size_t)nblk + 1) * sizeof(fr_t)), o_w = c.take((size_t)n_blobs * sizeof(fr_t));
+  struct Scratch {
+    uint8_t* p = nullptr;
+    ~Scratch() {
+      if (p) (void)hipFree(p);
+    }
+  } d;
+  HIP_TRY(hipMalloc(&d.p, c.off));
+  to_mont<FrParams>(r, r);
+  fr_t rpow2[64];
+  rpow2[0] = r;
+  for (int k = 1; k < 64; k++) fr_sqr(rpow2[k], rpow2[k - 1]);
+  hipStream_t st = nullptr;  // an introspection call, waited for here
+  fr_t *d_rpow2 = (fr_t*)(d.p + o_rpow2), *d_zero = (fr_t*)(d.p + o_zero), *d_rk = (fr_t*)(d.p + o_rk), *d_sb = (fr_t*)(d.p + o_sb), *d_ysum = (fr_t*)(d.p + o_ysum),
+       *d_w = (fr_t*)(d.p + o_w);
+  HIP_TRY(hipMemcpyAsync(d_rpow2, rpow2, sizeof(rpow2), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(d_zero, 0, n * sizeof(fr_t), st));
+  hipLaunchKernelGGL(k_batch_scalars, dim3(nblk), dim3(256), 0, st, d_rpow2, d_zero, d_zero, n, first_index, d_rk, d_sb, d_ysum);
+  hipLaunchKernelGGL(k_blob_weights, dim3((unsigned)n_blobs), dim3(CELLV_BLOB_ITEMS), 0, st, d_rk, d_w);
+  HIP_TRY(hipGetLastError());
+  std::vector<fr_t> w(n_blobs);
+  HIP_TRY(hipMemcpyAsync(w.data(), d_w, (size_t)n_blobs * sizeof(fr_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (uint64_t k = 0; k < n_blobs; k++) fr_to_be_bytes_plain(out_w32 + 32 * k, w[k]);
+  return 0;
 } catch (...) {
   return abi_exception();
 }

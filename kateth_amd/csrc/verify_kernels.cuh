@@ -1192,7 +1192,10 @@ static __global__ __launch_bounds__(256) void k_each_status(const int32_t* __res
 // test, so a rejected item (a row >= ncom among them: its status is KZG_ERR_COMMITMENT_INDEX) reads neither the index nor a base -- and
 // the commitment's position is the one 64-bit value the loop carries beyond the sibling's.  The body is shared; k_each_terms is its
 // ROWS = false instance with the figures it had (238 VGPRs, the adder's 352-byte frame, occupancy 2).
-template <bool ROWS>
+//
+// BLOB (k_each_blob_terms, the blob form kzg_verify_blob_cell_proofs_batch_each): the ROWS layout with the implicit row i >> 7 -- no
+// index array is read.
+template <bool ROWS, bool BLOB = false>
 __device__ __forceinline__ void each_terms_body(const fr_t* __restrict__ rpow2, const fr_t* __restrict__ z_plain, const fr_t* __restrict__ y_plain,
                                                 const uint4* __restrict__ aff, const int32_t* __restrict__ status,
                                                 const unsigned long long* __restrict__ commitment_indices, uint64_t ncom, uint64_t n, uint64_t first_index,
@@ -1234,7 +1237,9 @@ __device__ __forceinline__ void each_terms_body(const fr_t* __restrict__ rpow2, 
   // ROWS: where the item's commitment stands, and the tail behind the list (cells: y = 0, so the third base is never added, but its
   // position stays inside the array); a row the front did not accept never arrives here, the clamp keeps even that one in bounds
   uint64_t com_at = 0;
-  if (ROWS) {
+  if (BLOB) {
+    com_at = n + (i >> 7);
+  } else if (ROWS) {
     const unsigned long long row = commitment_indices[i];
     com_at = n + (row < ncom ? row : 0);
   }
@@ -1285,6 +1290,13 @@ static __global__ __launch_bounds__(64, 2) void k_each_rows_terms(const fr_t* __
                                                                  const unsigned long long* __restrict__ commitment_indices, uint64_t ncom, uint64_t n,
                                                                  uint64_t first_index, g1_xyzz28* __restrict__ leaves_a, g1_xyzz28* __restrict__ leaves_b) {
   each_terms_body<true>(rpow2, z_plain, y_plain, aff, status, commitment_indices, ncom, n, first_index, leaves_a, leaves_b);
+}
+// the blob form's terms (kzg_verify_blob_cell_proofs_batch_each): n = 128 ncom items, item i's commitment is aff[n + (i >> 7)]
+static __global__ __launch_bounds__(64, 2) void k_each_blob_terms(const fr_t* __restrict__ rpow2, const fr_t* __restrict__ z_plain, const fr_t* __restrict__ y_plain,
+                                                                 const uint4* __restrict__ aff /* n + ncom + tail */, const int32_t* __restrict__ status,
+                                                                 uint64_t ncom, uint64_t n, uint64_t first_index, g1_xyzz28* __restrict__ leaves_a,
+                                                                 g1_xyzz28* __restrict__ leaves_b) {
+  each_terms_body<true, true>(rpow2, z_plain, y_plain, aff, status, nullptr, ncom, n, first_index, leaves_a, leaves_b);
 }
 
 // one level of both sum trees: out[j] = in[2 j] + in[2 j + 1], a missing sibling being the identity; lanes [0, cnt_out) take

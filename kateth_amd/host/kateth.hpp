@@ -14,6 +14,8 @@
 //   verify_cell_proof_batch_each(...)    <- the same, one Verdict per tuple
 //   verify_cell_proof_batch_rows(cs, rows, idx, cells, ps) <- the same check on a block's commitment list and an index per cell
 //   verify_cell_proof_batch_rows_each(...) <- that form, one Verdict per cell (and the list's own statuses)
+//   verify_blob_cell_proofs(blobs, cs, cell_proofs) <- a blob's 128 cell proofs against the blob itself (transaction-pool form)
+//   verify_blob_cell_proofs_each(...)    <- the same, one Verdict per blob
 //   decompress(bytes48) -> P1            <- P1::decompress, src/bls.rs:505-531
 //   verify_blob_proof(blob, c, p)        <- src/kzg/setup.rs:208-221
 //   verify_blob_proof_batch(blobs,cs,ps) <- src/kzg/setup.rs:247-275
@@ -701,6 +703,41 @@ class Setup {
     check(kzg_verify_cell_proof_batch_rows_each(ctx_.get(), u ? cs.data() : nullptr, u, commitment_indices.data(), cell_indices.data(), cells, ps.data(), n,
                                                 ok_each.data(), status.data(), commitment_status && u ? commitment_status->data() : nullptr, &ok),
           "kzg_verify_cell_proof_batch_rows_each");
+    if (all_ok) *all_ok = ok != 0;
+    std::vector<Verdict> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = Verdict{ok_each[i] != 0, status[i]};
+    return out;
+  }
+
+  // The blob form (transaction-pool form): every blob's 128 cell proofs (cell_proofs[128 b + k] = proof k of blob b) against the blob
+  // and its commitment -- go-ethereum's kzg4844.VerifyCellProofs.  blobs = the blobs concatenated, 131,072 bytes each.  The verdict is
+  // verify_cell_proof_batch_rows' on the blobs' computed cells; neither cells nor indices exist on the way.  Throws Error with the kind
+  // of the first rejected input: every blob (BlobInvalidFieldElement) before any commitment, every commitment before any proof.
+  bool verify_blob_cell_proofs(const uint8_t* blobs, size_t blobs_len, const std::vector<Bytes48>& commitments, const std::vector<Bytes48>& cell_proofs) const {
+    const size_t n = commitments.size();
+    if (blobs_len != n * BLOB_BYTES || cell_proofs.size() != n * KZG_CELLS_PER_EXT_BLOB)
+      throw std::invalid_argument("verify_blob_cell_proofs: one 131072-byte blob and 128 cell proofs per commitment");
+    std::vector<uint8_t> cs(n * 48), ps(cell_proofs.size() * 48);
+    for (size_t i = 0; i < n; i++) std::copy(commitments[i].begin(), commitments[i].end(), cs.begin() + i * 48);
+    for (size_t i = 0; i < cell_proofs.size(); i++) std::copy(cell_proofs[i].begin(), cell_proofs[i].end(), ps.begin() + i * 48);
+    int32_t ok = 0;
+    int32_t rc = kzg_verify_blob_cell_proofs_batch(ctx_.get(), blobs, cs.data(), ps.data(), n, &ok);
+    return finish(rc, ok, "kzg_verify_blob_cell_proofs_batch");
+  }
+  // one Verdict per BLOB: `ok`, or with status != 0 the ErrorKind of the blob's own first rejected input (blob, commitment, lowest
+  // proof), reported in place: a rejected blob does not touch its neighbours' verdicts.  all_ok, if wanted, is the AND.
+  std::vector<Verdict> verify_blob_cell_proofs_each(const uint8_t* blobs, size_t blobs_len, const std::vector<Bytes48>& commitments,
+                                                    const std::vector<Bytes48>& cell_proofs, bool* all_ok = nullptr) const {
+    const size_t n = commitments.size();
+    if (blobs_len != n * BLOB_BYTES || cell_proofs.size() != n * KZG_CELLS_PER_EXT_BLOB)
+      throw std::invalid_argument("verify_blob_cell_proofs_each: one 131072-byte blob and 128 cell proofs per commitment");
+    std::vector<uint8_t> cs(n * 48), ps(cell_proofs.size() * 48), ok_each(n);
+    std::vector<int32_t> status(n);
+    for (size_t i = 0; i < n; i++) std::copy(commitments[i].begin(), commitments[i].end(), cs.begin() + i * 48);
+    for (size_t i = 0; i < cell_proofs.size(); i++) std::copy(cell_proofs[i].begin(), cell_proofs[i].end(), ps.begin() + i * 48);
+    int32_t ok = 0;
+    check(kzg_verify_blob_cell_proofs_batch_each(ctx_.get(), blobs, cs.data(), ps.data(), n, ok_each.data(), status.data(), &ok),
+          "kzg_verify_blob_cell_proofs_batch_each");
     if (all_ok) *all_ok = ok != 0;
     std::vector<Verdict> out(n);
     for (size_t i = 0; i < n; i++) out[i] = Verdict{ok_each[i] != 0, status[i]};

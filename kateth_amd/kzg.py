@@ -257,6 +257,13 @@ _SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p,
          _i32p, _i32p, ctypes.c_void_p]),
     "kzg_cell_row_weights": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, _u64p, ctypes.c_uint64, ctypes.c_uint64, _u8p]),
+    "kzg_verify_blob_cell_proofs_batch": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _i32p]),
+    "kzg_verify_blob_cell_proofs_batch_dev": (
+        ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _i32p, ctypes.c_void_p]),
+    "kzg_verify_blob_cell_proofs_batch_each": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p, _i32p]),
+    "kzg_verify_blob_cell_proofs_batch_each_dev": (
+        ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, _u8p, _i32p, _i32p, ctypes.c_void_p]),
+    "kzg_blob_cell_weights": (ctypes.c_int32, [ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.c_uint64, _u8p]),
     "kzg_verify_cell_proof_batch_each": (ctypes.c_int32, [ctypes.c_void_p, _u8p, _u64p, _u8p, _u8p, ctypes.c_uint64, _u8p, _i32p, _i32p]),
     "kzg_verify_cell_proof_batch_each_dev": (
         ctypes.c_int32,
@@ -1259,6 +1266,65 @@ class Setup:
             raise _cell_verify_error(rc)
         res = bytes(out)
         return [int.from_bytes(res[32 * k:32 * k + 32], "big") for k in range(u)]
+
+    # -- the blob form (transaction-pool form): a blob's 128 cell proofs against the blob itself --------------------------------------
+    @staticmethod
+    def _blob_cell_lists(blobs, commitments, cell_proofs):
+        """the length checks of the blob form's list calls, as verify_blob_proof_batch raises them -> (n, blobs, commitments, proofs) joined"""
+        assert len(blobs) == len(commitments), "assertion `left == right` failed"
+        assert len(cell_proofs) == CELLS_PER_EXT_BLOB * len(blobs), "assertion `left == right` failed"
+        blobs, commitments, cell_proofs = [_buf(v) for v in blobs], [_buf(v) for v in commitments], [_buf(v) for v in cell_proofs]
+        if any(len(b) != BYTES_PER_BLOB for b in blobs):
+            raise KzgError(BlobError("InvalidLen"))
+        if any(len(c) != 48 for c in commitments + cell_proofs):
+            raise KzgError(BlsError(ECGroupError("InvalidEncoding")))
+        return len(blobs), b"".join(blobs), b"".join(commitments), b"".join(cell_proofs)
+
+    def verify_blob_cell_proofs(self, blobs: Sequence[bytes], commitments: Sequence[bytes], cell_proofs: Sequence[bytes]) -> bool:
+        """Every blob's 128 cell proofs (cell_proofs[128 b + k] = proof k of blob b) against the blob and its commitment: what a
+        transaction pool checks for a blob transaction of wrapper version 1 (go-ethereum's kzg4844.VerifyCellProofs).  The boolean of
+        verify_cell_proof_batch_rows on the blobs' computed cells, without the cells or any index crossing to the device.  Raises as
+        verify_blob_proof_batch does: AssertionError for mismatched list lengths (len(cell_proofs) == 128 len(blobs) among them),
+        KzgError for a wrong-length or rejected blob, commitment or proof (every blob before any commitment, those before any proof)."""
+        n, blobs, commitments, cell_proofs = self._blob_cell_lists(blobs, commitments, cell_proofs)
+        return self.verify_blob_cell_proofs_batch_host(blobs, commitments, cell_proofs, n)
+
+    def verify_blob_cell_proofs_each(self, blobs: Sequence[bytes], commitments: Sequence[bytes], cell_proofs: Sequence[bytes]) -> List[Union[bool, Exception]]:
+        """verify_blob_cell_proofs with one entry per BLOB: True / False, or IN PLACE the KzgError of the blob's own first rejected input
+        (blob, commitment, lowest proof) -- which transaction to drop.  A rejected blob does not touch its neighbours' verdicts."""
+        n, blobs, commitments, cell_proofs = self._blob_cell_lists(blobs, commitments, cell_proofs)
+        ok_each, status, _ = self.verify_blob_cell_proofs_batch_each_host(blobs, commitments, cell_proofs, n)
+        return [_kzg_error(status[b]) if status[b] else ok_each[b] for b in range(n)]
+
+    def verify_blob_cell_proofs_batch_host(self, blobs, commitments, cell_proofs, n: int) -> bool:
+        """kzg_verify_blob_cell_proofs_batch on n CONTIGUOUS blobs, n commitments and 128 n cell proofs in host memory (bytes-like objects
+        or raw host addresses)"""
+        return self._verdict("kzg_verify_blob_cell_proofs_batch", self._host_args(blobs, commitments, cell_proofs) + [n])
+
+    def verify_blob_cell_proofs_batch_dev(self, d_blobs: int, d_commitments: int, d_cell_proofs: int, n: int, stream: int = 0) -> bool:
+        """kzg_verify_blob_cell_proofs_batch_dev: device pointers (16-byte aligned) to n blobs, n commitments, 128 n cell proofs"""
+        return self._verdict("kzg_verify_blob_cell_proofs_batch_dev", (d_blobs, d_commitments, d_cell_proofs, n), (stream,))
+
+    def verify_blob_cell_proofs_batch_each_host(self, blobs, commitments, cell_proofs, n: int):
+        """kzg_verify_blob_cell_proofs_batch_each on host memory -> (ok_each, status, ok), one entry per BLOB"""
+        return self._verdicts("kzg_verify_blob_cell_proofs_batch_each", self._host_args(blobs, commitments, cell_proofs), n)
+
+    def verify_blob_cell_proofs_batch_each_dev(self, d_blobs: int, d_commitments: int, d_cell_proofs: int, n: int, stream: int = 0):
+        """-> (ok_each: List[bool], status: List[int], ok: bool), one entry per BLOB; synchronous, results in host memory"""
+        return self._verdicts("kzg_verify_blob_cell_proofs_batch_each_dev", (d_blobs, d_commitments, d_cell_proofs), n, (stream,))
+
+    def blob_cell_weights(self, r: int, n_blobs: int, first_index: int = 0) -> List[int]:
+        """w_b = sum_{k<128} r^(first_index + 128 b + k) mod the group order, b < n_blobs, through the kernel behind the blob form's
+        commitment scalars (kzg_blob_cell_weights): cell_row_weights' values for the indices i >> 7.  r >= the modulus raises KzgError."""
+        if not 0 <= r < 1 << 256 or not 0 <= first_index < 1 << 64 or n_blobs < 0:
+            raise ValueError("blob_cell_weights: r is 32 bytes, first_index a uint64")
+        out = (ctypes.c_uint8 * (32 * max(n_blobs, 1)))()
+        rc = self._lib.kzg_blob_cell_weights(self._h, int(r).to_bytes(32, "big"), first_index, n_blobs, ctypes.cast(out, _u8p))
+        self._check(rc, "kzg_blob_cell_weights")
+        if rc > 0:
+            raise _kzg_error(rc)
+        res = bytes(out)
+        return [int.from_bytes(res[32 * k:32 * k + 32], "big") for k in range(n_blobs)]
 
     def g1_monomial(self, first: int = 0, count: int = 64) -> List[bytes]:
         """the 48-byte encodings of the monomial G1 setup points [tau^j]_1, first <= j < first + count <= 64, which the context derives
